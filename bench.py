@@ -7,6 +7,7 @@ fulldynamic_talos.py:538-541 — with all problem data resident in HBM.  Instanc
 data-path collective (weak scaling: B instances per GPU).  Prints ONE JSON line on rank 0.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs out/   # also writes the outputs of the last timed tick (out/*.npy)
   python bench.py --gpus 8                     # launches the 8 ranks itself (launch_ranks: one child process per GPU, this process never touches a GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8
 """
@@ -46,9 +47,42 @@ def _p50(v):
     return float(np.percentile(np.asarray(v), 50))
 
 
+DUMP_BYTES_MAX = 64 * 10 ** 6  # --dump-outputs: the files of one run in all
+
+
+def last_tick_outputs(shards):
+    """What a caller of the timed path receives after its last tick, for the instances of this rank in instance order: the trajectories xs, us
+    and the feedback gains K0, k0 of the first knot (what the scripts read from `results`; the same set as `value_with_result_download`)."""
+    ids, parts = [], []
+    for e in shards:
+        r = e.results(gains=False)
+        K0, k0 = e.native.get_gain(0)
+        ids.append(np.asarray(getattr(e, "instance_ids", np.arange(e.batch))))
+        parts.append({"xs": r["xs"], "us": r["us"], "K0": K0, "k0": k0})
+    order = np.argsort(np.concatenate(ids), kind="stable")
+    return {k: np.concatenate([p[k] for p in parts])[order] for k in parts[0]}
+
+
+def dump_outputs(out_dir, outputs, limit=DUMP_BYTES_MAX):
+    """``outputs``: {measurement: {array: (instances, ...)}} -> DIR/<measurement>_<array>.npy in float64.  Above ``limit`` bytes in all, every file
+    keeps the same fixed, seeded sample of instances (rows)."""
+    arrays = [(m + "_" + k, a) for m, o in outputs.items() for k, a in o.items()]
+    batch = arrays[0][1].shape[0]
+    payload = sum(a.size * 8 for _, a in arrays)
+    budget = limit - 1024 * len(arrays)  # (room for the .npy headers)
+    rows = np.arange(batch)
+    if payload > budget:
+        rows = np.sort(np.random.default_rng(0).choice(batch, max(1, batch * budget // payload), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays:
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[rows], dtype=np.float64))
+    return rows
+
+
 def cpu_worker(args):
     """One instance of the bench OCP on the CPU port (tests/_cpu_port.py), 8 OpenMP threads, 8 legs: a few cold iterations for a
-    warm start, then `--cpu-worker` timed MPC ticks.  Prints one JSON line (tick times and their wall-clock window)."""
+    warm start, then `--cpu-worker` timed MPC ticks.  Prints "ready" after the set-up and starts the timed ticks when a line arrives on stdin, then
+    prints one JSON line (tick times and their wall-clock window)."""
     from tests import _cpu_port
     from mpc_benchmark_amd.ensemble import EnsembleMPC
     from mpc_benchmark_amd.problems.fulldynamic import FullDynamicsProblem
@@ -60,6 +94,8 @@ def cpu_worker(args):
     e.options.num_threads, e.options.riccati_legs = 8, 8
     e.native.set_options(e.options)
     e.step()
+    print("ready", flush=True)
+    sys.stdin.readline()  # the parent releases its workers together: their timed ticks run side by side
     ms, ends = [], []
     t_start = time.time()
     for _ in range(args.cpu_worker):
@@ -267,7 +303,12 @@ def main():
                     help="legs of the batch-1 latency measurement (a single instance leaves the chip idle: more, shorter legs pay; with more "
                          "than 8 the cuts are resolved by a tree of pairwise compositions, csrc/legs_tree.h)")
     ap.add_argument("--lib", default=None, help="developer option: another build of the same HIP library (kernel tuning variants)")
-    ap.add_argument("--regions", type=int, default=0, help="how many times the region of --steps ticks is timed (0 = automatic: about one second in total, at most 8)")
+    ap.add_argument("--regions", type=int, default=1, help="how many times the region of --steps ticks is timed from the same checkpoint (0 = automatic: about one second in total, at most 8); "
+                                                            "ms_per_step is the mean over the regions")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed tick of every measurement computed as DIR/<measurement>_<array>.npy (float64: xs, us and "
+                         "the first knot's gains K0, k0 of every instance of this rank, in instance order; above %d MB in all, the same seeded sample of instances in every "
+                         "file).  The inputs are seeded: two builds run with the same arguments can be compared output for output" % (DUMP_BYTES_MAX // 10 ** 6))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-worker", type=int, default=0, help="(internal) run this many MPC ticks of one instance on the CPU port with 8 threads and print their times")
     ap.add_argument("--no-latency", action="store_true")
@@ -498,8 +539,8 @@ def main():
                 device_sync()
                 dist.barrier()
 
-        # The driver asks for K steps; K x 7 ms is a short sample, so the region of EXACTLY K steps (barrier + synchronize on both
-        # sides) is timed `regions` times (about a second in total) from the same starting point — a checkpoint (mpc_get_state) taken
+        # The driver asks for K steps: the region of EXACTLY K steps (barrier + synchronize on both sides) is timed once, so that K sets the
+        # number of timed steps.  With --regions R it is timed R times from the same starting point — a checkpoint (mpc_get_state) taken
         # one tick before it, restored between regions, one untimed tick to refill the records of tick reuse — and value /
         # ms_per_step come from all of them (steps per region and the number of regions are both in the JSON line).
         est = sum(v[1] for v in warm.values()) / max(1, args.warmup) * 1e-3 / max(1, nshard)
@@ -542,6 +583,7 @@ def main():
         replanning = replanning / regions
         for e in shards:
             e.native.profile(0)
+        outputs = last_tick_outputs(shards) if args.dump_outputs else None
         per_rank = [elapsed]
         if dist is not None:
             import torch
@@ -568,7 +610,7 @@ def main():
                 c0, m0 = prof.get(kname, (0, 0.0))
                 prof[kname] = (c0 + cnt, m0 + ms)
         return dict(shards=shards, ens=ens, legs=legs, cold=cold, n_conv=n_conv, n_conv100=n_conv100, worst_unconv=worst_unconv, regions=regions, nostep=nostep["n"], corrector_ticks=nostep["extra"], backtracking_ticks=nostep["back"], pace=pace, stagger=stagger, elapsed=elapsed,
-                    prof=prof, warm=warm, gather=gather, replanning_ticks=replanning, per_rank=per_rank)
+                    prof=prof, warm=warm, gather=gather, replanning_ticks=replanning, per_rank=per_rank, outputs=outputs)
 
     def whole_schedule(corrector, refine, floor=True):
         """The reference's WHOLE schedule (t_mpc - 1 ticks of fulldynamic_talos.py:438-550: seven swings) walked by the benchmarked ensemble in the
@@ -645,6 +687,12 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+
+    def measurement_name(w):
+        return w if isinstance(w, str) else ("walk" if w else "frozen_references")
+    if args.dump_outputs:
+        # every measurement, not only the headline: which of frozen / walk is the slower one may differ from run to run
+        dump_outputs(args.dump_outputs, {measurement_name(w): r["outputs"] for w, r in runs.items()})
 
     d = ens.dims
     n, m = d.ndx, d.nu
@@ -855,9 +903,17 @@ def main():
         cores = os.cpu_count() or 1
         nproc = max(1, cores // 8)
         cmd = [sys.executable, os.path.abspath(__file__), "--cpu-worker", "20", "--horizon", str(args.horizon), "--model", args.model]
-        one = json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.strip().split("\n")[-1])
+        one = json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True, input="go\n").stdout.strip().split("\n")[-1])
         t0c = time.perf_counter()
-        procs = [subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True) for _ in range(nproc)]
+        procs = [subprocess.Popen(cmd, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True) for _ in range(nproc)]
+        # the set-up of a worker (imports, problem, cold solve) takes longer than its timed ticks: started one after the other, the timed windows
+        # of many workers need not overlap at all.  Every worker finishes its set-up first, then all are released at once.
+        for pr in procs:
+            while pr.stdout.readline() not in ("ready\n", ""):
+                pass
+        for pr in procs:
+            pr.stdin.write("go\n")
+            pr.stdin.flush()
         outs = [json.loads(pr.communicate()[0].strip().split("\n")[-1]) for pr in procs]
         wall = time.perf_counter() - t0c
         # every worker reports the wall-clock window of its timed ticks: the host rate is the ticks inside the common window
@@ -909,10 +965,10 @@ def main():
         "tick_mode": ("walk: foot references regenerated and patched every tick (fulldynamic_talos.py:444-510)" if head else "frozen foot references"),
         "walk_references": ("per instance: every instance replans from its own measured foot poses (per-instance parameter tables, batched generator %s)" % ("in the library: mpc_walk_update" if args.walk_generator == "device" else "on the host") if args.walk_refs == "instance"
                             else "planned once per tick from instance 0's measured state and shared by the instances of an ensemble"),
-        "measurements": {(w if isinstance(w, str) else ("walk" if w else "frozen_references")): {"value": round(rate(r), 2), "ms_per_step": round(r["elapsed"] / args.steps * 1e3, 4),
-                                                                  "replanning_ticks": r["replanning_ticks"],
-                                                                  "instance_ticks_with_corrector_iteration": r["corrector_ticks"], "instance_ticks_backtracking": r["backtracking_ticks"],
-                                                                  "kernel_ms_per_step_warmup": {k: round(v[1] / max(1, args.warmup), 4) for k, v in sorted(r["warm"].items(), key=lambda kv: -kv[1][1])[:6]}}
+        "measurements": {measurement_name(w): {"value": round(rate(r), 2), "ms_per_step": round(r["elapsed"] / args.steps * 1e3, 4),
+                                               "replanning_ticks": r["replanning_ticks"],
+                                               "instance_ticks_with_corrector_iteration": r["corrector_ticks"], "instance_ticks_backtracking": r["backtracking_ticks"],
+                                               "kernel_ms_per_step_warmup": {k: round(v[1] / max(1, args.warmup), 4) for k, v in sorted(r["warm"].items(), key=lambda kv: -kv[1][1])[:6]}}
                          for w, r in runs.items()},
         "instance_ticks_without_step": nostep["n"] * world, "diverged_instance_rescues": sum(getattr(e, "rescues", 0) for e in shards),
         "instances_lost_and_revived": sum(getattr(e, "revived", 0) for e in shards),

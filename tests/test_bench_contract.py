@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,3 +102,36 @@ def test_launcher_does_not_wait_for_a_rendezvous_that_cannot_happen(cpu_lib):
     out = subprocess.run([sys.executable, BENCH, "--selftest-cpu", "--lib", cpu_lib, "--gpus", "2", "--no-latency", "--no-whole-schedule", "--no-cpu-baseline"] + SMALL,
                          capture_output=True, text=True, timeout=300, cwd=ROOT, env=dict({k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE")}, MPC_BENCH_TEST_FAIL_RANK="1"))
     assert out.returncode != 0 and time.time() - t0 < 120 and "ranks failed" in out.stderr
+
+
+def test_steps_are_the_timed_steps_and_the_dump_repeats(cpu_lib, tmp_path):
+    """Without --regions the region of --steps ticks is timed once; --dump-outputs writes the last timed tick of every measurement, the same
+    numbers in two runs with the same arguments."""
+    args = ["--selftest-cpu", "--lib", cpu_lib, "--no-latency", "--no-whole-schedule", "--no-cpu-baseline"] + SMALL[:SMALL.index("--regions")] + SMALL[SMALL.index("--regions") + 2:]
+    dumps = []
+    for run in ("a", "b"):
+        out, rows = _run(args + ["--dump-outputs", str(tmp_path / run)])
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads(rows[0])
+        assert d["steps"] == 2 and d["timed_regions"] == 1
+        dumps.append({f: np.load(str(tmp_path / run / f)) for f in sorted(os.listdir(str(tmp_path / run)))})
+    a, b = dumps
+    assert sorted(a) == sorted("%s_%s.npy" % (m, k) for m in d["measurements"] for k in ("xs", "us", "K0", "k0"))
+    for f, x in a.items():
+        assert x.dtype == np.float64 and x.shape[0] == 2 and np.isfinite(x).all(), f
+        assert np.array_equal(x, b[f]), f
+    assert a["walk_xs.npy"].shape == (2, 7, 57) and a["walk_us.npy"].shape == (2, 6, 22) and a["walk_K0.npy"].shape == (2, 22, 56)
+
+
+def test_dump_above_the_limit_keeps_one_seeded_sample_of_instances(tmp_path):
+    import bench
+    B = 50
+    outputs = {m: {"xs": np.arange(B * 300, dtype=float).reshape(B, 300) + i, "K0": np.arange(B * 100, dtype=float).reshape(B, 10, 10)} for i, m in enumerate(("frozen", "walk"))}
+    rows = bench.dump_outputs(str(tmp_path / "a"), outputs, limit=60000)
+    assert 1 <= len(rows) < B and np.all(np.diff(rows) > 0)
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))) <= 60000
+    for m, o in outputs.items():
+        for k, x in o.items():
+            assert np.array_equal(np.load(str(tmp_path / "a" / ("%s_%s.npy" % (m, k)))), x[rows])
+    assert np.array_equal(bench.dump_outputs(str(tmp_path / "b"), outputs, limit=60000), rows)
+    assert len(bench.dump_outputs(str(tmp_path / "c"), outputs)) == B
