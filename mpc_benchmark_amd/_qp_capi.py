@@ -52,6 +52,11 @@ def _bind(lib):
     lib.mpc_qp_low_level_steps.restype = C.c_int
     lib.mpc_qp_low_level_steps.argtypes = [C.c_void_p, C.POINTER(QpSettings), C.c_void_p, C.c_void_p, C.c_int32, _IP, _DP, _DP, C.c_double, _IP, _DP,
                                            _DP, C.c_int32, C.c_double, _DP, _DP, _DP, _DP, C.POINTER(QpInfo)]
+    if hasattr(lib, "mpc_qp_ikid_low_level_steps"):  # HIP library only (the oracle does not export it)
+        lib.mpc_qp_ikid_low_level_steps.restype = C.c_int
+        lib.mpc_qp_ikid_low_level_steps.argtypes = [C.c_void_p, C.POINTER(QpSettings), C.c_void_p, C.c_void_p, C.c_int32, _IP, C.c_int32, C.c_int32,
+                                                    _DP, _DP, _DP, _DP, _DP, _DP, _DP, C.c_double, _IP, _DP, _DP, C.c_int32, C.c_double,
+                                                    _DP, _DP, _DP, _DP, _DP, C.POINTER(QpInfo), _DP]
     _bound.add(id(lib))
     return lib
 
@@ -190,3 +195,39 @@ class BatchedQP:
         if rc != 0:
             raise RuntimeError("mpc_qp_solve_ikid: " + self.lib.mpc_qp_last_error(self._h).decode())
         return (x, y, z, zb, list(info), mats) if return_matrices else (x, y, z, zb, list(info))
+
+    def ikid_low_level_steps(self, plan, sim, frames, base_frame, torso_frame, weights, gains, cone, l_box, u_box, x_posture, foot_refs, ref_dt,
+                             contact_states, steps, dt, x=None, x_ik=None, cone_l=None, want_ik=False):
+        """mpc_qp_ikid_low_level_steps: ``steps`` periods of the centroidal low-level loop (task errors once; per period the centroidal state of the
+        measurement and the feedback forces of the plan's knot 0 -> IK + ID QP -> simulator step) without the host in between.  ``plan``, ``sim``:
+        NativeSolver handles of the same library; ``foot_refs`` [B][2][2][12]; ``x_ik`` None: the measurement the last call kept on the device.
+        -> x_prev, c_prev, x, tau, forces, info (, ik) (states before / after the last period, new_x of the one before, torques and forces of the last)."""
+        if not hasattr(self.lib, "mpc_qp_ikid_low_level_steps"):
+            raise RuntimeError("mpc_qp_ikid_low_level_steps is not exported by this library (the centroidal device loop is HIP only)")
+        d = self.dims
+        B, nv, nqv = d.batch, self._nv, self._nqv
+        frames = np.ascontiguousarray(frames, dtype=np.int32); nk = frames.size
+        f64 = lambda a, shape=None: np.ascontiguousarray(a if shape is None else np.broadcast_to(np.asarray(a, dtype=np.float64), shape), dtype=np.float64)
+        weights, gains, cone, l_box, u_box = f64(weights), f64(gains), self._cone_pair(cone, cone_l), f64(l_box), f64(u_box)
+        if weights.size != 5 or gains.size != 2 * nv * nv + 90 or l_box.size != d.n or u_box.size != d.n:
+            raise ValueError("ikid_low_level_steps: weights[5], gains[2 nv^2 + 90], l_box / u_box [n] expected")
+        x_posture = f64(x_posture)
+        if x_posture.size != nqv:
+            raise ValueError("ikid_low_level_steps: x_posture must have nq + nv entries")
+        foot_refs = f64(foot_refs, (B, 2, 2, 12))
+        cs = np.ascontiguousarray(np.broadcast_to(np.asarray(contact_states, dtype=np.int32), (B, nk)))
+        x = None if x is None else f64(x, (B, nqv))
+        x_ik = None if x_ik is None else f64(x_ik, (B, nqv))
+        x_prev, c_prev, x_out = np.zeros((B, nqv)), np.zeros((B, 9)), np.zeros((B, nqv))
+        tau, forces = np.zeros((B, nv - 6)), np.zeros((B, 6 * nk))
+        ik = np.zeros((B, 2 * nv + 42)) if want_ik else None
+        info = (QpInfo * B)()
+        IP = C.POINTER(C.c_int32)
+        rc = self.lib.mpc_qp_ikid_low_level_steps(self._h, C.byref(self.settings), plan._h, sim._h, nk, frames.ctypes.data_as(IP), int(base_frame),
+                                                  int(torso_frame), _dp(weights), _dp(gains), _dp(cone), _dp(l_box), _dp(u_box), _dp(x_posture),
+                                                  _dp(foot_refs), float(ref_dt), cs.ctypes.data_as(IP), _dp(x), _dp(x_ik), int(steps), float(dt),
+                                                  _dp(x_prev), _dp(c_prev), _dp(x_out), _dp(tau), _dp(forces), info, _dp(ik))
+        if rc != 0:
+            raise RuntimeError("mpc_qp_ikid_low_level_steps: " + self.lib.mpc_qp_last_error(self._h).decode())
+        out = (x_prev, c_prev, x_out, tau, forces, list(info))
+        return out + (ik,) if want_ik else out

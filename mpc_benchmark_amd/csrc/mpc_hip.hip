@@ -26,6 +26,7 @@
 #include "legs.h"
 #include "legs_tree.h"
 #include "pipeline_glue.h"
+#include "pipeline_ikid_glue.h"
 #include "qp_device_api.h"
 
 #define HIP_OK(expr)                                                                                  \
@@ -1373,6 +1374,89 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
     if (forces) HIP_OK(hipMemcpyAsync(forces, d_fnew, B * nf * sizeof(double), hipMemcpyDeviceToHost, st));
     if (info) HIP_OK(hipMemcpyAsync(info, q.info, B * sizeof(mpc_qp_info), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
+    sim->perfect_feedback = false;
+    return 0;
+  } catch (const std::exception& e) {
+    qp_set_error(qp, e.what());
+    return -1;
+  }
+}
+
+// include/mpc_qp_abi.h: the low-level loop of the centroidal pipeline (centroidal_talos.py:408-447) with nothing but the kernels between its stages:
+// the task errors once, then per step the centroidal state of the measurement and the feedback forces, the IK + ID QP and the simulator step.  Everything
+// is enqueued on the QP handle's stream (the plan and the simulator are idle: their streams are drained first); one synchronisation at the end.
+int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solver* plan, mpc_solver* sim, int32_t nk, const int32_t* frames,
+                                int32_t base_frame, int32_t torso_frame, const double* weights, const double* gains, const double* cone, const double* l_box,
+                                const double* u_box, const double* x_posture, const double* foot_refs, double ref_dt, const int32_t* contact_states,
+                                const double* x, const double* x_ik, int32_t steps, double dt, double* x_prev, double* c_prev, double* x_out, double* tau,
+                                double* forces, mpc_qp_info* info, double* ik_out) {
+  if (!qp) return -2;
+  try {
+    if (!S || !plan || !sim || !frames || !weights || !gains || !cone || !l_box || !u_box || !x_posture || !foot_refs || !contact_states)
+      throw std::runtime_error("qp_ikid_low_level_steps: null argument");
+    if (steps <= 0 || !(dt > 0.0) || !(ref_dt > 0.0)) throw std::runtime_error("qp_ikid_low_level_steps: steps, dt and ref_dt must be positive");
+    if (nk != 2) throw std::runtime_error("qp_ikid_low_level_steps: two contacts (nk = 2) expected");
+    qp_ikid_prepare(qp, nk, frames, base_frame, torso_frame, weights, gains, cone, l_box, u_box);
+    const QpIdBuffers q = qp_id_buffers(qp);
+    const Layout& P = plan->L;
+    const Layout& Z = sim->L;
+    const int nx = q.nq + q.nv, nu = q.nv - 6, nf = 6 * nk, nik = CG_IK_DOUBLES(q.nv);
+    if (plan->dims.device != q.device || sim->dims.device != q.device) throw std::runtime_error("qp_ikid_low_level_steps: the three handles must live on one device");
+    if (P.B != q.B || Z.B != q.B) throw std::runtime_error("qp_ikid_low_level_steps: the three handles must have the same batch size");
+    if (P.space != MPC_SPACE_VECTOR || P.nx != CG_NC || P.n != CG_NC || P.m != nf)
+      throw std::runtime_error("qp_ikid_low_level_steps: the plan must be a centroidal problem (vector space, nx = 9) with controls of 6 nk contact wrench components");
+    if (Z.space != MPC_SPACE_MULTIBODY || Z.nx != nx || Z.m != nu ||
+        sim->h_desc[(size_t)slot_of(sim, 0) * Z.max_stage_ints] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER)
+      throw std::runtime_error("qp_ikid_low_level_steps: the simulator handle must hold whole-body contact dynamics with nu = nv - 6 (the handle of mpc_simulate_torque)");
+    if (q.nj > CG_MAX_NJ) throw std::runtime_error("qp_ikid_low_level_steps: more moving joints than the glue kernels hold (64)");
+    if (plan->async_pending > 0) throw std::runtime_error("qp_ikid_low_level_steps: the plan has ticks in flight (mpc_wait first)");
+    HIP_OK(hipStreamSynchronize(plan->stream));
+    HIP_OK(hipStreamSynchronize(sim->stream));
+    if (!sim->d_simu) { sim->d_simu = sim->alloc<double>((size_t)Z.B * Z.m); sim->d_simwr = sim->alloc<double>((size_t)Z.B * 12); HIP_OK(hipStreamSynchronize(sim->stream)); }
+    const size_t B = q.B;
+    bool* kept = nullptr;
+    // x before the last step (kept for the next call) | its new_x | forces + df | x_posture | foot references
+    double* scr = qp_ikid_scratch(qp, B * nx + B * CG_NC + B * nf + nx + B * 48, &kept);
+    double *d_xprev = scr, *d_cprev = d_xprev + B * nx, *d_fnew = d_cprev + B * CG_NC, *d_xpost = d_fnew + B * nf, *d_refs = d_xpost + nx;
+    if (!x_ik && !*kept) throw std::runtime_error("qp_ikid_low_level_steps: x_ik is NULL and no earlier call kept a measurement");
+    hipStream_t st = q.stream;
+    if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
+    if (x_ik) HIP_OK(hipMemcpyAsync(d_xprev, x_ik, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_xpost, x_posture, nx * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_refs, foot_refs, B * 48 * sizeof(double), hipMemcpyHostToDevice, st));
+    IkidGlueArgs g = {};
+    g.mi = q.mi; g.md = q.md; g.nq = q.nq; g.nv = q.nv;
+    g.xs = plan->d_xs; g.us = plan->d_us; g.gains = plan->d_gains; g.knots = plan->d_knots;
+    g.N = P.N; g.m = P.m; g.gain_stride = P.gain_stride; g.oK = P.oK; g.knot_stride = P.knot_stride; g.oXD = P.oXD;
+    g.slot0 = plan->khead % P.N;
+    g.x_ik = d_xprev; g.x_post = d_xpost; g.refs = d_refs; g.ref_dt = ref_dt;
+    g.fr[0] = frames[0]; g.fr[1] = frames[1]; g.fr[2] = base_frame; g.fr[3] = torso_frame;
+    g.ik = q.ik;
+    g.x = sim->d_x0; g.xrob = q.xrob; g.f = q.f; g.c_prev = d_cprev;
+    g.sol = q.sol; g.nk = nk; g.qn = q.n; g.sim_u = sim->d_simu; g.f_new = d_fnew;
+    hipLaunchKernelGGL(k_ikid_task_errors, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+    HIP_OK(hipGetLastError());
+    if (ik_out) HIP_OK(hipMemcpyAsync(ik_out, q.ik, B * nik * sizeof(double), hipMemcpyDeviceToHost, st));
+    const SolverArgs za = sim->args();
+    for (int step = 0; step < steps; ++step) {
+      g.last = (step == steps - 1);
+      if (g.last) HIP_OK(hipMemcpyAsync(d_xprev, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(k_pipe_centroidal_feedback, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+      qp_ikid_enqueue(qp, S);
+      qp_launch_solve(qp, S);
+      hipLaunchKernelGGL(k_pipe_ikid_torque, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+      launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, nullptr, true, sim->d_simu, nullptr);
+      HIP_OK(hipGetLastError());
+    }
+    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (c_prev) HIP_OK(hipMemcpyAsync(c_prev, d_cprev, B * CG_NC * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (forces) HIP_OK(hipMemcpyAsync(forces, d_fnew, B * nf * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (info) HIP_OK(hipMemcpyAsync(info, q.info, B * sizeof(mpc_qp_info), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    *kept = true;
     sim->perfect_feedback = false;
     return 0;
   } catch (const std::exception& e) {

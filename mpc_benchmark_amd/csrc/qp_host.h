@@ -37,7 +37,8 @@ struct mpc_qp_solver {
   int id_nk = 0;
   bool id_const_uploaded = false;
   double *d_ik = nullptr, *d_gains = nullptr, *d_w = nullptr;  // mpc_qp_solve_ikid
-  int ikid_nk = 0;
+  int ikid_nk = 0, ikid_base = 0, ikid_torso = 0;
+  double* d_ikglue = nullptr; size_t ikglue_cap = 0; bool ikid_have_xprev = false;  // scratch of mpc_qp_ikid_low_level_steps (its x_prev stays for the next call)
   std::vector<double> ikid_const;
   std::vector<double> id_const;  // weights[2], cone[54], frames[nk] as last uploaded
   double* d_glue = nullptr; size_t glue_cap = 0;  // scratch of mpc_qp_low_level_steps (pipeline_glue.h)
@@ -246,6 +247,7 @@ QpIdBuffers qp_id_buffers(mpc_qp_solver* s) {
   QpIdBuffers o;
   o.stream = s->stream; o.xrob = s->d_xrob; o.acc = s->d_acc; o.f = s->d_f; o.cs = s->d_cs; o.sol = s->dx; o.info = s->dinfo;
   o.B = s->d.batch; o.n = s->d.n; o.nq = s->m_nq; o.nv = s->m_nv; o.nk = s->id_nk; o.device = s->d.device;
+  o.ik = s->d_ik; o.mi = s->d_mi; o.md = s->d_md; o.nj = s->m_nj;
   return o;
 }
 void qp_launch_solve(mpc_qp_solver* s, const mpc_qp_settings* S) { qp_launch(s, S); }
@@ -254,6 +256,80 @@ double* qp_scratch(mpc_qp_solver* s, size_t doubles) {
   return s->d_glue;
 }
 void qp_set_error(mpc_qp_solver* s, const char* what) { s->err = what; }
+double* qp_ikid_scratch(mpc_qp_solver* s, size_t doubles, bool** kept) {
+  if (s->ikglue_cap < doubles) { s->d_ikglue = s->alloc<double>(doubles); s->ikglue_cap = doubles; s->ikid_have_xprev = false; }
+  *kept = &s->ikid_have_xprev;
+  return s->d_ikglue;
+}
+
+// buffers and constants of the IK + ID QP (weights, gains, cone rows, frames, the torque box and u = 1e5: uploaded when they change)
+void qp_ikid_prepare(mpc_qp_solver* s, int32_t nk, const int32_t* frames, int32_t base_frame, int32_t torso_frame, const double* weights, const double* gains,
+                     const double* cone, const double* l_box, const double* u_box) {
+  HIP_OK(hipSetDevice(s->d.device));
+  if (!frames || !weights || !gains || !cone || !l_box || !u_box) throw std::runtime_error("qp_solve_ikid: null argument");
+  if (!s->d_mi) throw std::runtime_error("qp_solve_ikid: mpc_qp_set_model first");
+  const mpc_qp_dims& d = s->d;
+  const int nv = s->m_nv, nq = s->m_nq;
+  if (nk != 2 || d.n != 2 * nv - 6 + 6 * nk || d.neq != nv + 6 * nk || d.nin != 9 * nk || !d.box)
+    throw std::runtime_error("qp_solve_ikid: two contacts and the handle's dimensions n = 2 nv - 6 + 6 nk, neq = nv + 6 nk, nin = 9 nk, box = 1 expected");
+  for (int c = 0; c < nk + 2; ++c) {
+    const int fi = c < nk ? frames[c] : (c == nk ? base_frame : torso_frame);
+    if (fi < 0 || fi >= s->m_nframes) throw std::runtime_error("qp_solve_ikid: frame index out of range");
+  }
+  const size_t B = d.batch, n = d.n, nin = d.nin, ngain = (size_t)2 * nv * nv + 90, nik = QPA_IK_DOUBLES(nv);
+  if (!s->d_ik || s->ikid_nk != nk) {
+    if (!s->d_xrob || s->id_nk != nk) {
+      s->d_xrob = s->alloc<double>(B * (nq + nv)); s->d_acc = s->alloc<double>(B * nv); s->d_f = s->alloc<double>(B * 6 * nk);
+      s->d_cs = s->alloc<int32_t>(B * nk); s->d_frames = s->alloc<int32_t>(nk); s->d_cone = s->alloc<double>(108);
+      s->id_nk = nk;
+    }
+    s->d_ik = s->alloc<double>(B * nik); s->d_gains = s->alloc<double>(ngain); s->d_w = s->alloc<double>(8);
+    s->ikid_nk = nk; s->ikid_const.clear();
+    qp_lds_attr_max((const void*)k_qp_assemble<true>, (int)qp_assemble_lds_bytes(s->m_nj, nv, nq, nk, true));
+  }
+  s->id_const_uploaded = false;  // (H, g, u of a later mpc_qp_solve_id are uploaded again)
+  // constants: weights, gains, cone rows, frames, the torque box and u = 1e5 — uploaded when they change
+  std::vector<double> key;
+  key.reserve(5 + ngain + 54 + 2 * n + nk + 2);
+  key.insert(key.end(), weights, weights + 5); key.insert(key.end(), gains, gains + ngain); key.insert(key.end(), cone, cone + 108);
+  key.insert(key.end(), l_box, l_box + n); key.insert(key.end(), u_box, u_box + n);
+  for (int c = 0; c < nk; ++c) key.push_back(frames[c]);
+  key.push_back(base_frame); key.push_back(torso_frame);
+  if (key != s->ikid_const) {
+    std::vector<double> u(nin, 1e5);
+    HIP_OK(hipMemcpyAsync(s->d_w, weights, 5 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_OK(hipMemcpyAsync(s->d_gains, gains, ngain * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_OK(hipMemcpyAsync(s->d_cone, cone, 108 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_OK(hipMemcpyAsync(s->d_frames, frames, nk * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+    for (size_t bi = 0; bi < B; ++bi) {
+      HIP_OK(hipMemcpyAsync(s->du + bi * nin, u.data(), nin * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      HIP_OK(hipMemcpyAsync(s->dlb + bi * n, l_box, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      HIP_OK(hipMemcpyAsync(s->dub + bi * n, u_box, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    s->ikid_const = key;
+  }
+  s->ikid_base = base_frame; s->ikid_torso = torso_frame;
+}
+
+// assembly of the IK + ID QP from d_xrob / d_ik / d_f / d_cs (+ zeroed start unless warm_start), enqueued on the handle's stream
+void qp_ikid_enqueue(mpc_qp_solver* s, const mpc_qp_settings* S) {
+  const mpc_qp_dims& d = s->d;
+  const int nv = s->m_nv, nq = s->m_nq, nk = s->ikid_nk;
+  const size_t B = d.batch, n = d.n, neq = d.neq, nin = d.nin, m = nin + n;
+  QpAssembleArgs qa = {};
+  qa.mi = s->d_mi; qa.md = s->d_md; qa.x = s->d_xrob; qa.f = s->d_f; qa.cs = s->d_cs; qa.frames = s->d_frames; qa.cone = s->d_cone;
+  qa.nk = nk; qa.n = (int)n; qa.neq = (int)neq; qa.nin = (int)nin;
+  qa.A = s->dA; qa.b = s->db; qa.C = s->dC; qa.l = s->dl; qa.H = s->dH; qa.g = s->dg;
+  qa.base_frame = s->ikid_base; qa.torso_frame = s->ikid_torso; qa.w = s->d_w; qa.gains = s->d_gains; qa.ik = s->d_ik;
+  hipLaunchKernelGGL(k_qp_assemble<true>, dim3(d.batch), dim3(QPA_THREADS), qp_assemble_lds_bytes(s->m_nj, nv, nq, nk, true), s->stream, qa);
+  HIP_OK(hipGetLastError());
+  if (!S->warm_start) {
+    HIP_OK(hipMemsetAsync(s->dx, 0, B * n * sizeof(double), s->stream));
+    HIP_OK(hipMemsetAsync(s->dy, 0, B * neq * sizeof(double), s->stream));
+    HIP_OK(hipMemsetAsync(s->dz, 0, B * m * sizeof(double), s->stream));
+  }
+}
 
 extern "C" {
 
@@ -290,64 +366,15 @@ int mpc_qp_solve_ikid(mpc_qp_solver* s, const mpc_qp_settings* S, int32_t nk, co
   try {
     HIP_OK(hipSetDevice(s->d.device));
     if (!S || !frames || !weights || !gains || !cone || !l_box || !u_box || !xrob || !ik || !forces || !contact_states || !x || !info) throw std::runtime_error("qp_solve_ikid: null argument");
-    if (!s->d_mi) throw std::runtime_error("qp_solve_ikid: mpc_qp_set_model first");
+    qp_ikid_prepare(s, nk, frames, base_frame, torso_frame, weights, gains, cone, l_box, u_box);
     const mpc_qp_dims& d = s->d;
     const int nv = s->m_nv, nq = s->m_nq;
-    if (nk != 2 || d.n != 2 * nv - 6 + 6 * nk || d.neq != nv + 6 * nk || d.nin != 9 * nk || !d.box)
-      throw std::runtime_error("qp_solve_ikid: two contacts and the handle's dimensions n = 2 nv - 6 + 6 nk, neq = nv + 6 nk, nin = 9 nk, box = 1 expected");
-    for (int c = 0; c < nk + 2; ++c) {
-      const int fi = c < nk ? frames[c] : (c == nk ? base_frame : torso_frame);
-      if (fi < 0 || fi >= s->m_nframes) throw std::runtime_error("qp_solve_ikid: frame index out of range");
-    }
-    const size_t B = d.batch, n = d.n, neq = d.neq, nin = d.nin, m = nin + n, ngain = (size_t)2 * nv * nv + 90, nik = QPA_IK_DOUBLES(nv);
-    if (!s->d_ik || s->ikid_nk != nk) {
-      if (!s->d_xrob || s->id_nk != nk) {
-        s->d_xrob = s->alloc<double>(B * (nq + nv)); s->d_acc = s->alloc<double>(B * nv); s->d_f = s->alloc<double>(B * 6 * nk);
-        s->d_cs = s->alloc<int32_t>(B * nk); s->d_frames = s->alloc<int32_t>(nk); s->d_cone = s->alloc<double>(108);
-        s->id_nk = nk;
-      }
-      s->d_ik = s->alloc<double>(B * nik); s->d_gains = s->alloc<double>(ngain); s->d_w = s->alloc<double>(8);
-      s->ikid_nk = nk; s->ikid_const.clear();
-      qp_lds_attr_max((const void*)k_qp_assemble<true>, (int)qp_assemble_lds_bytes(s->m_nj, nv, nq, nk, true));
-    }
-    s->id_const_uploaded = false;  // (H, g, u of a later mpc_qp_solve_id are uploaded again)
-    // constants: weights, gains, cone rows, frames, the torque box and u = 1e5 — uploaded when they change
-    std::vector<double> key;
-    key.reserve(5 + ngain + 54 + 2 * n + nk + 2);
-    key.insert(key.end(), weights, weights + 5); key.insert(key.end(), gains, gains + ngain); key.insert(key.end(), cone, cone + 108);
-    key.insert(key.end(), l_box, l_box + n); key.insert(key.end(), u_box, u_box + n);
-    for (int c = 0; c < nk; ++c) key.push_back(frames[c]);
-    key.push_back(base_frame); key.push_back(torso_frame);
-    if (key != s->ikid_const) {
-      std::vector<double> u(nin, 1e5);
-      HIP_OK(hipMemcpyAsync(s->d_w, weights, 5 * sizeof(double), hipMemcpyHostToDevice, s->stream));
-      HIP_OK(hipMemcpyAsync(s->d_gains, gains, ngain * sizeof(double), hipMemcpyHostToDevice, s->stream));
-      HIP_OK(hipMemcpyAsync(s->d_cone, cone, 108 * sizeof(double), hipMemcpyHostToDevice, s->stream));
-      HIP_OK(hipMemcpyAsync(s->d_frames, frames, nk * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
-      for (size_t bi = 0; bi < B; ++bi) {
-        HIP_OK(hipMemcpyAsync(s->du + bi * nin, u.data(), nin * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        HIP_OK(hipMemcpyAsync(s->dlb + bi * n, l_box, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        HIP_OK(hipMemcpyAsync(s->dub + bi * n, u_box, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
-      }
-      HIP_OK(hipStreamSynchronize(s->stream));
-      s->ikid_const = key;
-    }
+    const size_t B = d.batch, n = d.n, neq = d.neq, nin = d.nin, nik = QPA_IK_DOUBLES(nv);
     HIP_OK(hipMemcpyAsync(s->d_xrob, xrob, B * (nq + nv) * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_OK(hipMemcpyAsync(s->d_ik, ik, B * nik * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_OK(hipMemcpyAsync(s->d_f, forces, B * 6 * nk * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_OK(hipMemcpyAsync(s->d_cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
-    QpAssembleArgs qa = {};
-    qa.mi = s->d_mi; qa.md = s->d_md; qa.x = s->d_xrob; qa.f = s->d_f; qa.cs = s->d_cs; qa.frames = s->d_frames; qa.cone = s->d_cone;
-    qa.nk = nk; qa.n = (int)n; qa.neq = (int)neq; qa.nin = (int)nin;
-    qa.A = s->dA; qa.b = s->db; qa.C = s->dC; qa.l = s->dl; qa.H = s->dH; qa.g = s->dg;
-    qa.base_frame = base_frame; qa.torso_frame = torso_frame; qa.w = s->d_w; qa.gains = s->d_gains; qa.ik = s->d_ik;
-    hipLaunchKernelGGL(k_qp_assemble<true>, dim3(d.batch), dim3(QPA_THREADS), qp_assemble_lds_bytes(s->m_nj, nv, nq, nk, true), s->stream, qa);
-    HIP_OK(hipGetLastError());
-    if (!S->warm_start) {
-      HIP_OK(hipMemsetAsync(s->dx, 0, B * n * sizeof(double), s->stream));
-      HIP_OK(hipMemsetAsync(s->dy, 0, B * neq * sizeof(double), s->stream));
-      HIP_OK(hipMemsetAsync(s->dz, 0, B * m * sizeof(double), s->stream));
-    }
+    qp_ikid_enqueue(s, S);
     if (H_out) HIP_OK(hipMemcpyAsync(H_out, s->dH, B * n * n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     if (g_out) HIP_OK(hipMemcpyAsync(g_out, s->dg, B * n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     if (A_out) HIP_OK(hipMemcpyAsync(A_out, s->dA, B * neq * n * sizeof(double), hipMemcpyDeviceToHost, s->stream));

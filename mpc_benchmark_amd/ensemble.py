@@ -146,10 +146,20 @@ class EnsembleMPC:
         trajectory has diverged (the library reports a failed factorisation) does not abort a long-running ensemble — the
         ensemble is re-solved from its initial states (counted in ``self.rescues``; the time of the re-solve stays inside
         whatever region the caller is timing)."""
+        self.plan_tick()
+        return self.solve_tick(rescue=rescue)
+
+    def plan_tick(self):
+        """First half of ``step``: what happens to the problem before the stage of this tick is rotated in — the closed-loop measurement and the
+        references of this tick written into every stage of the horizon (centroidal_talos.py:357-384).  A control loop that runs between the
+        references and the solve (pipeline.CentroidalPipeline) calls ``plan_tick``, its loop, then ``solve_tick``."""
         if self.closed_loop:
             self.native.simulate(*self.closed_loop)  # apply us[0] + feedback for one MPC period, measure
         if self._walk is not None:
             self._walk_references()
+
+    def solve_tick(self, rescue=False):
+        """Second half of ``step``: ``replaceStageCircular``, the terminal targets, ``setup`` and the solve (``rescue`` as in ``step``)."""
         desc, params = self._table_for_tick(self.tick % self.pd.t_mpc)
         self.native.cycle(desc, params)
         if self._walk is not None:
@@ -426,6 +436,7 @@ class EnsembleMPC:
         takeoff_RF, takeoff_LF, land_RF, land_LF = refgen.update_timings(land_LFs, land_RFs, takeoff_LFs, takeoff_RFs)
         self._walk_forward_rule(w["traj"], takeoff_RF, takeoff_LF, land_RF, land_LF)
         LF_refs, RF_refs = w["traj"].updateTrajectory(takeoff_RF, takeoff_LF, land_RF, land_LF, LF_pose, RF_pose)
+        w["refs"] = (LF_refs[:2], RF_refs[:2])  # the two samples of this tick the low-level task errors use (centroidal_talos.py:408)
         batch = []
         if w["kind"] == "contact_poses":
             w["feet"] = (LF_refs[1], RF_refs[1])

@@ -1,4 +1,7 @@
-"""The kinodynamic control pipeline of kinodynamic_talos.py:361-497 for an ensemble of robots, every stage on the solver library:
+"""The control pipelines of the kinodynamic and centroidal scripts for an ensemble of robots (``KinodynamicPipeline`` below;
+``CentroidalPipeline``, centroidal_talos.py:353-468, at the end of the file).
+
+The kinodynamic control pipeline of kinodynamic_talos.py:361-497, every stage on the solver library:
 
     MPC tick (kinodynamic OCP, one ProxDDP iteration)                                   kinodynamic_talos.py:482-490
       -> 10 low-level steps of 1 ms, each:
@@ -34,6 +37,44 @@ def _sim_options():
     return o
 
 
+def build_torque_simulator(lib, robot, batch, sim_dt, device):
+    """The simulator stand-in of both pipelines: one handle, horizon 1, whole-body contact dynamics of the three contact patterns (rigid contacts at
+    the robot's initial foot placements).  -> (NativeSolver, {(left, right): lowered stage 0})."""
+    m = robot.model
+    nu = m.nv - 6
+    space = _manifolds.MultibodyPhaseSpace(m)
+    ctx = core.LoweringContext()
+    cms = []
+    for name, fid, jid, oMf in zip(common.FOOT_FRAMES, robot.foot_frame_ids, robot.foot_joint_ids, robot.foot_placements):
+        cm = pin.RigidConstraintModel(pin.ContactType.CONTACT_6D, m, jid, m.frames[fid].placement, 0, oMf, pin.LOCAL)
+        cm.corrector.Kp[:] = (0, 0, 10, 0, 0, 0)      # fulldynamic_talos.py:93-94
+        cm.corrector.Kd[:] = (50, 50, 50, 50, 50, 50)
+        cm.name = name
+        cms.append(cm)
+    act, prox = np.eye(m.nv, nu, -6), pin.ProximalSettings(1e-9, 1e-10, 1)
+    tables = {}
+    for mask in ((True, True), (True, False), (False, True)):
+        ode = _dyn.MultibodyConstraintFwdDynamics(space, act, [c for c, on in zip(cms, mask) if on], prox)
+        cost = core.CostStack(space, nu)
+        cost.addCost(core.QuadraticControlCost(space, np.zeros(nu), np.eye(nu)))
+        st = core.StageModel(cost, _dyn.IntegratorSemiImplEuler(ode, sim_dt))
+        tables[mask] = core.lower_stage(ctx, st.cost, st.dynamics, st.constraints)
+    tcost = core.CostStack(space, nu)
+    tcost.addCost(core.QuadraticStateCost(space, nu, space.neutral(), np.eye(space.ndx)))
+    term = core.lower_stage(ctx, tcost, None, core._ConstraintStack())
+    d = K.MpcDims()
+    d.horizon, d.batch, d.space = 1, batch, K.SPACE_MULTIBODY
+    d.nx, d.ndx, d.nu, d.nc_max = space.nx, space.ndx, nu, 1
+    d.max_stage_ints = 8 + 8 * 24
+    d.max_stage_doubles = max(t[1].size for t in tables.values()) + term[1].size + 1024
+    d.device = device
+    sim = K.NativeSolver(lib, d)
+    sim.set_options(_sim_options())
+    sim.set_model(*ctx.model_tables())
+    sim.set_stage(1, *term)
+    return sim, tables
+
+
 class KinodynamicPipeline:
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
@@ -60,38 +101,7 @@ class KinodynamicPipeline:
 
     # -- simulator stand-in: one handle, horizon 1, whole-body contact dynamics of the three contact patterns ----------------------
     def _build_simulator(self):
-        m, rb = self.model, self.pd.robot
-        nu = m.nv - 6
-        space = _manifolds.MultibodyPhaseSpace(m)
-        ctx = core.LoweringContext()
-        cms = []
-        for name, fid, jid, oMf in zip(common.FOOT_FRAMES, rb.foot_frame_ids, rb.foot_joint_ids, rb.foot_placements):
-            cm = pin.RigidConstraintModel(pin.ContactType.CONTACT_6D, m, jid, m.frames[fid].placement, 0, oMf, pin.LOCAL)
-            cm.corrector.Kp[:] = (0, 0, 10, 0, 0, 0)      # fulldynamic_talos.py:93-94
-            cm.corrector.Kd[:] = (50, 50, 50, 50, 50, 50)
-            cm.name = name
-            cms.append(cm)
-        act, prox = np.eye(m.nv, nu, -6), pin.ProximalSettings(1e-9, 1e-10, 1)
-        self._sim_tables = {}
-        for mask in ((True, True), (True, False), (False, True)):
-            ode = _dyn.MultibodyConstraintFwdDynamics(space, act, [c for c, on in zip(cms, mask) if on], prox)
-            cost = core.CostStack(space, nu)
-            cost.addCost(core.QuadraticControlCost(space, np.zeros(nu), np.eye(nu)))
-            st = core.StageModel(cost, _dyn.IntegratorSemiImplEuler(ode, self.sim_dt))
-            self._sim_tables[mask] = core.lower_stage(ctx, st.cost, st.dynamics, st.constraints)
-        tcost = core.CostStack(space, nu)
-        tcost.addCost(core.QuadraticStateCost(space, nu, space.neutral(), np.eye(space.ndx)))
-        term = core.lower_stage(ctx, tcost, None, core._ConstraintStack())
-        d = K.MpcDims()
-        d.horizon, d.batch, d.space = 1, self.batch, K.SPACE_MULTIBODY
-        d.nx, d.ndx, d.nu, d.nc_max = space.nx, space.ndx, nu, 1
-        d.max_stage_ints = 8 + 8 * 24
-        d.max_stage_doubles = max(t[1].size for t in self._sim_tables.values()) + term[1].size + 1024
-        d.device = self.mpc.dims.device
-        self.sim = K.NativeSolver(self.lib, d)
-        self.sim.set_options(_sim_options())
-        self.sim.set_model(*ctx.model_tables())
-        self.sim.set_stage(1, *term)
+        self.sim, self._sim_tables = build_torque_simulator(self.lib, self.pd.robot, self.batch, self.sim_dt, self.mpc.dims.device)
         self._sim_mask = None
 
     def _set_sim_contacts(self, mask):
@@ -166,5 +176,178 @@ class KinodynamicPipeline:
         e.native.set_x0(self.x_prev)
         st = e.step()
         self.x_prev = x_last
+        self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
+        return st
+
+
+# -- the centroidal pipeline ------------------------------------------------------------------------------------------------------------
+def centroidal_state(model, x):
+    """new_x = [com(q) ; hg.linear ; hg.angular] of whole-body states x [B][nq+nv] (centroidal_talos.py:420-424) -> [B][9]."""
+    x = np.atleast_2d(np.asarray(x, dtype=float))
+    data = model.createData()
+    out = np.zeros((x.shape[0], 9))
+    for b, xb in enumerate(x):
+        out[b, :3] = pin.centerOfMass(model, data, xb[:model.nq])
+        hg = pin.computeCentroidalMomentum(model, data, xb[:model.nq], xb[model.nq:])
+        out[b, 3:6], out[b, 6:] = hg.linear, hg.angular
+    return out
+
+
+def posture_gains(nv):
+    """Kp, Kd of the posture task (centroidal_talos.py:309-319: g_q * 10 and 2 sqrt(g_q * 10)).  The script's diagonal is written for the 28 dofs of
+    the reduced model; for another model the base keeps the script's entries and every joint gets 1."""
+    if nv == 28:
+        g = np.array([0, 0, 0, 10, 10, 10] + [0.1] * 12 + [1, 1] + [10] * 8, dtype=float)
+    else:
+        g = np.array([0, 0, 0, 10, 10, 10] + [1.0] * (nv - 6), dtype=float)
+    G = np.diag(g * 10)
+    return G, 2 * np.sqrt(G)
+
+
+class CentroidalPipeline:
+    """The centroidal control pipeline of centroidal_talos.py:353-468 for an ensemble of robots, every stage on the solver library:
+
+        MPC tick (centroidal OCP, x = [com ; h_lin ; h_ang], one ProxDDP iteration)
+        -> the task errors of the IK + ID QP, once per period, at the stale measurement                        centroidal_talos.py:408-409
+        -> 10 low-level steps of 1 ms, each:
+             new_x = [com ; hg] of the measured whole-body state                                              :420-424
+             forces = us[0] - K_0 (xs[0] - new_x)                                                             :434
+             IK + ID QP (IKIDSolver_f6) assembled and solved on the device, no clamp (the QP's torque box)    :435-446
+             one simulator step under the QP's torque                                   (mpc_simulate_torque) :447 (device.execute)
+        -> x0 = new_x of the measurement before the last execute, then the solve                              :454-462
+
+    The order of one period is the script's, which is not the kinodynamic one (``tick``):
+      1. the foot references of tick t are planned and written into the contact maps (``EnsembleMPC.plan_tick``, :357-384); ``contact_state``
+         is read from ``problem.stages[0]`` BEFORE ``replaceStageCircular(stages_full[t])`` (:386);
+      2. the task errors are computed at the stale measurement — the one taken before the last execute of the previous period (``x_prev``),
+         with the reference samples LF_refs[0:2], RF_refs[0:2] of this tick and dH = xdot[3:9] of the current plan's knot 0 (:408-409);
+      3. the ten steps run on the current (previous tick's) plan;
+      4. only then is x0 = new_x of this period's last measurement set (``c_prev``), the stage of tick t rotated in and the solve run
+         (``EnsembleMPC.solve_tick``, :454-462).
+    The centroidal OCP has no whole-body model: its references follow the previous references (``EnsembleMPC.enable_walk``).  The measured robots
+    start from ``robot.x0``, perturbed as the kinodynamic pipeline's ensemble (``ensemble_initial_states``); the MPC starts from their centroidal
+    states.  The simulator is the kinodynamic pipeline's stand-in (``build_torque_simulator``).  ``library``: the HIP library by default; the device
+    loop (``low_level_loop``) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
+
+    WEIGHTS = (500.0, 50000.0, 10.0, 1000.0, 100.0)   # posture, foot pose, centroidal, base / torso rotation, force (centroidal_talos.py:325)
+    G_FOOT, G_ROT = 400.0, 10.0                        # g_p, g_b (:305-307)
+
+    def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
+                 sigma_v=0.05, perturb_dofs=None, **ens_kw):
+        """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps) or None
+        (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv]."""
+        from .ensemble import ensemble_initial_states
+        self.pd, self.batch = problem_def, int(batch)
+        self.lib = library if library is not None else K.load_hip_library()
+        rb = problem_def.robot
+        m = self.model = rb.model
+        self.nq, self.nv = m.nq, m.nv
+        self.substeps, self.sim_dt, self.ref_dt = int(substeps), float(sim_dt), float(problem_def.dt)
+        if x0 is not None:
+            self.x = np.array(np.broadcast_to(np.asarray(x0, dtype=float), (self.batch, m.nq + m.nv)))
+        elif perturb:
+            self.x = ensemble_initial_states(rb.x0, _manifolds.MultibodyPhaseSpace(m), self.batch, seed, sigma_q, sigma_v, perturb_dofs)
+        else:
+            self.x = np.tile(rb.x0, (self.batch, 1))
+        self.x_posture = np.array(rb.x0, dtype=float)     # x0_multibody: the posture reference of compute_ID_references
+        self.c_prev = centroidal_state(m, self.x)          # the next solve's initial condition
+        self.x_prev = self.x.copy()                        # the stale measurement the task errors are taken at
+        self.mpc = EnsembleMPC(problem_def, batch=batch, library=self.lib, x0=self.c_prev, **ens_kw)
+        self._walk_args = walk
+        Kq = posture_gains(m.nv)
+        gains = [Kq, (np.eye(6) * self.G_FOOT, np.eye(6) * 2 * np.sqrt(self.G_FOOT)), None,
+                 (np.eye(3) * self.G_ROT, np.eye(3) * 2 * np.sqrt(self.G_ROT))]
+        self.qp = qp_utils.IKIDSolver_f6(m, list(self.WEIGHTS), gains, 2, common.FRICTION_MU, common.FOOT_HALF_LENGTH, common.FOOT_HALF_WIDTH,
+                                         list(rb.foot_frame_ids), m.getFrameId("base_link"), m.getFrameId("torso_2_link"), 6, library=self.lib,
+                                         batch=self.batch)
+        self.qp.enable_device_assembly()
+        self.sim, self._sim_tables = build_torque_simulator(self.lib, rb, self.batch, self.sim_dt, self.mpc.dims.device)
+        self._sim_mask = None
+        self._set_sim_contacts((True, True))   # (the schedule starts in double support)
+        self.torques = np.zeros((self.batch, m.nv - 6))
+        self.forces = np.zeros((self.batch, 12))
+        self.ik = None                 # the task errors of the last period
+        self._plan_stale = True
+        self._xik_on_device = False    # the QP handle keeps x_prev of its last device loop
+
+    def _set_sim_contacts(self, mask):
+        mask = (bool(mask[0]), bool(mask[1]))
+        if mask != self._sim_mask:
+            self.sim.set_stage(0, *self._sim_tables[mask])
+            self._sim_mask = mask
+
+    def cold_solve(self, max_iters=100):
+        st = self.mpc.cold_solve(max_iters=max_iters)
+        if self._walk_args is not None:
+            self.mpc.enable_walk(**self._walk_args)
+        self._fetch()
+        return st
+
+    def _fetch(self):
+        self._plan_stale = False
+        r = self.mpc.native.get_results(gains=False)
+        self.xs0, self.us0 = r["xs"][:, 0].copy(), r["us"][:, 0].copy()
+        self.K0 = self.mpc.native.get_gain(0)[0]
+        self.dH = self.mpc.native.get_stage_data(0)[0][:, 3:9].copy()
+
+    def contact_state(self):
+        """[left, right] of ``problem.stages[0]`` as the script reads it (centroidal_talos.py:386): after the references of tick t are written and
+        BEFORE ``replaceStageCircular(stages_full[t])`` — the stage that was appended at tick t - N (the initial double support before that), the
+        stage of knot 0 of the plan the feedback terms come from."""
+        N, t = self.mpc.problem.num_steps, self.mpc.tick
+        return self.pd.contact_phases[max(0, t - N) % self.pd.t_mpc]
+
+    def foot_refs(self):
+        """[B][2 feet][2 samples][12]: LF_refs[0:2], RF_refs[0:2] of this tick (R row-major, p); without a walk the initial footholds, twice."""
+        w = self.mpc._walk
+        pair = w["refs"] if (w is not None and "refs" in w) else tuple([M, M] for M in self.pd.robot.foot_placements)
+        flat = lambda M: np.concatenate([np.asarray(M.rotation, dtype=float).reshape(-1), np.asarray(M.translation, dtype=float)])
+        one = np.array([[flat(M) for M in pair[f][:2]] for f in range(2)])
+        return np.ascontiguousarray(np.broadcast_to(one, (self.batch, 2, 2, 12)))
+
+    def low_level_step(self, cs, ik):
+        """One 1 kHz step of centroidal_talos.py:420-447 for every robot, the glue between the library calls on the host.  -> new_x of the
+        measurement the step started from."""
+        if self._plan_stale:
+            self._fetch()
+        x = self.x
+        new_x = centroidal_state(self.model, x)
+        forces = self.us0 - np.einsum("bij,bj->bi", self.K0, self.xs0 - new_x)   # us[0] - K_0 difference(new_x, xs[0])
+        _, f_new, tau = self.qp.solve_batch_device_ik(x, ik, forces, np.tile(np.asarray(cs, dtype=np.int32), (self.batch, 1)))
+        self.x = self.sim.simulate_torque(x, tau, 1, self.sim_dt)
+        self.torques, self.forces = tau, f_new
+        return new_x
+
+    def low_level_loop(self, cs, refs):
+        """The ``substeps`` low-level periods of one MPC period inside the library (mpc_qp_ikid_low_level_steps: task errors, centroidal state,
+        feedback forces, QP and simulator step chained on the device, one synchronisation)."""
+        cs_all = np.tile(np.asarray(cs, dtype=np.int32), (self.batch, 1))
+        x_ik = None if self._xik_on_device else self.x_prev
+        self.x_prev, self.c_prev, self.x, self.torques, self.forces, self.ik = self.qp.low_level_steps(
+            self.mpc.native, self.sim, self.x_posture, refs, self.ref_dt, cs_all, self.substeps, self.sim_dt, x=self.x, x_ik=x_ik, want_ik=True)
+        self._xik_on_device = True
+
+    def tick(self, host_glue=False):
+        """One MPC period in the script's order (class docstring).  ``host_glue``: the task errors from ``references.compute_ID_references`` and
+        the low-level periods one at a time with the small vectors travelling through the host (``low_level_step``: the readable form, what the
+        library call is tested against)."""
+        e = self.mpc
+        cs = self.contact_state()
+        e.plan_tick()
+        refs = self.foot_refs()
+        self._set_sim_contacts(cs)
+        if host_glue:
+            if self._plan_stale:
+                self._fetch()
+            self.ik = self.qp.task_errors(self.x_prev, self.x_posture, refs, self.ref_dt, self.dH)
+            for _ in range(self.substeps):
+                x_last = self.x.copy()   # (the script's x_measured is read BEFORE the last execute of the period)
+                c_last = self.low_level_step(cs, self.ik)
+            self.x_prev, self.c_prev = x_last, c_last
+            self._xik_on_device = False
+        else:
+            self.low_level_loop(cs, refs)
+        e.native.set_x0(self.c_prev)
+        st = e.solve_tick()
         self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
         return st

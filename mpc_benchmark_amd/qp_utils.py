@@ -248,3 +248,45 @@ class IKIDSolver_f6:
         forces = np.broadcast_to(np.asarray(forces, dtype=float), (B, fs * nk))
         res = (sol[:, :nv].copy(), forces + sol[:, nv:nv + fs * nk], sol[:, nv + fs * nk:].copy())
         return res + (out[5],) if return_matrices else res
+
+    # ---- the centroidal pipeline's low-level loop (centroidal_talos.py:408-447) ----
+    def task_errors(self, x, x_posture, foot_refs, ref_dt, dH):
+        """The ``ik`` block of ``solve_ikid`` for B robots on the host: ``references.compute_ID_references`` at each state of ``x`` [B][nq+nv] with
+        the posture reference ``x_posture`` and the reference samples ``foot_refs`` [B][2 feet][2 samples][12] (R row-major, p), then ``dH`` [B][6].
+        -> [B][2 nv + 42]."""
+        from . import references
+        from .aligator import manifolds
+        from .robot import minipin as pin
+        m = self.model
+        space = manifolds.MultibodyPhaseSpace(m)
+        x, foot_refs = np.asarray(x, dtype=float), np.asarray(foot_refs, dtype=float).reshape(-1, 2, 2, 12)
+        dH = np.broadcast_to(np.asarray(dH, dtype=float), (x.shape[0], 6))
+        data = m.createData()
+        out = []
+        for xb, rb, hb in zip(x, foot_refs, dH):
+            pin.forwardKinematics(m, data, xb[:m.nq], xb[m.nq:])
+            pin.updateFramePlacements(m, data)
+            se3 = [[pin.SE3(rb[f, k, :9].reshape(3, 3), rb[f, k, 9:]) for k in range(2)] for f in range(2)]
+            e = references.compute_ID_references(space, m, data, self.contact_ids[0], self.contact_ids[1], self.base_id, self.torso_id, x_posture, xb,
+                                                 se3[0], se3[1], ref_dt)
+            out.append(np.concatenate([np.asarray(a, dtype=float).reshape(-1) for a in e] + [hb]))
+        return np.array(out)
+
+    def solve_batch_device_ik(self, x, ik, forces, cs):
+        """``solve_batch_device`` with the task errors as one block ``ik`` [B][2 nv + 42] (the layout of ``task_errors``)."""
+        nv = self.model.nv
+        ik = np.asarray(ik, dtype=float)
+        cuts = np.cumsum([nv, nv, 6, 6, 6, 6, 3, 3, 3, 3])
+        parts = np.split(ik, cuts, axis=1)
+        return self.solve_batch_device(x, *parts[:10], forces, parts[10], cs)
+
+    def low_level_steps(self, plan, sim, x_posture, foot_refs, ref_dt, cs, steps, dt, x=None, x_ik=None, want_ik=False):
+        """``steps`` periods of the centroidal script's low-level loop (centroidal_talos.py:408-447) inside the library (mpc_qp_ikid_low_level_steps,
+        HIP only): ``plan`` / ``sim`` the NativeSolver handles of the centroidal MPC problem and of the simulator stand-in.  The task errors are taken
+        at ``x_ik`` (None: the measurement the last call kept on the device).  -> x_prev, c_prev, x, torque, new_forces (, ik)."""
+        if not hasattr(self, "_frame_idx"):
+            self.enable_device_assembly()
+        out = self.qp.ikid_low_level_steps(plan, sim, self._frame_idx, self._base_idx, self._torso_idx, self.weights, self._gains, self.Cmin, self.l_box,
+                                           self.u_box, x_posture, foot_refs, ref_dt, cs, steps, dt, x=x, x_ik=x_ik, cone_l=self.Cl, want_ik=want_ik)
+        self.last_info = out[5]
+        return out[:5] + out[6:]
