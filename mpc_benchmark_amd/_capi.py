@@ -125,6 +125,14 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# include/mpc_sim_ext.h: exported by the HIP library alone, bound when present (``NativeSolver.set_push`` / ``record`` / ``read_record``)
+_SIM_EXT_SIGNATURES = {
+    "mpc_sim_set_push": (C.c_int, [C.c_void_p, _DP, C.c_int32]),
+    "mpc_sim_record": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mpc_sim_record_read": (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32)]),
+    "mpc_sim_record_width": (C.c_int32, [C.c_void_p]),
+}
+
 
 def bind_library(path):
     """dlopen ``path`` and attach the argument/return types of every entry point of mpc_abi.h."""
@@ -133,6 +141,11 @@ def bind_library(path):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in _SIM_EXT_SIGNATURES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     if lib.mpc_abi_version() != ABI_VERSION:
         raise RuntimeError("%s: ABI version %d, expected %d" % (path, lib.mpc_abi_version(), ABI_VERSION))
     return lib
@@ -263,6 +276,50 @@ class NativeSolver:
         self._check(self.lib.mpc_simulate_torque(self._h, _dp(xa), _dp(ta), int(substeps), float(dt), _dp(wr)), "mpc_simulate_torque")
         x0 = self.get_x0()
         return (x0, wr) if wrenches else x0
+
+    # -- include/mpc_sim_ext.h (HIP library only): push and per-step record of the torque-driven simulator ----------------------------
+    def _sim_ext(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the push and the record of torque-driven simulator steps are HIP only "
+                               "(libmpc_hip.so, include/mpc_sim_ext.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def set_push(self, f_ext):
+        """Arm a push for every torque-driven simulator step of this handle until re-armed (mpc_sim_set_push); None disarms.  f_ext (B, 3) or (3,):
+        a world-frame force at the base origin (``simulate_push``'s convention); (B, 6) or (6,): (force, fixed world point it acts at)."""
+        fn = self._sim_ext("mpc_sim_set_push")
+        if f_ext is None:
+            self._check(fn(self._h, None, 3), "mpc_sim_set_push")
+            return
+        f = _f64(f_ext)
+        w = f.shape[-1] if f.ndim in (1, 2) else 0
+        if w not in (3, 6) or (f.ndim == 2 and f.shape[0] != self.dims.batch):
+            raise ValueError("set_push: f_ext of shape (B, 3), (3,), (B, 6) or (6,) expected (B = %d), got %s" % (self.dims.batch, f.shape))
+        f = np.ascontiguousarray(np.broadcast_to(f.reshape(-1, w), (self.dims.batch, w)))
+        self._check(fn(self._h, _dp(f), w), "mpc_sim_set_push")
+
+    def record(self, cap):
+        """Record every torque-driven simulator step of this handle into a device ring of ``cap`` steps (mpc_sim_record); 0: off."""
+        self._check(self._sim_ext("mpc_sim_record")(self._h, int(cap)), "mpc_sim_record")
+
+    def read_record(self):
+        """The recorded steps, oldest first, and an empty ring (mpc_sim_record_read) -> dict of arrays shaped (steps, B, ...): x, tau,
+        wrenches (2, 6) LOCAL, com (3), momentum (6: linear, angular about the com), sole_R (2, 3, 3), sole_p (2, 3), push (6: force, point)."""
+        fn = self._sim_ext("mpc_sim_record_read")
+        w = self._sim_ext("mpc_sim_record_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_record_width")
+        n = C.c_int32(0)
+        self._check(fn(self._h, None, C.byref(n)), "mpc_sim_record_read")
+        d = self.dims
+        out = np.zeros((n.value, d.batch, w))
+        self._check(fn(self._h, _dp(out), C.byref(n)), "mpc_sim_record_read")
+        out = out[:n.value]
+        nx, nu, S, B = d.nx, d.nu, out.shape[0], d.batch
+        o = nx + nu
+        soles = out[:, :, o + 21:o + 45].reshape(S, B, 2, 12)
+        return {"x": out[:, :, :nx], "tau": out[:, :, nx:o], "wrenches": out[:, :, o:o + 12].reshape(S, B, 2, 6), "com": out[:, :, o + 12:o + 15],
+                "momentum": out[:, :, o + 15:o + 21], "sole_R": soles[..., :9].reshape(S, B, 2, 3, 3), "sole_p": soles[..., 9:], "push": out[:, :, o + 45:o + 51]}
 
     def get_x0(self):
         x0 = np.zeros((self.dims.batch, self.dims.nx))

@@ -149,9 +149,18 @@ class BulletRobot:
         if tau.size != m.nv - 6:
             raise ValueError("expected %d joint torques, got %d" % (m.nv - 6, tau.size))
         self._upload_mask()
-        if self._pending_force is not None:  # (apply_force: the push of fulldynamic_talos.py:524-526 — generalized force on the base)
-            raise NotImplementedError("apply_force: use mpc_simulate_push through EnsembleMPC for disturbance runs")
-        x, wr = self._native.simulate_torque(self.x, tau, 1, self.dt, wrenches=True)
+        push = self._pending_force
+        if push is not None:  # (apply_force: the push of the scripts, e.g. kinodynamic_talos.py:459-461 — a world force at a world point, this step only)
+            if not hasattr(self._native.lib, "mpc_sim_set_push"):
+                raise NotImplementedError("apply_force needs the HIP library (libmpc_hip.so, mpc_sim_set_push of include/mpc_sim_ext.h): %s does not "
+                                          "export it; mpc_simulate_push through EnsembleMPC pushes the full-dynamics loop on either library" % self._native.backend)
+            self._native.set_push(np.concatenate([push[0], push[1]]))
+        try:
+            x, wr = self._native.simulate_torque(self.x, tau, 1, self.dt, wrenches=True)
+        finally:
+            if push is not None:
+                self._pending_force = None
+                self._native.set_push(None)
         self.x = x[0]
         self.steps += 1
         if self.trace_from is not None and self.steps >= self.trace_from:
@@ -208,7 +217,13 @@ class BulletRobot:
         self.x[m.nq:] = 0.0
 
     def apply_force(self, force, position):
-        self._pending_force = (np.asarray(force, dtype=float), np.asarray(position, dtype=float))
+        """PyBullet's applyExternalForce(robot, -1, force, position, WORLD_FRAME): a world-frame force on the base link at a world point, acting
+        during the NEXT ``execute`` only (the scripts call it after every execute of their push window).  HIP library only (mpc_sim_set_push)."""
+        f = np.asarray(force, dtype=float).reshape(-1)
+        p = np.asarray(position, dtype=float).reshape(-1)
+        if f.size != 3 or p.size != 3:
+            raise ValueError("apply_force: a 3-vector force and a 3-vector world position expected")
+        self._pending_force = (f, p)
 
     # -- GUI calls of the scripts: recorded, nothing to draw ------------------------------------------------------------------------
     def changeCamera(self, cameraDistance, cameraYaw, cameraPitch, cameraTargetPos):

@@ -798,7 +798,14 @@ sim_u_set:
           s = -bias[l] + (l >= nv - nu ? u[l - (nv - nu)] : 0.0);
           // disturbance of the simulation stand-in: a world-frame force f at the base origin acts on the linear base dofs only
           // (J_l . [f ; p x f] = (R e_l) . f ; the angular dofs cancel)
-          if (TRIAL == 2 && mb.f_ext && l < 3) s += J[0 * nv + l] * mb.f_ext[3 * b] + J[1 * nv + l] * mb.f_ext[3 * b + 1] + J[2 * nv + l] * mb.f_ext[3 * b + 2];
+          if (TRIAL == 2 && mb.f_ext && mb.f_ext_width != 6 && l < 3) s += J[0 * nv + l] * mb.f_ext[3 * b] + J[1 * nv + l] * mb.f_ext[3 * b + 1] + J[2 * nv + l] * mb.f_ext[3 * b + 2];
+          // width 6: f at a fixed world point p, the wrench [f ; p x f] about the world origin on the base columns (the columns are world-frame
+          // twists at the origin: J_lin . f + J_ang . (p x f) = (R e_l) . f on the translations, (R e_l) . ((p - p_base) x f) on the rotations)
+          if (TRIAL == 2 && mb.f_ext && mb.f_ext_width == 6 && l < 6) {
+            const double* fe = mb.f_ext + 6 * (size_t)b;
+            const V3 mo = cross(v3(fe[3], fe[4], fe[5]), v3(fe[0], fe[1], fe[2]));
+            s += (J[0 * nv + l] * fe[0] + J[1 * nv + l] * fe[1] + J[2 * nv + l] * fe[2]) + (J[3 * nv + l] * mo.x + J[4 * nv + l] * mo.y + J[5 * nv + l] * mo.z);
+          }
         }
       }
       Y16[l * MB_LDY + j] = s;

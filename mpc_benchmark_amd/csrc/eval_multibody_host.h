@@ -120,7 +120,8 @@ struct MbArgs {
   int ncand_loop;         // TRIAL == 1: > 0 = the workgroup walks this many candidates itself (grid z = 1)
   int sim_substeps;       // TRIAL == 2 (closed-loop simulation stand-in): integration steps ...
   double sim_dt;          // ... of this length
-  const double* f_ext;    // TRIAL == 2: world-frame force at the base origin per instance [B][3] (mpc_simulate_push), or nullptr
+  const double* f_ext;    // TRIAL == 2: the push on the base per instance, or nullptr: f_ext_width 3: [B][3] world-frame force at the base origin
+  int f_ext_width;        // (mpc_simulate_push) ; 6: [B][6] = (world-frame force, fixed world point it acts at) (include/mpc_sim_ext.h)
   const double* sim_u;    // TRIAL == 2: joint torques per instance [B][nu] held during the call (mpc_simulate_torque: the start state is
                           // then a.x0, no feedback law), or nullptr
   double* sim_wrench;     // TRIAL == 2: contact wrenches of the last sub-step [B][2][6], or nullptr
@@ -130,5 +131,6 @@ struct MbArgs {
 // defined in eval_multibody.hip
 void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
                            bool trial, int cand0 = 0, int ncand = 1, int sim_substeps = 0, double sim_dt = 0.0, bool with_derivs = false,
-                           const double* f_ext = nullptr, bool contact_dyn = true, const double* sim_u = nullptr, double* sim_wrench = nullptr);
+                           const double* f_ext = nullptr, bool contact_dyn = true, const double* sim_u = nullptr, double* sim_wrench = nullptr,
+                           int f_ext_width = 3);
 const void* eval_multibody_kernel(int trial);  // entry point of k_eval_multibody<trial> (occupancy tooling)

@@ -27,6 +27,8 @@
 #include "legs_tree.h"
 #include "pipeline_glue.h"
 #include "pipeline_ikid_glue.h"
+#include "sim_record.h"
+#include "../../include/mpc_sim_ext.h"
 #include "qp_device_api.h"
 
 #define HIP_OK(expr)                                                                                  \
@@ -116,6 +118,11 @@ struct mpc_solver {
   bool refine_now = false;         // ... and this run refines the warm start of the appended knot after k_begin_run
   double* d_simu = nullptr;  // [B][nu] torques, [B][12] wrenches of mpc_simulate_torque
   double* d_simwr = nullptr;
+  // include/mpc_sim_ext.h: the push armed for the torque-driven steps (push_width 0: none) and the record ring [rec_cap][B][rec]
+  double* d_push = nullptr;  // [B][6]
+  int push_width = 0;
+  double* d_rec = nullptr;
+  int rec_cap = 0, rec_count = 0;
   // per-slot invalidation (mpc_update_stage_params*): slots whose parameters changed since the last pass was enqueued ; dirty_all:
   // an update on a horizon too long for the mask of SolverArgs
   std::vector<uint8_t> slot_dirty;
@@ -907,7 +914,7 @@ void mpc_destroy(mpc_solver* s) {
   for (int i = 0; i < mpc_solver::ASYNC_DEPTH; ++i) if (s->h_xnext[i]) (void)hipHostFree(s->h_xnext[i]);
   if (s->d_patch) (void)hipFree(s->d_patch);
   for (void* p : s->allocs) (void)hipFree(p);
-  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf}) if (p) (void)hipFree(p);
+  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec}) if (p) (void)hipFree(p);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1303,6 +1310,96 @@ int mpc_simulate_push(mpc_solver* s, int32_t substeps, double dt, const double* 
   MPC_TRY(s, { simulate_impl(s, substeps, dt, f_ext); })
 }
 
+// ---- include/mpc_sim_ext.h: push and record of the torque-driven simulator steps --------------------------------------------------------------
+// the handle of mpc_simulate_torque: whole-body, nu = nv - 6.  (Its stage 0 may be set later, as the pipelines do per contact state: the contact dynamics
+// are checked by the simulator steps themselves.)
+static void sim_check(mpc_solver* s, const char* what) {
+  const Layout& L = s->L;
+  if (L.space != MPC_SPACE_MULTIBODY || L.m != L.n / 2 - 6 || L.nx != L.n / 2 + (L.n / 2 + 1))
+    throw std::runtime_error(std::string(what) + ": the simulator handle must be a whole-body handle with nu = nv - 6 (the handle of mpc_simulate_torque)");
+}
+static const double* sim_push(const mpc_solver* s) { return s->push_width ? s->d_push : nullptr; }
+static int sim_push_width(const mpc_solver* s) { return s->push_width ? s->push_width : 3; }
+static double* sim_wrench_out(const mpc_solver* s, bool wanted) { return (wanted || s->rec_cap > 0) ? s->d_simwr : nullptr; }
+// every one of the `steps` simulator steps about to be enqueued gets its record slot, or the call fails before anything is enqueued
+static void sim_record_reserve(const mpc_solver* s, int steps) {
+  if (s->rec_cap > 0 && s->rec_count + steps > s->rec_cap)
+    throw std::runtime_error("sim_record: the record ring is full (" + std::to_string(s->rec_count) + " of " + std::to_string(s->rec_cap) + " steps held, " +
+                             std::to_string(steps) + " more asked for): read it with mpc_sim_record_read or enlarge it with mpc_sim_record");
+}
+// after a simulator step on stream st: its record (sim_record.h), when recording is on
+static void sim_record_enqueue(mpc_solver* s, hipStream_t st) {
+  if (s->rec_cap <= 0) return;
+  const Layout& L = s->L;
+  SimRecordArgs r;
+  r.mi = s->d_model_i; r.md = s->d_model_d; r.nv = L.n / 2; r.nq = L.nx - L.n / 2;
+  r.x = s->d_x0; r.tau = s->d_simu; r.wr = s->d_simwr; r.push = sim_push(s); r.push_width = s->push_width;
+  r.out = s->d_rec + (size_t)s->rec_count * L.B * sim_record_width(L.nx, L.m);
+  hipLaunchKernelGGL(k_sim_record, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, r);
+  HIP_OK(hipGetLastError());
+  s->rec_count++;
+}
+
+int mpc_sim_set_push(mpc_solver* s, const double* f_ext, int32_t width) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_set_push");
+    if (!f_ext) { s->push_width = 0; return 0; }
+    if (width != 3 && width != 6) throw std::runtime_error("sim_set_push: width must be 3 (force at the base origin) or 6 (force, world point)");
+    const Layout& L = s->L;
+    if (!s->d_push) s->d_push = s->alloc<double>((size_t)L.B * 6);
+    // (a small synchronous upload: the push changes a few times per run, not part of the steady loop)
+    copy_sync(s, s->d_push, f_ext, (size_t)L.B * width * sizeof(double), hipMemcpyHostToDevice);
+    s->push_width = width;
+  })
+}
+
+int mpc_sim_record(mpc_solver* s, int32_t cap) {
+  MPC_TRY(s, {
+    if (cap < 0) throw std::runtime_error("sim_record: cap must be >= 0 (0: recording off)");
+    sim_check(s, "sim_record");
+    const Layout& L = s->L;
+    if (cap > 0 && (s->h_model_i.size() < 5 || s->h_model_i[4] < 2))
+      throw std::runtime_error("sim_record: the model of the simulator handle must hold the two sole contacts (contacts 0 and 1)");
+    if (cap > 0 && L.nj > CG_MAX_NJ) throw std::runtime_error("sim_record: more moving joints than the record kernel holds (64)");
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (s->d_rec) { HIP_OK(hipFree(s->d_rec)); s->d_rec = nullptr; }
+    s->rec_cap = s->rec_count = 0;
+    if (cap > 0) {
+      void* p = nullptr;
+      HIP_OK(hipMalloc(&p, (size_t)cap * L.B * sim_record_width(L.nx, L.m) * sizeof(double)));
+      s->d_rec = (double*)p;
+      s->rec_cap = cap;
+      if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
+      HIP_OK(hipStreamSynchronize(s->stream));
+    }
+  })
+}
+
+int mpc_sim_record_read(mpc_solver* s, double* out, int32_t* count) {
+  MPC_TRY(s, {
+    if (!count) throw std::runtime_error("sim_record_read: count must not be null");
+    sim_check(s, "sim_record_read");
+    HIP_OK(hipStreamSynchronize(s->stream));
+    *count = s->rec_count;
+    if (out) {
+      const Layout& L = s->L;
+      if (s->rec_count > 0) copy_sync(s, out, s->d_rec, (size_t)s->rec_count * L.B * sim_record_width(L.nx, L.m) * sizeof(double), hipMemcpyDeviceToHost);
+      s->rec_count = 0;
+    }
+  })
+}
+
+int32_t mpc_sim_record_width(mpc_solver* s) {
+  if (!s) return -1;
+  try {
+    sim_check(s, "sim_record_width");
+    return sim_record_width(s->L.nx, s->L.m);
+  } catch (const std::exception& e) {
+    s->err = e.what();
+    return -1;
+  }
+}
+
 int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32_t substeps, double dt, double* wrenches) {
   MPC_TRY(s, {
     if (substeps <= 0 || !(dt > 0.0)) throw std::runtime_error("simulate: substeps and dt must be positive");
@@ -1310,12 +1407,14 @@ int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32
     if (s->L.space != MPC_SPACE_MULTIBODY || s->h_desc[(size_t)slot_of(s, 0) * s->L.max_stage_ints] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER)
       throw std::runtime_error("simulate: only contact-constrained whole-body dynamics are supported");
     const Layout& L = s->L;
+    sim_record_reserve(s, 1);
     if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
     if (x) copy_sync(s, s->d_x0, x, (size_t)L.B * L.nx * sizeof(double), hipMemcpyHostToDevice);
     copy_sync(s, s->d_simu, tau, (size_t)L.B * L.m * sizeof(double), hipMemcpyHostToDevice);
-    launch_eval_multibody(s->stream, s->args(), s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, nullptr, true,
-                          s->d_simu, wrenches ? s->d_simwr : nullptr);
+    launch_eval_multibody(s->stream, s->args(), s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, sim_push(s), true,
+                          s->d_simu, sim_wrench_out(s, wrenches != nullptr), sim_push_width(s));
     HIP_OK(hipGetLastError());
+    sim_record_enqueue(s, s->stream);
     if (wrenches) copy_sync(s, wrenches, s->d_simwr, (size_t)L.B * 12 * sizeof(double), hipMemcpyDeviceToHost);
     s->perfect_feedback = false;
   })
@@ -1343,6 +1442,7 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
         sim->h_desc[(size_t)slot_of(sim, 0) * Z.max_stage_ints] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER)
       throw std::runtime_error("qp_low_level_steps: the simulator handle must hold whole-body contact dynamics with nu = nv - 6 (the handle of mpc_simulate_torque)");
     if (plan->async_pending > 0) throw std::runtime_error("qp_low_level_steps: the plan has ticks in flight (mpc_wait first)");
+    sim_record_reserve(sim, steps);
     HIP_OK(hipStreamSynchronize(plan->stream));
     HIP_OK(hipStreamSynchronize(sim->stream));
     if (!sim->d_simu) { sim->d_simu = sim->alloc<double>((size_t)Z.B * Z.m); sim->d_simwr = sim->alloc<double>((size_t)Z.B * 12); HIP_OK(hipStreamSynchronize(sim->stream)); }
@@ -1365,8 +1465,10 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
       qp_id_enqueue(qp, S, kd);
       qp_launch_solve(qp, S);
       hipLaunchKernelGGL(k_pipe_torque, dim3((unsigned)B), dim3(64), 0, st, p);
-      launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, nullptr, true, sim->d_simu, nullptr);
+      launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
+                            sim_wrench_out(sim, false), sim_push_width(sim));
       HIP_OK(hipGetLastError());
+      sim_record_enqueue(sim, st);
     }
     if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1410,6 +1512,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
       throw std::runtime_error("qp_ikid_low_level_steps: the simulator handle must hold whole-body contact dynamics with nu = nv - 6 (the handle of mpc_simulate_torque)");
     if (q.nj > CG_MAX_NJ) throw std::runtime_error("qp_ikid_low_level_steps: more moving joints than the glue kernels hold (64)");
     if (plan->async_pending > 0) throw std::runtime_error("qp_ikid_low_level_steps: the plan has ticks in flight (mpc_wait first)");
+    sim_record_reserve(sim, steps);
     HIP_OK(hipStreamSynchronize(plan->stream));
     HIP_OK(hipStreamSynchronize(sim->stream));
     if (!sim->d_simu) { sim->d_simu = sim->alloc<double>((size_t)Z.B * Z.m); sim->d_simwr = sim->alloc<double>((size_t)Z.B * 12); HIP_OK(hipStreamSynchronize(sim->stream)); }
@@ -1446,8 +1549,10 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
       qp_ikid_enqueue(qp, S);
       qp_launch_solve(qp, S);
       hipLaunchKernelGGL(k_pipe_ikid_torque, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
-      launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, nullptr, true, sim->d_simu, nullptr);
+      launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
+                            sim_wrench_out(sim, false), sim_push_width(sim));
       HIP_OK(hipGetLastError());
+      sim_record_enqueue(sim, st);
     }
     if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     if (c_prev) HIP_OK(hipMemcpyAsync(c_prev, d_cprev, B * CG_NC * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -49,12 +49,13 @@ DEV S6 cg_col(int kind, int loc, const M3& R, V3 p) {
   return mk6(cross(p, w), w);
 }
 
-// forward kinematics with velocities of the state x = (q, v): every body's oR, op and ov (lane i: body i)
-DEV void cg_kinematics(const IkidGlueArgs& a, const double* x, CgBodies& K, int tid) {
-  const int nj = a.mi[0];
-  const int32_t* mj = a.mi + MPC_MODEL_HEADER_WORDS;
-  const double* jd = a.md + MPC_MODEL_HEADER_DOUBLES;
-  const double *q = x, *v = x + a.nq;
+// forward kinematics with velocities of the state x = (q, v): every body's oR, op and ov (lane i: body i).  mi, md: model tables
+// (mpc_set_model / mpc_qp_set_model layout); the helpers below are shared with the simulator record (sim_record.h).
+DEV void cg_kinematics(const int32_t* mi, const double* md, int nq, const double* x, CgBodies& K, int tid) {
+  const int nj = mi[0];
+  const int32_t* mj = mi + MPC_MODEL_HEADER_WORDS;
+  const double* jd = md + MPC_MODEL_HEADER_DOUBLES;
+  const double *q = x, *v = x + nq;
   for (int i = tid; i < nj; i += CG_THREADS) {
     const int kind = mj[4 * i + 1], iq = mj[4 * i + 2];
     const M3 Rp = ldm3(jd + 25 * i);
@@ -98,10 +99,10 @@ DEV void cg_kinematics(const IkidGlueArgs& a, const double* x, CgBodies& K, int 
 }
 
 // placement (R, p) and LOCAL velocity of model frame fi
-DEV void cg_frame(const IkidGlueArgs& a, const CgBodies& K, int fi, M3& Rc, V3& pc, S6& vl) {
-  const int nj = a.mi[0];
-  const int i = a.mi[MPC_MODEL_HEADER_WORDS + MPC_MODEL_JOINT_WORDS * nj + fi];
-  const double* fd = a.md + MPC_MODEL_HEADER_DOUBLES + MPC_MODEL_JOINT_DOUBLES * nj + MPC_MODEL_FRAME_DOUBLES * fi;
+DEV void cg_frame(const int32_t* mi, const double* md, const CgBodies& K, int fi, M3& Rc, V3& pc, S6& vl) {
+  const int nj = mi[0];
+  const int i = mi[MPC_MODEL_HEADER_WORDS + MPC_MODEL_JOINT_WORDS * nj + fi];
+  const double* fd = md + MPC_MODEL_HEADER_DOUBLES + MPC_MODEL_JOINT_DOUBLES * nj + MPC_MODEL_FRAME_DOUBLES * fi;
   const M3 Ri = ldm3(K.oR + 9 * i);
   Rc = mul(Ri, ldm3(fd));
   pc = mul(Ri, ldv3(fd + 9)) + ldv3(K.op + 3 * i);
@@ -117,7 +118,7 @@ __global__ void __launch_bounds__(CG_THREADS) k_ikid_task_errors(IkidGlueArgs a)
   const int b = blockIdx.x, tid = threadIdx.x, nq = a.nq, nv = a.nv, nx = nq + nv;
   __shared__ CgBodies K;
   const double* x = a.x_ik + (size_t)b * nx;
-  cg_kinematics(a, x, K, tid);
+  cg_kinematics(a.mi, a.md, a.nq, x, K, tid);
   double* ik = a.ik + (size_t)b * CG_IK_DOUBLES(nv);
   const double* refs = a.refs + (size_t)b * 48;  // [foot][sample][12]
   const double idt = 1.0 / a.ref_dt;
@@ -125,7 +126,7 @@ __global__ void __launch_bounds__(CG_THREADS) k_ikid_task_errors(IkidGlueArgs a)
     M3 Rc;
     V3 pc;
     S6 vl;
-    cg_frame(a, K, a.fr[tid], Rc, pc, vl);
+    cg_frame(a.mi, a.md, K, a.fr[tid], Rc, pc, vl);
     if (tid < 2) {
       const double *r0 = refs + 24 * tid, *r1 = r0 + 12;
       const M3 R0 = ldm3(r0), R1 = ldm3(r1);
@@ -162,16 +163,11 @@ __global__ void __launch_bounds__(CG_THREADS) k_ikid_task_errors(IkidGlueArgs a)
   if (tid < 6) ik[2 * nv + 36 + tid] = a.knots[((size_t)b * (a.N + 1) + a.slot0) * a.knot_stride + a.oXD + 3 + tid];
 }
 
-// Per step: new_x = [com ; hg] of the measured state (Pinocchio's hg: momentum about the centre of mass, world axes), forces = us[0] - K_0 (xs[0] - new_x)
-// (centroidal_talos.py:420-434), the QP inputs, and on the last step new_x into c_prev.
-__global__ void __launch_bounds__(CG_THREADS) k_pipe_centroidal_feedback(IkidGlueArgs a) {
-  const int b = blockIdx.x, tid = threadIdx.x, nx = a.nq + a.nv, nj = a.mi[0], nf = 6 * a.nk;
-  __shared__ CgBodies K;
-  __shared__ double body[10 * CG_MAX_NJ];  // per body: m c (3), linear momentum (3), angular momentum about the origin (3), m
-  __shared__ double cx[CG_NC];
-  const double* x = a.x + (size_t)b * nx;
-  cg_kinematics(a, x, K, tid);
-  const double* jd = a.md + MPC_MODEL_HEADER_DOUBLES;
+// centroidal state of the bodies K: cx = [com ; hg.linear ; hg.angular] (Pinocchio's hg: momentum about the centre of mass, world axes).
+// body: LDS scratch of 10 doubles per body (m c, linear momentum, angular momentum about the origin, m).  Ends with a barrier.
+DEV void cg_centroidal(const int32_t* mi, const double* md, const CgBodies& K, double* body, double* cx, int tid) {
+  const int nj = mi[0];
+  const double* jd = md + MPC_MODEL_HEADER_DOUBLES;
   for (int i = tid; i < nj; i += CG_THREADS) {
     const M3 R = ldm3(K.oR + 9 * i);
     const double mass = jd[25 * i + 12];
@@ -192,6 +188,18 @@ __global__ void __launch_bounds__(CG_THREADS) k_pipe_centroidal_feedback(IkidGlu
     cx[0] = com.x; cx[1] = com.y; cx[2] = com.z; cx[3] = L.x; cx[4] = L.y; cx[5] = L.z; cx[6] = A.x; cx[7] = A.y; cx[8] = A.z;
   }
   __syncthreads();
+}
+
+// Per step: new_x = [com ; hg] of the measured state, forces = us[0] - K_0 (xs[0] - new_x) (centroidal_talos.py:420-434), the QP inputs, and on the
+// last step new_x into c_prev.
+__global__ void __launch_bounds__(CG_THREADS) k_pipe_centroidal_feedback(IkidGlueArgs a) {
+  const int b = blockIdx.x, tid = threadIdx.x, nx = a.nq + a.nv, nf = 6 * a.nk;
+  __shared__ CgBodies K;
+  __shared__ double body[10 * CG_MAX_NJ];
+  __shared__ double cx[CG_NC];
+  const double* x = a.x + (size_t)b * nx;
+  cg_kinematics(a.mi, a.md, a.nq, x, K, tid);
+  cg_centroidal(a.mi, a.md, K, body, cx, tid);
   const double* xs0 = a.xs + (size_t)b * (a.N + 1) * CG_NC;
   const double* us0 = a.us + (size_t)b * a.N * a.m;
   const double* K0 = a.gains + (size_t)b * (a.N + 1) * a.gain_stride + a.oK;

@@ -37,6 +37,38 @@ def _sim_options():
     return o
 
 
+# -- the push experiment of the scripts (commented out there): device.apply_force(f_disturbance, [0, 0, 0]) on ticks 160 - 170 -------------------------
+PUSH_TICKS = (160, 171)        # `if t >= 160 and t < 171` (centroidal_talos.py:450-452, kinodynamic_talos.py:459-461, fulldynamic_talos.py:524-526)
+PUSH_THETA = 6 * np.pi / 4     # theta of all three scripts
+PUSH_FORCE = {"fulldynamic": 300.0, "kinodynamic": 300.0, "centroidal": 100.0}   # fd (fulldynamic_talos.py:433, kinodynamic_talos.py:357, centroidal_talos.py:350)
+
+
+def push_schedule(t, fd, theta=PUSH_THETA, ticks=PUSH_TICKS):
+    """The scripts' disturbance at MPC tick ``t`` (the script's loop index; a pipeline's ``mpc.tick`` before its ``tick()``): the world-frame force
+    [cos theta, sin theta, 0] fd inside ticks 160 - 170, else None.  Pass it as ``tick(push=...)`` (tiled to (B, 3): at the base origin, or with a
+    world point to (B, 6)); the pipelines arm it for the ten low-level steps of that period.
+
+    The offset this leaves: the script calls ``device.apply_force`` AFTER each ``device.execute`` of the window, and PyBullet applies an external
+    force during the next simulation step only, so there the push acts on steps 2 - 10 of tick 160, ..., steps 1 - 10 of tick 170 and step 1 of tick 171:
+    one 1 ms step later than the per-period arm here (steps 1 - 10 of ticks 160 - 170).  The same impulse, not emulated (``BulletRobot.apply_force``
+    reproduces the script's timing exactly)."""
+    if not (ticks[0] <= t < ticks[1]):
+        return None
+    return np.array([np.cos(theta), np.sin(theta), 0.0]) * float(fd)
+
+
+def _push_array(push, batch):
+    """``tick(push=...)``: None, or (B, 3) (force at the base origin) / (B, 6) (force, world point), checked before any library call"""
+    if push is None:
+        return None
+    p = np.asarray(push, dtype=float)
+    if p.ndim != 2 or p.shape[0] != batch or p.shape[1] not in (3, 6):
+        raise ValueError("push: (B, 3) (force at the base origin) or (B, 6) (force, world point) expected with B = %d, got shape %s" % (batch, p.shape))
+    if not np.all(np.isfinite(p)):
+        raise ValueError("push: non-finite entries")
+    return np.ascontiguousarray(p)
+
+
 def build_torque_simulator(lib, robot, batch, sim_dt, device):
     """The simulator stand-in of both pipelines: one handle, horizon 1, whole-body contact dynamics of the three contact patterns (rigid contacts at
     the robot's initial foot placements).  -> (NativeSolver, {(left, right): lowered stage 0})."""
@@ -155,19 +187,28 @@ class KinodynamicPipeline:
         x_last, self.x, self.torques, self.forces = self.qp.low_level_steps(self.mpc.native, self.sim, cs_all, self.umax, self.substeps, self.sim_dt, x=self.x)
         return x_last
 
-    def tick(self, host_glue=False):
+    def tick(self, host_glue=False, push=None):
         """One MPC period: the low-level loop on the current plan, then the next solve from the measurement of the tick before.  ``host_glue``: the low-level
-        periods one at a time with the small vectors travelling through the host (``low_level_step``: the readable form, what the library call is tested against)."""
+        periods one at a time with the small vectors travelling through the host (``low_level_step``: the readable form, what the library call is tested against).
+        ``push``: (B, 3) world force at the base origin or (B, 6) (force, world point), armed on the simulator for the low-level steps of this period
+        only (mpc_sim_set_push, HIP library; ``push_schedule``)."""
+        push = _push_array(push, self.batch)
         cs = self.contact_state()
         self._set_sim_contacts(cs)
-        if host_glue:
-            if self._plan_stale:
-                self._fetch()
-            for _ in range(self.substeps):
-                x_last = self.x.copy()   # (the script's x_measured is read BEFORE the last execute of the tick)
-                self.low_level_step(cs)
-        else:
-            x_last = self.low_level_loop(cs)
+        if push is not None:
+            self.sim.set_push(push)
+        try:
+            if host_glue:
+                if self._plan_stale:
+                    self._fetch()
+                for _ in range(self.substeps):
+                    x_last = self.x.copy()   # (the script's x_measured is read BEFORE the last execute of the tick)
+                    self.low_level_step(cs)
+            else:
+                x_last = self.low_level_loop(cs)
+        finally:
+            if push is not None:
+                self.sim.set_push(None)
         e = self.mpc
         if e._walk is not None:     # the references are planned from the state that becomes the initial condition (walking_loop.py)
             e._walk["x_measured"] = self.x_prev[0].copy()
@@ -327,26 +368,34 @@ class CentroidalPipeline:
             self.mpc.native, self.sim, self.x_posture, refs, self.ref_dt, cs_all, self.substeps, self.sim_dt, x=self.x, x_ik=x_ik, want_ik=True)
         self._xik_on_device = True
 
-    def tick(self, host_glue=False):
+    def tick(self, host_glue=False, push=None):
         """One MPC period in the script's order (class docstring).  ``host_glue``: the task errors from ``references.compute_ID_references`` and
         the low-level periods one at a time with the small vectors travelling through the host (``low_level_step``: the readable form, what the
-        library call is tested against)."""
+        library call is tested against).  ``push``: (B, 3) world force at the base origin or (B, 6) (force, world point), armed on the simulator for
+        the low-level steps of this period only (mpc_sim_set_push, HIP library; ``push_schedule``)."""
+        push = _push_array(push, self.batch)
         e = self.mpc
         cs = self.contact_state()
         e.plan_tick()
         refs = self.foot_refs()
         self._set_sim_contacts(cs)
-        if host_glue:
-            if self._plan_stale:
-                self._fetch()
-            self.ik = self.qp.task_errors(self.x_prev, self.x_posture, refs, self.ref_dt, self.dH)
-            for _ in range(self.substeps):
-                x_last = self.x.copy()   # (the script's x_measured is read BEFORE the last execute of the period)
-                c_last = self.low_level_step(cs, self.ik)
-            self.x_prev, self.c_prev = x_last, c_last
-            self._xik_on_device = False
-        else:
-            self.low_level_loop(cs, refs)
+        if push is not None:
+            self.sim.set_push(push)
+        try:
+            if host_glue:
+                if self._plan_stale:
+                    self._fetch()
+                self.ik = self.qp.task_errors(self.x_prev, self.x_posture, refs, self.ref_dt, self.dH)
+                for _ in range(self.substeps):
+                    x_last = self.x.copy()   # (the script's x_measured is read BEFORE the last execute of the period)
+                    c_last = self.low_level_step(cs, self.ik)
+                self.x_prev, self.c_prev = x_last, c_last
+                self._xik_on_device = False
+            else:
+                self.low_level_loop(cs, refs)
+        finally:
+            if push is not None:
+                self.sim.set_push(None)
         e.native.set_x0(self.c_prev)
         st = e.solve_tick()
         self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
