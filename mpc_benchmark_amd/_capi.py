@@ -133,6 +133,11 @@ _SIM_EXT_SIGNATURES = {
     "mpc_sim_record_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_feedback_pipeline.h: exported by the HIP library alone, bound when present (``NativeSolver.feedback_low_level_steps``)
+_FEEDBACK_PIPELINE_SIGNATURES = {
+    "mpc_feedback_low_level_steps": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int32, C.c_double, _DP, _DP, _DP, _DP]),
+}
+
 
 def bind_library(path):
     """dlopen ``path`` and attach the argument/return types of every entry point of mpc_abi.h."""
@@ -141,7 +146,7 @@ def bind_library(path):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in _SIM_EXT_SIGNATURES.items():
+    for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -320,6 +325,23 @@ class NativeSolver:
         soles = out[:, :, o + 21:o + 45].reshape(S, B, 2, 12)
         return {"x": out[:, :, :nx], "tau": out[:, :, nx:o], "wrenches": out[:, :, o:o + 12].reshape(S, B, 2, 6), "com": out[:, :, o + 12:o + 15],
                 "momentum": out[:, :, o + 15:o + 21], "sole_R": soles[..., :9].reshape(S, B, 2, 3, 3), "sole_p": soles[..., 9:], "push": out[:, :, o + 45:o + 51]}
+
+    # -- include/mpc_feedback_pipeline.h (HIP library only): the low-level loop of the full-dynamics pipeline --------------------------------
+    def feedback_low_level_steps(self, sim, steps, dt, x=None):
+        """mpc_feedback_low_level_steps: ``steps`` periods of the full-dynamics low-level loop on the device, this handle the plan (xs[0], us[0], K_0
+        where its last run left them), ``sim`` the torque-driven simulator handle: per period tau = us[0] - K_0 difference(x, xs[0]), then one simulator
+        step of ``dt`` under tau (the push armed on ``sim``; a record per step when ``sim`` records).  ``x`` (B, nx): the states to start from (None: the
+        simulator's).  -> (x_prev: the states before the last period, x_out: after it, tau (B, nu) and contact wrenches (B, 2, 6) of the last period)."""
+        if not hasattr(self.lib, "mpc_feedback_low_level_steps"):
+            raise RuntimeError("mpc_feedback_low_level_steps is not exported by this library (%s): the full-dynamics device loop is HIP only "
+                               "(libmpc_hip.so, include/mpc_feedback_pipeline.h)" % self.backend)
+        d = sim.dims
+        xa = None if x is None else np.ascontiguousarray(np.broadcast_to(_f64(x).reshape(-1, d.nx), (d.batch, d.nx)))
+        x_prev, x_out = np.zeros((d.batch, d.nx)), np.zeros((d.batch, d.nx))
+        tau, wr = np.zeros((d.batch, d.nu)), np.zeros((d.batch, 2, 6))
+        self._check(self.lib.mpc_feedback_low_level_steps(self._h, sim._h, _dp(xa), int(steps), float(dt), _dp(x_prev), _dp(x_out), _dp(tau), _dp(wr)),
+                    "mpc_feedback_low_level_steps")
+        return x_prev, x_out, tau, wr
 
     def get_x0(self):
         x0 = np.zeros((self.dims.batch, self.dims.nx))

@@ -27,8 +27,10 @@
 #include "legs_tree.h"
 #include "pipeline_glue.h"
 #include "pipeline_ikid_glue.h"
+#include "pipeline_fd_glue.h"
 #include "sim_record.h"
 #include "../../include/mpc_sim_ext.h"
+#include "../../include/mpc_feedback_pipeline.h"
 #include "qp_device_api.h"
 
 #define HIP_OK(expr)                                                                                  \
@@ -118,6 +120,7 @@ struct mpc_solver {
   bool refine_now = false;         // ... and this run refines the warm start of the appended knot after k_begin_run
   double* d_simu = nullptr;  // [B][nu] torques, [B][12] wrenches of mpc_simulate_torque
   double* d_simwr = nullptr;
+  double* d_xlast = nullptr;  // [B][nx] the states before the last period of mpc_feedback_low_level_steps
   // include/mpc_sim_ext.h: the push armed for the torque-driven steps (push_width 0: none) and the record ring [rec_cap][B][rec]
   double* d_push = nullptr;  // [B][6]
   int push_width = 0;
@@ -1568,6 +1571,54 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     qp_set_error(qp, e.what());
     return -1;
   }
+}
+
+// include/mpc_feedback_pipeline.h: the low-level loop of the full-dynamics pipeline (fulldynamic_talos.py:512-530) with one kernel between the plan and
+// the simulator step.  Everything is enqueued on the simulator handle's stream (the plan's is drained first); one synchronisation at the end.  Errors
+// are reported on the plan's handle.
+int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double* x, int32_t steps, double dt, double* x_prev, double* x_out, double* tau,
+                                 double* wrenches) {
+  MPC_TRY(plan, {
+    if (!plan || !sim) throw std::runtime_error("feedback_low_level_steps: null handle");
+    if (steps <= 0 || !(dt > 0.0)) throw std::runtime_error("feedback_low_level_steps: steps and dt must be positive");
+    if (plan->dims.device != sim->dims.device) throw std::runtime_error("feedback_low_level_steps: the two handles must live on one device");
+    const Layout& P = plan->L;
+    const Layout& Z = sim->L;
+    if (P.B != Z.B) throw std::runtime_error("feedback_low_level_steps: the two handles must have the same batch size");
+    sim_check(sim, "feedback_low_level_steps");
+    if (sim->h_desc[(size_t)slot_of(sim, 0) * Z.max_stage_ints] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER)
+      throw std::runtime_error("feedback_low_level_steps: the simulator handle must hold whole-body contact dynamics (stage 0 of the handle of mpc_simulate_torque)");
+    if (P.space != MPC_SPACE_MULTIBODY || P.nx != Z.nx || P.n != Z.n || P.m != Z.m || P.n > PIPE_MAX_N)
+      throw std::runtime_error("feedback_low_level_steps: the plan must be a multibody problem with the simulator's nx and joint-torque controls (m = nu = nv - 6)");
+    if (plan->async_pending > 0) throw std::runtime_error("feedback_low_level_steps: the plan has ticks in flight (mpc_wait first)");
+    sim_record_reserve(sim, steps);
+    HIP_OK(hipStreamSynchronize(plan->stream));
+    const size_t B = Z.B;
+    const int nx = Z.nx, nu = Z.m;
+    if (!sim->d_simu) { sim->d_simu = sim->alloc<double>(B * nu); sim->d_simwr = sim->alloc<double>(B * 12); }
+    if (x_prev && !sim->d_xlast) sim->d_xlast = sim->alloc<double>(B * nx);
+    hipStream_t st = sim->stream;
+    if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
+    FdPipeArgs p;
+    p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains;
+    p.N = P.N; p.nx = nx; p.nv = Z.n / 2; p.nq = nx - Z.n / 2; p.n = P.n; p.m = nu; p.gain_stride = P.gain_stride; p.oK = P.oK;
+    p.x = sim->d_x0; p.sim_u = sim->d_simu;
+    const SolverArgs za = sim->args();
+    for (int step = 0; step < steps; ++step) {
+      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(sim->d_xlast, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(k_pipe_state_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
+      launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
+                            sim_wrench_out(sim, wrenches != nullptr), sim_push_width(sim));
+      HIP_OK(hipGetLastError());
+      sim_record_enqueue(sim, st);
+    }
+    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, sim->d_xlast, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (wrenches) HIP_OK(hipMemcpyAsync(wrenches, sim->d_simwr, B * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    sim->perfect_feedback = false;
+  })
 }
 
 int mpc_get_x0(mpc_solver* s, double* x0) {

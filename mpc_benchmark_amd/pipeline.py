@@ -1,5 +1,5 @@
-"""The control pipelines of the kinodynamic and centroidal scripts for an ensemble of robots (``KinodynamicPipeline`` below;
-``CentroidalPipeline``, centroidal_talos.py:353-468, at the end of the file).
+"""The control pipelines of the three scripts for an ensemble of robots (``KinodynamicPipeline`` below; ``CentroidalPipeline``,
+centroidal_talos.py:353-468, and ``FullDynamicPipeline``, fulldynamic_talos.py:437-550, at the end of the file).
 
 The kinodynamic control pipeline of kinodynamic_talos.py:361-497, every stage on the solver library:
 
@@ -398,5 +398,124 @@ class CentroidalPipeline:
                 self.sim.set_push(None)
         e.native.set_x0(self.c_prev)
         st = e.solve_tick()
+        self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
+        return st
+
+
+# -- the full-dynamics pipeline ---------------------------------------------------------------------------------------------------------
+class FullDynamicPipeline:
+    """The full-dynamics control pipeline of fulldynamic_talos.py:437-550 for an ensemble of robots, every stage on the solver library:
+
+        MPC tick (full-dynamics OCP, one ProxDDP iteration)                                                    fulldynamic_talos.py:536-541
+        -> 10 low-level steps of 1 ms, each:
+             measured state of every robot                                                                     :514-520
+             tau = us[0] - K_0 difference(x_measured, xs[0]), no clamp                                         :522
+             one simulator step under that torque                                       (mpc_simulate_torque)  :523 (device.execute)
+        -> the measurement of the period before becomes the initial condition of the next solve               :534-546
+
+    The order of one period (``tick``) is the script's: the loop runs on the previous plan; the walk references are planned from ``x_prev`` (the
+    measurement before the last execute of the period before, :440-462); x0 = ``x_prev`` and the solve; ``x_prev`` becomes the measurement
+    before the last execute of this period.  Unlike ``EnsembleMPC(closed_loop=...)`` (mpc_simulate: knot 0's own model integrated from xs[0]) the
+    measured robots carry over from period to period on the torque-driven simulator the other two pipelines use (``build_torque_simulator``, the
+    contact set of ``contact_state``).  ``library``: the HIP library by default; the device loop (``low_level_loop``,
+    mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
+
+    def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, **ens_kw):
+        """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
+        ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
+        the pipeline is the closed loop."""
+        if ens_kw.get("closed_loop") is not None:
+            raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
+                             "EnsembleMPC(closed_loop=...) would simulate a second time)")
+        ens_kw.pop("closed_loop", None)
+        self.pd, self.batch = problem_def, int(batch)
+        self.lib = library if library is not None else K.load_hip_library()
+        rb = problem_def.robot
+        m = self.model = rb.model
+        self.nq, self.nv = m.nq, m.nv
+        self.substeps, self.sim_dt = int(substeps), float(sim_dt)
+        self.mpc = EnsembleMPC(problem_def, batch=batch, library=self.lib, x0=x0, **ens_kw)
+        self._walk_args = walk
+        self.sim, self._sim_tables = build_torque_simulator(self.lib, rb, self.batch, self.sim_dt, self.mpc.dims.device)
+        self._sim_mask = None
+        self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
+        self.x_prev = self.x.copy()                      # the measurement of the period before (the solve's initial condition)
+        self.torques = np.zeros((self.batch, m.nv - 6))
+        self.wrenches = np.zeros((self.batch, 2, 6))     # contact wrenches of the last simulator step (LOCAL frame of the sole)
+        self._plan_stale = True
+
+    def _set_sim_contacts(self, mask):
+        mask = (bool(mask[0]), bool(mask[1]))
+        if mask != self._sim_mask:
+            self.sim.set_stage(0, *self._sim_tables[mask])
+            self._sim_mask = mask
+
+    def cold_solve(self, max_iters=100):
+        st = self.mpc.cold_solve(max_iters=max_iters)
+        if self._walk_args is not None:
+            self.mpc.enable_walk(**self._walk_args)
+        self._fetch()
+        return st
+
+    def _fetch(self):
+        self._plan_stale = False
+        r = self.mpc.native.get_results(gains=False)
+        self.xs0, self.us0 = r["xs"][:, 0].copy(), r["us"][:, 0].copy()
+        self.K0 = self.mpc.native.get_gain(0)[0]
+
+    def contact_state(self):
+        """[left, right] the low-level loop of this MPC period works with: the rule of ``KinodynamicPipeline.contact_state``."""
+        N, t = self.mpc.problem.num_steps, self.mpc.tick
+        return self.pd.contact_phases[max(0, t + 1 - N) % self.pd.t_mpc]
+
+    def low_level_step(self, cs):
+        """One 1 kHz step of fulldynamic_talos.py:514-523 for every robot, the feedback law on the host (``cs``: the simulator's contact set is
+        set by ``tick``).  -> the torques."""
+        if self._plan_stale:
+            self._fetch()
+        nq = self.nq
+        x = self.x
+        d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], self.xs0[:, :nq]), self.xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
+        tau = self.us0 - np.einsum("bij,bj->bi", self.K0, d)
+        self.x, wr = self.sim.simulate_torque(x, tau, 1, self.sim_dt, wrenches=True)
+        self.torques, self.wrenches = tau, wr
+        return tau
+
+    def low_level_loop(self, cs):
+        """The ``substeps`` low-level periods of one MPC period inside the library (mpc_feedback_low_level_steps: feedback kernel and simulator step
+        chained on the device, one synchronisation).  -> the measured states before the last period."""
+        x_last, self.x, self.torques, self.wrenches = self.mpc.native.feedback_low_level_steps(self.sim, self.substeps, self.sim_dt, x=self.x)
+        return x_last
+
+    def tick(self, host_glue=False, push=None):
+        """One MPC period in the script's order (class docstring).  ``host_glue``: the low-level periods one at a time with the small vectors
+        travelling through the host (``low_level_step``: the readable form, what the library call is tested against).  ``push``: (B, 3) world force
+        at the base origin or (B, 6) (force, world point), armed on the simulator for the low-level steps of this period only (mpc_sim_set_push,
+        HIP library; ``push_schedule``)."""
+        push = _push_array(push, self.batch)
+        cs = self.contact_state()
+        self._set_sim_contacts(cs)
+        if push is not None:
+            self.sim.set_push(push)
+        try:
+            if host_glue:
+                if self._plan_stale:
+                    self._fetch()
+                for _ in range(self.substeps):
+                    x_last = self.x.copy()   # (x_measured_prev is read BEFORE the last execute of the period)
+                    self.low_level_step(cs)
+            else:
+                x_last = self.low_level_loop(cs)
+        finally:
+            if push is not None:
+                self.sim.set_push(None)
+        e = self.mpc
+        if e._walk is not None:     # the references are planned from the state that becomes the initial condition (fulldynamic_talos.py:440-462)
+            e._walk["x_measured"] = self.x_prev[0].copy()
+            if "x_measured_all" in e._walk:
+                e._walk["x_measured_all"] = self.x_prev.copy()
+        e.native.set_x0(self.x_prev)
+        st = e.step()
+        self.x_prev = x_last
         self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
         return st

@@ -4,8 +4,9 @@
   kinodynamic   KinodynamicPipeline, device loop (mpc_qp_low_level_steps), push armed per period (mpc_sim_set_push), 300 N in the script
   centroidal    CentroidalPipeline, device loop (mpc_qp_ikid_low_level_steps), the same, 100 N in the script
   fulldynamic   EnsembleMPC closed loop (mpc_simulate_push: the force at the base origin), 300 N in the script
+  fulldynamic_pipeline  (opt-in: name it on the command line) FullDynamicPipeline, device loop (mpc_feedback_low_level_steps), 300 N in the script
 
-The two pipelines push at the script's point, the world origin (width 6); the full-dynamics loop at the base origin, the only form mpc_simulate_push has.
+The pipelines push at the script's point, the world origin (width 6); the full-dynamics loop at the base origin, the only form mpc_simulate_push has.
 The pipelines' 1 kHz response comes from the simulator record (mpc_sim_record); the full-dynamics loop is sampled once per MPC period.
 Per robot: recovered or fallen (fallen: the base more than 0.2 m below its start, or both soles more than 2 cm above theirs, or a non-finite state, or its
 MPC solve failed — failure isolation, the robot sits the rest of the run out),
@@ -14,7 +15,7 @@ period with record off (unpushed, and push armed) and with record on.  usage: py
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from mpc_benchmark_amd.pipeline import PUSH_FORCE, PUSH_THETA, PUSH_TICKS, CentroidalPipeline, KinodynamicPipeline, centroidal_state
+from mpc_benchmark_amd.pipeline import PUSH_FORCE, PUSH_THETA, PUSH_TICKS, CentroidalPipeline, FullDynamicPipeline, KinodynamicPipeline, centroidal_state
 from mpc_benchmark_amd.problems.centroidal import CentroidalProblem
 from mpc_benchmark_amd.problems.kinodynamic import KinodynamicProblem
 from mpc_benchmark_amd.robot import minipin as pin
@@ -41,6 +42,9 @@ def grid(fd):
 def make_pipeline(model):
     if model == "kinodynamic":
         p = KinodynamicPipeline(KinodynamicProblem(horizon=N), batch=B, walk={}, perturb=True, sigma_q=0.005, sigma_v=0.01, tick_reuse=True)
+    elif model == "fulldynamic_pipeline":
+        from mpc_benchmark_amd.problems.fulldynamic import FullDynamicsProblem
+        p = FullDynamicPipeline(FullDynamicsProblem(horizon=N), batch=B, walk={}, sigma_q=0.005, sigma_v=0.01, tick_reuse=True)
     else:
         p = CentroidalPipeline(CentroidalProblem(horizon=N), batch=B, walk={}, sigma_q=0.005, sigma_v=0.01, tick_reuse=True)
     p.mpc.prepare_schedule(T_END + 16)
@@ -121,7 +125,7 @@ def verdict(tr, ref):
 lines = ["Push recovery sweep (tools/push_recovery.py %d %d): 64 robots per formulation, 8 directions (theta = 3 pi / 2 + k pi / 4) x 8 magnitudes (0 .. 2 fd,"
          " evenly spaced), pushed on MPC ticks %d - %d, run to tick %d, the script's walk, N = %d, MI355X." % (N, T_END, PUSH_TICKS[0], PUSH_TICKS[1] - 1, T_END, N), ""]
 for model in MODELS:
-    fd = PUSH_FORCE[model]
+    fd = PUSH_FORCE["fulldynamic" if model == "fulldynamic_pipeline" else model]
     f, th, mag = grid(fd)
     W, P = slice(100, PUSH_TICKS[0]), slice(*PUSH_TICKS)
     lines.append("== %s (script: %g N, %s) ==" % (model, fd, "device loop, push at the world origin" if model != "fulldynamic"
