@@ -1,5 +1,6 @@
 """bench.py's contract with the driver, held without a GPU by RUNNING bench.py: ``--selftest-cpu`` takes the same code path — launcher, rank set-up, shard
-construction, warm-up, timed region, whole-schedule walk, batch-1 latency, PCIe-inclusive loop, CPU-baseline workers, all-gather, JSON line — on the CPU port
+construction, warm-up, timed region, all-gather, JSON line, and with ``--full`` the whole-schedule walk, batch-1 latency, PCIe-inclusive loop and CPU-baseline
+workers — on the CPU port
 (``oracle/cpu_port``, test infrastructure) with gloo and tiny sizes.  The numbers are meaningless and the line says so (``selftest``, ``metric``); what is
 checked is the layout of the line, the arithmetic between its fields and that ``--gpus N`` launches N ranks.  Result-valued assertions (no instance lost over
 the schedule, ...) live in the GPU tests (tests/test_gpu_bench_config.py)."""
@@ -44,7 +45,7 @@ def test_refuses_a_cpu_library_outside_the_selftest(cpu_lib):
 
 
 def test_line_of_the_cpu_rehearsal_has_the_contract_keys(cpu_lib):
-    out, rows = _run(["--selftest-cpu", "--lib", cpu_lib] + SMALL)
+    out, rows = _run(["--selftest-cpu", "--lib", cpu_lib, "--full"] + SMALL)
     assert out.returncode == 0, out.stderr[-2000:]
     assert len(rows) == 1, "bench.py prints ONE JSON line"
     d = json.loads(rows[0])
@@ -71,6 +72,27 @@ def test_line_of_the_cpu_rehearsal_has_the_contract_keys(cpu_lib):
     assert d["per_rank_ms_per_step"] == {"min": d["ms_per_step"], "max": d["ms_per_step"], "ranks": 1}
     assert d["p50_ms_per_solve_batch1"] > 0 and d["latency_ticks"] == 6
     assert set(d["measurements"]) >= {"frozen_references", "walk"}
+
+
+def test_plain_run_measures_the_headline_only(cpu_lib):
+    """Without ``--full`` the line keeps its layout and its headline, and everything that takes runs of its own is null: no supplementary
+    measurement, no latency, no whole schedule, no download loop, no CPU baseline."""
+    out = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout
+    out, rows = _run(["--selftest-cpu", "--lib", cpu_lib] + SMALL)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert len(rows) == 1, "bench.py prints ONE JSON line"
+    d = json.loads(rows[0])
+    assert d["selftest"] is True and d["metric"].startswith("mpc_solves_per_sec") and d["unit"] == "solves/s" and d["higher_is_better"] is True
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f64"
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 0.02 * d["value"]
+    assert set(d["measurements"]) == {"frozen_references", "walk"}
+    assert d["value"] == min(m["value"] for m in d["measurements"].values())      # the headline is the lower of the two
+    for k in ("cpu_baseline", "whole_schedule", "whole_schedule_plain_warm_start", "whole_schedule_exact_iteration_budget", "value_with_result_download",
+              "p50_ms_per_solve_batch1", "p90_ms_per_solve_batch1", "p95_ms_per_solve_batch1"):
+        assert k in d and d[k] is None, k
+    assert d["latency_ticks"] == 0 and "--full" in d["cpu_baseline_note"]
+    assert d["per_rank_ms_per_step"] == {"min": d["ms_per_step"], "max": d["ms_per_step"], "ranks": 1}
 
 
 def test_gpus_n_launches_n_ranks(cpu_lib):

@@ -25,13 +25,13 @@ step rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_s2 -o pw -
 python3 tools/pmc/summarize.py $OUT/traffic_streams2.json $OUT/pmc_fetch_s2 $OUT/pmc_write_s2 $OUT/cal_fetch $OUT/cal_write 1073741824 > $OUT/traffic_streams2.log 2>&1 || { echo "summarize failed" >&2; exit 1; }
 # on the box: the bench lines below quote them (one launch of the default bench serves all 64 instances)
 cp $OUT/traffic.json profiles/traffic_b64_n100_complete.json; cp $OUT/traffic_streams2.json profiles/traffic_b32_n100_complete.json
-python3 bench.py > $OUT/bench.log 2> $OUT/bench.err || { echo "bench failed" >&2; tail -5 $OUT/bench.err; exit 1; }
+python3 bench.py --full > $OUT/bench.log 2> $OUT/bench.err || { echo "bench failed" >&2; tail -5 $OUT/bench.err; exit 1; }
 tail -c 3500 $OUT/bench.log
 python3 tools/overlap_report.py $TRACE 0.08 > $OUT/overlap_report.txt 2>&1
 python3 tools/overlap_report.py $TRACE 0.08 chain | tail -24 >> $OUT/overlap_report.txt 2>&1
-python3 bench.py --streams 2 --no-cpu-baseline --no-latency --no-whole-schedule > $OUT/bench_streams2.log 2>&1
-python3 bench.py --legs 8 --no-cpu-baseline --no-latency --no-whole-schedule > $OUT/bench_legs8.log 2>&1
-python3 bench.py --batch 256 --no-cpu-baseline --no-latency --no-whole-schedule > $OUT/bench_batch256.log 2>&1
+python3 bench.py --full --streams 2 --no-cpu-baseline --no-latency --no-whole-schedule > $OUT/bench_streams2.log 2>&1
+python3 bench.py --full --legs 8 --no-cpu-baseline --no-latency --no-whole-schedule > $OUT/bench_legs8.log 2>&1
+python3 bench.py --full --batch 256 --no-cpu-baseline --no-latency --no-whole-schedule > $OUT/bench_batch256.log 2>&1
 python3 tools/phase_timers.py > $OUT/phase_timers.txt 2>&1
 MPC_LEGS_CHAIN=1 python3 tools/legs_phase_timers.py 4 > $OUT/legs_phase_timers.txt 2>&1  # (the chain over the cuts: its kernel carries the phase timers of the elimination)
 python3 tools/config_sweep.py > $OUT/other_configs.txt 2>&1
