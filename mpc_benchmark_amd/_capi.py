@@ -12,6 +12,8 @@ import os
 
 import numpy as np
 
+from . import locomotion_metrics as _metrics
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPC_HIP_LIBRARY: developer override pointing at another build of the SAME HIP library (kernel tuning variants)
 HIP_LIBRARY_PATH = os.environ.get("MPC_HIP_LIBRARY") or os.path.join(_HERE, "csrc", "libmpc_hip.so")
@@ -133,6 +135,17 @@ _SIM_EXT_SIGNATURES = {
     "mpc_sim_record_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_metrics.h: exported by the HIP library alone, bound when present (``NativeSolver.metrics`` / ``read_metrics``)
+class MpcSimMetricsConfig(C.Structure):
+    _fields_ = [(n, C.c_double) for n in _metrics.DEFAULTS]
+
+
+_SIM_METRICS_SIGNATURES = {
+    "mpc_sim_metrics": (C.c_int, [C.c_void_p, C.POINTER(MpcSimMetricsConfig)]),
+    "mpc_sim_metrics_read": (C.c_int, [C.c_void_p, _DP, C.c_int32]),
+    "mpc_sim_metrics_width": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_feedback_pipeline.h: exported by the HIP library alone, bound when present (``NativeSolver.feedback_low_level_steps``)
 _FEEDBACK_PIPELINE_SIGNATURES = {
     "mpc_feedback_low_level_steps": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int32, C.c_double, _DP, _DP, _DP, _DP]),
@@ -146,7 +159,7 @@ def bind_library(path):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()):
+    for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -325,6 +338,34 @@ class NativeSolver:
         soles = out[:, :, o + 21:o + 45].reshape(S, B, 2, 12)
         return {"x": out[:, :, :nx], "tau": out[:, :, nx:o], "wrenches": out[:, :, o:o + 12].reshape(S, B, 2, 6), "com": out[:, :, o + 12:o + 15],
                 "momentum": out[:, :, o + 15:o + 21], "sole_R": soles[..., :9].reshape(S, B, 2, 3, 3), "sole_p": soles[..., 9:], "push": out[:, :, o + 45:o + 51]}
+
+    # -- include/mpc_sim_metrics.h (HIP library only): locomotion metrics of the torque-driven simulator steps ---------------------------------
+    def _sim_metrics(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the locomotion metrics of torque-driven simulator steps are HIP only "
+                               "(libmpc_hip.so, include/mpc_sim_metrics.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def metrics(self, cfg):
+        """Accumulate the locomotion metrics of every robot on the device after every torque-driven simulator step of this handle (mpc_sim_metrics):
+        ``cfg`` a dict over ``locomotion_metrics.DEFAULTS`` ({} for the defaults) turns them on and resets them; None turns them off."""
+        fn = self._sim_metrics("mpc_sim_metrics")
+        if cfg is None:
+            self._check(fn(self._h, None), "mpc_sim_metrics")
+            return
+        c = MpcSimMetricsConfig(*_metrics.config(cfg).values())
+        self._check(fn(self._h, C.byref(c)), "mpc_sim_metrics")
+
+    def read_metrics(self, reset=False):
+        """The metric rows since the last reset (mpc_sim_metrics_read) -> dict of (B,) arrays by ``locomotion_metrics.FIELDS`` name (``sole_z0``
+        (B, 2), ``com_first`` / ``com_last`` (B, 3)).  ``reset``: then zero them; the next step latches the heights again."""
+        fn = self._sim_metrics("mpc_sim_metrics_read")
+        w = self._sim_metrics("mpc_sim_metrics_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_metrics_width")
+        out = np.zeros((self.dims.batch, w))
+        self._check(fn(self._h, _dp(out), int(bool(reset))), "mpc_sim_metrics_read")
+        return _metrics.unpack(out)
 
     # -- include/mpc_feedback_pipeline.h (HIP library only): the low-level loop of the full-dynamics pipeline --------------------------------
     def feedback_low_level_steps(self, sim, steps, dt, x=None):

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <map>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +30,7 @@
 #include "pipeline_ikid_glue.h"
 #include "pipeline_fd_glue.h"
 #include "sim_record.h"
+#include "sim_metrics.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
 #include "qp_device_api.h"
@@ -126,6 +128,9 @@ struct mpc_solver {
   int push_width = 0;
   double* d_rec = nullptr;
   int rec_cap = 0, rec_count = 0;
+  // include/mpc_sim_metrics.h: the metric rows (nullptr: metrics off), [B][W] rows | [B] frozen flags | [B][nx] the state the next step starts from
+  double* d_met = nullptr;
+  mpc_sim_metrics_config met_cfg = {};
   // per-slot invalidation (mpc_update_stage_params*): slots whose parameters changed since the last pass was enqueued ; dirty_all:
   // an update on a horizon too long for the mask of SolverArgs
   std::vector<uint8_t> slot_dirty;
@@ -917,7 +922,7 @@ void mpc_destroy(mpc_solver* s) {
   for (int i = 0; i < mpc_solver::ASYNC_DEPTH; ++i) if (s->h_xnext[i]) (void)hipHostFree(s->h_xnext[i]);
   if (s->d_patch) (void)hipFree(s->d_patch);
   for (void* p : s->allocs) (void)hipFree(p);
-  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec}) if (p) (void)hipFree(p);
+  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec, s->d_met}) if (p) (void)hipFree(p);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1323,7 +1328,7 @@ static void sim_check(mpc_solver* s, const char* what) {
 }
 static const double* sim_push(const mpc_solver* s) { return s->push_width ? s->d_push : nullptr; }
 static int sim_push_width(const mpc_solver* s) { return s->push_width ? s->push_width : 3; }
-static double* sim_wrench_out(const mpc_solver* s, bool wanted) { return (wanted || s->rec_cap > 0) ? s->d_simwr : nullptr; }
+static double* sim_wrench_out(const mpc_solver* s, bool wanted) { return (wanted || s->rec_cap > 0 || s->d_met) ? s->d_simwr : nullptr; }
 // every one of the `steps` simulator steps about to be enqueued gets its record slot, or the call fails before anything is enqueued
 static void sim_record_reserve(const mpc_solver* s, int steps) {
   if (s->rec_cap > 0 && s->rec_count + steps > s->rec_cap)
@@ -1341,6 +1346,36 @@ static void sim_record_enqueue(mpc_solver* s, hipStream_t st) {
   hipLaunchKernelGGL(k_sim_record, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, r);
   HIP_OK(hipGetLastError());
   s->rec_count++;
+}
+// before the first simulator step of a call, on its stream (after the state is uploaded): the state that step starts from, for its joint power
+static void sim_metrics_begin(mpc_solver* s, hipStream_t st) {
+  if (!s->d_met) return;
+  const Layout& L = s->L;
+  HIP_OK(hipMemcpyAsync(s->d_met + (size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1), s->d_x0, (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+}
+// after a simulator step of length dt on stream st: its metrics (sim_metrics.h), when they are on
+static void sim_metrics_enqueue(mpc_solver* s, hipStream_t st, double dt) {
+  if (!s->d_met) return;
+  const Layout& L = s->L;
+  SimMetricsArgs m;
+  m.mi = s->d_model_i; m.md = s->d_model_d; m.nv = L.n / 2; m.nq = L.nx - L.n / 2;
+  m.x = s->d_x0; m.tau = s->d_simu; m.wr = s->d_simwr; m.dt = dt; m.cfg = s->met_cfg;
+  m.acc = s->d_met; m.frozen = s->d_met + (size_t)L.B * MPC_SIM_METRICS_WIDTH; m.xs = m.frozen + L.B;
+  hipLaunchKernelGGL(k_sim_metrics, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, m);
+  HIP_OK(hipGetLastError());
+}
+// the rows after a reset: nothing accumulated, no fall, nothing latched (the margin's minimum, the heights and the centres of mass NaN); not frozen
+static void sim_metrics_reset(mpc_solver* s) {
+  const Layout& L = s->L;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<double> h((size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1), 0.0);
+  for (int b = 0; b < L.B; ++b) {
+    double* r = h.data() + (size_t)b * MPC_SIM_METRICS_WIDTH;
+    r[6] = nan;
+    r[11] = -1.0;
+    for (int i = 12; i < MPC_SIM_METRICS_WIDTH; ++i) r[i] = nan;
+  }
+  copy_sync(s, s->d_met, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
 }
 
 int mpc_sim_set_push(mpc_solver* s, const double* f_ext, int32_t width) {
@@ -1392,6 +1427,52 @@ int mpc_sim_record_read(mpc_solver* s, double* out, int32_t* count) {
   })
 }
 
+int mpc_sim_metrics(mpc_solver* s, const mpc_sim_metrics_config* cfg) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_metrics");
+    const Layout& L = s->L;
+    if (cfg) {
+      if (s->h_model_i.size() < 5 || s->h_model_i[4] < 2)
+        throw std::runtime_error("sim_metrics: the model of the simulator handle must hold the two sole contacts (contacts 0 and 1)");
+      if (L.nj > CG_MAX_NJ) throw std::runtime_error("sim_metrics: more moving joints than the metrics kernel holds (64)");
+      for (double v : {cfg->min_force, cfg->half_length, cfg->half_width, cfg->fall_drop, cfg->sole_lift})
+        if (!std::isfinite(v) || v < 0.0) throw std::runtime_error("sim_metrics: every field of the configuration must be finite and >= 0");
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (s->d_met) { HIP_OK(hipFree(s->d_met)); s->d_met = nullptr; }
+    if (cfg) {
+      void* p = nullptr;
+      HIP_OK(hipMalloc(&p, (size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1 + L.nx) * sizeof(double)));
+      s->d_met = (double*)p;
+      s->met_cfg = *cfg;
+      if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
+      sim_metrics_reset(s);
+    }
+  })
+}
+
+int mpc_sim_metrics_read(mpc_solver* s, double* out, int32_t reset) {
+  MPC_TRY(s, {
+    if (!out) throw std::runtime_error("sim_metrics_read: out must not be null");
+    sim_check(s, "sim_metrics_read");
+    if (!s->d_met) throw std::runtime_error("sim_metrics_read: metrics are off on this handle (turn them on with mpc_sim_metrics)");
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, out, s->d_met, (size_t)s->L.B * MPC_SIM_METRICS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
+    if (reset) sim_metrics_reset(s);
+  })
+}
+
+int32_t mpc_sim_metrics_width(mpc_solver* s) {
+  if (!s) return -1;
+  try {
+    sim_check(s, "sim_metrics_width");
+    return MPC_SIM_METRICS_WIDTH;
+  } catch (const std::exception& e) {
+    s->err = e.what();
+    return -1;
+  }
+}
+
 int32_t mpc_sim_record_width(mpc_solver* s) {
   if (!s) return -1;
   try {
@@ -1414,10 +1495,12 @@ int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32
     if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
     if (x) copy_sync(s, s->d_x0, x, (size_t)L.B * L.nx * sizeof(double), hipMemcpyHostToDevice);
     copy_sync(s, s->d_simu, tau, (size_t)L.B * L.m * sizeof(double), hipMemcpyHostToDevice);
+    sim_metrics_begin(s, s->stream);
     launch_eval_multibody(s->stream, s->args(), s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, sim_push(s), true,
                           s->d_simu, sim_wrench_out(s, wrenches != nullptr), sim_push_width(s));
     HIP_OK(hipGetLastError());
     sim_record_enqueue(s, s->stream);
+    sim_metrics_enqueue(s, s->stream, substeps * dt);
     if (wrenches) copy_sync(s, wrenches, s->d_simwr, (size_t)L.B * 12 * sizeof(double), hipMemcpyDeviceToHost);
     s->perfect_feedback = false;
   })
@@ -1454,6 +1537,7 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
     double *d_xprev = scr, *d_fnew = scr + B * nx, *d_taumax = d_fnew + B * nf;
     hipStream_t st = q.stream;
     if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
+    sim_metrics_begin(sim, st);
     HIP_OK(hipMemcpyAsync(q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_taumax, tau_max, nu * sizeof(double), hipMemcpyHostToDevice, st));
     PipeArgs p;
@@ -1472,6 +1556,7 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
                             sim_wrench_out(sim, false), sim_push_width(sim));
       HIP_OK(hipGetLastError());
       sim_record_enqueue(sim, st);
+      sim_metrics_enqueue(sim, st, dt);
     }
     if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1527,6 +1612,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     if (!x_ik && !*kept) throw std::runtime_error("qp_ikid_low_level_steps: x_ik is NULL and no earlier call kept a measurement");
     hipStream_t st = q.stream;
     if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
+    sim_metrics_begin(sim, st);
     if (x_ik) HIP_OK(hipMemcpyAsync(d_xprev, x_ik, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_xpost, x_posture, nx * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1556,6 +1642,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
                             sim_wrench_out(sim, false), sim_push_width(sim));
       HIP_OK(hipGetLastError());
       sim_record_enqueue(sim, st);
+      sim_metrics_enqueue(sim, st, dt);
     }
     if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     if (c_prev) HIP_OK(hipMemcpyAsync(c_prev, d_cprev, B * CG_NC * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1599,6 +1686,7 @@ int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double
     if (x_prev && !sim->d_xlast) sim->d_xlast = sim->alloc<double>(B * nx);
     hipStream_t st = sim->stream;
     if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
+    sim_metrics_begin(sim, st);
     FdPipeArgs p;
     p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains;
     p.N = P.N; p.nx = nx; p.nv = Z.n / 2; p.nq = nx - Z.n / 2; p.n = P.n; p.m = nu; p.gain_stride = P.gain_stride; p.oK = P.oK;
@@ -1611,6 +1699,7 @@ int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double
                             sim_wrench_out(sim, wrenches != nullptr), sim_push_width(sim));
       HIP_OK(hipGetLastError());
       sim_record_enqueue(sim, st);
+      sim_metrics_enqueue(sim, st, dt);
     }
     if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, sim->d_xlast, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -20,6 +20,17 @@ struct SimRecordArgs {
   double* out;          // [B][rec] this step's slot of the ring
 };
 
+// placement of the sole of contact c (contacts 0 and 1 of the model: left, right) in the bodies K: its body's placement times the contact placement
+// (mpc_set_model contact table).  Shared with the metrics (sim_metrics.h).
+DEV void sim_sole_placement(const int32_t* mi, const double* md, const CgBodies& K, int c, M3& Rc, V3& pc) {
+  const int nj = mi[0], nframes = mi[3];
+  const int i = mi[MPC_MODEL_HEADER_WORDS + MPC_MODEL_JOINT_WORDS * nj + nframes + c];
+  const double* cm = md + MPC_MODEL_HEADER_DOUBLES + MPC_MODEL_JOINT_DOUBLES * nj + MPC_MODEL_FRAME_DOUBLES * nframes + MPC_MODEL_CONTACT_DOUBLES * c;
+  const M3 Ri = ldm3(K.oR + 9 * i);
+  Rc = mul(Ri, ldm3(cm));
+  pc = mul(Ri, ldv3(cm + 9)) + ldv3(K.op + 3 * i);
+}
+
 // rec = [x | tau | wrenches (2 x 6) | com (3) | hg (linear, angular about the com) | soles (2 x (R row-major, p)) | push (f, p)]
 __global__ void __launch_bounds__(CG_THREADS) k_sim_record(SimRecordArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, nx = a.nq + a.nv, nu = a.nv - 6;
@@ -37,13 +48,10 @@ __global__ void __launch_bounds__(CG_THREADS) k_sim_record(SimRecordArgs a) {
   if (tid < 12) o[tid] = a.wr[(size_t)b * 12 + tid];
   if (tid < CG_NC) o[12 + tid] = cx[tid];
   o += 12 + CG_NC;
-  if (tid < 2) {  // the sole of contact c: its body's placement times the contact placement (mpc_set_model contact table)
-    const int nj = a.mi[0], nframes = a.mi[3];
-    const int i = a.mi[MPC_MODEL_HEADER_WORDS + MPC_MODEL_JOINT_WORDS * nj + nframes + tid];
-    const double* cm = a.md + MPC_MODEL_HEADER_DOUBLES + MPC_MODEL_JOINT_DOUBLES * nj + MPC_MODEL_FRAME_DOUBLES * nframes + MPC_MODEL_CONTACT_DOUBLES * tid;
-    const M3 Ri = ldm3(K.oR + 9 * i);
-    const M3 Rc = mul(Ri, ldm3(cm));
-    const V3 pc = mul(Ri, ldv3(cm + 9)) + ldv3(K.op + 3 * i);
+  if (tid < 2) {
+    M3 Rc;
+    V3 pc;
+    sim_sole_placement(a.mi, a.md, K, tid, Rc, pc);
     double* so = o + 12 * tid;
     for (int e = 0; e < 9; ++e) so[e] = Rc.m[e];
     so[9] = pc.x; so[10] = pc.y; so[11] = pc.z;
