@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 
+from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -146,6 +147,18 @@ _SIM_METRICS_SIGNATURES = {
     "mpc_sim_metrics_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_contacts.h: exported by the HIP library alone, bound when present (``NativeSolver.contacts`` / ``read_contacts`` / ``set_contacts``)
+class MpcSimContactsConfig(C.Structure):
+    _fields_ = [("ground_z", C.c_double), ("ground_tol", C.c_double), ("release_force", C.c_double), ("release_steps", C.c_int32), ("reserved", C.c_int32)]
+
+
+_SIM_CONTACTS_SIGNATURES = {
+    "mpc_sim_contacts": (C.c_int, [C.c_void_p, C.POINTER(MpcSimContactsConfig)]),
+    "mpc_sim_contacts_set": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_contacts_read": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_contacts_width": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_feedback_pipeline.h: exported by the HIP library alone, bound when present (``NativeSolver.feedback_low_level_steps``)
 _FEEDBACK_PIPELINE_SIGNATURES = {
     "mpc_feedback_low_level_steps": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int32, C.c_double, _DP, _DP, _DP, _DP]),
@@ -159,7 +172,8 @@ def bind_library(path):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()):
+    for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
+            list(_SIM_CONTACTS_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -366,6 +380,44 @@ class NativeSolver:
         out = np.zeros((self.dims.batch, w))
         self._check(fn(self._h, _dp(out), int(bool(reset))), "mpc_sim_metrics_read")
         return _metrics.unpack(out)
+
+    # -- include/mpc_sim_contacts.h (HIP library only): the unilateral contact rule of the torque-driven simulator steps ------------------------
+    def _sim_contacts(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the contact rule of torque-driven simulator steps is HIP only "
+                               "(libmpc_hip.so, include/mpc_sim_contacts.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def contacts(self, cfg):
+        """Decide every robot's foot contacts on the device after every torque-driven simulator step of this handle (mpc_sim_contacts): ``cfg`` a
+        dict over ``contact_rule.DEFAULTS`` ({} for the defaults) turns the rule on and resets it (both soles in contact at the model's anchors);
+        None turns it off.  While it is on, stage 0 of this handle must be the double-support stage."""
+        fn = self._sim_contacts("mpc_sim_contacts")
+        if cfg is None:
+            self._check(fn(self._h, None), "mpc_sim_contacts")
+            return
+        c = _contact_rule.config(cfg)
+        cc = MpcSimContactsConfig(c["ground_z"], c["ground_tol"], c["release_force"], c["release_steps"], 0)
+        self._check(fn(self._h, C.byref(cc)), "mpc_sim_contacts")
+
+    def read_contacts(self, raw=False):
+        """The rows of the contact rule (mpc_sim_contacts_read) -> dict of arrays by ``contact_rule.FIELDS`` name (``anchor_R`` (B, 2, 3, 3),
+        ``anchor_p`` (B, 2, 3)); ``raw``: the (B, WIDTH) rows themselves."""
+        fn = self._sim_contacts("mpc_sim_contacts_read")
+        w = self._sim_contacts("mpc_sim_contacts_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_contacts_width")
+        out = np.zeros((self.dims.batch, w))
+        self._check(fn(self._h, _dp(out)), "mpc_sim_contacts_read")
+        return out if raw else _contact_rule.unpack(out)
+
+    def set_contacts(self, rows):
+        """Impose the rows of the contact rule (mpc_sim_contacts_set): (B, WIDTH), e.g. ``read_contacts(raw=True)`` of an earlier point."""
+        fn = self._sim_contacts("mpc_sim_contacts_set")
+        r = _f64(rows)
+        if r.shape != (self.dims.batch, _contact_rule.WIDTH):
+            raise ValueError("set_contacts: rows of shape (%d, %d) expected, got %s" % (self.dims.batch, _contact_rule.WIDTH, r.shape))
+        self._check(fn(self._h, _dp(r)), "mpc_sim_contacts_set")
 
     # -- include/mpc_feedback_pipeline.h (HIP library only): the low-level loop of the full-dynamics pipeline --------------------------------
     def feedback_low_level_steps(self, sim, steps, dt, x=None):

@@ -11,7 +11,9 @@ plane z = 0 ... and pushes on it: a contact whose normal force stays below ``-re
 transient — the torque jump of the low-level QP when a stage changes its contact state — only unloads a real sole for a millisecond, it does not
 lift it), a free foot that has left the ground and comes back to it, or that sinks below the ground plane, is caught there (its world-side
 placement is re-captured at the landing pose).  That is a deliberately simple contact rule — enough to close the loop around the MPC headlessly
-and deterministically; it is not a physics engine.
+and deterministically; it is not a physics engine.  ``device_contacts=True`` (HIP library only) runs the same rule on the device after every step
+(mpc_sim_contacts, include/mpc_sim_contacts.h): stage 0 stays the double-support stage, the rule picks the contacts and their ground-side
+placements, and a catch needs no new model.
 
 Differences from PyBullet worth knowing: ``measureState`` returns the base velocity in the LOCAL frame of the base (Pinocchio's
 convention, which is what the scripts assume when they copy it into the state, talos_utils.py:337-348); PyBullet reports it in the
@@ -38,7 +40,8 @@ class BulletRobot:
     record_default = False  # tools: keep (state, contact flags, sole heights) of every step in ``history``
 
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
-                 inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0):
+                 inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
+                 device_contacts=False):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -49,6 +52,7 @@ class BulletRobot:
         self.ground_tol = float(ground_tol)
         self.release_steps = int(release_steps)
         self.release_force = float(release_force)  # N: the ground "pulls" when the normal force is below minus this
+        self.device_contacts = bool(device_contacts)  # the contact rule on the device (in_contact and the rest are read back after every step)
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
         self._native = None
@@ -88,6 +92,10 @@ class BulletRobot:
         self._pulling = [0, 0]   # consecutive steps with a negative normal force
         self._contact_pose = [self.data.oMf[f].copy() for f in self.frame_ids]
         self._build_native()
+        if self.device_contacts:  # stage 0 is double support once; the rule on the device picks each step's contacts
+            self._upload_mask()
+            self._native.contacts({"ground_z": self.ground_z, "ground_tol": self.ground_tol, "release_force": self.release_force,
+                                   "release_steps": self.release_steps})
 
     def _contact_models(self):
         m = self.model
@@ -148,7 +156,8 @@ class BulletRobot:
         m = self.model
         if tau.size != m.nv - 6:
             raise ValueError("expected %d joint torques, got %d" % (m.nv - 6, tau.size))
-        self._upload_mask()
+        if not self.device_contacts:
+            self._upload_mask()
         push = self._pending_force
         if push is not None:  # (apply_force: the push of the scripts, e.g. kinodynamic_talos.py:459-461 — a world force at a world point, this step only)
             if not hasattr(self._native.lib, "mpc_sim_set_push"):
@@ -166,7 +175,10 @@ class BulletRobot:
         if self.trace_from is not None and self.steps >= self.trace_from:
             import sys
             sys.stderr.write("   [sim] step %d in_contact %s fz L %.2f R %.2f z %s\n" % (self.steps, self.in_contact, wr[0][0][2], wr[0][1][2], ["%.4f" % v for v in self._z_prev]))
-        self._update_contacts(wr[0])
+        if self.device_contacts:
+            self._read_device_contacts()
+        else:
+            self._update_contacts(wr[0])
         if self.record:
             self.history.append((self.x.copy(), tuple(self.in_contact), tuple(self._z_prev)))
 
@@ -198,6 +210,14 @@ class BulletRobot:
             self._z_prev[i] = z
         if relanded:
             self._build_native()
+
+    def _read_device_contacts(self):
+        """``in_contact`` and the rule's per-foot state after a step, from the device rows (mpc_sim_contacts_read)."""
+        r = self._native.read_contacts()
+        self.in_contact = [bool(v) for v in r["in_contact"][0]]
+        self._lifted = [bool(v) for v in r["lifted"][0]]
+        self._pulling = [int(v) for v in r["pulling"][0]]
+        self._z_prev = [float(v) for v in r["z_prev"][0]]
 
     def measureState(self):
         """-> (q, v) of the COMPLETE model (bullet_robot.py:172-196): locked joints at their initial positions, zero velocity."""

@@ -1,0 +1,113 @@
+"""The unilateral foot-contact rule of the torque-driven simulator, in numpy: one step for B robots.  It is the definition the device rule
+(``mpc_sim_contacts``, include/mpc_sim_contacts.h; ``NativeSolver.contacts`` / ``read_contacts`` / ``set_contacts``) is held to, and it is
+``BulletRobot._update_contacts`` applied to a batch, in the same order:
+
+  feet 0 (left), then 1 (right); foot 0's release already counts for foot 1's "other foot in contact" test of the same step;
+  - a foot in contact: ``pulling`` counts the consecutive steps whose LOCAL-frame normal force is below ``-release_force``; at
+    ``release_steps`` the foot is released if the other foot is in contact (the last contact is never released), and ``lifted`` clears;
+  - a free foot: above ``ground_z + 2 ground_tol`` it has ``lifted``; it is caught when it is back within ``ground_tol`` of the ground after
+    lifting, or when it sinks below the ground plane (``z < ground_z`` and lower than the step before); the ground side of the caught contact
+    is its landing pose flattened onto the plane: ``p = (x, y, ground_z)``, ``R = Rz(yaw)``;
+  - ``z_prev`` of both feet becomes this step's sole height.
+
+A robot's state is one row of ``WIDTH`` doubles (the layout of include/mpc_sim_contacts.h, ``FIELDS``)."""
+from __future__ import annotations
+
+import numpy as np
+
+# (name, doubles) in the order of a row; MPC_SIM_CONTACTS_WIDTH = 41
+FIELDS = (("in_contact", 2), ("lifted", 2), ("pulling", 2), ("z_prev", 2), ("anchor", 24), ("touchdowns", 2), ("liftoffs", 2),
+          ("last_touchdown", 2), ("last_liftoff", 2), ("steps", 1))
+WIDTH = sum(w for _, w in FIELDS)
+O_IN, O_LIFTED, O_PULLING, O_ZPREV, O_ANCHOR, O_TD, O_LO, O_LAST_TD, O_LAST_LO, O_STEPS = 0, 2, 4, 6, 8, 32, 34, 36, 38, 40
+
+# mpc_sim_contacts_config, in the order of its fields (``reserved`` is not a setting)
+DEFAULTS = {
+    "ground_z": 0.0,        # m: the ground plane (BulletRobot: the lower sole at initializeJoints; the pipelines: the lower initial foothold)
+    "ground_tol": 5e-3,     # m: BulletRobot's ground_tol
+    "release_force": 1.0,   # N: a contact pulls when its LOCAL-frame f_z < -release_force
+    "release_steps": 5,     # consecutive pulling steps before the release (>= 1)
+}
+
+
+def config(cfg=None, ground_z=None):
+    """``cfg`` (dict or None) over ``DEFAULTS``; unknown keys are an error.  ``ground_z``: the default of the ground height when ``cfg`` names none."""
+    out = dict(DEFAULTS)
+    if ground_z is not None:
+        out["ground_z"] = float(ground_z)
+    if cfg:
+        bad = sorted(set(cfg) - set(DEFAULTS))
+        if bad:
+            raise ValueError("contact rule: unknown configuration keys %s (known: %s)" % (bad, ", ".join(DEFAULTS)))
+        out.update(cfg)
+    for k in out:
+        out[k] = int(out[k]) if k == "release_steps" else float(out[k])
+    return out
+
+
+def unpack(rows):
+    """(B, WIDTH) rows -> dict of arrays by ``FIELDS`` name: flags and counters (B, 2) (``steps`` (B,)), ``anchor_R`` (B, 2, 3, 3), ``anchor_p`` (B, 2, 3)."""
+    rows = np.asarray(rows, dtype=float)
+    out, o = {}, 0
+    for name, w in FIELDS:
+        out[name] = rows[:, o] if w == 1 else rows[:, o:o + w]
+        o += w
+    a = out.pop("anchor").reshape(-1, 2, 12)
+    out["anchor_R"], out["anchor_p"] = a[..., :9].reshape(-1, 2, 3, 3), a[..., 9:]
+    return out
+
+
+def reset_rows(anchor_R, anchor_p):
+    """The rows after ``mpc_sim_contacts(cfg)``: both soles in contact at the anchors (R (B, 2, 3, 3) or (2, 3, 3), p (B, 2, 3) or (2, 3): the model's
+    ground-side contact placements), nothing counted, ``z_prev`` the anchors' heights, no touchdown or lift-off yet (step index -1)."""
+    R = np.asarray(anchor_R, dtype=float).reshape(-1, 2, 9)
+    p = np.asarray(anchor_p, dtype=float).reshape(-1, 2, 3)
+    B = max(R.shape[0], p.shape[0])
+    R, p = np.broadcast_to(R, (B, 2, 9)), np.broadcast_to(p, (B, 2, 3))
+    r = np.zeros((B, WIDTH))
+    r[:, O_IN:O_IN + 2] = 1.0
+    r[:, O_ZPREV:O_ZPREV + 2] = p[..., 2]
+    r[:, O_ANCHOR:O_ANCHOR + 24] = np.concatenate([R, p], axis=-1).reshape(-1, 24)
+    r[:, O_LAST_TD:O_LAST_LO + 2] = -1.0
+    return r
+
+
+def flatten(R, p, ground_z):
+    """The landing pose of a sole flattened onto the ground plane: (Rz(yaw), (x, y, ground_z)), yaw = atan2(R[1, 0], R[0, 0])."""
+    yaw = np.arctan2(R[1, 0], R[0, 0])
+    c, s = np.cos(yaw), np.sin(yaw)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]), np.array([p[0], p[1], ground_z])
+
+
+def step(rows, sole_z, fz, sole_R, sole_p, cfg=None):
+    """One step of the rule for B robots -> the new rows (a copy).  rows (B, WIDTH); sole_z (B, 2) the sole heights of the state AFTER the step;
+    fz (B, 2) the step's LOCAL-frame normal forces (0 for a free foot); sole_R (B, 2, 3, 3), sole_p (B, 2, 3) the sole placements after the step
+    (only a catch reads them); ``cfg`` over ``DEFAULTS``."""
+    c = config(cfg)
+    gz, tol, rf, rs = c["ground_z"], c["ground_tol"], c["release_force"], c["release_steps"]
+    r = np.array(rows, dtype=float, copy=True).reshape(-1, WIDTH)
+    sole_z, fz = np.asarray(sole_z, dtype=float).reshape(-1, 2), np.asarray(fz, dtype=float).reshape(-1, 2)
+    sole_R, sole_p = np.asarray(sole_R, dtype=float).reshape(-1, 2, 3, 3), np.asarray(sole_p, dtype=float).reshape(-1, 2, 3)
+    for b in range(r.shape[0]):
+        row = r[b]
+        n = row[O_STEPS]
+        for i in range(2):
+            z = sole_z[b, i]
+            if row[O_IN + i] != 0.0:
+                row[O_PULLING + i] = row[O_PULLING + i] + 1.0 if fz[b, i] < -rf else 0.0
+                if row[O_PULLING + i] >= rs and row[O_IN] + row[O_IN + 1] > 1.0:
+                    row[O_IN + i] = row[O_LIFTED + i] = row[O_PULLING + i] = 0.0
+                    row[O_LO + i] += 1.0
+                    row[O_LAST_LO + i] = n
+            elif z > gz + 2.0 * tol:
+                row[O_LIFTED + i] = 1.0
+            elif (z <= gz + tol and row[O_LIFTED + i] != 0.0) or (z < gz and z < row[O_ZPREV + i]):
+                R, p = flatten(sole_R[b, i], sole_p[b, i], gz)
+                row[O_ANCHOR + 12 * i:O_ANCHOR + 12 * i + 9] = R.reshape(-1)
+                row[O_ANCHOR + 12 * i + 9:O_ANCHOR + 12 * i + 12] = p
+                row[O_IN + i] = 1.0
+                row[O_TD + i] += 1.0
+                row[O_LAST_TD + i] = n
+            row[O_ZPREV + i] = z
+        row[O_STEPS] = n + 1.0
+    return r

@@ -251,7 +251,15 @@ __global__ void __launch_bounds__(EVAL_THREADS, EVAL_MIN_WAVES) k_eval_multibody
   if (has_dyn && !S.contact_dyn) { if (threadIdx.x == 0) a.inst[b].done = 5; return; }  // (host bug guard: this carve-out has no room for the factor of M)
   const bool kino = dyn == MPC_DYN_KINODYNAMICS_SEMIEULER;               // kinodynamics: u = [wrenches ; joint accelerations]
   const int m = (has_dyn || kino) ? nu : 0, nz = n + m, nterms = desc[5], c = desc[6];
-  const int nk = has_dyn ? desc[1] : 0, nl = 6 * nk;
+  int nk_ = has_dyn ? desc[1] : 0;
+  if constexpr (TRIAL == 2) {  // the contact rule (include/mpc_sim_contacts.h): robot b's soles in contact, in descriptor order
+    if (has_dyn && mb.sim_contacts) {
+      const double* cr = mb.sim_contacts + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
+      nk_ = 0;
+      for (int j = 0; j < desc[1]; ++j) nk_ += (desc[2 + j] < 2 && cr[desc[2 + j]] != 0.0) ? 1 : 0;
+    }
+  }
+  const int nk = nk_, nl = 6 * nk;
   const unsigned mg_nz = m ? S.mg_nz : S.mg_n;  // nz = n + nu on a stage with dynamics, n on the terminal knot
   const bool derivs = (TRIAL == 0 || TRIAL == 3);
 cand_loop:  // (TRIAL == 1 with mb.ncand_loop: next backtracking candidate of the same knot)
@@ -341,7 +349,17 @@ cand_loop:  // (TRIAL == 1 with mb.ncand_loop: next backtracking candidate of th
       below[i] = gmask[3 * nj + i];
     }
     if (tid == 0) s_cost = 0.0;
-    if (has_dyn && tid < nk) { const int cid = desc[2 + tid]; ccid_s[tid] = cid; cbody_s[tid] = mcontact[cid]; }
+    if (has_dyn && tid < nk) {
+      int cid = desc[2 + tid];
+      if constexpr (TRIAL == 2) {
+        if (mb.sim_contacts) {  // the tid-th contact of the descriptor that robot b's row holds
+          const double* cr = mb.sim_contacts + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
+          for (int j = 0, seen = 0; j < desc[1]; ++j)
+            if (desc[2 + j] < 2 && cr[desc[2 + j]] != 0.0 && seen++ == tid) { cid = desc[2 + j]; break; }
+        }
+      }
+      ccid_s[tid] = cid; cbody_s[tid] = mcontact[cid];
+    }
   }
   // model constants of body `tid`, requested here: their round trip to L2 overlaps the loads above and the barrier
   // (the kernels with derivatives only: the value-only candidates are short of registers right here)
@@ -462,8 +480,12 @@ sim_u_set:
     double* cf = cfr + 54 * cc;
     for (int e = 0; e < 9; ++e) cf[e] = Rc.m[e];
     cf[9] = pc.x; cf[10] = pc.y; cf[11] = pc.z;
-    const M3 R2 = ldm3(cm + 12);
-    const V3 p2 = ldv3(cm + 21);
+    const double* gside = cm + 12;  // ground side of the contact: R2 (row-major), p2 at + 9
+    if constexpr (TRIAL == 2) {
+      if (mb.sim_contacts) gside = mb.sim_contacts + (size_t)b * MPC_SIM_CONTACTS_WIDTH + 8 + 12 * cid;  // robot b's anchor of the sole
+    }
+    const M3 R2 = ldm3(gside);
+    const V3 p2 = ldv3(gside + 9);
     V3 ev, ew;
     log6(tmul(Rc, R2), tmul(Rc, p2 - pc), ev, ew);
     gam[6 * cc] = ev.x; gam[6 * cc + 1] = ev.y; gam[6 * cc + 2] = ev.z; gam[6 * cc + 3] = ew.x; gam[6 * cc + 4] = ew.y; gam[6 * cc + 5] = ew.z;

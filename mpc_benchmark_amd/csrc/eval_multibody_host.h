@@ -3,6 +3,7 @@
 #pragma once
 #include <stdexcept>
 #include "solver_args.h"
+#include "../../include/mpc_sim_contacts.h"
 
 #ifndef EVAL_THREADS
 #define EVAL_THREADS 256  // threads per stage workgroup: 4 wavefronts, two workgroups per CU (measured against 512 = 8 wavefronts with a 128-VGPR cap, profiles/r03_*)
@@ -125,6 +126,8 @@ struct MbArgs {
   const double* sim_u;    // TRIAL == 2: joint torques per instance [B][nu] held during the call (mpc_simulate_torque: the start state is
                           // then a.x0, no feedback law), or nullptr
   double* sim_wrench;     // TRIAL == 2: contact wrenches of the last sub-step [B][2][6], or nullptr
+  const double* sim_contacts;  // TRIAL == 2: the rows of the contact rule [B][MPC_SIM_CONTACTS_WIDTH] (include/mpc_sim_contacts.h), or nullptr:
+                               // each robot integrates the contacts of stage 0 its row holds, at the row's anchors
 };
 
 
@@ -132,5 +135,5 @@ struct MbArgs {
 void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
                            bool trial, int cand0 = 0, int ncand = 1, int sim_substeps = 0, double sim_dt = 0.0, bool with_derivs = false,
                            const double* f_ext = nullptr, bool contact_dyn = true, const double* sim_u = nullptr, double* sim_wrench = nullptr,
-                           int f_ext_width = 3);
+                           int f_ext_width = 3, const double* sim_contacts = nullptr);
 const void* eval_multibody_kernel(int trial);  // entry point of k_eval_multibody<trial> (occupancy tooling)

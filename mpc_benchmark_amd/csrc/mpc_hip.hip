@@ -31,6 +31,7 @@
 #include "pipeline_fd_glue.h"
 #include "sim_record.h"
 #include "sim_metrics.h"
+#include "sim_contacts.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
 #include "qp_device_api.h"
@@ -131,6 +132,9 @@ struct mpc_solver {
   // include/mpc_sim_metrics.h: the metric rows (nullptr: metrics off), [B][W] rows | [B] frozen flags | [B][nx] the state the next step starts from
   double* d_met = nullptr;
   mpc_sim_metrics_config met_cfg = {};
+  // include/mpc_sim_contacts.h: the rows of the contact rule (nullptr: rule off, stage 0 decides the contacts), [B][W]
+  double* d_con = nullptr;
+  mpc_sim_contacts_config con_cfg = {};
   // per-slot invalidation (mpc_update_stage_params*): slots whose parameters changed since the last pass was enqueued ; dirty_all:
   // an update on a horizon too long for the mask of SolverArgs
   std::vector<uint8_t> slot_dirty;
@@ -922,7 +926,7 @@ void mpc_destroy(mpc_solver* s) {
   for (int i = 0; i < mpc_solver::ASYNC_DEPTH; ++i) if (s->h_xnext[i]) (void)hipHostFree(s->h_xnext[i]);
   if (s->d_patch) (void)hipFree(s->d_patch);
   for (void* p : s->allocs) (void)hipFree(p);
-  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec, s->d_met}) if (p) (void)hipFree(p);
+  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec, s->d_met, s->d_con}) if (p) (void)hipFree(p);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1328,7 +1332,7 @@ static void sim_check(mpc_solver* s, const char* what) {
 }
 static const double* sim_push(const mpc_solver* s) { return s->push_width ? s->d_push : nullptr; }
 static int sim_push_width(const mpc_solver* s) { return s->push_width ? s->push_width : 3; }
-static double* sim_wrench_out(const mpc_solver* s, bool wanted) { return (wanted || s->rec_cap > 0 || s->d_met) ? s->d_simwr : nullptr; }
+static double* sim_wrench_out(const mpc_solver* s, bool wanted) { return (wanted || s->rec_cap > 0 || s->d_met || s->d_con) ? s->d_simwr : nullptr; }
 // every one of the `steps` simulator steps about to be enqueued gets its record slot, or the call fails before anything is enqueued
 static void sim_record_reserve(const mpc_solver* s, int steps) {
   if (s->rec_cap > 0 && s->rec_count + steps > s->rec_cap)
@@ -1376,6 +1380,46 @@ static void sim_metrics_reset(mpc_solver* s) {
     for (int i = 12; i < MPC_SIM_METRICS_WIDTH; ++i) r[i] = nan;
   }
   copy_sync(s, s->d_met, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+}
+// with the contact rule on, stage 0 must be the double-support stage: the rule picks each robot's contacts out of its two (checked by every
+// stepping call before anything is enqueued)
+static void sim_contacts_check(const mpc_solver* s, const char* what) {
+  if (!s->d_con) return;
+  const int32_t* d = s->h_desc.data() + (size_t)slot_of(s, 0) * s->L.max_stage_ints;
+  if (d[0] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER || d[1] != 2 || !((d[2] == 0 && d[3] == 1) || (d[2] == 1 && d[3] == 0)))
+    throw std::runtime_error(std::string(what) + ": the contact rule is on (mpc_sim_contacts), so stage 0 of the simulator handle must be the double-support "
+                             "stage (contact dynamics of contacts 0 and 1)");
+}
+static const double* sim_contacts_rows(const mpc_solver* s) { return s->d_con; }
+// after a simulator step on stream st (after its record and metrics): the contact rule (sim_contacts.h), when it is on
+static void sim_contacts_enqueue(mpc_solver* s, hipStream_t st) {
+  if (!s->d_con) return;
+  const Layout& L = s->L;
+  SimContactsArgs c;
+  c.mi = s->d_model_i; c.md = s->d_model_d; c.nv = L.n / 2; c.nq = L.nx - L.n / 2;
+  c.x = s->d_x0; c.wr = s->d_simwr; c.cfg = s->con_cfg; c.rows = s->d_con;
+  hipLaunchKernelGGL(k_sim_contacts, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, c);
+  HIP_OK(hipGetLastError());
+}
+// the rows after a reset: both soles in contact at the model's ground-side placements (contacts 0 and 1), nothing counted
+static void sim_contacts_reset(mpc_solver* s) {
+  const Layout& L = s->L;
+  const int nj = s->h_model_i[0], nframes = s->h_model_i[3];
+  const size_t off = MPC_MODEL_HEADER_DOUBLES + (size_t)MPC_MODEL_JOINT_DOUBLES * nj + (size_t)MPC_MODEL_FRAME_DOUBLES * nframes;
+  double cm[2 * MPC_MODEL_CONTACT_DOUBLES];
+  copy_sync(s, cm, s->d_model_d + off, sizeof(cm), hipMemcpyDeviceToHost);
+  std::vector<double> h((size_t)L.B * MPC_SIM_CONTACTS_WIDTH, 0.0);
+  for (int b = 0; b < L.B; ++b) {
+    double* r = h.data() + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
+    for (int i = 0; i < 2; ++i) {
+      const double* c = cm + MPC_MODEL_CONTACT_DOUBLES * i;
+      r[i] = 1.0;
+      r[6 + i] = c[23];                                          // z_prev: the anchor's height
+      for (int e = 0; e < 12; ++e) r[8 + 12 * i + e] = c[12 + e];  // R2 (9), p2 (3)
+      r[36 + i] = r[38 + i] = -1.0;
+    }
+  }
+  copy_sync(s, s->d_con, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
 }
 
 int mpc_sim_set_push(mpc_solver* s, const double* f_ext, int32_t width) {
@@ -1473,6 +1517,87 @@ int32_t mpc_sim_metrics_width(mpc_solver* s) {
   }
 }
 
+int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_contacts");
+    const Layout& L = s->L;
+    if (cfg) {
+      if (s->h_model_i.size() < 5 || s->h_model_i[4] < 2)
+        throw std::runtime_error("sim_contacts: the model of the simulator handle must hold the two sole contacts (contacts 0 and 1)");
+      if (L.nj > CG_MAX_NJ) throw std::runtime_error("sim_contacts: more moving joints than the contact-rule kernel holds (64)");
+      if (!std::isfinite(cfg->ground_z) || !std::isfinite(cfg->ground_tol) || !std::isfinite(cfg->release_force))
+        throw std::runtime_error("sim_contacts: ground_z, ground_tol and release_force must be finite");
+      if (cfg->ground_tol < 0.0 || cfg->release_force < 0.0) throw std::runtime_error("sim_contacts: ground_tol and release_force must be >= 0");
+      if (cfg->release_steps < 1) throw std::runtime_error("sim_contacts: release_steps must be >= 1");
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (s->d_con) { HIP_OK(hipFree(s->d_con)); s->d_con = nullptr; }
+    if (cfg) {
+      void* p = nullptr;
+      HIP_OK(hipMalloc(&p, (size_t)L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double)));
+      s->d_con = (double*)p;
+      s->con_cfg = *cfg;
+      s->con_cfg.reserved = 0;
+      if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
+      sim_contacts_reset(s);
+    }
+  })
+}
+
+int mpc_sim_contacts_set(mpc_solver* s, const double* rows) {
+  MPC_TRY(s, {
+    if (!rows) throw std::runtime_error("sim_contacts_set: rows must not be null");
+    sim_check(s, "sim_contacts_set");
+    if (!s->d_con) throw std::runtime_error("sim_contacts_set: the contact rule is off on this handle (turn it on with mpc_sim_contacts)");
+    const Layout& L = s->L;
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = rows + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
+      const std::string row = "sim_contacts_set: row " + std::to_string(b);
+      for (int e = 0; e < MPC_SIM_CONTACTS_WIDTH; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      for (int e = 0; e < 4; ++e)
+        if (r[e] != 0.0 && r[e] != 1.0) throw std::runtime_error(row + ": in_contact and lifted must be 0 or 1");
+      if (r[0] == 0.0 && r[1] == 0.0) throw std::runtime_error(row + " has no sole in contact (flight phases are not simulated)");
+      for (int e : {4, 5, 32, 33, 34, 35, 40})
+        if (r[e] < 0.0) throw std::runtime_error(row + ": pulling, the counts and steps must be >= 0");
+      for (int i = 0; i < 2; ++i) {
+        const double* R = r + 8 + 12 * i;
+        double dev = 0.0;
+        for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) {
+          double d = (a == c) ? -1.0 : 0.0;
+          for (int k = 0; k < 3; ++k) d += R[3 * k + a] * R[3 * k + c];
+          dev = std::fmax(dev, std::fabs(d));
+        }
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (dev > 1e-9 || det < 0.0) throw std::runtime_error(row + ": the anchor of sole " + std::to_string(i) + " is not a rotation");
+      }
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, s->d_con, rows, (size_t)L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+int mpc_sim_contacts_read(mpc_solver* s, double* rows) {
+  MPC_TRY(s, {
+    if (!rows) throw std::runtime_error("sim_contacts_read: rows must not be null");
+    sim_check(s, "sim_contacts_read");
+    if (!s->d_con) throw std::runtime_error("sim_contacts_read: the contact rule is off on this handle (turn it on with mpc_sim_contacts)");
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, rows, s->d_con, (size_t)s->L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int32_t mpc_sim_contacts_width(mpc_solver* s) {
+  if (!s) return -1;
+  try {
+    sim_check(s, "sim_contacts_width");
+    return MPC_SIM_CONTACTS_WIDTH;
+  } catch (const std::exception& e) {
+    s->err = e.what();
+    return -1;
+  }
+}
+
 int32_t mpc_sim_record_width(mpc_solver* s) {
   if (!s) return -1;
   try {
@@ -1492,15 +1617,17 @@ int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32
       throw std::runtime_error("simulate: only contact-constrained whole-body dynamics are supported");
     const Layout& L = s->L;
     sim_record_reserve(s, 1);
+    sim_contacts_check(s, "simulate_torque");
     if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
     if (x) copy_sync(s, s->d_x0, x, (size_t)L.B * L.nx * sizeof(double), hipMemcpyHostToDevice);
     copy_sync(s, s->d_simu, tau, (size_t)L.B * L.m * sizeof(double), hipMemcpyHostToDevice);
     sim_metrics_begin(s, s->stream);
     launch_eval_multibody(s->stream, s->args(), s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, sim_push(s), true,
-                          s->d_simu, sim_wrench_out(s, wrenches != nullptr), sim_push_width(s));
+                          s->d_simu, sim_wrench_out(s, wrenches != nullptr), sim_push_width(s), sim_contacts_rows(s));
     HIP_OK(hipGetLastError());
     sim_record_enqueue(s, s->stream);
     sim_metrics_enqueue(s, s->stream, substeps * dt);
+    sim_contacts_enqueue(s, s->stream);
     if (wrenches) copy_sync(s, wrenches, s->d_simwr, (size_t)L.B * 12 * sizeof(double), hipMemcpyDeviceToHost);
     s->perfect_feedback = false;
   })
@@ -1529,6 +1656,7 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
       throw std::runtime_error("qp_low_level_steps: the simulator handle must hold whole-body contact dynamics with nu = nv - 6 (the handle of mpc_simulate_torque)");
     if (plan->async_pending > 0) throw std::runtime_error("qp_low_level_steps: the plan has ticks in flight (mpc_wait first)");
     sim_record_reserve(sim, steps);
+    sim_contacts_check(sim, "qp_low_level_steps");
     HIP_OK(hipStreamSynchronize(plan->stream));
     HIP_OK(hipStreamSynchronize(sim->stream));
     if (!sim->d_simu) { sim->d_simu = sim->alloc<double>((size_t)Z.B * Z.m); sim->d_simwr = sim->alloc<double>((size_t)Z.B * 12); HIP_OK(hipStreamSynchronize(sim->stream)); }
@@ -1553,10 +1681,11 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
       qp_launch_solve(qp, S);
       hipLaunchKernelGGL(k_pipe_torque, dim3((unsigned)B), dim3(64), 0, st, p);
       launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
-                            sim_wrench_out(sim, false), sim_push_width(sim));
+                            sim_wrench_out(sim, false), sim_push_width(sim), sim_contacts_rows(sim));
       HIP_OK(hipGetLastError());
       sim_record_enqueue(sim, st);
       sim_metrics_enqueue(sim, st, dt);
+      sim_contacts_enqueue(sim, st);
     }
     if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1601,6 +1730,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     if (q.nj > CG_MAX_NJ) throw std::runtime_error("qp_ikid_low_level_steps: more moving joints than the glue kernels hold (64)");
     if (plan->async_pending > 0) throw std::runtime_error("qp_ikid_low_level_steps: the plan has ticks in flight (mpc_wait first)");
     sim_record_reserve(sim, steps);
+    sim_contacts_check(sim, "qp_ikid_low_level_steps");
     HIP_OK(hipStreamSynchronize(plan->stream));
     HIP_OK(hipStreamSynchronize(sim->stream));
     if (!sim->d_simu) { sim->d_simu = sim->alloc<double>((size_t)Z.B * Z.m); sim->d_simwr = sim->alloc<double>((size_t)Z.B * 12); HIP_OK(hipStreamSynchronize(sim->stream)); }
@@ -1639,10 +1769,11 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
       qp_launch_solve(qp, S);
       hipLaunchKernelGGL(k_pipe_ikid_torque, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
       launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
-                            sim_wrench_out(sim, false), sim_push_width(sim));
+                            sim_wrench_out(sim, false), sim_push_width(sim), sim_contacts_rows(sim));
       HIP_OK(hipGetLastError());
       sim_record_enqueue(sim, st);
       sim_metrics_enqueue(sim, st, dt);
+      sim_contacts_enqueue(sim, st);
     }
     if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     if (c_prev) HIP_OK(hipMemcpyAsync(c_prev, d_cprev, B * CG_NC * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1679,6 +1810,7 @@ int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double
       throw std::runtime_error("feedback_low_level_steps: the plan must be a multibody problem with the simulator's nx and joint-torque controls (m = nu = nv - 6)");
     if (plan->async_pending > 0) throw std::runtime_error("feedback_low_level_steps: the plan has ticks in flight (mpc_wait first)");
     sim_record_reserve(sim, steps);
+    sim_contacts_check(sim, "feedback_low_level_steps");
     HIP_OK(hipStreamSynchronize(plan->stream));
     const size_t B = Z.B;
     const int nx = Z.nx, nu = Z.m;
@@ -1696,10 +1828,11 @@ int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double
       if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(sim->d_xlast, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(k_pipe_state_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
       launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
-                            sim_wrench_out(sim, wrenches != nullptr), sim_push_width(sim));
+                            sim_wrench_out(sim, wrenches != nullptr), sim_push_width(sim), sim_contacts_rows(sim));
       HIP_OK(hipGetLastError());
       sim_record_enqueue(sim, st);
       sim_metrics_enqueue(sim, st, dt);
+      sim_contacts_enqueue(sim, st);
     }
     if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, sim->d_xlast, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));

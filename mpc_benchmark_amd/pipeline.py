@@ -15,12 +15,18 @@ The kinodynamic control pipeline of kinodynamic_talos.py:361-497, every stage on
 The three native pieces are the library's own (include/mpc_abi.h, include/mpc_qp_abi.h); between them travel the small per-robot
 vectors (states, K_0, torques), not problem data.  The simulator is the stand-in of ``mpc_simulate_torque``: the whole-body contact
 dynamics of the CONTACT STATE OF KNOT 0 of the schedule (what ``problem.stages[0]`` says, :419) — rigid contacts at the measured-at-start
-foot placements, no physics engine.  ``library``: the HIP library by default; tests pass the oracle to get the reference run."""
+foot placements, no physics engine.  ``library``: the HIP library by default; tests pass the oracle to get the reference run.
+
+``contact_rule`` (all three pipelines): None, the simulator of the schedule above; or a dict over ``contact_rule.DEFAULTS`` ({} for the defaults,
+the ground at the lower initial foothold): the simulator's stage 0 is double support and the unilateral rule of the headless BulletRobot decides
+every robot's contacts on the device after every step (mpc_sim_contacts, include/mpc_sim_contacts.h; HIP library only).  The low-level QPs keep
+the schedule's ``contact_state``, as the scripts do with ``problem.stages[0]``."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _capi as K
+from . import contact_rule as _contact_rule
 from . import qp_utils
 from .aligator import _core as core
 from .aligator import dynamics as _dyn
@@ -107,11 +113,21 @@ def build_torque_simulator(lib, robot, batch, sim_dt, device):
     return sim, tables
 
 
+def _enable_contact_rule(sim, tables, robot, cfg):
+    """``contact_rule`` of a pipeline: stage 0 of the simulator is the double-support stage once, and the rule is on from the initial footholds
+    (the ground plane at the lower one unless ``cfg`` names ``ground_z``)."""
+    sim.set_stage(0, *tables[(True, True)])
+    gz = min(float(np.asarray(M.translation)[2]) for M in robot.foot_placements)
+    sim.contacts(_contact_rule.config(cfg, ground_z=gz))
+
+
 class KinodynamicPipeline:
-    def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, **ens_kw):
+    def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
+                 **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
-        or None (references frozen at the initial footholds)."""
+        or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict (module docstring)."""
         self.pd, self.batch = problem_def, int(batch)
+        self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
         rb = problem_def.robot
         m = self.model = rb.model
@@ -135,8 +151,12 @@ class KinodynamicPipeline:
     def _build_simulator(self):
         self.sim, self._sim_tables = build_torque_simulator(self.lib, self.pd.robot, self.batch, self.sim_dt, self.mpc.dims.device)
         self._sim_mask = None
+        if self.contact_rule is not None:
+            _enable_contact_rule(self.sim, self._sim_tables, self.pd.robot, self.contact_rule)
 
     def _set_sim_contacts(self, mask):
+        if self.contact_rule is not None:   # (the rule decides every robot's contacts on the device)
+            return
         mask = (bool(mask[0]), bool(mask[1]))
         if mask != self._sim_mask:
             self.sim.set_stage(0, *self._sim_tables[mask])
@@ -274,11 +294,13 @@ class CentroidalPipeline:
     G_FOOT, G_ROT = 400.0, 10.0                        # g_p, g_b (:305-307)
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
-                 sigma_v=0.05, perturb_dofs=None, **ens_kw):
+                 sigma_v=0.05, perturb_dofs=None, contact_rule=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps) or None
-        (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv]."""
+        (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
+        dict (module docstring)."""
         from .ensemble import ensemble_initial_states
         self.pd, self.batch = problem_def, int(batch)
+        self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
         rb = problem_def.robot
         m = self.model = rb.model
@@ -304,6 +326,8 @@ class CentroidalPipeline:
         self.qp.enable_device_assembly()
         self.sim, self._sim_tables = build_torque_simulator(self.lib, rb, self.batch, self.sim_dt, self.mpc.dims.device)
         self._sim_mask = None
+        if self.contact_rule is not None:
+            _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule)
         self._set_sim_contacts((True, True))   # (the schedule starts in double support)
         self.torques = np.zeros((self.batch, m.nv - 6))
         self.forces = np.zeros((self.batch, 12))
@@ -312,6 +336,8 @@ class CentroidalPipeline:
         self._xik_on_device = False    # the QP handle keeps x_prev of its last device loop
 
     def _set_sim_contacts(self, mask):
+        if self.contact_rule is not None:   # (the rule decides every robot's contacts on the device)
+            return
         mask = (bool(mask[0]), bool(mask[1]))
         if mask != self._sim_mask:
             self.sim.set_stage(0, *self._sim_tables[mask])
@@ -420,15 +446,16 @@ class FullDynamicPipeline:
     contact set of ``contact_state``).  ``library``: the HIP library by default; the device loop (``low_level_loop``,
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
-    def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, **ens_kw):
+    def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
-        the pipeline is the closed loop."""
+        the pipeline is the closed loop.  ``contact_rule``: None or a config dict (module docstring of pipeline.py)."""
         if ens_kw.get("closed_loop") is not None:
             raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
                              "EnsembleMPC(closed_loop=...) would simulate a second time)")
         ens_kw.pop("closed_loop", None)
         self.pd, self.batch = problem_def, int(batch)
+        self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
         rb = problem_def.robot
         m = self.model = rb.model
@@ -438,6 +465,8 @@ class FullDynamicPipeline:
         self._walk_args = walk
         self.sim, self._sim_tables = build_torque_simulator(self.lib, rb, self.batch, self.sim_dt, self.mpc.dims.device)
         self._sim_mask = None
+        if self.contact_rule is not None:
+            _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
         self.x_prev = self.x.copy()                      # the measurement of the period before (the solve's initial condition)
         self.torques = np.zeros((self.batch, m.nv - 6))
@@ -445,6 +474,8 @@ class FullDynamicPipeline:
         self._plan_stale = True
 
     def _set_sim_contacts(self, mask):
+        if self.contact_rule is not None:   # (the rule decides every robot's contacts on the device)
+            return
         mask = (bool(mask[0]), bool(mask[1]))
         if mask != self._sim_mask:
             self.sim.set_stage(0, *self._sim_tables[mask])
