@@ -50,7 +50,8 @@ typedef struct mpc_sim_contacts_config {
  *               (in_contact, lifted, pulling = 0).  The last contact is never released.
  *   free:       z > ground_z + 2 ground_tol: lifted = 1; else caught if (z <= ground_z + ground_tol and lifted) or (z < ground_z and z < z_prev):
  *               in_contact = 1, anchor = (Rz(yaw), (x, y, ground_z)) of the sole's placement (yaw = atan2(R[1][0], R[0][0])).
- *   z_prev = z for both soles. */
+ *   z_prev = z for both soles.
+ * With a terrain (include/mpc_sim_terrain.h) the free branch reads g_i, the terrain height under the origin of sole i, wherever it says ground_z. */
 #define MPC_SIM_CONTACTS_WIDTH 41
 
 /* cfg != NULL: the rule on and reset (allocates the device rows: both soles in contact at the model's anchors, counters at zero; a second call

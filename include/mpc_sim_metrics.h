@@ -48,7 +48,10 @@ typedef struct mpc_sim_metrics_config {
  *  15 - 17 com_first centre of mass after the first step (NaN before it)
  *  18 - 20 com_last  centre of mass after the latest step (NaN before the first)
  * The CoP, the support box and the 1 N threshold are talos_utils.computeCoP's and plot.py:145-164's, from the step's contact wrenches (LOCAL frame)
- * and the sole placements of the state after the step.  After a step whose state is non-finite the row freezes (that step is not accumulated). */
+ * and the sole placements of the state after the step.  After a step whose state is non-finite the row freezes (that step is not accumulated).
+ * On a handle with a terrain (include/mpc_sim_terrain.h) the heights of the fall verdict, latched ones included, are heights above the ground: a sole's
+ * above the terrain under the origin of its frame, the base's above the mean anchor height of the soles in contact (the contact row the step was
+ * integrated with); everything else in the row is unchanged. */
 #define MPC_SIM_METRICS_WIDTH 21
 
 /* cfg != NULL: metrics on and reset (allocates the device rows; a second call resets them); NULL: off (frees them; no kernel is launched). */

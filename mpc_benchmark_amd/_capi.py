@@ -159,6 +159,17 @@ _SIM_CONTACTS_SIGNATURES = {
     "mpc_sim_contacts_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_terrain.h: exported by the HIP library alone, bound when present (``NativeSolver.terrain`` / ``read_terrain`` / ``terrain_height``)
+class MpcSimTerrainConfig(C.Structure):
+    _fields_ = [("n_boxes", C.c_int32), ("per_robot", C.c_int32)]
+
+
+_SIM_TERRAIN_SIGNATURES = {
+    "mpc_sim_terrain": (C.c_int, [C.c_void_p, C.POINTER(MpcSimTerrainConfig), _DP]),
+    "mpc_sim_terrain_read": (C.c_int, [C.c_void_p, C.POINTER(MpcSimTerrainConfig), _DP]),
+    "mpc_sim_terrain_height": (C.c_int, [C.c_void_p, _DP, C.c_int32, _DP]),
+}
+
 # include/mpc_feedback_pipeline.h: exported by the HIP library alone, bound when present (``NativeSolver.feedback_low_level_steps``)
 _FEEDBACK_PIPELINE_SIGNATURES = {
     "mpc_feedback_low_level_steps": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int32, C.c_double, _DP, _DP, _DP, _DP]),
@@ -173,7 +184,7 @@ def bind_library(path):
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()):
+            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -418,6 +429,47 @@ class NativeSolver:
         if r.shape != (self.dims.batch, _contact_rule.WIDTH):
             raise ValueError("set_contacts: rows of shape (%d, %d) expected, got %s" % (self.dims.batch, _contact_rule.WIDTH, r.shape))
         self._check(fn(self._h, _dp(r)), "mpc_sim_contacts_set")
+
+    # -- include/mpc_sim_terrain.h (HIP library only): the box terrain under the contact rule ------------------------------------------------------
+    def _sim_terrain(self, name):
+        if not hasattr(self.lib, name):
+            raise NotImplementedError("%s is not exported by this library (%s): the terrain of the contact rule needs the HIP library "
+                                      "(libmpc_hip.so, include/mpc_sim_terrain.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def terrain(self, boxes):
+        """The ground under the contact rule of this handle (mpc_sim_terrain; the rule must be on): ``boxes`` ``(n, 5)`` for every robot or
+        ``(B, n, 5)`` per robot, rows ``(x_lo, x_hi, y_lo, y_hi, z_top)``, n <= 16 (``contact_rule.terrain_height`` is the height function,
+        ``contact_rule.stairs`` the reference's staircase); None: the plane z = ground_z again."""
+        fn = self._sim_terrain("mpc_sim_terrain")
+        if boxes is None:
+            self._check(fn(self._h, None, None), "mpc_sim_terrain")
+            return
+        b = _contact_rule.terrain_boxes(boxes, self.dims.batch)
+        cfg = MpcSimTerrainConfig(b.shape[-2], int(b.ndim == 3))
+        self._check(fn(self._h, C.byref(cfg), _dp(b) if b.size else None), "mpc_sim_terrain")
+
+    def read_terrain(self):
+        """The terrain in force (mpc_sim_terrain_read): the boxes in the form they were given, ``(n, 5)`` or ``(B, n, 5)`` (``(0, 5)`` when none is set)."""
+        fn = self._sim_terrain("mpc_sim_terrain_read")
+        cfg = MpcSimTerrainConfig()
+        self._check(fn(self._h, C.byref(cfg), None), "mpc_sim_terrain_read")
+        shape = ((self.dims.batch,) if cfg.per_robot else ()) + (cfg.n_boxes, _contact_rule.TERRAIN_BOX_WIDTH)
+        out = np.zeros(shape)
+        if out.size:
+            self._check(fn(self._h, C.byref(cfg), _dp(out)), "mpc_sim_terrain_read")
+        return out
+
+    def terrain_height(self, xy):
+        """The device's height function (mpc_sim_terrain_height): ``xy`` (B, n, 2) -> (B, n), robot b's points on robot b's terrain (``ground_z`` of the
+        rule where no terrain is set): where the ground is under a planned foothold."""
+        fn = self._sim_terrain("mpc_sim_terrain_height")
+        p = _f64(xy)
+        if p.ndim != 3 or p.shape[0] != self.dims.batch or p.shape[2] != 2:
+            raise ValueError("terrain_height: points of shape (%d, n, 2) expected, got %s" % (self.dims.batch, p.shape))
+        out = np.zeros(p.shape[:2])
+        self._check(fn(self._h, _dp(p) if p.size else None, p.shape[1], _dp(out) if out.size else None), "mpc_sim_terrain_height")
+        return out
 
     # -- include/mpc_feedback_pipeline.h (HIP library only): the low-level loop of the full-dynamics pipeline --------------------------------
     def feedback_low_level_steps(self, sim, steps, dt, x=None):

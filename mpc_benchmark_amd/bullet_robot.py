@@ -13,7 +13,9 @@ lift it), a free foot that has left the ground and comes back to it, or that sin
 placement is re-captured at the landing pose).  That is a deliberately simple contact rule — enough to close the loop around the MPC headlessly
 and deterministically; it is not a physics engine.  ``device_contacts=True`` (HIP library only) runs the same rule on the device after every step
 (mpc_sim_contacts, include/mpc_sim_contacts.h): stage 0 stays the double-support stage, the rule picks the contacts and their ground-side
-placements, and a catch needs no new model.
+placements, and a catch needs no new model.  ``createStairs(pose_stairs, height_step)`` (the reference's three boxes) and ``setTerrain(boxes)`` put a
+box terrain under the rule, host or device: a foot is caught on the highest box top under the ORIGIN of its sole frame (``contact_rule.terrain_height``);
+risers, soles hanging over an edge and slopes are not modelled.  ``addStairs`` (a URDF in the reference) stays unavailable.
 
 Differences from PyBullet worth knowing: ``measureState`` returns the base velocity in the LOCAL frame of the base (Pinocchio's
 convention, which is what the scripts assume when they copy it into the state, talos_utils.py:337-348); PyBullet reports it in the
@@ -23,6 +25,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi as K
+from . import contact_rule as _contact_rule
 from .aligator import _core as core
 from .aligator import dynamics as _dyn
 from .aligator import manifolds as _manifolds
@@ -53,6 +56,7 @@ class BulletRobot:
         self.release_steps = int(release_steps)
         self.release_force = float(release_force)  # N: the ground "pulls" when the normal force is below minus this
         self.device_contacts = bool(device_contacts)  # the contact rule on the device (in_contact and the rest are read back after every step)
+        self.terrain = None  # boxes (n, 5) under the contact rule (setTerrain / createStairs); None: the plane z = ground_z
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
         self._native = None
@@ -96,6 +100,8 @@ class BulletRobot:
             self._upload_mask()
             self._native.contacts({"ground_z": self.ground_z, "ground_tol": self.ground_tol, "release_force": self.release_force,
                                    "release_steps": self.release_steps})
+            if self.terrain is not None:
+                self._native.terrain(self.terrain)
 
     def _contact_models(self):
         m = self.model
@@ -190,17 +196,18 @@ class BulletRobot:
         relanded = False
         for i, fid in enumerate(self.frame_ids):
             z = float(self.data.oMf[fid].translation[2])
+            ground_z = self._ground_under(self.data.oMf[fid].translation)
             if self.in_contact[i]:
                 self._pulling[i] = self._pulling[i] + 1 if wrenches[i][2] < -self.release_force else 0  # (an unloaded sole, 0 +- round-off, rests on the ground)
                 if self._pulling[i] >= self.release_steps and sum(self.in_contact) > 1:
                     self.in_contact[i] = False
                     self._lifted[i] = False
                     self._pulling[i] = 0
-            elif z > self.ground_z + 2.0 * self.ground_tol:
+            elif z > ground_z + 2.0 * self.ground_tol:
                 self._lifted[i] = True  # (a released foot is caught again only after it has really left the ground ...)
-            elif (z <= self.ground_z + self.ground_tol and self._lifted[i]) or (z < self.ground_z and z < self._z_prev[i]):  # (... or sinks into it)
+            elif (z <= ground_z + self.ground_tol and self._lifted[i]) or (z < ground_z and z < self._z_prev[i]):  # (... or sinks into it)
                 pose = self.data.oMf[fid].copy()
-                pose.translation[2] = self.ground_z
+                pose.translation[2] = ground_z
                 yaw = np.arctan2(pose.rotation[1, 0], pose.rotation[0, 0])
                 c, s = np.cos(yaw), np.sin(yaw)
                 pose.rotation = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
@@ -210,6 +217,12 @@ class BulletRobot:
             self._z_prev[i] = z
         if relanded:
             self._build_native()
+
+    def _ground_under(self, p):
+        """height of the ground under the point p: the plane, or the terrain at (x, y) (the origin of a sole frame decides, nothing else of the sole)"""
+        if self.terrain is None:
+            return self.ground_z
+        return float(_contact_rule.terrain_height(self.terrain, np.asarray(p, dtype=float)[:2], self.ground_z))
 
     def _read_device_contacts(self):
         """``in_contact`` and the rule's per-foot state after a step, from the device rows (mpc_sim_contacts_read)."""
@@ -265,7 +278,27 @@ class BulletRobot:
         pass
 
     def addStairs(self, path, position, orientation):
-        raise NotImplementedError("headless BulletRobot: flat ground only")
+        raise NotImplementedError("headless BulletRobot: flat ground only")  # (a URDF staircase; createStairs / setTerrain lay boxes under the contact rule)
+
+    def setTerrain(self, boxes):
+        """The ground under the contact rule: boxes (n, 5) ``(x_lo, x_hi, y_lo, y_hi, z_top)``, n <= 16, over the plane z = ``ground_z``
+        (``contact_rule.terrain_height``); None: the plane again.  The host rule takes it at once, ``device_contacts=True`` passes it to the device.
+        What stands is not moved: a sole in contact keeps its anchor.  Only the height under the ORIGIN of a sole frame counts: no risers, no sole
+        edges hanging over a step, no slopes."""
+        if boxes is None:
+            self.terrain = None
+        else:
+            b = _contact_rule.terrain_boxes(boxes)
+            if b.ndim != 2:
+                raise ValueError("setTerrain: boxes of shape (n, 5) expected (one robot)")
+            self.terrain = b
+        if self.device_contacts and self._native is not None:  # (the rule is on since initializeJoints)
+            self._native.terrain(self.terrain)
+
+    def createStairs(self, pose_stairs, height_step):
+        """bullet_robot.py:275-340 of the reference: three steps of half extents 0.2 x 0.5 x height_step / 2, each 0.3 m further and height_step higher,
+        the first centred at ``pose_stairs`` (``contact_rule.stairs``)."""
+        self.setTerrain(_contact_rule.stairs(pose_stairs, height_step))
 
     def close(self):
         if self._native is not None:

@@ -10,7 +10,19 @@
     is its landing pose flattened onto the plane: ``p = (x, y, ground_z)``, ``R = Rz(yaw)``;
   - ``z_prev`` of both feet becomes this step's sole height.
 
-A robot's state is one row of ``WIDTH`` doubles (the layout of include/mpc_sim_contacts.h, ``FIELDS``)."""
+A robot's state is one row of ``WIDTH`` doubles (the layout of include/mpc_sim_contacts.h, ``FIELDS``).
+
+Terrain (``mpc_sim_terrain``, include/mpc_sim_terrain.h; ``NativeSolver.terrain``): up to ``TERRAIN_MAX_BOXES`` axis-aligned boxes
+``(x_lo, x_hi, y_lo, y_hi, z_top)`` per robot, one set for all robots ``(n, 5)`` or one per robot ``(B, n, 5)``.  The ground height is
+
+    h(x, y) = max(ground_z, max{z_top of the boxes with x_lo <= x <= x_hi and y_lo <= y <= y_hi})
+
+(closed intervals; boxes may overlap, the higher wins; a box below ``ground_z`` has no effect; comparisons and ``max`` only, so the device agrees
+bit for bit).  The ground under sole i is ``g_i = h`` at the ORIGIN of the sole frame, and the rule is the one above with ``g_i`` in place of
+``ground_z`` in the free-foot branch: lifted above ``g_i + 2 ground_tol``, caught within ``ground_tol`` of ``g_i`` after lifting or when sinking
+below ``g_i``, the anchor at ``(x, y, g_i)``.  Without a terrain ``g_i`` is ``ground_z`` itself.  Deliberately not modelled, in keeping with a rule
+that is not a physics engine: risers (nothing stops a foot horizontally), a sole that hangs over an edge, a toe inside the next step (only the
+origin decides, so a toe that has crossed the next riser does not catch a descending foot on the step above), slopes."""
 from __future__ import annotations
 
 import numpy as np
@@ -28,6 +40,10 @@ DEFAULTS = {
     "release_force": 1.0,   # N: a contact pulls when its LOCAL-frame f_z < -release_force
     "release_steps": 5,     # consecutive pulling steps before the release (>= 1)
 }
+
+
+TERRAIN_MAX_BOXES = 16   # MPC_SIM_TERRAIN_MAX_BOXES
+TERRAIN_BOX_WIDTH = 5    # MPC_SIM_TERRAIN_BOX_WIDTH: x_lo, x_hi, y_lo, y_hi, z_top
 
 
 def config(cfg=None, ground_z=None):
@@ -79,20 +95,82 @@ def flatten(R, p, ground_z):
     return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]), np.array([p[0], p[1], ground_z])
 
 
-def step(rows, sole_z, fz, sole_R, sole_p, cfg=None):
+def terrain_boxes(boxes, batch=None):
+    """Checked boxes as float64: ``(n, 5)`` (shared) or ``(B, n, 5)`` (per robot; ``batch`` checks B), 0 <= n <= ``TERRAIN_MAX_BOXES``, finite,
+    ``x_lo <= x_hi`` and ``y_lo <= y_hi``.  An empty sequence is zero shared boxes."""
+    b = np.asarray(boxes, dtype=float)
+    if b.size == 0 and b.ndim < 3:
+        b = b.reshape(0, TERRAIN_BOX_WIDTH)
+    if b.ndim not in (2, 3) or b.shape[-1] != TERRAIN_BOX_WIDTH:
+        raise ValueError("terrain: boxes of shape (n, 5) or (B, n, 5) expected (x_lo, x_hi, y_lo, y_hi, z_top), got %s" % (b.shape,))
+    if b.shape[-2] > TERRAIN_MAX_BOXES:
+        raise ValueError("terrain: at most %d boxes per robot, got %d" % (TERRAIN_MAX_BOXES, b.shape[-2]))
+    if b.ndim == 3 and batch is not None and b.shape[0] != batch:
+        raise ValueError("terrain: per-robot boxes for %d robots expected, got %d" % (batch, b.shape[0]))
+    if not np.all(np.isfinite(b)):
+        raise ValueError("terrain: the boxes must be finite")
+    if np.any(b[..., 0] > b[..., 1]) or np.any(b[..., 2] > b[..., 3]):
+        raise ValueError("terrain: x_lo <= x_hi and y_lo <= y_hi expected")
+    return np.ascontiguousarray(b)
+
+
+def terrain_height(boxes, xy, ground_z):
+    """h at the points ``xy`` (..., 2) of shared boxes ``(n, 5)``, or (B, ..., 2) of per-robot boxes ``(B, n, 5)`` (robot b's points on robot b's
+    terrain) -> heights of shape ``xy.shape[:-1]``."""
+    b = terrain_boxes(boxes)
+    xy = np.asarray(xy, dtype=float)
+    h = np.full(xy.shape[:-1], float(ground_z))
+    if b.ndim == 3 and (xy.ndim < 2 or xy.shape[0] != b.shape[0]):
+        raise ValueError("terrain_height: per-robot boxes need points of shape (B, ..., 2) with B = %d, got %s" % (b.shape[0], xy.shape))
+    x, y = xy[..., 0], xy[..., 1]
+    for k in range(b.shape[-2]):
+        # (+ 0.0: a top of -0 counts as +0, on the device too, so that equal tops are equal bits whatever the order of the max)
+        bk = b[k] if b.ndim == 2 else b[:, k].reshape((b.shape[0],) + (1,) * (xy.ndim - 2) + (TERRAIN_BOX_WIDTH,))
+        inside = (bk[..., 0] <= x) & (x <= bk[..., 1]) & (bk[..., 2] <= y) & (y <= bk[..., 3])
+        top = bk[..., 4] + 0.0
+        h = np.where(inside & (top > h), top, h)
+    return h
+
+
+def stairs(pose_stairs, height_step, n_steps=3, pitch=0.3, half_extents=(0.2, 0.5)):
+    """The boxes of the reference's ``createStairs(pose_stairs, height_step)`` (bullet_robot.py:275-340): step k is a box of half extents
+    (0.2, 0.5, height_step / 2) centred at ``pose_stairs + (k pitch, 0, k height_step)``, so its top is at the centre's z + height_step / 2 and
+    consecutive steps overlap by 0.1 m (the visible tread is ``pitch``).  -> (n_steps, 5), ``n_steps <= TERRAIN_MAX_BOXES``."""
+    n_steps = int(n_steps)
+    if not 0 <= n_steps <= TERRAIN_MAX_BOXES:
+        raise ValueError("stairs: 0 .. %d steps, got %d" % (TERRAIN_MAX_BOXES, n_steps))
+    p = np.asarray(pose_stairs, dtype=float).reshape(-1)
+    if p.size != 3:
+        raise ValueError("stairs: pose_stairs is a 3-vector")
+    h, hx, hy = float(height_step), float(half_extents[0]), float(half_extents[1])
+    out = np.zeros((n_steps, TERRAIN_BOX_WIDTH))
+    for k in range(n_steps):
+        cx, cz = p[0] + k * pitch, p[2] + k * h
+        out[k] = (cx - hx, cx + hx, p[1] - hy, p[1] + hy, cz + h / 2)
+    return out
+
+
+def step(rows, sole_z, fz, sole_R, sole_p, cfg=None, terrain=None):
     """One step of the rule for B robots -> the new rows (a copy).  rows (B, WIDTH); sole_z (B, 2) the sole heights of the state AFTER the step;
     fz (B, 2) the step's LOCAL-frame normal forces (0 for a free foot); sole_R (B, 2, 3, 3), sole_p (B, 2, 3) the sole placements after the step
-    (only a catch reads them); ``cfg`` over ``DEFAULTS``."""
+    (a catch reads them, and the terrain the origins' x, y); ``cfg`` over ``DEFAULTS``; ``terrain``: None, or boxes (n, 5) / (B, n, 5): the ground
+    under sole i is ``terrain_height`` at ``sole_p[b, i, :2]`` instead of ``ground_z`` (module docstring)."""
     c = config(cfg)
     gz, tol, rf, rs = c["ground_z"], c["ground_tol"], c["release_force"], c["release_steps"]
     r = np.array(rows, dtype=float, copy=True).reshape(-1, WIDTH)
     sole_z, fz = np.asarray(sole_z, dtype=float).reshape(-1, 2), np.asarray(fz, dtype=float).reshape(-1, 2)
     sole_R, sole_p = np.asarray(sole_R, dtype=float).reshape(-1, 2, 3, 3), np.asarray(sole_p, dtype=float).reshape(-1, 2, 3)
+    ground = None
+    if terrain is not None:
+        boxes = terrain_boxes(terrain, r.shape[0])
+        ground = terrain_height(boxes, sole_p[..., :2], gz)
+    plane = gz
     for b in range(r.shape[0]):
         row = r[b]
         n = row[O_STEPS]
         for i in range(2):
             z = sole_z[b, i]
+            gz = plane if ground is None else ground[b, i]
             if row[O_IN + i] != 0.0:
                 row[O_PULLING + i] = row[O_PULLING + i] + 1.0 if fz[b, i] < -rf else 0.0
                 if row[O_PULLING + i] >= rs and row[O_IN] + row[O_IN + 1] > 1.0:

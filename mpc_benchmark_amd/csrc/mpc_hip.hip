@@ -135,6 +135,10 @@ struct mpc_solver {
   // include/mpc_sim_contacts.h: the rows of the contact rule (nullptr: rule off, stage 0 decides the contacts), [B][W]
   double* d_con = nullptr;
   mpc_sim_contacts_config con_cfg = {};
+  // include/mpc_sim_terrain.h: the boxes under the contact rule (nullptr: the plane; also with zero boxes), [n] or [B][n] boxes; h_ter as they were given
+  double* d_ter = nullptr;
+  mpc_sim_terrain_config ter_cfg = {};
+  std::vector<double> h_ter;
   // per-slot invalidation (mpc_update_stage_params*): slots whose parameters changed since the last pass was enqueued ; dirty_all:
   // an update on a horizon too long for the mask of SolverArgs
   std::vector<uint8_t> slot_dirty;
@@ -926,7 +930,7 @@ void mpc_destroy(mpc_solver* s) {
   for (int i = 0; i < mpc_solver::ASYNC_DEPTH; ++i) if (s->h_xnext[i]) (void)hipHostFree(s->h_xnext[i]);
   if (s->d_patch) (void)hipFree(s->d_patch);
   for (void* p : s->allocs) (void)hipFree(p);
-  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec, s->d_met, s->d_con}) if (p) (void)hipFree(p);
+  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec, s->d_met, s->d_con, s->d_ter}) if (p) (void)hipFree(p);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1357,6 +1361,14 @@ static void sim_metrics_begin(mpc_solver* s, hipStream_t st) {
   const Layout& L = s->L;
   HIP_OK(hipMemcpyAsync(s->d_met + (size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1), s->d_x0, (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
 }
+// the terrain of the contact rule as the kernels take it (sim_terrain.h): boxes nullptr without one
+static SimTerrain sim_terrain_args(const mpc_solver* s) {
+  SimTerrain t;
+  t.boxes = s->d_con ? s->d_ter : nullptr;
+  t.n = s->ter_cfg.n_boxes;
+  t.stride = s->ter_cfg.per_robot ? s->ter_cfg.n_boxes * MPC_SIM_TERRAIN_BOX_WIDTH : 0;
+  return t;
+}
 // after a simulator step of length dt on stream st: its metrics (sim_metrics.h), when they are on
 static void sim_metrics_enqueue(mpc_solver* s, hipStream_t st, double dt) {
   if (!s->d_met) return;
@@ -1365,6 +1377,7 @@ static void sim_metrics_enqueue(mpc_solver* s, hipStream_t st, double dt) {
   m.mi = s->d_model_i; m.md = s->d_model_d; m.nv = L.n / 2; m.nq = L.nx - L.n / 2;
   m.x = s->d_x0; m.tau = s->d_simu; m.wr = s->d_simwr; m.dt = dt; m.cfg = s->met_cfg;
   m.acc = s->d_met; m.frozen = s->d_met + (size_t)L.B * MPC_SIM_METRICS_WIDTH; m.xs = m.frozen + L.B;
+  m.ter = sim_terrain_args(s); m.con = s->d_con; m.ground_z = s->con_cfg.ground_z;
   hipLaunchKernelGGL(k_sim_metrics, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, m);
   HIP_OK(hipGetLastError());
 }
@@ -1397,7 +1410,7 @@ static void sim_contacts_enqueue(mpc_solver* s, hipStream_t st) {
   const Layout& L = s->L;
   SimContactsArgs c;
   c.mi = s->d_model_i; c.md = s->d_model_d; c.nv = L.n / 2; c.nq = L.nx - L.n / 2;
-  c.x = s->d_x0; c.wr = s->d_simwr; c.cfg = s->con_cfg; c.rows = s->d_con;
+  c.x = s->d_x0; c.wr = s->d_simwr; c.cfg = s->con_cfg; c.rows = s->d_con; c.ter = sim_terrain_args(s);
   hipLaunchKernelGGL(k_sim_contacts, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, c);
   HIP_OK(hipGetLastError());
 }
@@ -1517,6 +1530,12 @@ int32_t mpc_sim_metrics_width(mpc_solver* s) {
   }
 }
 
+static void sim_terrain_drop(mpc_solver* s) {
+  if (s->d_ter) { HIP_OK(hipFree(s->d_ter)); s->d_ter = nullptr; }
+  s->ter_cfg = {};
+  s->h_ter.clear();
+}
+
 int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
   MPC_TRY(s, {
     sim_check(s, "sim_contacts");
@@ -1532,6 +1551,7 @@ int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
     }
     HIP_OK(hipStreamSynchronize(s->stream));
     if (s->d_con) { HIP_OK(hipFree(s->d_con)); s->d_con = nullptr; }
+    if (!cfg) sim_terrain_drop(s);  // (the terrain goes with the rows; a reset keeps it)
     if (cfg) {
       void* p = nullptr;
       HIP_OK(hipMalloc(&p, (size_t)L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double)));
@@ -1584,6 +1604,82 @@ int mpc_sim_contacts_read(mpc_solver* s, double* rows) {
     if (!s->d_con) throw std::runtime_error("sim_contacts_read: the contact rule is off on this handle (turn it on with mpc_sim_contacts)");
     HIP_OK(hipStreamSynchronize(s->stream));
     copy_sync(s, rows, s->d_con, (size_t)s->L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int mpc_sim_terrain(mpc_solver* s, const mpc_sim_terrain_config* cfg, const double* boxes) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_terrain");
+    if (!s->d_con) throw std::runtime_error("sim_terrain: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    const Layout& L = s->L;
+    size_t count = 0;
+    if (cfg) {
+      if (cfg->n_boxes < 0 || cfg->n_boxes > MPC_SIM_TERRAIN_MAX_BOXES)
+        throw std::runtime_error("sim_terrain: n_boxes must be 0 .. " + std::to_string(MPC_SIM_TERRAIN_MAX_BOXES));
+      if (cfg->per_robot != 0 && cfg->per_robot != 1) throw std::runtime_error("sim_terrain: per_robot must be 0 or 1");
+      if (cfg->n_boxes > 0 && !boxes) throw std::runtime_error("sim_terrain: boxes must not be null with n_boxes > 0");
+      count = (size_t)(cfg->per_robot ? L.B : 1) * cfg->n_boxes;
+      for (size_t k = 0; k < count; ++k) {
+        const double* bx = boxes + k * MPC_SIM_TERRAIN_BOX_WIDTH;
+        for (int e = 0; e < MPC_SIM_TERRAIN_BOX_WIDTH; ++e)
+          if (!std::isfinite(bx[e])) throw std::runtime_error("sim_terrain: box " + std::to_string(k) + " holds a non-finite number");
+        if (bx[0] > bx[1] || bx[2] > bx[3]) throw std::runtime_error("sim_terrain: box " + std::to_string(k) + " has x_lo > x_hi or y_lo > y_hi");
+      }
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    sim_terrain_drop(s);
+    if (cfg) {
+      s->ter_cfg = *cfg;
+      s->h_ter.assign(boxes, boxes + count * MPC_SIM_TERRAIN_BOX_WIDTH);
+      if (count > 0) {  // (zero boxes: the plane, by the old path)
+        std::vector<double> h(s->h_ter);
+        for (size_t k = 0; k < count; ++k) h[k * MPC_SIM_TERRAIN_BOX_WIDTH + 4] += 0.0;  // (a top of -0 counts as +0, as in the numpy definition)
+        void* p = nullptr;
+        HIP_OK(hipMalloc(&p, h.size() * sizeof(double)));
+        s->d_ter = (double*)p;
+        copy_sync(s, s->d_ter, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+      }
+    }
+  })
+}
+
+int mpc_sim_terrain_read(mpc_solver* s, mpc_sim_terrain_config* cfg, double* boxes) {
+  MPC_TRY(s, {
+    if (!cfg) throw std::runtime_error("sim_terrain_read: cfg must not be null");
+    sim_check(s, "sim_terrain_read");
+    if (!s->d_con) throw std::runtime_error("sim_terrain_read: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    *cfg = s->ter_cfg;
+    if (boxes) std::copy(s->h_ter.begin(), s->h_ter.end(), boxes);
+  })
+}
+
+int mpc_sim_terrain_height(mpc_solver* s, const double* xy, int32_t n, double* h) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_terrain_height");
+    if (!s->d_con) throw std::runtime_error("sim_terrain_height: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    if (n < 0) throw std::runtime_error("sim_terrain_height: n must be >= 0");
+    if (n > 0 && (!xy || !h)) throw std::runtime_error("sim_terrain_height: xy and h must not be null");
+    const Layout& L = s->L;
+    const size_t np = (size_t)L.B * n;
+    for (size_t i = 0; i < 2 * np; ++i)
+      if (!std::isfinite(xy[i])) throw std::runtime_error("sim_terrain_height: xy holds a non-finite number");
+    if (n > 0) {
+      void* p = nullptr;
+      HIP_OK(hipMalloc(&p, 3 * np * sizeof(double)));
+      double* d_xy = (double*)p;
+      try {
+        copy_sync(s, d_xy, xy, 2 * np * sizeof(double), hipMemcpyHostToDevice);
+        SimTerrainHeightArgs a;
+        a.t = sim_terrain_args(s); a.ground_z = s->con_cfg.ground_z; a.xy = d_xy; a.n = n; a.h = d_xy + 2 * np;
+        hipLaunchKernelGGL(k_sim_terrain_height, dim3((unsigned)L.B), dim3(64), 0, s->stream, a);
+        HIP_OK(hipGetLastError());
+        copy_sync(s, h, a.h, np * sizeof(double), hipMemcpyDeviceToHost);
+      } catch (...) {
+        (void)hipFree(p);
+        throw;
+      }
+      HIP_OK(hipFree(p));
+    }
   })
 }
 

@@ -3,10 +3,13 @@
 // evaluation of a run (centre of pressure against the support box, angular momentum, joint power and energy) and a fall verdict are read once at the
 // end instead of downloading the per-step record.  The kinematics, centre of mass and centroidal momentum are the centroidal pipeline's
 // (pipeline_ikid_glue.h), the sole placements the record's (sim_record.h).  One workgroup owns each row and stream order serialises the steps: no
-// atomics, and the same sums in the same order on every run.
+// atomics, and the same sums in the same order on every run.  On a handle with a terrain (mpc_sim_terrain, sim_terrain.h) the heights of the fall
+// verdict are taken above the ground: a sole's above the terrain under its origin, the base's above the mean anchor height of the soles in contact.
 #pragma once
 #include "sim_record.h"
+#include "sim_terrain.h"
 #include "../../include/mpc_sim_metrics.h"
+#include "../../include/mpc_sim_contacts.h"
 
 struct SimMetricsArgs {
   const int32_t* mi;    // model tables of the simulator handle (contacts 0 and 1: the two soles)
@@ -20,6 +23,9 @@ struct SimMetricsArgs {
   double* acc;          // [B][MPC_SIM_METRICS_WIDTH] the rows (include/mpc_sim_metrics.h)
   double* frozen;       // [B] 1 after a non-finite state: the row no longer changes
   double* xs;           // [B][nq + nv] the state the step started from; left holding x for the next step
+  SimTerrain ter;       // boxes nullptr: no terrain, absolute heights in the fall verdict
+  const double* con;    // with a terrain: [B][MPC_SIM_CONTACTS_WIDTH] the rows of the contact rule the step was integrated with
+  double ground_z;      // with a terrain: the rule's ground_z
 };
 
 __global__ void __launch_bounds__(CG_THREADS) k_sim_metrics(SimMetricsArgs a) {
@@ -32,6 +38,8 @@ __global__ void __launch_bounds__(CG_THREADS) k_sim_metrics(SimMetricsArgs a) {
   const double* x = a.x + (size_t)b * nx;
   double* xs = a.xs + (size_t)b * nx;
   double* r = a.acc + (size_t)b * MPC_SIM_METRICS_WIDTH;
+  TerrainBox bx = {};
+  if (a.ter.boxes) bx = terrain_load_box(a.ter, b, tid);  // (one branch for the whole launch)
   // joint power sum_j |tau_j v_j| with v of the state the step started from (plot.py pairs u[i] with x[i]), reduced over the wavefront
   double p = 0.0;
   for (int j = tid; j < nu; j += CG_THREADS) p += fabs(a.tau[(size_t)b * nu + j] * xs[nq + 6 + j]);
@@ -57,12 +65,29 @@ __global__ void __launch_bounds__(CG_THREADS) k_sim_metrics(SimMetricsArgs a) {
     sole[tid][9] = pc.x; sole[tid][10] = pc.y; sole[tid][11] = pc.z;
   }
   __syncthreads();
+  // with a terrain: the ground under the two soles' origins (lanes 0 - 15 sole 0, 16 - 31 sole 1), as the contact rule takes it
+  double g0 = 0.0, g1 = 0.0;
+  if (a.ter.boxes) {
+    const int i = (tid / TERRAIN_GROUP) & 1;
+    const double gi = terrain_height(bx, sole[i][9], sole[i][10], a.ground_z);
+    g0 = __shfl(gi, 0);
+    g1 = __shfl(gi, TERRAIN_GROUP);
+  }
   if (tid != 0) return;
   const mpc_sim_metrics_config& c = a.cfg;
   const double n = r[0];
   const V3 pl = ldv3(sole[0] + 9), pr = ldv3(sole[1] + 9);
+  // the heights of the fall rule: absolute, or above the ground (the base above the mean anchor height of the soles in contact; there is always one)
+  double zb = x[2], zl = pl.z, zr = pr.z;
+  if (a.ter.boxes) {
+    const double* cr = a.con + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
+    const double al = cr[8 + 11], ar = cr[20 + 11];
+    zb -= (cr[0] != 0.0 && cr[1] != 0.0) ? 0.5 * (al + ar) : (cr[0] != 0.0 ? al : ar);
+    zl -= g0;
+    zr -= g1;
+  }
   if (n == 0.0) {  // the first step since the reset: the heights of the fall rule, the centre of mass the run starts from
-    r[12] = x[2]; r[13] = pl.z; r[14] = pr.z;
+    r[12] = zb; r[13] = zl; r[14] = zr;
     r[15] = cx[0]; r[16] = cx[1]; r[17] = cx[2];
   }
   r[0] = n + 1.0;
@@ -103,6 +128,6 @@ __global__ void __launch_bounds__(CG_THREADS) k_sim_metrics(SimMetricsArgs a) {
   if (hl > r[8]) r[8] = hl;
   if (ha > r[9]) r[9] = ha;
   r[10] += cx[8] * cx[8];
-  if (r[11] < 0.0 && (x[2] < r[12] - c.fall_drop || (pl.z > r[13] + c.sole_lift && pr.z > r[14] + c.sole_lift))) r[11] = n;
+  if (r[11] < 0.0 && (zb < r[12] - c.fall_drop || (zl > r[13] + c.sole_lift && zr > r[14] + c.sole_lift))) r[11] = n;
   r[18] = cx[0]; r[19] = cx[1]; r[20] = cx[2];
 }

@@ -10,10 +10,17 @@ They are plot.py's evaluation of a recorded run of the scripts, reduced to one r
   - the fall verdict of tools/push_recovery.py (base more than 0.2 m below, or both soles more than 2 cm above, their heights after the first
     step; or a non-finite state).
 
+On a handle with a terrain (``NativeSolver.terrain``, include/mpc_sim_terrain.h) the fall verdict is taken above the ground, so that a robot that
+has climbed a step is not "fallen": sole i by ``z_i - g_i`` (``g_i`` the terrain height under the origin of the sole frame after the step, as the
+contact rule takes it), the base by ``z_base - a``, ``a`` the mean anchor height of the soles in contact in the contact row the step was integrated
+with; ``base_z0`` and ``sole_z0`` are latched in the same terms.  Nothing else in a row changes.
+
 ``from_record`` computes the row of every robot from the per-step record (``NativeSolver.read_record``) of the same steps."""
 from __future__ import annotations
 
 import numpy as np
+
+from . import contact_rule as _contact_rule
 
 # (name, doubles) in the order of a row; MPC_SIM_METRICS_WIDTH = 21
 FIELDS = (("steps", 1), ("time", 1), ("energy", 1), ("peak_power", 1), ("cop_steps", 1), ("cop_outside", 1), ("margin_min", 1), ("margin_sum", 1),
@@ -104,11 +111,22 @@ def joint_power(tau, x_before, nq):
     return np.sum(np.abs(np.asarray(tau) * np.asarray(x_before)[..., nq + 6:]), axis=-1)
 
 
-def from_record(rec, x_start, dt, cfg=None):
+def from_record(rec, x_start, dt, cfg=None, terrain=None, contact_rows=None, ground_z=0.0):
     """The metric rows of every robot over the recorded steps, as ``NativeSolver.read_metrics`` returns them after the same steps from a reset.
     ``rec``: the dict of ``NativeSolver.read_record`` (steps, B, ...); ``x_start`` (B, nx): the states the first recorded step started from;
-    ``dt``: the length of each step, a scalar or (steps,) (substeps * dt of the call)."""
+    ``dt``: the length of each step, a scalar or (steps,) (substeps * dt of the call).  ``terrain``: None, or the boxes (n, 5) / (B, n, 5) of the
+    handle's terrain over the plane ``ground_z`` (the contact rule's): the fall verdict above the ground (module docstring); it needs
+    ``contact_rows`` (steps, B, ``contact_rule.WIDTH``), the rows of the contact rule each step was integrated with (before that step's update).
+    Zero boxes are no terrain, as on the device."""
     c = config(cfg)
+    if terrain is not None:
+        terrain = _contact_rule.terrain_boxes(terrain, np.asarray(rec["x"]).shape[1])
+        if terrain.shape[-2] == 0:
+            terrain = None
+    if terrain is not None:
+        if contact_rows is None:
+            raise ValueError("from_record: terrain needs contact_rows (the anchors the steps were integrated with)")
+        contact_rows = np.asarray(contact_rows, dtype=float)
     x, tau = np.asarray(rec["x"], dtype=float), np.asarray(rec["tau"], dtype=float)
     S, B, nx = x.shape
     nq = nx - (tau.shape[2] + 6)
@@ -127,9 +145,16 @@ def from_record(rec, x_start, dt, cfg=None):
         with np.errstate(invalid="ignore", over="ignore"):
             p = joint_power(tau[k], x_before, nq)
             sole_p = np.asarray(rec["sole_p"][k], dtype=float)
+            zb, zs = xk[:, 2], sole_p[:, :, 2]
+            if terrain is not None:   # heights above the ground
+                cr = contact_rows[k]
+                on = cr[:, _contact_rule.O_IN:_contact_rule.O_IN + 2] != 0.0
+                az = cr[:, [_contact_rule.O_ANCHOR + 11, _contact_rule.O_ANCHOR + 23]]
+                zb = zb - np.where(on[:, 0] & on[:, 1], 0.5 * (az[:, 0] + az[:, 1]), np.where(on[:, 0], az[:, 0], az[:, 1]))
+                zs = zs - _contact_rule.terrain_height(terrain, sole_p[:, :, :2], ground_z)
             first = a & (n == 0)
-            r[first, 12] = xk[first, 2]
-            r[first, 13:15] = sole_p[first, :, 2]
+            r[first, 12] = zb[first]
+            r[first, 13:15] = zs[first]
             r[first, 15:18] = rec["com"][k][first]
             r[a, 0] = n[a] + 1.0
             r[a, 1] += dts[k]
@@ -148,8 +173,8 @@ def from_record(rec, x_start, dt, cfg=None):
             r[a, 8] = np.where(hl[a] > r[a, 8], hl[a], r[a, 8])
             r[a, 9] = np.where(ha[a] > r[a, 9], ha[a], r[a, 9])
             r[a, 10] += h[a, 5] ** 2
-            fell = a & (r[:, 11] < 0) & ((xk[:, 2] < r[:, 12] - c["fall_drop"]) |
-                                          ((sole_p[:, 0, 2] > r[:, 13] + c["sole_lift"]) & (sole_p[:, 1, 2] > r[:, 14] + c["sole_lift"])))
+            fell = a & (r[:, 11] < 0) & ((zb < r[:, 12] - c["fall_drop"]) |
+                                          ((zs[:, 0] > r[:, 13] + c["sole_lift"]) & (zs[:, 1] > r[:, 14] + c["sole_lift"])))
             r[fell, 11] = n[fell]
             r[a, 18:21] = rec["com"][k][a]
         x_before = xk

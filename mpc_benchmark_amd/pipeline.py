@@ -20,7 +20,11 @@ foot placements, no physics engine.  ``library``: the HIP library by default; te
 ``contact_rule`` (all three pipelines): None, the simulator of the schedule above; or a dict over ``contact_rule.DEFAULTS`` ({} for the defaults,
 the ground at the lower initial foothold): the simulator's stage 0 is double support and the unilateral rule of the headless BulletRobot decides
 every robot's contacts on the device after every step (mpc_sim_contacts, include/mpc_sim_contacts.h; HIP library only).  The low-level QPs keep
-the schedule's ``contact_state``, as the scripts do with ``problem.stages[0]``."""
+the schedule's ``contact_state``, as the scripts do with ``problem.stages[0]``.
+
+``terrain`` (all three pipelines, with ``contact_rule`` only): None, the ground is the plane; or boxes ``(n, 5)`` for every robot / ``(B, n, 5)`` per
+robot under the rule (mpc_sim_terrain, include/mpc_sim_terrain.h; ``contact_rule.stairs`` lays the reference's staircase).  Nothing else about a
+tick changes: the planner and the low-level QPs keep the schedule's footholds and ``contact_state``; the plant decides where a foot is caught."""
 from __future__ import annotations
 
 import numpy as np
@@ -113,20 +117,57 @@ def build_torque_simulator(lib, robot, batch, sim_dt, device):
     return sim, tables
 
 
-def _enable_contact_rule(sim, tables, robot, cfg):
+def _checked_terrain(name, terrain, contact_rule, batch):
+    """``terrain`` of a pipeline: checked boxes or None; refused without ``contact_rule`` (the terrain is an input of the rule)"""
+    if terrain is None:
+        return None
+    if contact_rule is None:
+        raise ValueError("%s: terrain needs contact_rule (the terrain is the ground of the unilateral contact rule; contact_rule={} turns it on)" % name)
+    return _contact_rule.terrain_boxes(terrain, batch)
+
+
+def _enable_contact_rule(sim, tables, robot, cfg, terrain=None):
     """``contact_rule`` of a pipeline: stage 0 of the simulator is the double-support stage once, and the rule is on from the initial footholds
-    (the ground plane at the lower one unless ``cfg`` names ``ground_z``)."""
+    (the ground plane at the lower one unless ``cfg`` names ``ground_z``), over ``terrain`` if there is one."""
     sim.set_stage(0, *tables[(True, True)])
     gz = min(float(np.asarray(M.translation)[2]) for M in robot.foot_placements)
     sim.contacts(_contact_rule.config(cfg, ground_z=gz))
+    if terrain is not None:
+        sim.terrain(terrain)
+
+
+def stairs_under_walk(robot, x_forward, z_height, y_gap=0.18, n_steps=3, half_extents=(0.2, 0.5)):
+    """The reference's staircase (``contact_rule.stairs``, pitch = the step length) laid under the footholds the walk generator plans for the nominal
+    robot: right foot first, every swing ``x_forward`` ahead of the stance foot and ``z_height`` above it (``references.FootTrajectory``).  The
+    planned landing point of swing k lies in the middle of the visible tread of step k (with the reference's 0.4 m boxes at a pitch of 0.3 m: 5 cm
+    behind the box's centre, 15 cm from the edge in front and from the riser of the next step), and the top of step k is exactly
+    ``ground_z + (k + 1) z_height``, ``ground_z`` the lower initial foothold (where the pipelines put the rule's plane).
+    -> (boxes (n_steps, 5), footholds (n_steps, 3))."""
+    from . import references as refgen
+    lf, rf = (M.copy() for M in robot.foot_placements)
+    gz = min(float(np.asarray(M.translation)[2]) for M in (lf, rf))
+    traj = refgen.FootTrajectory(lf.copy(), rf.copy(), 1, 1, 1, 0.0, x_forward, 0.0, 0.0, y_gap, z_height)
+    holds = []
+    while len(holds) < n_steps:   # (the generator's own foothold rule, two landings per call: right beside left, then left beside the new right)
+        traj._plan_right_then_left(lf, rf)
+        lf, rf = traj.final_pose_left.copy(), traj.final_pose_right.copy()
+        holds += [np.array(rf.translation, dtype=float), np.array(lf.translation, dtype=float)]
+    holds = np.array(holds[:n_steps])
+    y_mid = 0.5 * float(np.asarray(robot.foot_placements[0].translation)[1] + np.asarray(robot.foot_placements[1].translation)[1])
+    pose = np.array([holds[0, 0] + half_extents[0] - 0.5 * x_forward, y_mid, gz + 0.5 * z_height]) if n_steps else np.zeros(3)
+    boxes = _contact_rule.stairs(pose, z_height, n_steps=n_steps, pitch=x_forward, half_extents=half_extents)
+    boxes[:, 4] = gz + (np.arange(n_steps) + 1.0) * z_height
+    return boxes, holds
 
 
 class KinodynamicPipeline:
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
-                 **ens_kw):
+                 terrain=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
-        or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict (module docstring)."""
+        or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes (module
+        docstring)."""
         self.pd, self.batch = problem_def, int(batch)
+        self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
         rb = problem_def.robot
@@ -152,7 +193,7 @@ class KinodynamicPipeline:
         self.sim, self._sim_tables = build_torque_simulator(self.lib, self.pd.robot, self.batch, self.sim_dt, self.mpc.dims.device)
         self._sim_mask = None
         if self.contact_rule is not None:
-            _enable_contact_rule(self.sim, self._sim_tables, self.pd.robot, self.contact_rule)
+            _enable_contact_rule(self.sim, self._sim_tables, self.pd.robot, self.contact_rule, self.terrain)
 
     def _set_sim_contacts(self, mask):
         if self.contact_rule is not None:   # (the rule decides every robot's contacts on the device)
@@ -294,12 +335,13 @@ class CentroidalPipeline:
     G_FOOT, G_ROT = 400.0, 10.0                        # g_p, g_b (:305-307)
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
-                 sigma_v=0.05, perturb_dofs=None, contact_rule=None, **ens_kw):
+                 sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
-        dict (module docstring)."""
+        dict, ``terrain``: None or boxes (module docstring)."""
         from .ensemble import ensemble_initial_states
         self.pd, self.batch = problem_def, int(batch)
+        self.terrain = _checked_terrain("CentroidalPipeline", terrain, contact_rule, self.batch)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
         rb = problem_def.robot
@@ -327,7 +369,7 @@ class CentroidalPipeline:
         self.sim, self._sim_tables = build_torque_simulator(self.lib, rb, self.batch, self.sim_dt, self.mpc.dims.device)
         self._sim_mask = None
         if self.contact_rule is not None:
-            _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule)
+            _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule, self.terrain)
         self._set_sim_contacts((True, True))   # (the schedule starts in double support)
         self.torques = np.zeros((self.batch, m.nv - 6))
         self.forces = np.zeros((self.batch, 12))
@@ -446,10 +488,11 @@ class FullDynamicPipeline:
     contact set of ``contact_state``).  ``library``: the HIP library by default; the device loop (``low_level_loop``,
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
-    def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, **ens_kw):
+    def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
-        the pipeline is the closed loop.  ``contact_rule``: None or a config dict (module docstring of pipeline.py)."""
+        the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes (module docstring of pipeline.py)."""
+        self.terrain = _checked_terrain("FullDynamicPipeline", terrain, contact_rule, int(batch))
         if ens_kw.get("closed_loop") is not None:
             raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
                              "EnsembleMPC(closed_loop=...) would simulate a second time)")
@@ -466,7 +509,7 @@ class FullDynamicPipeline:
         self.sim, self._sim_tables = build_torque_simulator(self.lib, rb, self.batch, self.sim_dt, self.mpc.dims.device)
         self._sim_mask = None
         if self.contact_rule is not None:
-            _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule)
+            _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule, self.terrain)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
         self.x_prev = self.x.copy()                      # the measurement of the period before (the solve's initial condition)
         self.torques = np.zeros((self.batch, m.nv - 6))

@@ -1,0 +1,257 @@
+"""Developer tool (GPU box): the three control pipelines climb the reference's staircase closed-loop, the plant being the torque-driven simulator with
+the unilateral contact rule over a box terrain (mpc_sim_terrain, include/mpc_sim_terrain.h).  64 perturbed robots per pipeline, N = 100, the walk with
+z_height = 0.10 and the script's step length (the full-dynamics script steps in place, x_forward = 0: a staircase needs a pitch, so it walks the
+kinodynamic script's 0.3 m here), device loops, failure isolation (a robot whose MPC fails sits the rest out).
+
+  shared     ``stairs_under_walk``: one staircase for all robots, laid under the footholds the generator plans for the nominal robot, rise = z_height,
+             one tread per landing of the schedule (the reference's createStairs has three)
+  per robot  the same treads, but robot b's rise is one of 16 values between 0.06 and 0.14 m (four robots each): the planner still aims 0.10 m higher
+             per step, the ground is where it is
+
+The shared climb is run with the scripts' swing_apex = 0.15 (a Bezier control height: the planned sole passes the front edge of a 0.10 m tread at 0.09 m,
+below it) and with 0.35 (0.144 m there), to tell what the swing clearance costs from what the formulation does once the foot lands on the tread.
+
+Per run: steps climbed per robot (the highest tread a sole was caught on), falls by the verdict above the ground (mpc_sim_metrics on a handle with a
+terrain), the touchdown of every landing against the schedule, a summary of the metric rows; ms per MPC period with and without the terrain (p50 over
+periods 20 - 79, all in double support, runs of their own without the per-period reads).
+
+``--profile``: 30 periods of the full-dynamics pipeline with the complete model and 0, 3 and 16 boxes, for
+``rocprofv3 --kernel-trace --stats -d DIR -- python tools/stairs_walk.py --profile`` (k_sim_contacts per launch: the launches come in that order, 300 each;
+``--boxes 0`` alone also runs on a library without the terrain entry points, e.g. ``MPC_HIP_LIBRARY=<a build of the parent commit>``).
+``--summarize DIR [--boxes ...]`` prints the per-launch times of that trace, split by box count.
+usage: python tools/stairs_walk.py [--horizon N] [--models kinodynamic centroidal fulldynamic] [--apex 0.15 0.35] [--out PATH] [--profile [--boxes 0 3 16]]"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+from mpc_benchmark_amd import contact_rule
+from mpc_benchmark_amd.pipeline import CentroidalPipeline, FullDynamicPipeline, KinodynamicPipeline, stairs_under_walk
+from mpc_benchmark_amd.problems.centroidal import CentroidalProblem
+from mpc_benchmark_amd.problems.common import Robot
+from mpc_benchmark_amd.problems.fulldynamic import FullDynamicsProblem
+from mpc_benchmark_amd.problems.kinodynamic import KinodynamicProblem
+
+B = 64
+Z_HEIGHT = 0.10
+RISES = np.repeat(np.linspace(0.06, 0.14, 16), 4)   # per-robot runs: robot b's rise
+STEADY = slice(20, 80)
+
+
+def problem(model, N, complete=False):
+    if model == "kinodynamic":
+        return KinodynamicProblem(horizon=N, complete_model=complete)
+    if model == "centroidal":
+        return CentroidalProblem(horizon=N, robot=Robot(complete=complete))
+    return FullDynamicsProblem(horizon=N, complete_model=complete)
+
+
+def landings(pd):
+    """number of landings in the schedule of this problem (one tread each)"""
+    ph = pd.contact_phases
+    return sum(1 for a, b in zip(ph, ph[1:]) for f in range(2) if b[f] and not a[f])
+
+
+def staircase(pd, n_steps=None):
+    """-> (boxes (n, 5), footholds (n, 3), x_forward) for the walk of this problem: one tread per landing of its schedule unless ``n_steps`` says otherwise"""
+    xf = pd.walk_spec()["x_forward"] or 0.3
+    n_steps = landings(pd) if n_steps is None else n_steps
+    boxes, holds = stairs_under_walk(pd.robot, xf, Z_HEIGHT, n_steps=n_steps)
+    return boxes, holds, xf
+
+
+def make_pipeline(model, N, T, terrain, rule=True, complete=False, n_steps=None, apex=0.15):
+    pd = problem(model, N, complete)
+    boxes, holds, xf = staircase(pd, n_steps)
+    if isinstance(terrain, str) and terrain == "shared":
+        ter = boxes
+    elif isinstance(terrain, str) and terrain == "per robot":
+        gz = boxes[0, 4] - Z_HEIGHT
+        ter = np.tile(boxes, (B, 1, 1))
+        ter[:, :, 4] = gz + RISES[:, None] * (np.arange(boxes.shape[0]) + 1.0)[None, :]
+    else:
+        ter = terrain   # None, or explicit boxes
+    kw = dict(batch=B, walk=dict(z_height=Z_HEIGHT, x_forward=xf, swing_apex=apex), sigma_q=0.005, sigma_v=0.01, tick_reuse=True, contact_rule={} if rule else None, terrain=ter)
+    if model == "kinodynamic":
+        p = KinodynamicPipeline(pd, perturb=True, **kw)
+    elif model == "centroidal":
+        p = CentroidalPipeline(pd, **kw)
+    else:
+        p = FullDynamicPipeline(pd, **kw)
+    p.mpc.prepare_schedule(T + 16)
+    p.cold_solve()
+    p.mpc.enable_failure_isolation(auto_revive=False)
+    return p, ter, holds
+
+
+def timing(model, N, terrain):
+    p, _, _ = make_pipeline(model, N, STEADY.stop, terrain)
+    ms = []
+    for _ in range(STEADY.stop):
+        t0 = time.perf_counter()
+        p.tick()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return float(np.percentile(np.array(ms)[STEADY], 50))
+
+
+def climb(model, N, terrain, apex=0.15):
+    """the whole walk -> lines of the report"""
+    T = len(problem(model, N).contact_phases) - N   # the whole schedule: the last landing and a horizon of double support after it
+    p, ter, holds = make_pipeline(model, N, T, terrain, apex=apex)
+    front = (ter[0] if ter.ndim == 3 else ter)[:, 0]                               # x_lo of every tread (the same for all robots)
+    p.sim.metrics({})
+    tops = ter[:, :, 4] if ter.ndim == 3 else np.tile(ter[:, 4], (B, 1))          # (B, n) the tread heights of every robot
+    gz = float(p.sim.terrain_height(np.zeros((B, 1, 2)) - 10.0)[0, 0])              # (far behind the staircase: the plane)
+    level = np.zeros((B, 2), dtype=int)          # highest tread (1-based) each sole was caught on
+    first_td = np.full((B, tops.shape[1]), -1.0)  # step of the first catch on tread k
+    first_x = np.full((B, tops.shape[1]), np.nan)  # x of that catch's anchor
+    off_h = 0                                     # catches whose anchor is not on the height function (must stay 0)
+    landings, prev_cs, prev_td = [], (True, True), np.zeros((B, 2))
+    for t in range(T):
+        cs = tuple(bool(c) for c in p.contact_state())
+        for f in range(2):
+            if cs[f] and not prev_cs[f]:
+                landings.append((t, f))
+        prev_cs = cs
+        p.tick()
+        r = p.sim.read_contacts()
+        new = r["touchdowns"] > prev_td
+        prev_td = r["touchdowns"].copy()
+        az = r["anchor_p"][..., 2]
+        h = p.sim.terrain_height(np.ascontiguousarray(r["anchor_p"][..., :2]))
+        off_h += int(np.sum(new & (az != h)))
+        for k in range(tops.shape[1]):
+            on = new & (az == tops[:, k, None])
+            level[on] = np.maximum(level[on], k + 1)
+            hit = on.any(axis=1) & (first_td[:, k] < 0)
+            first_td[hit, k] = np.where(on[hit], r["last_touchdown"][hit], np.inf).min(axis=1)
+            first_x[hit, k] = np.where(on[hit], r["anchor_p"][hit][..., 0], np.inf).min(axis=1)
+    r, met = p.sim.read_contacts(), p.sim.read_metrics()
+    lost = sorted({b for (_, b, _, _) in p.mpc.lost})
+    lost_at = sorted(t for (t, _, _, _) in p.mpc.lost)
+    climbed = level.max(axis=1)
+    fallen = met["fall_step"] >= 0
+    S = p.substeps
+    out = ["  %-11s %-9s swing_apex %.2f, %d periods; scheduled landings (period, foot) %s" % (model, terrain, apex, T, [(t, "LR"[f]) for t, f in landings]),
+           "      steps climbed (highest tread a sole was caught on) of %d treads: %s ; robots per count 0 .. %d: %s" % (
+               tops.shape[1], "all %d" % climbed[0] if np.all(climbed == climbed[0]) else "min %d max %d" % (climbed.min(), climbed.max()),
+               tops.shape[1], [int(np.sum(climbed == k)) for k in range(tops.shape[1] + 1)]),
+           "      fallen (verdict above the ground) %d of %d%s ; MPC instances lost %d%s ; catches off the height function %d" % (
+               int(fallen.sum()), B, "" if not fallen.any() else " (first at step %d, median %d)" % (met["fall_step"][fallen].min(), np.median(met["fall_step"][fallen])),
+               len(lost), "" if not lost else " (periods %d - %d)" % (lost_at[0], lost_at[-1]), off_h)]
+    for k in range(tops.shape[1]):
+        got = first_td[:, k] >= 0
+        sched = [t for t, _ in landings][k] if k < len(landings) else None
+        if got.any():
+            out.append("      tread %d: first caught by %d robots at steps %d - %d (median %d), %.0f - %.0f mm behind the planned foothold (the tread's front edge: %.0f mm behind it)%s" % (
+                k + 1, int(got.sum()), first_td[got, k].min(), first_td[got, k].max(), np.median(first_td[got, k]),
+                1e3 * (holds[k, 0] - first_x[got, k].max()), 1e3 * (holds[k, 0] - first_x[got, k].min()), 1e3 * (holds[k, 0] - front[k]),
+                "" if sched is None else " ; scheduled landing step %d: %+.1f to %+.1f periods" % (S * sched, (first_td[got, k].min() - S * sched) / S,
+                                                                                                  (first_td[got, k].max() - S * sched) / S)))
+        else:
+            out.append("      tread %d: caught by nobody" % (k + 1))
+    up = ~fallen
+    line = "      touchdowns per robot L %d R %d (max) ; lift-offs L %d R %d (max)" % (
+        int(r["touchdowns"][:, 0].max()), int(r["touchdowns"][:, 1].max()), int(r["liftoffs"][:, 0].max()), int(r["liftoffs"][:, 1].max()))
+    if up.any():
+        line += (" ; metrics of the %d robots not fallen: energy %.1f J (mean), peak power %.0f W (max), CoP outside the support box %.1f %% of the steps, "
+                 "min margin %.1f mm, CoM advanced %.3f m and rose %.3f m (mean)" % (
+                     int(up.sum()), met["energy"][up].mean(), met["peak_power"][up].max(), 100.0 * met["cop_outside"][up].sum() / max(1.0, met["cop_steps"][up].sum()),
+                     1e3 * np.nanmin(met["margin_min"][up]), (met["com_last"][up, 0] - met["com_first"][up, 0]).mean(),
+                     (met["com_last"][up, 2] - met["com_first"][up, 2]).mean()))
+    else:
+        line += " ; no robot left standing: no metrics summary"
+    out.append(line)
+    if terrain == "per robot":
+        by_rise = ["%.3f:%s%s" % (RISES[4 * g], "".join(str(int(c)) for c in climbed[4 * g:4 * g + 4]), "" if not fallen[4 * g:4 * g + 4].any() else "(%d fell)" % fallen[4 * g:4 * g + 4].sum())
+                   for g in range(16)]
+        out.append("      rise [m]: steps climbed by its four robots  " + "  ".join(by_rise))
+    return out
+
+
+def profile(counts):
+    """30 periods each with 0, 3 and 16 boxes (the 16: the staircase's three and thirteen more treads behind the robots, never stepped on)"""
+    N, T = 40, 30
+    for n in counts:
+        pd = problem("fulldynamic", N, complete=True)
+        boxes, _, _ = staircase(pd, 3)
+        if n == 0:
+            ter = None
+        elif n == 3:
+            ter = boxes
+        else:
+            extra = contact_rule.stairs([-6.0, 0.0, 0.05], 0.1, n_steps=13)
+            ter = np.concatenate([boxes, extra])
+        p, _, _ = make_pipeline("fulldynamic", N, T, ter, complete=True)
+        for _ in range(T):
+            p.tick()
+        print("profile: %d boxes, %d periods, %d launches of k_sim_contacts" % (n, T, T * p.substeps), flush=True)
+
+
+def summarize(trace_dir, counts, launches=300):
+    """k_sim_contacts (and k_sim_metrics, k_eval_multibody) per launch from the kernel trace of a ``--profile`` run, split by the order of the box counts"""
+    import csv
+    import glob
+    files = sorted(glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True))
+    if not files:
+        raise SystemExit("no *kernel_trace.csv under %s" % trace_dir)
+    rows = []
+    for f in files:
+        with open(f) as fh:
+            rows += [(int(r["Start_Timestamp"]), r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3) for r in csv.DictReader(fh)]
+    rows.sort()
+    for name in ("k_sim_contacts", "k_eval_multibody<2"):
+        us = np.array([d for _, k, d in rows if name in k.replace(" ", "")] if "<" in name else [d for _, k, d in rows if name in k])
+        if name != "k_sim_contacts":
+            us = us[-launches * len(counts):] if us.size >= launches * len(counts) else us
+        if us.size != launches * len(counts):
+            print("%s: %d launches, expected %d x %d" % (name, us.size, len(counts), launches))
+            continue
+        for i, n in enumerate(counts):
+            g = us[i * launches:(i + 1) * launches]
+            print("%-20s %2d boxes: %d launches, mean %.2f us, p50 %.2f, min %.2f, max %.2f" % (name, n, g.size, g.mean(), np.percentile(g, 50), g.min(), g.max()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--horizon", type=int, default=100)
+    ap.add_argument("--models", nargs="*", default=["kinodynamic", "centroidal", "fulldynamic"])
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--apex", type=float, nargs="*", default=[0.15, 0.35], help="swing_apex of the shared-staircase climbs (the first one also for the per-robot run)")
+    ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--boxes", type=int, nargs="*", default=[0, 3, 16], help="--profile: the box counts to run, in this order (0, 3 or 16)")
+    ap.add_argument("--summarize", default=None, metavar="DIR", help="print the per-launch times from the rocprofv3 output of a --profile run with the same --boxes")
+    a = ap.parse_args()
+    if a.summarize:
+        summarize(a.summarize, a.boxes)
+        return
+    if a.profile:
+        profile(a.boxes)
+        return
+    lines = ["Stairs walk (tools/stairs_walk.py --horizon %d): %d robots per pipeline, perturbed (sigma_q 0.005, sigma_v 0.01), walk with z_height = %.2f, device loops, "
+             "reduced model, contact rule on, MI355X." % (a.horizon, B, Z_HEIGHT), ""]
+
+    def say(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    say("1. ms per MPC period (ten low-level steps + the solve), p50 over periods 20 - 79 (double support), each number one run:")
+    for model in a.models:
+        runs = [timing(model, a.horizon, ter) for ter in (None, None, "shared", "per robot")]
+        say("  %-11s no terrain %.3f ms (a second run: %.3f) ; shared staircase (3 boxes) %.3f ms (%+.3f) ; per-robot staircases %.3f ms (%+.3f)" % (
+            model, runs[0], runs[1], runs[2], runs[2] - runs[0], runs[3], runs[3] - runs[0]))
+    say("")
+    say("2. The climb: one staircase for all (rise 0.10 m = the planned z_height), then per-robot rises of 0.06 - 0.14 m against the planned 0.10 m:")
+    for model in a.models:
+        for terrain, apex in [("shared", x) for x in a.apex] + [("per robot", a.apex[0])]:
+            for s in climb(model, a.horizon, terrain, apex):
+                say(s)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
