@@ -27,7 +27,8 @@ extern "C" {
  * xdot of knot 0 are read where the last run left them.  `sim`: the simulator handle as in mpc_qp_low_level_steps.  The three handles live on
  * one device and share the batch size; nk = 2.  frames, base_frame, torso_frame, weights, gains, cone, l_box, u_box as in mpc_qp_solve_ikid.
  * x_posture[nq+nv]: the posture reference (x0_multibody); foot_refs[B][2 feet][2 samples][12] (R row-major, p): LF_refs[0:2], RF_refs[0:2] of
- * this period; ref_dt: the dt of the rate terms (the MPC's).  x[B][nq+nv]: the states to start from (NULL: the simulator handle's).
+ * this period (NULL on a plan with mpc_walk_poses_init: the samples its generator keeps on the device, include/mpc_walk_poses.h; an error on any
+ * other plan); ref_dt: the dt of the rate terms (the MPC's).  x[B][nq+nv]: the states to start from (NULL: the simulator handle's).
  * x_ik[B][nq+nv]: the measurement the task errors are taken at (NULL: the x_prev the last call kept on the device).  Outputs (each may be NULL):
  * x_prev[B][nq+nv] the measured states BEFORE the last period, c_prev[B][9] their new_x (the next solve's x0, :454-458), x_out[B][nq+nv] after it,
  * tau[B][nv-6] and forces[B][6 nk] (= forces + df) of the last period, info[B] of its QP, ik_out[B][2 nv + 42] the task errors used. */

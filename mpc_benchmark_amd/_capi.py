@@ -175,6 +175,21 @@ _FEEDBACK_PIPELINE_SIGNATURES = {
     "mpc_feedback_low_level_steps": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int32, C.c_double, _DP, _DP, _DP, _DP]),
 }
 
+# include/mpc_walk_poses.h: exported by the HIP library alone, bound when present (``NativeSolver.walk_poses_*``)
+class MpcWalkPosesConfig(C.Structure):
+    _fields_ = [("T_ss", C.c_int32), ("T_ds", C.c_int32), ("frame_lf", C.c_int32), ("frame_rf", C.c_int32), ("pose_offs", C.c_int32 * 6),
+                ("state_offs", C.c_int32 * 4), ("swing_apex", C.c_double), ("t_left", C.c_double * 3), ("t_right", C.c_double * 3),
+                ("rot_diff", C.c_double * 9), ("lf0", C.c_double * 12), ("rf0", C.c_double * 12), ("floor_z", C.c_double)]
+
+
+_WALK_POSES_SIGNATURES = {
+    "mpc_walk_poses_init": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MpcWalkPosesConfig)]),
+    "mpc_walk_poses_update": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP]),
+    "mpc_walk_poses_get_state": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_walk_poses_set_state": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_walk_poses_get_samples": (C.c_int, [C.c_void_p, _DP]),
+}
+
 
 def bind_library(path):
     """dlopen ``path`` and attach the argument/return types of every entry point of mpc_abi.h."""
@@ -184,7 +199,7 @@ def bind_library(path):
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()):
+            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -556,6 +571,50 @@ class NativeSolver:
     def walk_set_state(self, plan):
         plan = _f64(plan).reshape(-1)
         self._check(self.lib.mpc_walk_set_state(self._h, plan.ctypes.data_as(_DP)), "mpc_walk_set_state")
+
+    # -- include/mpc_walk_poses.h (HIP library only): the generator of the centroidal problem's contact poses, per robot ---------------------------
+    def _walk_poses(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the device generator of the contact-pose references is HIP only "
+                               "(libmpc_hip.so, include/mpc_walk_poses.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def walk_poses_init(self, model, cfg: "MpcWalkPosesConfig"):
+        """``model``: the NativeSolver handle whose model tables the forward kinematics run on (mpc_walk_poses_init)."""
+        self._check(self._walk_poses("mpc_walk_poses_init")(self._h, model._h, C.byref(cfg)), "mpc_walk_poses_init")
+
+    def walk_poses_update(self, model, x, qp, takeoff_RF, takeoff_LF, land_RF, land_LF, forward=None):
+        """One tick of the generator for every robot, BEFORE ``cycle``.  ``x`` (B, nq + nv): the measured states, or None and ``qp``: the QP handle
+        (``_qp_capi.QpSolver``) whose centroidal device loop kept them on the device.  ``forward`` as ``walk_update``."""
+        fn = self._walk_poses("mpc_walk_poses_update")
+        fw = None
+        if forward is not None:
+            fw = _f64(np.concatenate([np.asarray(forward[0], dtype=float), np.asarray(forward[1], dtype=float), [float(forward[2])]]))
+        xa = None
+        if x is not None:
+            xa = _f64(x)
+            if xa.shape != (self.dims.batch, model.dims.nx):
+                raise ValueError("walk_poses_update: measured states of shape (%d, %d) expected, got %s" % (self.dims.batch, model.dims.nx, xa.shape))
+        self._check(fn(self._h, model._h, _dp(xa), None if qp is None else qp._h, int(takeoff_RF), int(takeoff_LF), int(land_RF), int(land_LF), _dp(fw)),
+                    "mpc_walk_poses_update")
+
+    def walk_poses_get_state(self):
+        """-> [B, 4, 12]: start / final pose of the left foot, start / final pose of the right foot (R row-major, p)."""
+        out = np.zeros((self.dims.batch, 4, 12))
+        self._check(self._walk_poses("mpc_walk_poses_get_state")(self._h, _dp(out)), "mpc_walk_poses_get_state")
+        return out
+
+    def walk_poses_set_state(self, plan):
+        plan = _f64(plan).reshape(-1)
+        if plan.size != self.dims.batch * 48:
+            raise ValueError("walk_poses_set_state: a plan of shape (%d, 4, 12) expected" % self.dims.batch)
+        self._check(self._walk_poses("mpc_walk_poses_set_state")(self._h, _dp(plan)), "mpc_walk_poses_set_state")
+
+    def walk_poses_samples(self):
+        """-> [B, 2 feet, 2 samples, 12]: the reference samples of knots 0 and 1 the last update kept on the device."""
+        out = np.zeros((self.dims.batch, 2, 2, 12))
+        self._check(self._walk_poses("mpc_walk_poses_get_samples")(self._h, _dp(out)), "mpc_walk_poses_get_samples")
+        return out
 
     def update_instance_params_batch(self, patches):
         """``patches``: iterable of (instance, stage k, offset, values)."""

@@ -214,7 +214,7 @@ class BatchedQP:
         x_posture = f64(x_posture)
         if x_posture.size != nqv:
             raise ValueError("ikid_low_level_steps: x_posture must have nq + nv entries")
-        foot_refs = f64(foot_refs, (B, 2, 2, 12))
+        foot_refs = None if foot_refs is None else f64(foot_refs, (B, 2, 2, 12))   # (None: the samples the plan's pose generator keeps on the device)
         cs = np.ascontiguousarray(np.broadcast_to(np.asarray(contact_states, dtype=np.int32), (B, nk)))
         x = None if x is None else f64(x, (B, nqv))
         x_ik = None if x_ik is None else f64(x_ik, (B, nqv))

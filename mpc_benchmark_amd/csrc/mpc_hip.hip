@@ -34,6 +34,7 @@
 #include "sim_contacts.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
+#include "../../include/mpc_walk_poses.h"
 #include "qp_device_api.h"
 
 #define HIP_OK(expr)                                                                                  \
@@ -119,6 +120,11 @@ struct mpc_solver {
   std::vector<uint8_t> walk_poisoned;  // per ring slot: the host mirror of the ranges k_walk_refs writes holds NaN (see mpc_walk_update)
   mpc_walk_config walk{};
   double* d_walk_state = nullptr;  // [B][48]
+  // include/mpc_walk_poses.h: the generator of the centroidal problem's contact poses (k_walk_poses): plan [B][48], reference samples [B][48], host-given measurements
+  bool poses_on = false;
+  mpc_walk_poses_config poses{};
+  double *d_poses_state = nullptr, *d_poses_samples = nullptr, *d_poses_x = nullptr;
+  size_t poses_x_cap = 0;
   int since_change = 1 << 20;      // mpc_cycle calls since the appended stage last changed its contact pattern (corrector_window)
   bool refine_now = false;         // ... and this run refines the warm start of the appended knot after k_begin_run
   double* d_simu = nullptr;  // [B][nu] torques, [B][12] wrenches of mpc_simulate_torque
@@ -1807,8 +1813,10 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
                                 double* forces, mpc_qp_info* info, double* ik_out) {
   if (!qp) return -2;
   try {
-    if (!S || !plan || !sim || !frames || !weights || !gains || !cone || !l_box || !u_box || !x_posture || !foot_refs || !contact_states)
+    if (!S || !plan || !sim || !frames || !weights || !gains || !cone || !l_box || !u_box || !x_posture || !contact_states)
       throw std::runtime_error("qp_ikid_low_level_steps: null argument");
+    // foot_refs = NULL: the samples the plan's own generator keeps on the device (mpc_walk_poses_update) ; without one that is the null argument it was
+    if (!foot_refs && !plan->poses_on) throw std::runtime_error("qp_ikid_low_level_steps: null argument");
     if (steps <= 0 || !(dt > 0.0) || !(ref_dt > 0.0)) throw std::runtime_error("qp_ikid_low_level_steps: steps, dt and ref_dt must be positive");
     if (nk != 2) throw std::runtime_error("qp_ikid_low_level_steps: two contacts (nk = 2) expected");
     qp_ikid_prepare(qp, nk, frames, base_frame, torso_frame, weights, gains, cone, l_box, u_box);
@@ -1842,7 +1850,8 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     if (x_ik) HIP_OK(hipMemcpyAsync(d_xprev, x_ik, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_xpost, x_posture, nx * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_refs, foot_refs, B * 48 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (foot_refs) HIP_OK(hipMemcpyAsync(d_refs, foot_refs, B * 48 * sizeof(double), hipMemcpyHostToDevice, st));
+    else HIP_OK(hipMemcpyAsync(d_refs, plan->d_poses_samples, B * 48 * sizeof(double), hipMemcpyDeviceToDevice, st));
     IkidGlueArgs g = {};
     g.mi = q.mi; g.md = q.md; g.nq = q.nq; g.nv = q.nv;
     g.xs = plan->d_xs; g.us = plan->d_us; g.gains = plan->d_gains; g.knots = plan->d_knots;
@@ -2344,3 +2353,4 @@ int mpc_debug_get(mpc_solver* s, const char* name, int32_t b, int32_t k, double*
 
 }  // extern "C"
 
+#include "walk_poses.h"

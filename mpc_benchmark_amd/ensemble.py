@@ -119,9 +119,11 @@ class EnsembleMPC:
         import copy
         walk = None
         if self._walk is not None:
-            walk = copy.deepcopy({k: self._walk[k] for k in ("lists", "traj", "x_measured", "last", "replanning", "batch", "x_measured_all", "last_all") if k in self._walk})
+            walk = copy.deepcopy({k: self._walk[k] for k in ("lists", "traj", "x_measured", "last", "replanning", "batch", "x_measured_all", "last_all", "feet_all") if k in self._walk})
             if self._walk.get("device"):
                 walk["device_plan"] = self.native.walk_get_state()
+            if self._walk.get("poses") == "device":
+                walk["device_poses_plan"] = self.native.walk_poses_get_state()
         self._episode = (self.native.get_state(), self.tick, walk, getattr(self, "replanning_ticks", 0))
 
     def restart_episode(self):
@@ -134,10 +136,12 @@ class EnsembleMPC:
         self.episodes = getattr(self, "episodes", 0) + 1
         if self._walk is not None and walk is not None:
             walk = copy.deepcopy(walk)
-            plan = walk.pop("device_plan", None)
+            plan, poses_plan = walk.pop("device_plan", None), walk.pop("device_poses_plan", None)
             self._walk.update(walk)
             if plan is not None:
                 self.native.walk_set_state(plan)
+            if poses_plan is not None:
+                self.native.walk_poses_set_state(poses_plan)
         elif self._walk is not None:
             self.enable_walk(**self._walk_args)  # saved before the walk was enabled: back to the start of the schedule
 
@@ -172,7 +176,8 @@ class EnsembleMPC:
                 self.native.run_shifted_async()
                 stats, xn = self.native.wait_state()
                 self._walk["x_measured"] = xn[0].copy()
-                self._walk["x_measured_all"] = xn
+                if not self._walk.get("poses"):  # (contact-pose references are planned from whole-body measurements, which only a plant has)
+                    self._walk["x_measured_all"] = xn
                 return self._handle_lost(stats)
             return self._handle_lost(self.native.run_shifted())
         except RuntimeError as e:
@@ -210,7 +215,8 @@ class EnsembleMPC:
             if self._walk is not None:
                 stats, xn = self.native.wait_state()
                 self._walk["x_measured"] = xn[0].copy()  # instance 0's predicted next state: the measurement the generators plan from
-                self._walk["x_measured_all"] = xn     # (per-instance references: everybody's)
+                if not self._walk.get("poses"):
+                    self._walk["x_measured_all"] = xn     # (per-instance references: everybody's)
                 return self._handle_lost(stats)
             return self._handle_lost(self.native.wait())
         except RuntimeError as e:
@@ -252,13 +258,19 @@ class EnsembleMPC:
                     plan = self.native.walk_get_state()
                     plan[b] = plan[src]
                     self.native.walk_set_state(plan)   # (the next update rewrites every knot's references)
+                if self._walk is not None and self._walk.get("poses") == "device":
+                    plan = self.native.walk_poses_get_state()
+                    plan[b] = plan[src]
+                    self.native.walk_poses_set_state(plan)
                 if self._walk is not None and "batch" in self._walk:  # per-instance references: the generator state of the source as well
                     g = self._walk["batch"]
                     for name in ("sL", "fL", "sR", "fR"):
                         R, p = getattr(g, name)
                         R[b], p[b] = R[src], p[src]
-                    self._walk["x_measured_all"] = np.array(self._walk["x_measured_all"])
-                    self._walk["x_measured_all"][b] = self._walk["x_measured_all"][src]
+                    for key in ("x_measured_all", "feet_all"):  # (None: a contact-pose ensemble without a plant / before its first tick)
+                        if self._walk.get(key) is not None:
+                            self._walk[key] = np.array(self._walk[key])
+                            self._walk[key][b] = self._walk[key][src]
                 for rec in self.lost:
                     if rec[1] == b and rec[3] is None:
                         rec[3] = self.tick
@@ -268,7 +280,8 @@ class EnsembleMPC:
         return [tuple(r) for r in self.lost if r[3] is None]
 
     # -- the reference loop's per-tick problem updates on the shared stage tables ---------------------------------
-    def enable_walk(self, swing_apex=0.15, x_forward=None, y_forward=0.0, foot_yaw=0.0, y_gap=0.18, z_height=0.0, per_instance=False, generator="host", floor=False):
+    def enable_walk(self, swing_apex=0.15, x_forward=None, y_forward=0.0, foot_yaw=0.0, y_gap=0.18, z_height=0.0, per_instance=False, generator="host", floor=False,
+                    model_handle=None):
         """From now on every tick does what the loop bodies of the scripts do to the problem before solving (fulldynamic_talos.py:444-510,
         kinodynamic_talos.py:361-409, centroidal_talos.py:357-384): ``FootTrajectory.updateTrajectory`` from the measured foot poses, the
         references written into every stage of the horizon (``setReference`` on the two foot-placement costs — integer keys 3 / 4 or the
@@ -283,7 +296,15 @@ class EnsembleMPC:
 
         The stage tables of an ensemble are shared by its instances, so the references are planned from instance 0's state (the state
         the last COMPLETED tick predicted: with two ticks in flight that is one tick older than the reference script's measurement)
-        and every instance tracks them.  The centroidal OCP has no whole-body model: its feet are where their references put them.
+        and every instance tracks them.  The centroidal OCP has no whole-body model: on the shared path its feet are where their references put them.
+
+        ``per_instance=True``, centroidal problem (``walk_spec()["kind"] == "contact_poses"``): every instance plans from the soles of the whole-body
+        state in ``_walk["x_measured_all"]`` (B, nq + nv) — set before ``plan_tick`` by whoever has a plant (``pipeline.CentroidalPipeline``: its stale
+        measurement) — and the translations go into the instance's own tables for the feet that stand in a knot's stage (centroidal_talos.py:369-384);
+        ``_walk["refs_all"]`` (B, 2 feet, 2 samples, 12) are the samples of the low-level task errors.  Without a measurement (None: no plant) every
+        instance's feet are where its own previous references put them, which are the shared path's references.  ``generator="device"``: one kernel per
+        tick (include/mpc_walk_poses.h, HIP library only; ``model_handle``: a NativeSolver with whole-body model tables and its LoweringContext as
+        ``.ctx``, e.g. the pipeline's simulator handle — by default a handle that holds nothing else is made); it needs a measurement every tick.
 
         ``per_instance=True`` (whole-body problems): every instance plans from ITS OWN measured foot poses and gets its own references
         (mpc_enable_instance_params: per-instance parameter tables; ``references.FootTrajectoryBatch`` and
@@ -305,8 +326,11 @@ class EnsembleMPC:
         spec = pd.walk_spec()
         if x_forward is None:
             x_forward = spec["x_forward"]
+        if per_instance and generator == "device" and spec["kind"] == "contact_poses" and not hasattr(self.lib, "mpc_walk_poses_init"):
+            raise RuntimeError("mpc_walk_poses_init is not exported by this library (%s): the device generator of the contact-pose references is HIP only "
+                               "(libmpc_hip.so, include/mpc_walk_poses.h)" % self.native.backend)
         self._walk_args = dict(swing_apex=swing_apex, x_forward=x_forward, y_forward=y_forward, foot_yaw=foot_yaw, y_gap=y_gap, z_height=z_height, per_instance=per_instance,
-                               generator=generator, floor=floor)
+                               generator=generator, floor=floor, model_handle=model_handle)
         if floor is not False and floor is not None and (not per_instance or z_height != 0.0):
             raise ValueError("floor=True: per-instance references on flat ground")
         if generator not in ("host", "device") or (generator == "device" and not per_instance):
@@ -348,7 +372,8 @@ class EnsembleMPC:
             w["pose_offs"] = [[dyn + 5 + 3 * i, slots[keys.index("angular_acc_cost")][1] + 4 + 4 * i + 1,
                                slots[keys.index("linear_acc_cost")][1] + 4 + 4 * i + 1] for i in (0, 1)]
             if per_instance:
-                raise NotImplementedError("per-instance references: whole-body problems only")
+                self._enable_walk_poses(generator, model_handle)
+                return
         if per_instance and generator == "device":
             self.native.enable_instance_params()
             cfg = K.MpcWalkConfig()
@@ -400,6 +425,8 @@ class EnsembleMPC:
         w, N = self._walk, self.problem.num_steps
         rb, pin, refgen = self.pd.robot, self._walk["pin"], self._walk["refgen"]
         takeoff_RFs, takeoff_LFs, land_RFs, land_LFs = w["lists"]
+        if w.get("poses"):  # contact-pose problem, per-instance references
+            return self._walk_pose_references()
         if w.get("device"):  # the generator runs in the library: only the countdowns (and the scripts' updateForward rule) are host work
             takeoff_RF, takeoff_LF, land_RF, land_LF = refgen.update_timings(land_LFs, land_RFs, takeoff_LFs, takeoff_RFs)
             forward = None
@@ -464,6 +491,100 @@ class EnsembleMPC:
         w["replanning"] = (land_LF < 0 or land_RF < 0 or 0 <= takeoff_RF < w["traj"].T_ds or 0 <= takeoff_LF < w["traj"].T_ds)
         self.replanning_ticks = getattr(self, "replanning_ticks", 0) + int(w["replanning"])
 
+    # -- per-instance references of the contact-pose (centroidal) problem ----------------------------------------------------
+    def _enable_walk_poses(self, generator, model_handle):
+        """``enable_walk(per_instance=True)`` of a problem whose references are the contact poses of its stages: every robot's footholds are planned
+        from the soles of ITS measured whole-body state (``_walk["x_measured_all"]`` (B, nq + nv), set by whoever has a plant: the pipeline), and the
+        translations go into the instance's own tables — for the feet that stand in a knot's stage, as the script writes them."""
+        w, B, N = self._walk, self.batch, self.problem.num_steps
+        refgen, rb = w["refgen"], self.pd.robot
+        lf, rf = rb.foot_placements
+        gen = w["traj"]
+        self.native.enable_instance_params()
+        w["x_measured_all"], w["feet_all"], w["refs_all"], w["pose_idx"] = None, None, None, {}
+        bc = lambda M: (np.tile(np.asarray(M.rotation, dtype=float), (B, 1, 1)), np.tile(np.asarray(M.translation, dtype=float), (B, 1)))
+        (LR, Lp), (RR, Rp) = bc(lf), bc(rf)
+        p = w["step"]
+        w["batch"] = refgen.FootTrajectoryBatch(LR, Lp, RR, Rp, gen.T_ss, gen.T_ds, N, p["swing_apex"], p["x_forward"], p["y_forward"], self._walk_args["foot_yaw"],
+                                                p["y_gap"], p["z_height"])
+        w["batch"].floor_z = w["floor_z"]
+        w["poses"] = generator
+        if generator != "device":
+            return
+        if model_handle is None:  # an ensemble by itself has no whole-body handle: one that holds nothing but the model tables
+            model_handle = _model_handle(self.lib, rb.model, self.dims.device)
+        ctx = model_handle.ctx
+        cfg = K.MpcWalkPosesConfig()
+        cfg.T_ss, cfg.T_ds = int(gen.T_ss), int(gen.T_ds)
+        cfg.frame_lf, cfg.frame_rf = (ctx.frame_index(rb.model, f) for f in rb.foot_frame_ids)
+        if ctx.changed:  # (a frame that handle's stages had not referenced yet)
+            model_handle.set_model(*ctx.model_tables())
+            ctx.changed = False
+        for i in (0, 1):
+            cfg.pose_offs[3 * i:3 * i + 3] = [int(o) for o in w["pose_offs"][i]]
+            cfg.state_offs[2 * i:2 * i + 2] = [int(w["pose_offs"][i][1]) - 1, int(w["pose_offs"][i][2]) - 1]  # `state` precedes p[3] (mpc_abi.h)
+        cfg.swing_apex = float(p["swing_apex"])
+        cfg.t_left[:], cfg.t_right[:] = list(gen.translationLeft), list(gen.translationRight)
+        cfg.rot_diff[:] = list(np.asarray(gen.rotationDiff, dtype=float).reshape(-1))
+        flat = lambda M: list(np.concatenate([np.asarray(M.rotation, dtype=float).reshape(-1), np.asarray(M.translation, dtype=float)]))
+        cfg.lf0[:], cfg.rf0[:] = flat(lf), flat(rf)
+        cfg.floor_z = w["floor_z"] if w["floor_z"] is not None else -1e308
+        self.native.walk_poses_init(model_handle, cfg)
+        w["model_handle"] = model_handle
+        w["xik_from"] = None   # a QP handle whose device loop kept the measurement (pipeline.CentroidalPipeline): the kernel reads it there
+
+    def _pose_patch_index(self, stance):
+        """index arrays of ``update_instance_params_arrays`` for one tick: per instance, per (knot, stance foot), the three places of its translation"""
+        w, B = self._walk, self.batch
+        key = stance.tobytes()
+        if key not in w["pose_idx"]:
+            if len(w["pose_idx"]) > 64:
+                w["pose_idx"].clear()
+            js, fs = np.nonzero(stance)
+            offs = np.array(w["pose_offs"], dtype=np.int32)[fs].reshape(-1)   # (P, 3) -> 3 P
+            i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+            w["pose_idx"][key] = (js, fs, (i32(np.repeat(np.arange(B), offs.size)), i32(np.tile(np.repeat(js, 3), B)), i32(np.tile(offs, B)),
+                                           i32(np.full(B * offs.size, 3))))
+        return w["pose_idx"][key]
+
+    def _walk_pose_references(self):
+        w, N, B = self._walk, self.problem.num_steps, self.batch
+        rb, pin, refgen = self.pd.robot, w["pin"], w["refgen"]
+        takeoff_RFs, takeoff_LFs, land_RFs, land_LFs = w["lists"]
+        takeoff_RF, takeoff_LF, land_RF, land_LF = refgen.update_timings(land_LFs, land_RFs, takeoff_LFs, takeoff_RFs)
+        T_ds = w["traj"].T_ds
+        w["replanning"] = (land_LF < 0 or land_RF < 0 or 0 <= takeoff_RF < T_ds or 0 <= takeoff_LF < T_ds)
+        self.replanning_ticks = getattr(self, "replanning_ticks", 0) + int(w["replanning"])
+        X = w["x_measured_all"]
+        if w["poses"] == "device":
+            forward = None
+            if w["spec"]["forward_rule"](takeoff_RF, takeoff_LF, land_RF, land_LF):
+                p = w["step"]
+                forward = ([0.0, p["y_gap"], w["spec"]["forward_z_left"]], [0.0, -p["y_gap"] - p["y_forward"], 0.0], p["swing_apex"])
+            self.native.walk_poses_update(w["model_handle"], X, w["xik_from"], takeoff_RF, takeoff_LF, land_RF, land_LF, forward)
+            w["refs_all"] = None   # (the samples stay on the device: ``walk_poses_samples`` fetches them)
+            return
+        if X is not None:
+            (LR, Lp), (RR, Rp) = pin.frame_placements_batch(rb.model, np.asarray(X, dtype=float)[:, :rb.model.nq], rb.foot_frame_ids)
+        elif w["feet_all"] is not None:  # no plant: every instance's feet are where its previous references put them for this tick
+            F = w["feet_all"]
+            (LR, Lp), (RR, Rp) = ((F[:, f, :9].reshape(B, 3, 3).copy(), F[:, f, 9:].copy()) for f in (0, 1))
+        else:
+            g = w["batch"]
+            (LR, Lp), (RR, Rp) = (g.sL[0].copy(), g.sL[1].copy()), (g.sR[0].copy(), g.sR[1].copy())
+        self._walk_forward_rule(w["batch"], takeoff_RF, takeoff_LF, land_RF, land_LF)
+        Lb, Rb = w["batch"].updateTrajectory(takeoff_RF, takeoff_LF, land_RF, land_LF, LR, Lp, RR, Rp)
+        w["refs_all"] = np.ascontiguousarray(np.stack([Lb[:, :2], Rb[:, :2]], axis=1))   # (B, 2 feet, 2 samples, 12)
+        w["feet_all"] = w["refs_all"][:, :, 1].copy()
+        # knot j holds the stage of schedule index j - N + tick before this tick's rotation: only the feet that stand there get their pose
+        phases = np.asarray(self.pd.contact_phases, dtype=bool)
+        stance = phases[np.maximum(0, np.arange(N) - N + self.tick) % self.pd.t_mpc][:, :2]
+        js, fs, idx = self._pose_patch_index(stance)
+        if js.size:
+            both = np.stack([Lb[:, :, 9:12], Rb[:, :, 9:12]], axis=2)   # (B, N, 2, 3)
+            vals = np.ascontiguousarray(np.repeat(both[:, js, fs][:, :, None, :], 3, axis=2)).reshape(-1)
+            self.native.update_instance_params_arrays(*idx, vals)
+
     def _walk_terminal(self):
         w, N = self._walk, self.problem.num_steps
         if w["kind"] == "contact_poses":
@@ -493,6 +614,21 @@ class EnsembleMPC:
 
     def results(self, **kw):
         return self.native.get_results(**kw)
+
+
+def _model_handle(lib, model, device=0):
+    """A handle that holds nothing but the model tables of ``model`` (``handle.ctx``: its LoweringContext, to which frames are added): what the
+    device generator of the contact-pose references runs its forward kinematics on when no simulator handle is at hand."""
+    ctx = core.LoweringContext()
+    ctx.set_model(model)
+    d = K.MpcDims()
+    d.horizon, d.batch, d.space = 1, 1, K.SPACE_MULTIBODY
+    d.nx, d.ndx, d.nu, d.nc_max = model.nq + model.nv, 2 * model.nv, model.nv - 6, 1
+    d.max_stage_ints, d.max_stage_doubles = 8 + 8 * 24, 64
+    d.device = int(device)
+    h = K.NativeSolver(lib, d)
+    h.ctx = ctx
+    return h
 
 
 def ensemble_initial_states(x0, space, total, seed=20250304, sigma_q=0.02, sigma_v=0.05, perturb_dofs=None):

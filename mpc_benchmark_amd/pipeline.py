@@ -114,6 +114,7 @@ def build_torque_simulator(lib, robot, batch, sim_dt, device):
     sim.set_options(_sim_options())
     sim.set_model(*ctx.model_tables())
     sim.set_stage(1, *term)
+    sim.ctx = ctx   # (whoever needs a frame of this handle's model tables adds it here: EnsembleMPC.enable_walk(model_handle=...))
     return sim, tables
 
 
@@ -326,7 +327,10 @@ class CentroidalPipeline:
       3. the ten steps run on the current (previous tick's) plan;
       4. only then is x0 = new_x of this period's last measurement set (``c_prev``), the stage of tick t rotated in and the solve run
          (``EnsembleMPC.solve_tick``, :454-462).
-    The centroidal OCP has no whole-body model: its references follow the previous references (``EnsembleMPC.enable_walk``).  The measured robots
+    The centroidal OCP has no whole-body model: by default one set of references, which follows the previous references, serves every robot
+    (``EnsembleMPC.enable_walk``).  ``walk=dict(per_instance=True)``: every robot's footholds are planned from the soles of ITS stale measurement
+    ``x_prev``, as the script plans from ``rdata.oMf`` (:369-371), and its task errors are taken against its own samples; with ``generator="device"``
+    the generator is one kernel per tick that reads ``x_prev`` where the device loop kept it (include/mpc_walk_poses.h).  The measured robots
     start from ``robot.x0``, perturbed as the kinodynamic pipeline's ensemble (``ensemble_initial_states``); the MPC starts from their centroidal
     states.  The simulator is the kinodynamic pipeline's stand-in (``build_torque_simulator``).  ``library``: the HIP library by default; the device
     loop (``low_level_loop``) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
@@ -336,7 +340,8 @@ class CentroidalPipeline:
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
                  sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, **ens_kw):
-        """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps) or None
+        """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
+        every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
         dict, ``terrain``: None or boxes (module docstring)."""
         from .ensemble import ensemble_initial_states
@@ -388,7 +393,10 @@ class CentroidalPipeline:
     def cold_solve(self, max_iters=100):
         st = self.mpc.cold_solve(max_iters=max_iters)
         if self._walk_args is not None:
-            self.mpc.enable_walk(**self._walk_args)
+            kw = dict(self._walk_args)
+            if kw.get("per_instance") and kw.get("generator") == "device":
+                kw.setdefault("model_handle", self.sim)   # the forward kinematics of the soles run on the simulator handle's model tables
+            self.mpc.enable_walk(**kw)
         self._fetch()
         return st
 
@@ -407,8 +415,14 @@ class CentroidalPipeline:
         return self.pd.contact_phases[max(0, t - N) % self.pd.t_mpc]
 
     def foot_refs(self):
-        """[B][2 feet][2 samples][12]: LF_refs[0:2], RF_refs[0:2] of this tick (R row-major, p); without a walk the initial footholds, twice."""
+        """[B][2 feet][2 samples][12]: LF_refs[0:2], RF_refs[0:2] of this tick (R row-major, p); without a walk the initial footholds, twice.  With
+        ``walk=dict(per_instance=True)`` every robot's own (``generator="device"``: fetched from the device, where the device loop reads them)."""
         w = self.mpc._walk
+        if w is not None and w.get("poses"):
+            if w["poses"] == "device":
+                return self.mpc.native.walk_poses_samples()
+            if w["refs_all"] is not None:
+                return w["refs_all"]
         pair = w["refs"] if (w is not None and "refs" in w) else tuple([M, M] for M in self.pd.robot.foot_placements)
         flat = lambda M: np.concatenate([np.asarray(M.rotation, dtype=float).reshape(-1), np.asarray(M.translation, dtype=float)])
         one = np.array([[flat(M) for M in pair[f][:2]] for f in range(2)])
@@ -444,8 +458,15 @@ class CentroidalPipeline:
         push = _push_array(push, self.batch)
         e = self.mpc
         cs = self.contact_state()
+        w = e._walk
+        on_device = w is not None and w.get("poses") == "device"
+        if w is not None and w.get("poses"):
+            # every robot plans from the soles of its stale measurement (what rdata holds at centroidal_talos.py:369-371); the device generator reads
+            # it where the device loop kept it, so nothing per robot travels for the references
+            keep = on_device and not host_glue and self._xik_on_device
+            w["x_measured_all"], w["xik_from"] = (None, self.qp.qp) if keep else (self.x_prev, None)
         e.plan_tick()
-        refs = self.foot_refs()
+        refs = None if (on_device and not host_glue) else self.foot_refs()
         self._set_sim_contacts(cs)
         if push is not None:
             self.sim.set_push(push)

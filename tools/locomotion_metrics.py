@@ -9,7 +9,8 @@ include/mpc_sim_metrics.h) read once at the end of each run.
 Built as tools/push_recovery.py builds them: 64 perturbed robots, the scripts' walks, N = 100, the reduced model, failure isolation (a robot whose MPC
 fails sits the rest out and counts as fallen).  Unpushed.  The cost: ms per MPC period (one tick: the ten low-level steps and the solve) at p50 over
 periods 100 - 199, once with metrics off (a run of its own over the first 200 periods) and once with metrics on (the whole run).
-usage: python tools/locomotion_metrics.py [--horizon N] [--ticks T (every formulation; default: the script's)] [--out PATH | --out -]"""
+usage: python tools/locomotion_metrics.py [--horizon N] [--ticks T (every formulation; default: the script's)] [--centroidal-per-robot host|device]
+       [--out PATH | --out -]"""
 import argparse
 import os
 import sys
@@ -26,6 +27,7 @@ B = 64
 G = 9.81
 SCRIPT_TICKS = {"kinodynamic": 820, "centroidal": 420, "fulldynamic": 1000}
 STEADY = slice(100, 200)
+CENTROIDAL_WALK = {}   # --centroidal-per-robot: per_instance / generator of the centroidal pipeline's walk (every robot plans from its own soles)
 
 
 def make_pipeline(model, N, T):
@@ -33,7 +35,7 @@ def make_pipeline(model, N, T):
     if model == "kinodynamic":
         p = KinodynamicPipeline(KinodynamicProblem(horizon=N), perturb=True, **kw)
     elif model == "centroidal":
-        p = CentroidalPipeline(CentroidalProblem(horizon=N), **kw)
+        p = CentroidalPipeline(CentroidalProblem(horizon=N), **dict(kw, walk=dict(CENTROIDAL_WALK)))
     else:
         p = FullDynamicPipeline(FullDynamicsProblem(horizon=N), **kw)
     p.mpc.prepare_schedule(T + 16)
@@ -63,8 +65,12 @@ def main():
     ap.add_argument("--horizon", type=int, default=100)
     ap.add_argument("--ticks", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "locomotion_metrics.txt"))
+    ap.add_argument("--centroidal-per-robot", choices=["host", "device"], default=None,
+                    help="the centroidal pipeline plans every robot's footholds from its own measured soles (enable_walk(per_instance=True, generator=...))")
     ap.add_argument("models", nargs="*", default=["kinodynamic", "centroidal", "fulldynamic"])
     a = ap.parse_args()
+    if a.centroidal_per_robot:
+        CENTROIDAL_WALK.update(per_instance=True, generator=a.centroidal_per_robot)
     N = a.horizon
     rows, cost = [], []
     for model in a.models:

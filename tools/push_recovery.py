@@ -15,7 +15,10 @@ period with record off (unpushed, and push armed) and with record on.  usage: py
 
 PUSH_RECOVERY_CONTACT_RULE=1 (opt-in): the pipelines' simulator with the unilateral contact rule on the device (``contact_rule={}``: every robot's feet
 decided by its own state, mpc_sim_contacts) instead of the schedule's contact set; the default models are then the three pipelines (kinodynamic,
-centroidal, fulldynamic_pipeline), and the EnsembleMPC closed loop (fulldynamic), which has no torque-driven simulator, is refused."""
+centroidal, fulldynamic_pipeline), and the EnsembleMPC closed loop (fulldynamic), which has no torque-driven simulator, is refused.
+
+PUSH_RECOVERY_CENTROIDAL_PER_ROBOT=host|device (opt-in; 1 = device): the centroidal pipeline plans every robot's footholds from the soles of its own
+measured state (``walk=dict(per_instance=True, generator=...)``) instead of one plan for all 64: a pushed robot steps from where it stands."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -31,6 +34,10 @@ MODELS = sys.argv[3:] or (["kinodynamic", "centroidal", "fulldynamic_pipeline"] 
 if RULE and "fulldynamic" in MODELS:
     sys.exit("PUSH_RECOVERY_CONTACT_RULE: the EnsembleMPC closed loop (fulldynamic) has no torque-driven simulator; name fulldynamic_pipeline")
 KW = {"contact_rule": {}} if RULE else {}
+PER_ROBOT = os.environ.get("PUSH_RECOVERY_CENTROIDAL_PER_ROBOT", "")
+if PER_ROBOT not in ("", "0", "1", "host", "device"):
+    sys.exit("PUSH_RECOVERY_CENTROIDAL_PER_ROBOT: host, device (or 1), or unset")
+CENTROIDAL_WALK = {} if PER_ROBOT in ("", "0") else dict(per_instance=True, generator=("host" if PER_ROBOT == "host" else "device"))
 B = 64
 DIRS = 8
 MAGS = 8
@@ -54,7 +61,7 @@ def make_pipeline(model):
         from mpc_benchmark_amd.problems.fulldynamic import FullDynamicsProblem
         p = FullDynamicPipeline(FullDynamicsProblem(horizon=N), batch=B, walk={}, sigma_q=0.005, sigma_v=0.01, tick_reuse=True, **KW)
     else:
-        p = CentroidalPipeline(CentroidalProblem(horizon=N), batch=B, walk={}, sigma_q=0.005, sigma_v=0.01, tick_reuse=True, **KW)
+        p = CentroidalPipeline(CentroidalProblem(horizon=N), batch=B, walk=dict(CENTROIDAL_WALK), sigma_q=0.005, sigma_v=0.01, tick_reuse=True, **KW)
     p.mpc.prepare_schedule(T_END + 16)
     p.cold_solve()
     p.mpc.enable_failure_isolation(auto_revive=False)  # (a robot whose MPC fails sits the rest out and counts as fallen)
@@ -136,6 +143,8 @@ if RULE:
     lines[0] = "PUSH_RECOVERY_CONTACT_RULE=1 " + lines[0]
     lines.insert(1, "Simulator: the unilateral contact rule on the device (contact_rule={}: release after 5 pulling steps at -1 N, catch within 5 mm of "
                     "the ground at the lower initial foothold), not the schedule's contact set.")
+if CENTROIDAL_WALK:
+    lines.insert(1, "Centroidal pipeline: every robot's footholds planned from its own measured soles (PUSH_RECOVERY_CENTROIDAL_PER_ROBOT, generator %s)." % CENTROIDAL_WALK["generator"])
 for model in MODELS:
     fd = PUSH_FORCE["fulldynamic" if model == "fulldynamic_pipeline" else model]
     f, th, mag = grid(fd)

@@ -19,7 +19,7 @@ periods 20 - 79, all in double support, runs of their own without the per-period
 ``rocprofv3 --kernel-trace --stats -d DIR -- python tools/stairs_walk.py --profile`` (k_sim_contacts per launch: the launches come in that order, 300 each;
 ``--boxes 0`` alone also runs on a library without the terrain entry points, e.g. ``MPC_HIP_LIBRARY=<a build of the parent commit>``).
 ``--summarize DIR [--boxes ...]`` prints the per-launch times of that trace, split by box count.
-usage: python tools/stairs_walk.py [--horizon N] [--models kinodynamic centroidal fulldynamic] [--apex 0.15 0.35] [--out PATH] [--profile [--boxes 0 3 16]]"""
+usage: python tools/stairs_walk.py [--horizon N] [--models kinodynamic centroidal fulldynamic] [--apex 0.15 0.35] [--centroidal-per-robot host|device] [--out PATH] [--profile [--boxes 0 3 16]]"""
 import argparse
 import os
 import sys
@@ -38,6 +38,7 @@ B = 64
 Z_HEIGHT = 0.10
 RISES = np.repeat(np.linspace(0.06, 0.14, 16), 4)   # per-robot runs: robot b's rise
 STEADY = slice(20, 80)
+CENTROIDAL_WALK = {}   # --centroidal-per-robot: per_instance / generator of the centroidal pipeline's walk (every robot plans from its own soles)
 
 
 def problem(model, N, complete=False):
@@ -77,6 +78,7 @@ def make_pipeline(model, N, T, terrain, rule=True, complete=False, n_steps=None,
     if model == "kinodynamic":
         p = KinodynamicPipeline(pd, perturb=True, **kw)
     elif model == "centroidal":
+        kw["walk"] = dict(kw["walk"], **CENTROIDAL_WALK)
         p = CentroidalPipeline(pd, **kw)
     else:
         p = FullDynamicPipeline(pd, **kw)
@@ -220,10 +222,14 @@ def main():
     ap.add_argument("--models", nargs="*", default=["kinodynamic", "centroidal", "fulldynamic"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--apex", type=float, nargs="*", default=[0.15, 0.35], help="swing_apex of the shared-staircase climbs (the first one also for the per-robot run)")
+    ap.add_argument("--centroidal-per-robot", choices=["host", "device"], default=None,
+                    help="the centroidal pipeline plans every robot's footholds from its own measured soles (enable_walk(per_instance=True, generator=...))")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--boxes", type=int, nargs="*", default=[0, 3, 16], help="--profile: the box counts to run, in this order (0, 3 or 16)")
     ap.add_argument("--summarize", default=None, metavar="DIR", help="print the per-launch times from the rocprofv3 output of a --profile run with the same --boxes")
     a = ap.parse_args()
+    if a.centroidal_per_robot:
+        CENTROIDAL_WALK.update(per_instance=True, generator=a.centroidal_per_robot)
     if a.summarize:
         summarize(a.summarize, a.boxes)
         return
