@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
+from . import contact_rule as _contact_rule
 
 
 class QpDims(C.Structure):
@@ -25,6 +26,12 @@ class QpInfo(C.Structure):
 
 _DP = C.POINTER(C.c_double)
 _bound = set()
+
+# include/mpc_qp_contacts.h (HIP library only): name -> (restype, argtypes)
+_QP_CONTACTS_SIGNATURES = {
+    "mpc_qp_contact_source": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mpc_qp_contact_source_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+}
 
 
 def _bind(lib):
@@ -57,6 +64,9 @@ def _bind(lib):
         lib.mpc_qp_ikid_low_level_steps.argtypes = [C.c_void_p, C.POINTER(QpSettings), C.c_void_p, C.c_void_p, C.c_int32, _IP, C.c_int32, C.c_int32,
                                                     _DP, _DP, _DP, _DP, _DP, _DP, _DP, C.c_double, _IP, _DP, _DP, C.c_int32, C.c_double,
                                                     _DP, _DP, _DP, _DP, _DP, C.POINTER(QpInfo), _DP]
+    for name, (res, args) in _QP_CONTACTS_SIGNATURES.items():
+        if hasattr(lib, name):  # HIP library only
+            getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
     _bound.add(id(lib))
     return lib
 
@@ -103,6 +113,32 @@ class BatchedQP:
         if rc != 0:
             raise RuntimeError("mpc_qp_solve: " + self.lib.mpc_qp_last_error(self._h).decode())
         return x, y, z, zb, list(info)
+
+    # ---- include/mpc_qp_contacts.h (HIP library only): where the QPs of the device loops take every robot's contact set from ----
+    def _qp_contacts(self, name):
+        if not hasattr(self.lib, name):
+            raise NotImplementedError("%s is not exported by this library: the contact source of the low-level QPs needs the HIP library "
+                                      "(libmpc_hip.so, include/mpc_qp_contacts.h)" % name)
+        return getattr(self.lib, name)
+
+    def contact_source(self, source):
+        """mpc_qp_contact_source: ``source`` a name of ``contact_rule.QP_SOURCES`` ("schedule": the caller's contact states, the default; "plant": each
+        robot's row of the simulator's contact rule; "both": their intersection, the plant's set where that is empty).  Sticky; zeroes the counts."""
+        fn = self._qp_contacts("mpc_qp_contact_source")
+        if fn(self._h, _contact_rule.qp_source(source)) != 0:
+            raise RuntimeError("mpc_qp_contact_source: " + self.lib.mpc_qp_last_error(self._h).decode())
+
+    def read_contact_source(self):
+        """mpc_qp_contact_source_read -> dict(source=name, used=(B, 2) int32 the contact set of the last QP of the last loop call, counts=(B, 2, 4)
+        int32 ``counts[b, c, 2 s + p]`` since the last ``contact_source``)."""
+        fn = self._qp_contacts("mpc_qp_contact_source_read")
+        B = self.dims.batch
+        src, used, counts = C.c_int32(-1), np.zeros((B, 2), dtype=np.int32), np.zeros((B, 2, 4), dtype=np.int32)
+        IP = C.POINTER(C.c_int32)
+        if fn(self._h, C.byref(src), used.ctypes.data_as(IP), counts.ctypes.data_as(IP)) != 0:
+            raise RuntimeError("mpc_qp_contact_source_read: " + self.lib.mpc_qp_last_error(self._h).decode())
+        names = {v: k for k, v in _contact_rule.QP_SOURCES.items()}
+        return dict(source=names[src.value], used=used, counts=counts)
 
     # ---- on-device assembly of the inverse-dynamics QP (mpc_qp_set_model / mpc_qp_solve_id) ----
     def set_model(self, itab, dtab):

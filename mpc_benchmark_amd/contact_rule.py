@@ -22,7 +22,13 @@ bit for bit).  The ground under sole i is ``g_i = h`` at the ORIGIN of the sole 
 ``ground_z`` in the free-foot branch: lifted above ``g_i + 2 ground_tol``, caught within ``ground_tol`` of ``g_i`` after lifting or when sinking
 below ``g_i``, the anchor at ``(x, y, g_i)``.  Without a terrain ``g_i`` is ``ground_z`` itself.  Deliberately not modelled, in keeping with a rule
 that is not a physics engine: risers (nothing stops a foot horizontally), a sole that hangs over an edge, a toe inside the next step (only the
-origin decides, so a toe that has crossed the next riser does not catch a descending foot on the step above), slopes."""
+origin decides, so a toe that has crossed the next riser does not catch a descending foot on the step above), slopes.
+
+The contact set of the low-level QPs (``mpc_qp_contact_source``, include/mpc_qp_contacts.h; ``BatchedQP.contact_source``, the pipelines'
+``contact_source=``): ``qp_contact_states`` and ``qp_contact_counts`` below are the definition the device loops are held to.  Per robot, with ``s`` the
+schedule's pair (what the plan's stage says) and ``p`` the rule's ``in_contact`` pair: ``"schedule"``: ``used = s``; ``"plant"``: ``used = p``;
+``"both"``: ``used = s & p``, and a robot for which that is empty takes ``p`` (the rule never releases the last contact, so ``p`` holds one).  The QP of
+step k reads the rows as they stand before step k: the state the rule left after step k - 1, which is the state the QP is solved at."""
 from __future__ import annotations
 
 import numpy as np
@@ -44,6 +50,53 @@ DEFAULTS = {
 
 TERRAIN_MAX_BOXES = 16   # MPC_SIM_TERRAIN_MAX_BOXES
 TERRAIN_BOX_WIDTH = 5    # MPC_SIM_TERRAIN_BOX_WIDTH: x_lo, x_hi, y_lo, y_hi, z_top
+
+
+QP_SOURCES = {"schedule": 0, "plant": 1, "both": 2}   # MPC_QP_CONTACTS_SCHEDULE, _PLANT, _BOTH
+
+
+def qp_source(source):
+    """the name of a contact source, checked -> its value in ``QP_SOURCES``"""
+    if not isinstance(source, str) or source not in QP_SOURCES:
+        raise ValueError("contact_source: one of %s expected, got %r" % (", ".join(repr(k) for k in QP_SOURCES), source))
+    return QP_SOURCES[source]
+
+
+def _pairs(schedule, in_contact):
+    p = (np.asarray(in_contact).reshape(-1, 2) != 0).astype(np.int32)
+    s = (np.broadcast_to(np.asarray(schedule), p.shape) != 0).astype(np.int32)
+    return s, p
+
+
+def qp_contact_states(source, schedule, in_contact):
+    """The contact set of every robot's low-level QP -> ``used`` (B, 2) int32.  ``source``: a name of ``QP_SOURCES``; ``schedule`` (2,) or (B, 2): the
+    plan's contact state; ``in_contact`` (B, 2): columns 0 and 1 of the rule's rows (module docstring)."""
+    k = qp_source(source)
+    s, p = _pairs(schedule, in_contact)
+    if k == QP_SOURCES["schedule"]:
+        return s.copy()
+    if k == QP_SOURCES["plant"]:
+        return p.copy()
+    both = s & p
+    return np.where(both.any(axis=1, keepdims=True), both, p).astype(np.int32)
+
+
+def qp_contact_counts(counts, schedule, in_contact):
+    """One step of the count of plan against plant -> a copy of ``counts`` (B, 2, 4) int32 (None: zeros) with ``counts[b, c, 2 s + p] += 1``:
+    index 0 both have the foot in the air, 3 both on the ground, 1 the plant holds a foot the plan has in the air, 2 the plan stands on a foot the
+    plant has released."""
+    s, p = _pairs(schedule, in_contact)
+    out = np.zeros(p.shape + (4,), dtype=np.int32) if counts is None else np.array(counts, dtype=np.int32, copy=True).reshape(p.shape + (4,))
+    b, c = np.indices(p.shape)
+    out[b, c, 2 * s + p] += 1
+    return out
+
+
+def qp_zero_unused(forces, used):
+    """``forces`` (B, 12) of a QP that worked with ``used`` (B, 2): the six components of a contact it did not use are 0 (a copy)."""
+    f = np.array(forces, dtype=float, copy=True).reshape(-1, 2, 6)
+    f[np.asarray(used).reshape(-1, 2) == 0] = 0.0
+    return f.reshape(-1, 12)
 
 
 def config(cfg=None, ground_z=None):

@@ -28,6 +28,7 @@
 #include "legs_tree.h"
 #include "pipeline_glue.h"
 #include "pipeline_ikid_glue.h"
+#include "pipeline_contacts.h"
 #include "pipeline_fd_glue.h"
 #include "sim_record.h"
 #include "sim_metrics.h"
@@ -1735,6 +1736,21 @@ int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32
   })
 }
 
+// include/mpc_qp_contacts.h: a loop call on a QP handle whose contact source is not the schedule.  The checks (throws), then the arguments of
+// k_pipe_contact_states: the caller's contact_states go to the schedule buffer and q.cs becomes an output of that kernel, once per step.
+static PipeContactsArgs pipe_contacts_args(const char* who, const QpContactSource& qc, const mpc_solver* sim, int nk, int B, int32_t* cs) {
+  if (nk != 2) throw std::runtime_error(std::string(who) + ": a contact source other than the schedule needs two contacts (nk = 2: the soles of mpc_sim_contacts)");
+  if (!sim_contacts_rows(sim))
+    throw std::runtime_error(std::string(who) + ": a contact source other than the schedule needs the contact rule on the simulator handle (mpc_sim_contacts first)");
+  PipeContactsArgs c;
+  c.rows = sim_contacts_rows(sim); c.width = MPC_SIM_CONTACTS_WIDTH; c.B = B; c.source = qc.source;
+  c.sched = qc.sched; c.cs = cs; c.used = qc.used; c.counts = qc.counts;
+  return c;
+}
+static void pipe_contacts_enqueue(const PipeContactsArgs& c, hipStream_t st) {
+  hipLaunchKernelGGL(k_pipe_contact_states, dim3((unsigned)((2 * c.B + 63) / 64)), dim3(64), 0, st, c);
+}
+
 // include/mpc_qp_abi.h: the low-level loop of the kinodynamic pipeline with nothing but the kernels between its stages.  Everything is enqueued on
 // the QP handle's stream (the plan and the simulator are idle: their streams are drained first); one synchronisation at the end.
 int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solver* plan, mpc_solver* sim, int32_t nk, const int32_t* frames,
@@ -1744,6 +1760,9 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
   try {
     if (!S || !plan || !sim || !contact_states || !tau_max) throw std::runtime_error("qp_low_level_steps: null argument");
     if (steps <= 0 || !(dt > 0.0)) throw std::runtime_error("qp_low_level_steps: steps and dt must be positive");
+    const QpContactSource qc = qp_contact_source(qp);
+    const bool from_plant = qc.source != MPC_QP_CONTACTS_SCHEDULE;
+    if (from_plant) (void)pipe_contacts_args("qp_low_level_steps", qc, sim, nk, 0, nullptr);  // (the checks, before anything is allocated for another nk)
     qp_id_prepare(qp, nk, frames, weights, cone);
     const QpIdBuffers q = qp_id_buffers(qp);
     const Layout& P = plan->L;
@@ -1768,17 +1787,21 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
     hipStream_t st = q.stream;
     if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
     sim_metrics_begin(sim, st);
-    HIP_OK(hipMemcpyAsync(q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(from_plant ? qc.sched : q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_taumax, tau_max, nu * sizeof(double), hipMemcpyHostToDevice, st));
+    PipeContactsArgs pc = {};
+    if (from_plant) pc = pipe_contacts_args("qp_low_level_steps", qc, sim, nk, (int)B, q.cs);
     PipeArgs p;
     p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains; p.knots = plan->d_knots;
     p.N = P.N; p.nx = nx; p.nq = q.nq; p.nv = q.nv; p.n = P.n; p.m = P.m; p.gain_stride = P.gain_stride; p.oK = P.oK; p.knot_stride = P.knot_stride; p.oXD = P.oXD;
     p.slot0 = plan->khead % P.N;
     p.x = sim->d_x0; p.xrob = q.xrob; p.acc = q.acc; p.f = q.f; p.sol = q.sol; p.nk = nk; p.qn = q.n; p.tau_max = d_taumax; p.sim_u = sim->d_simu; p.f_new = d_fnew;
+    p.used = from_plant ? qc.used : nullptr;
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
       if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(d_xprev, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(k_pipe_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
+      if (from_plant) pipe_contacts_enqueue(pc, st);  // (the rows as the rule left them after the step before: the state this QP is solved at)
       qp_id_enqueue(qp, S, kd);
       qp_launch_solve(qp, S);
       hipLaunchKernelGGL(k_pipe_torque, dim3((unsigned)B), dim3(64), 0, st, p);
@@ -1819,6 +1842,9 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     if (!foot_refs && !plan->poses_on) throw std::runtime_error("qp_ikid_low_level_steps: null argument");
     if (steps <= 0 || !(dt > 0.0) || !(ref_dt > 0.0)) throw std::runtime_error("qp_ikid_low_level_steps: steps, dt and ref_dt must be positive");
     if (nk != 2) throw std::runtime_error("qp_ikid_low_level_steps: two contacts (nk = 2) expected");
+    const QpContactSource qc = qp_contact_source(qp);
+    const bool from_plant = qc.source != MPC_QP_CONTACTS_SCHEDULE;
+    if (from_plant) (void)pipe_contacts_args("qp_ikid_low_level_steps", qc, sim, nk, 0, nullptr);
     qp_ikid_prepare(qp, nk, frames, base_frame, torso_frame, weights, gains, cone, l_box, u_box);
     const QpIdBuffers q = qp_id_buffers(qp);
     const Layout& P = plan->L;
@@ -1848,7 +1874,9 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
     sim_metrics_begin(sim, st);
     if (x_ik) HIP_OK(hipMemcpyAsync(d_xprev, x_ik, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(from_plant ? qc.sched : q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    PipeContactsArgs pc = {};
+    if (from_plant) pc = pipe_contacts_args("qp_ikid_low_level_steps", qc, sim, nk, (int)B, q.cs);
     HIP_OK(hipMemcpyAsync(d_xpost, x_posture, nx * sizeof(double), hipMemcpyHostToDevice, st));
     if (foot_refs) HIP_OK(hipMemcpyAsync(d_refs, foot_refs, B * 48 * sizeof(double), hipMemcpyHostToDevice, st));
     else HIP_OK(hipMemcpyAsync(d_refs, plan->d_poses_samples, B * 48 * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -1862,6 +1890,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     g.ik = q.ik;
     g.x = sim->d_x0; g.xrob = q.xrob; g.f = q.f; g.c_prev = d_cprev;
     g.sol = q.sol; g.nk = nk; g.qn = q.n; g.sim_u = sim->d_simu; g.f_new = d_fnew;
+    g.used = from_plant ? qc.used : nullptr;
     hipLaunchKernelGGL(k_ikid_task_errors, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
     HIP_OK(hipGetLastError());
     if (ik_out) HIP_OK(hipMemcpyAsync(ik_out, q.ik, B * nik * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1870,6 +1899,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
       g.last = (step == steps - 1);
       if (g.last) HIP_OK(hipMemcpyAsync(d_xprev, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(k_pipe_centroidal_feedback, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+      if (from_plant) pipe_contacts_enqueue(pc, st);  // (the rows as the rule left them after the step before: the state this QP is solved at)
       qp_ikid_enqueue(qp, S);
       qp_launch_solve(qp, S);
       hipLaunchKernelGGL(k_pipe_ikid_torque, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);

@@ -16,6 +16,7 @@ struct PipeArgs {
   const double* tau_max;  // [nv - 6]
   double *sim_u;          // [B][nv - 6] torques of the simulator step
   double *f_new;          // [B][6 nk] forces + df
+  const int32_t* used;    // [B][nk] contact set the QP worked with (pipeline_contacts.h), or nullptr: the caller's contact_states, f_new as it is
 };
 
 #define PIPE_MAX_N 160  // tangent dimension 2 nv of the plan
@@ -50,7 +51,7 @@ __global__ void __launch_bounds__(64) k_pipe_feedback(PipeArgs p) {
   for (int i = lane; i < nx; i += 64) p.xrob[(size_t)b * nx + i] = x[i];
 }
 
-// tau = clamp(QP torque, +-tau_max) into the simulator's input ; forces + df
+// tau = clamp(QP torque, +-tau_max) into the simulator's input ; forces + df (with `used`: 0 for a contact the QP did not use)
 __global__ void __launch_bounds__(64) k_pipe_torque(PipeArgs p) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nv = p.nv, nf = 6 * p.nk, nu = nv - 6;
@@ -59,5 +60,9 @@ __global__ void __launch_bounds__(64) k_pipe_torque(PipeArgs p) {
     const double t = sol[nv + nf + i], lim = p.tau_max[i];
     p.sim_u[(size_t)b * nu + i] = fmin(fmax(t, -lim), lim);
   }
-  for (int i = lane; i < nf; i += 64) p.f_new[(size_t)b * nf + i] = p.f[(size_t)b * nf + i] + sol[nv + i];
+  if (!p.used) {
+    for (int i = lane; i < nf; i += 64) p.f_new[(size_t)b * nf + i] = p.f[(size_t)b * nf + i] + sol[nv + i];
+    return;
+  }
+  for (int i = lane; i < nf; i += 64) p.f_new[(size_t)b * nf + i] = p.used[(size_t)b * p.nk + i / 6] ? p.f[(size_t)b * nf + i] + sol[nv + i] : 0.0;
 }

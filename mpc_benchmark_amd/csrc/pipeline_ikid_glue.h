@@ -35,6 +35,7 @@ struct IkidGlueArgs {
   int nk, qn;
   double* sim_u;         // [B][nv - 6]
   double* f_new;         // [B][6 nk] forces + df
+  const int32_t* used;   // [B][nk] contact set the QP worked with (pipeline_contacts.h), or nullptr: the caller's contact_states, f_new as it is
 };
 
 struct CgBodies {  // LDS of the kinematics: per body local and world placement, spatial velocity at the world origin
@@ -212,10 +213,15 @@ __global__ void __launch_bounds__(CG_THREADS) k_pipe_centroidal_feedback(IkidGlu
   if (a.last && tid < CG_NC) a.c_prev[(size_t)b * CG_NC + tid] = cx[tid];
 }
 
-// the QP's torque into the simulator's input (no clamp: the QP's torque box is the limit, centroidal_talos.py:435-447) ; forces + df
+// the QP's torque into the simulator's input (no clamp: the QP's torque box is the limit, centroidal_talos.py:435-447) ; forces + df (with `used`: 0 for a
+// contact the QP did not use)
 __global__ void __launch_bounds__(CG_THREADS) k_pipe_ikid_torque(IkidGlueArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, nv = a.nv, nf = 6 * a.nk, nu = nv - 6;
   const double* sol = a.sol + (size_t)b * a.qn;
   for (int i = tid; i < nu; i += CG_THREADS) a.sim_u[(size_t)b * nu + i] = sol[nv + nf + i];
-  for (int i = tid; i < nf; i += CG_THREADS) a.f_new[(size_t)b * nf + i] = a.f[(size_t)b * nf + i] + sol[nv + i];
+  if (!a.used) {
+    for (int i = tid; i < nf; i += CG_THREADS) a.f_new[(size_t)b * nf + i] = a.f[(size_t)b * nf + i] + sol[nv + i];
+    return;
+  }
+  for (int i = tid; i < nf; i += CG_THREADS) a.f_new[(size_t)b * nf + i] = a.used[(size_t)b * a.nk + i / 6] ? a.f[(size_t)b * nf + i] + sol[nv + i] : 0.0;
 }

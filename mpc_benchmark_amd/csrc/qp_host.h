@@ -42,6 +42,8 @@ struct mpc_qp_solver {
   std::vector<double> ikid_const;
   std::vector<double> id_const;  // weights[2], cone[54], frames[nk] as last uploaded
   double* d_glue = nullptr; size_t glue_cap = 0;  // scratch of mpc_qp_low_level_steps (pipeline_glue.h)
+  int contact_source = MPC_QP_CONTACTS_SCHEDULE;  // mpc_qp_contact_source (pipeline_contacts.h)
+  int32_t *d_sched = nullptr, *d_used = nullptr, *d_counts = nullptr;  // [B][2], [B][2], [B][2][4]: allocated by the first source other than the schedule
   std::vector<void*> allocs;
   std::string err;
   template <class T> T* alloc(size_t count) {
@@ -256,6 +258,11 @@ double* qp_scratch(mpc_qp_solver* s, size_t doubles) {
   return s->d_glue;
 }
 void qp_set_error(mpc_qp_solver* s, const char* what) { s->err = what; }
+QpContactSource qp_contact_source(mpc_qp_solver* s) {
+  QpContactSource o;
+  o.source = s->contact_source; o.sched = s->d_sched; o.used = s->d_used; o.counts = s->d_counts;
+  return o;
+}
 double* qp_ikid_scratch(mpc_qp_solver* s, size_t doubles, bool** kept) {
   if (s->ikglue_cap < doubles) { s->d_ikglue = s->alloc<double>(doubles); s->ikglue_cap = doubles; s->ikid_have_xprev = false; }
   *kept = &s->ikid_have_xprev;
@@ -382,6 +389,45 @@ int mpc_qp_solve_ikid(mpc_qp_solver* s, const mpc_qp_settings* S, int32_t nk, co
     if (C_out) HIP_OK(hipMemcpyAsync(C_out, s->dC, B * nin * n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     if (l_out) HIP_OK(hipMemcpyAsync(l_out, s->dl, B * nin * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     qp_launch_and_fetch(s, S, x, y, z, z_box, info);
+    return 0;
+  } catch (const std::exception& e) { s->err = e.what(); return -1; }
+}
+
+// include/mpc_qp_contacts.h
+int mpc_qp_contact_source(mpc_qp_solver* s, int32_t source) {
+  if (!s) return -2;
+  try {
+    HIP_OK(hipSetDevice(s->d.device));
+    if (source != MPC_QP_CONTACTS_SCHEDULE && source != MPC_QP_CONTACTS_PLANT && source != MPC_QP_CONTACTS_BOTH)
+      throw std::runtime_error("qp_contact_source: unknown source (0 schedule, 1 plant, 2 both: include/mpc_qp_contacts.h)");
+    const size_t B = s->d.batch;
+    if (source != MPC_QP_CONTACTS_SCHEDULE && !s->d_counts) {
+      s->d_sched = s->alloc<int32_t>(B * 2); s->d_used = s->alloc<int32_t>(B * 2); s->d_counts = s->alloc<int32_t>(B * 8);
+    }
+    if (s->d_counts) HIP_OK(hipMemsetAsync(s->d_counts, 0, B * 8 * sizeof(int32_t), s->stream));
+    HIP_OK(hipStreamSynchronize(s->stream));
+    s->contact_source = source;
+    return 0;
+  } catch (const std::exception& e) { s->err = e.what(); return -1; }
+}
+
+int mpc_qp_contact_source_read(mpc_qp_solver* s, int32_t* source, int32_t* used, int32_t* counts) {
+  if (!s) return -2;
+  try {
+    HIP_OK(hipSetDevice(s->d.device));
+    const size_t B = s->d.batch;
+    if (source) *source = s->contact_source;
+    // the schedule as the source: the loops wrote nothing but the contact states of the assembly themselves
+    const int32_t* d_used = s->contact_source != MPC_QP_CONTACTS_SCHEDULE ? s->d_used : (s->id_nk == 2 ? s->d_cs : nullptr);
+    if (used) {
+      if (d_used) HIP_OK(hipMemcpyAsync(used, d_used, B * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+      else std::memset(used, 0, B * 2 * sizeof(int32_t));
+    }
+    if (counts) {
+      if (s->d_counts) HIP_OK(hipMemcpyAsync(counts, s->d_counts, B * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+      else std::memset(counts, 0, B * 8 * sizeof(int32_t));
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
     return 0;
   } catch (const std::exception& e) { s->err = e.what(); return -1; }
 }

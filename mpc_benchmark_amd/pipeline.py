@@ -19,12 +19,21 @@ foot placements, no physics engine.  ``library``: the HIP library by default; te
 
 ``contact_rule`` (all three pipelines): None, the simulator of the schedule above; or a dict over ``contact_rule.DEFAULTS`` ({} for the defaults,
 the ground at the lower initial foothold): the simulator's stage 0 is double support and the unilateral rule of the headless BulletRobot decides
-every robot's contacts on the device after every step (mpc_sim_contacts, include/mpc_sim_contacts.h; HIP library only).  The low-level QPs keep
-the schedule's ``contact_state``, as the scripts do with ``problem.stages[0]``.
+every robot's contacts on the device after every step (mpc_sim_contacts, include/mpc_sim_contacts.h; HIP library only).  By default the low-level
+QPs keep the schedule's ``contact_state``, as the scripts do with ``problem.stages[0]``; ``contact_source`` changes that.
+
+``contact_source`` (``KinodynamicPipeline`` and ``CentroidalPipeline``; the full-dynamics pipeline has no QP): ``"schedule"``, the default: every
+robot's low-level QP works with ``contact_state()``, bit for bit what the pipelines did without the argument.  With ``contact_rule``, ``"plant"``: each
+robot's QP takes the contact set of its own row of the rule, as it stands before the step; ``"both"``: the intersection of the two, and the plant's
+set for a robot whose intersection is empty (``contact_rule.qp_contact_states`` is the definition).  The six ``forces`` components of a contact the QP
+did not use are then 0.  ``tick()`` selects on the device, step by step, with no host round trip inside the period (mpc_qp_contact_source,
+include/mpc_qp_contacts.h; HIP library only); ``tick(host_glue=True)`` reads the rows before every step and applies the numpy mirror.
+``qp_contacts()`` returns the set of the last QP and the counts of plan against plant on either path.
 
 ``terrain`` (all three pipelines, with ``contact_rule`` only): None, the ground is the plane; or boxes ``(n, 5)`` for every robot / ``(B, n, 5)`` per
 robot under the rule (mpc_sim_terrain, include/mpc_sim_terrain.h; ``contact_rule.stairs`` lays the reference's staircase).  Nothing else about a
-tick changes: the planner and the low-level QPs keep the schedule's footholds and ``contact_state``; the plant decides where a foot is caught."""
+tick changes: the planner keeps the schedule's footholds, the low-level QPs the contact set ``contact_source`` names (by default the schedule's
+``contact_state``); the plant decides where a foot is caught."""
 from __future__ import annotations
 
 import numpy as np
@@ -161,13 +170,64 @@ def stairs_under_walk(robot, x_forward, z_height, y_gap=0.18, n_steps=3, half_ex
     return boxes, holds
 
 
-class KinodynamicPipeline:
+class _QpContactSource:
+    """``contact_source`` of the two pipelines with a low-level QP (module docstring): the checks, the host-glue form of the selection (the numpy mirror
+    ``contact_rule.qp_contact_states`` on the rows read before every step) and ``qp_contacts``."""
+
+    def _init_contact_source(self, name, source, contact_rule):
+        """checked before any library call"""
+        _contact_rule.qp_source(source)
+        if source != "schedule" and contact_rule is None:
+            raise ValueError("%s: contact_source=%r needs contact_rule (the plant's contact set is a row of the unilateral contact rule; "
+                             "contact_rule={} turns it on)" % (name, source))
+        self.contact_source = source
+        self._qp_used = np.zeros((self.batch, 2), dtype=np.int32)          # the set of the last QP on the host-glue path (and of "schedule")
+        self._qp_counts = np.zeros((self.batch, 2, 4), dtype=np.int32)     # counted on the host-glue path
+        self._qp_last_on_device = False
+        self._qp_source_on_device = False
+
+    def _host_contact_set(self, cs):
+        """host glue, before a low-level step: the contact set of every robot's QP from the rows as they stand -> (B, 2) int32"""
+        self._qp_last_on_device = False
+        if self.contact_source == "schedule":
+            self._qp_used = _contact_rule.qp_contact_states("schedule", cs, np.ones((self.batch, 2)))
+            return self._qp_used
+        p = self.sim.read_contacts()["in_contact"]
+        self._qp_used = _contact_rule.qp_contact_states(self.contact_source, cs, p)
+        self._qp_counts = _contact_rule.qp_contact_counts(self._qp_counts, cs, p)
+        return self._qp_used
+
+    def _device_contact_source(self, cs):
+        """device loop: the mode is set once on the QP handle (never for "schedule": the handle's default, and the call is HIP only)"""
+        if self.contact_source == "schedule":
+            self._qp_used = _contact_rule.qp_contact_states("schedule", cs, np.ones((self.batch, 2)))
+            return
+        if not self._qp_source_on_device:
+            self.qp.qp.contact_source(self.contact_source)
+            self._qp_source_on_device = True
+        self._qp_last_on_device = True
+
+    def qp_contacts(self):
+        """-> dict(used=(B, 2) int32: the contact set of every robot's last low-level QP; counts=(B, 2, 4) int32: ``counts[b, c, 2 s + p]``, how many
+        steps the schedule (s) and the plant (p) had contact c of robot b off / on (``contact_rule.qp_contact_counts``)).  With ``"schedule"`` nothing
+        is read from the plant and the counts stay 0."""
+        used, counts = self._qp_used.copy(), self._qp_counts.copy()
+        if self._qp_source_on_device:
+            r = self.qp.qp.read_contact_source()
+            counts += r["counts"]
+            if self._qp_last_on_device:
+                used = r["used"]
+        return dict(used=used, counts=counts)
+
+
+class KinodynamicPipeline(_QpContactSource):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
-                 terrain=None, **ens_kw):
+                 terrain=None, contact_source="schedule", **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
-        or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes (module
-        docstring)."""
+        or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
+        ``contact_source``: "schedule", "plant" or "both" (module docstring)."""
         self.pd, self.batch = problem_def, int(batch)
+        self._init_contact_source("KinodynamicPipeline", contact_source, contact_rule)
         self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
@@ -227,7 +287,8 @@ class KinodynamicPipeline:
         return self.pd.contact_phases[max(0, t + 1 - N) % self.pd.t_mpc]
 
     def low_level_step(self, cs):
-        """One 1 kHz step of kinodynamic_talos.py:411-462 for every robot, the glue between the library calls on the host."""
+        """One 1 kHz step of kinodynamic_talos.py:411-462 for every robot, the glue between the library calls on the host.  ``cs``: (2,) for every
+        robot or (B, 2) per robot."""
         if self._plan_stale:
             self._fetch()
         nq, nv = self.nq, self.nv
@@ -236,7 +297,7 @@ class KinodynamicPipeline:
         a0 = self.xdot0[:, nv:].copy()
         a0[:, 6:] = self.us0[:, 12:] - np.einsum("bij,bj->bi", self.K0[:, 12:], d)
         forces = self.us0[:, :12] - np.einsum("bij,bj->bi", self.K0[:, :12], d)
-        a_new, f_new, tau = self.qp.solve_batch_device(x, a0, forces, np.tile(np.asarray(cs, dtype=np.int32), (self.batch, 1)))
+        a_new, f_new, tau = self.qp.solve_batch_device(x, a0, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
         tau = np.clip(tau, -self.umax, self.umax)
         self.x = self.sim.simulate_torque(x, tau, 1, self.sim_dt)
         self.torques, self.forces = tau, f_new
@@ -245,6 +306,7 @@ class KinodynamicPipeline:
     def low_level_loop(self, cs):
         """The ``substeps`` low-level periods of one MPC period inside the library (mpc_qp_low_level_steps: feedback terms, QP, clamp and simulator step chained
         on the device, one synchronisation).  -> the measured states before the last period (the script reads x_measured BEFORE the last execute of the tick)."""
+        self._device_contact_source(cs)
         cs_all = np.tile(np.asarray(cs, dtype=np.int32), (self.batch, 1))
         x_last, self.x, self.torques, self.forces = self.qp.low_level_steps(self.mpc.native, self.sim, cs_all, self.umax, self.substeps, self.sim_dt, x=self.x)
         return x_last
@@ -265,7 +327,10 @@ class KinodynamicPipeline:
                     self._fetch()
                 for _ in range(self.substeps):
                     x_last = self.x.copy()   # (the script's x_measured is read BEFORE the last execute of the tick)
-                    self.low_level_step(cs)
+                    used = self._host_contact_set(cs)
+                    self.low_level_step(used)
+                    if self.contact_source != "schedule":
+                        self.forces = _contact_rule.qp_zero_unused(self.forces, used)
             else:
                 x_last = self.low_level_loop(cs)
         finally:
@@ -307,7 +372,7 @@ def posture_gains(nv):
     return G, 2 * np.sqrt(G)
 
 
-class CentroidalPipeline:
+class CentroidalPipeline(_QpContactSource):
     """The centroidal control pipeline of centroidal_talos.py:353-468 for an ensemble of robots, every stage on the solver library:
 
         MPC tick (centroidal OCP, x = [com ; h_lin ; h_ang], one ProxDDP iteration)
@@ -339,13 +404,14 @@ class CentroidalPipeline:
     G_FOOT, G_ROT = 400.0, 10.0                        # g_p, g_b (:305-307)
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
-                 sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, **ens_kw):
+                 sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
-        dict, ``terrain``: None or boxes (module docstring)."""
+        dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both" (module docstring)."""
         from .ensemble import ensemble_initial_states
         self.pd, self.batch = problem_def, int(batch)
+        self._init_contact_source("CentroidalPipeline", contact_source, contact_rule)
         self.terrain = _checked_terrain("CentroidalPipeline", terrain, contact_rule, self.batch)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
@@ -429,14 +495,14 @@ class CentroidalPipeline:
         return np.ascontiguousarray(np.broadcast_to(one, (self.batch, 2, 2, 12)))
 
     def low_level_step(self, cs, ik):
-        """One 1 kHz step of centroidal_talos.py:420-447 for every robot, the glue between the library calls on the host.  -> new_x of the
-        measurement the step started from."""
+        """One 1 kHz step of centroidal_talos.py:420-447 for every robot, the glue between the library calls on the host (``cs``: (2,) for every
+        robot or (B, 2) per robot).  -> new_x of the measurement the step started from."""
         if self._plan_stale:
             self._fetch()
         x = self.x
         new_x = centroidal_state(self.model, x)
         forces = self.us0 - np.einsum("bij,bj->bi", self.K0, self.xs0 - new_x)   # us[0] - K_0 difference(new_x, xs[0])
-        _, f_new, tau = self.qp.solve_batch_device_ik(x, ik, forces, np.tile(np.asarray(cs, dtype=np.int32), (self.batch, 1)))
+        _, f_new, tau = self.qp.solve_batch_device_ik(x, ik, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
         self.x = self.sim.simulate_torque(x, tau, 1, self.sim_dt)
         self.torques, self.forces = tau, f_new
         return new_x
@@ -444,6 +510,7 @@ class CentroidalPipeline:
     def low_level_loop(self, cs, refs):
         """The ``substeps`` low-level periods of one MPC period inside the library (mpc_qp_ikid_low_level_steps: task errors, centroidal state,
         feedback forces, QP and simulator step chained on the device, one synchronisation)."""
+        self._device_contact_source(cs)
         cs_all = np.tile(np.asarray(cs, dtype=np.int32), (self.batch, 1))
         x_ik = None if self._xik_on_device else self.x_prev
         self.x_prev, self.c_prev, self.x, self.torques, self.forces, self.ik = self.qp.low_level_steps(
@@ -477,7 +544,10 @@ class CentroidalPipeline:
                 self.ik = self.qp.task_errors(self.x_prev, self.x_posture, refs, self.ref_dt, self.dH)
                 for _ in range(self.substeps):
                     x_last = self.x.copy()   # (the script's x_measured is read BEFORE the last execute of the period)
-                    c_last = self.low_level_step(cs, self.ik)
+                    used = self._host_contact_set(cs)
+                    c_last = self.low_level_step(used, self.ik)
+                    if self.contact_source != "schedule":
+                        self.forces = _contact_rule.qp_zero_unused(self.forces, used)
                 self.x_prev, self.c_prev = x_last, c_last
                 self._xik_on_device = False
             else:
