@@ -190,6 +190,15 @@ _WALK_POSES_SIGNATURES = {
     "mpc_walk_poses_get_samples": (C.c_int, [C.c_void_p, _DP]),
 }
 
+# include/mpc_walk_commands.h: exported by the HIP library alone, bound when present (``NativeSolver.walk_set_commands`` / ``walk_poses_set_commands`` ...)
+WALK_COMMAND_WIDTH = 16
+_WALK_COMMANDS_SIGNATURES = {
+    "mpc_walk_set_commands": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_walk_get_commands": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_walk_poses_set_commands": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_walk_poses_get_commands": (C.c_int, [C.c_void_p, _DP]),
+}
+
 
 def bind_library(path):
     """dlopen ``path`` and attach the argument/return types of every entry point of mpc_abi.h."""
@@ -199,7 +208,7 @@ def bind_library(path):
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()):
+            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -615,6 +624,45 @@ class NativeSolver:
         out = np.zeros((self.dims.batch, 2, 2, 12))
         self._check(self._walk_poses("mpc_walk_poses_get_samples")(self._h, _dp(out)), "mpc_walk_poses_get_samples")
         return out
+
+    # -- include/mpc_walk_commands.h (HIP library only): a walk command per robot for the two device generators -----------------------------------
+    def _walk_commands(self, name):
+        if not hasattr(self.lib, name):
+            raise NotImplementedError("%s is not exported by this library (%s): a walk command per robot on the device generators needs the HIP library "
+                                      "(libmpc_hip.so, include/mpc_walk_commands.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def _set_commands(self, name, cmd):
+        fn = self._walk_commands(name)
+        if cmd is None:
+            self._check(fn(self._h, None), name)
+            return
+        c = _f64(cmd)
+        if c.shape != (self.dims.batch, WALK_COMMAND_WIDTH):
+            raise ValueError("%s: a table of shape (%d, %d) expected, got %s" % (name, self.dims.batch, WALK_COMMAND_WIDTH, c.shape))
+        self._check(fn(self._h, _dp(c)), name)
+
+    def _get_commands(self, name):
+        fn = self._walk_commands(name)
+        out = np.zeros((self.dims.batch, WALK_COMMAND_WIDTH))
+        self._check(fn(self._h, _dp(out)), name)
+        return out
+
+    def walk_set_commands(self, cmd):
+        """``cmd`` (B, 16): robot b's row of ``references.walk_commands`` for the generator of ``walk_update`` from now on; None: the shared
+        configuration again (mpc_walk_set_commands)."""
+        self._set_commands("mpc_walk_set_commands", cmd)
+
+    def walk_get_commands(self):
+        """-> (B, 16): the table in force (mpc_walk_get_commands; an error when none is set)."""
+        return self._get_commands("mpc_walk_get_commands")
+
+    def walk_poses_set_commands(self, cmd):
+        """``walk_set_commands`` for the generator of ``walk_poses_update`` (mpc_walk_poses_set_commands)."""
+        self._set_commands("mpc_walk_poses_set_commands", cmd)
+
+    def walk_poses_get_commands(self):
+        return self._get_commands("mpc_walk_poses_get_commands")
 
     def update_instance_params_batch(self, patches):
         """``patches``: iterable of (instance, stage k, offset, values)."""

@@ -121,6 +121,9 @@ struct mpc_solver {
   std::vector<uint8_t> walk_poisoned;  // per ring slot: the host mirror of the ranges k_walk_refs writes holds NaN (see mpc_walk_update)
   mpc_walk_config walk{};
   double* d_walk_state = nullptr;  // [B][48]
+  // include/mpc_walk_commands.h: the command tables [B][16] of the two generators (allocated once) and whether they are in force
+  double *d_walk_cmd = nullptr, *d_poses_cmd = nullptr;
+  bool walk_cmd_on = false, poses_cmd_on = false;
   // include/mpc_walk_poses.h: the generator of the centroidal problem's contact poses (k_walk_poses): plan [B][48], reference samples [B][48], host-given measurements
   bool poses_on = false;
   mpc_walk_poses_config poses{};
@@ -1100,6 +1103,7 @@ int mpc_walk_init(mpc_solver* s, const mpc_walk_config* cfg) {
     }
     copy_sync(s, s->d_walk_state, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice);
     s->walk_on = true;
+    s->walk_cmd_on = false;  // (include/mpc_walk_commands.h: a new configuration starts without a table)
   })
 }
 
@@ -1108,9 +1112,12 @@ int mpc_walk_update(mpc_solver* s, int32_t takeoff_RF, int32_t takeoff_LF, int32
     const Layout& L = s->L;
     if (!s->walk_on) throw std::runtime_error("walk_update: mpc_walk_init first");
     mpc_walk_config& c = s->walk;
+    if (forward && s->walk_cmd_on)
+      throw std::runtime_error("walk_update: forward is refused while a command table is set (mpc_walk_set_commands: every robot walks its own row; set the stopped rows instead)");
     if (forward) { std::memcpy(c.t_left, forward, 24); std::memcpy(c.t_right, forward + 3, 24); c.swing_apex = forward[6]; }
     const bool replanning = land_LF < 0 || land_RF < 0 || (takeoff_RF >= 0 && takeoff_RF < c.T_ds) || (takeoff_LF >= 0 && takeoff_LF < c.T_ds);
-    hipLaunchKernelGGL(k_walk_refs, dim3(L.B), dim3(128), 0, s->stream, s->args(), c, s->d_walk_state, (int)takeoff_RF, (int)takeoff_LF, (int)land_RF, (int)land_LF, replanning ? 1 : 0, (replanning || s->walk_force_all) ? 1 : 0);
+    hipLaunchKernelGGL(k_walk_refs, dim3(L.B), dim3(128), 0, s->stream, s->args(), c, s->d_walk_state, (int)takeoff_RF, (int)takeoff_LF, (int)land_RF, (int)land_LF, replanning ? 1 : 0, (replanning || s->walk_force_all) ? 1 : 0,
+                       (const double*)(s->walk_cmd_on ? s->d_walk_cmd : nullptr));
     HIP_OK(hipGetLastError());
     // tick reuse: the records of the knots whose references were rewritten are stale (on a replanning tick: all of them)
     if (replanning || s->walk_force_all) for (int k = 0; k < L.N; ++k) s->slot_dirty[slot_of(s, k)] = 1;
@@ -2384,3 +2391,4 @@ int mpc_debug_get(mpc_solver* s, const char* name, int32_t b, int32_t k, double*
 }  // extern "C"
 
 #include "walk_poses.h"
+#include "walk_commands.h"

@@ -885,10 +885,15 @@ __global__ void k_shift(SolverArgs a, const double* xs_in, const double* us_in, 
 // as the stage tables are, BEFORE the rotation of this tick — and the owner of knot N - 1 the terminal node's targets.
 // ------------------------------------------------------------------------------------------------
 #include "walk_generator.h"
-__global__ void __launch_bounds__(128) k_walk_refs(SolverArgs a, mpc_walk_config c, double* state, int takeoff_RF, int takeoff_LF, int land_RF, int land_LF, int replanning, int write_all) {
+#include "../../include/mpc_walk_commands.h"
+// cmd: nullptr (every robot walks the configuration's command) or the [B][16] table of include/mpc_walk_commands.h: robot b's row is staged into LDS by
+// 16 lanes that are idle while the plan is loaded (before the barrier that is there anyway), and the same rules run on it.  The test is the same in
+// every lane of the grid.
+__global__ void __launch_bounds__(128) k_walk_refs(SolverArgs a, mpc_walk_config c, double* state, int takeoff_RF, int takeoff_LF, int land_RF, int land_LF, int replanning, int write_all,
+                                                   const double* cmd) {
   const Layout& L = a.L;
   const int b = blockIdx.x, tid = threadIdx.x, N = L.N;
-  __shared__ double st[48], meas[24];
+  __shared__ double st[48], meas[24], cw[MPC_WALK_COMMAND_WIDTH];
   double* gst = state + (size_t)b * 48;
   if (replanning) {
     if (tid < 2) {
@@ -898,19 +903,25 @@ __global__ void __launch_bounds__(128) k_walk_refs(SolverArgs a, mpc_walk_config
       walk_pose_store(meas + 12 * tid, R, p);
     }
     if (tid >= 64 && tid < 112) st[tid - 64] = gst[tid - 64];
+    else if (cmd && tid >= 112) cw[tid - 112] = cmd[(size_t)b * MPC_WALK_COMMAND_WIDTH + (tid - 112)];
     __syncthreads();
-    if (tid == 0) walk_plan(st, meas, meas + 12, takeoff_RF, takeoff_LF, land_RF, land_LF, c.T_ds, c.t_left, c.t_right, c.rot_diff, c.floor_z);
+    if (tid == 0) {
+      if (cmd) walk_plan(st, meas, meas + 12, takeoff_RF, takeoff_LF, land_RF, land_LF, c.T_ds, cw, cw + 3, cw + 6, c.floor_z);
+      else walk_plan(st, meas, meas + 12, takeoff_RF, takeoff_LF, land_RF, land_LF, c.T_ds, c.t_left, c.t_right, c.rot_diff, c.floor_z);
+    }
     __syncthreads();
     if (tid < 48) gst[tid] = st[tid];
   } else {
     if (tid < 48) st[tid] = gst[tid];
+    else if (cmd && tid < 48 + MPC_WALK_COMMAND_WIDTH) cw[tid - 48] = cmd[(size_t)b * MPC_WALK_COMMAND_WIDTH + (tid - 48)];
     __syncthreads();
   }
+  const double apex = cmd ? cw[15] : c.swing_apex;
   double* tables = const_cast<double*>(a.inst_params) + (size_t)b * (N + 1) * L.max_stage_doubles;
   for (int j = (write_all ? 0 : N - 1) + tid; j < N; j += blockDim.x) {
     double Lr[12], Rr[12];
-    walk_ref(Lr, st, st + 12, land_LF, j, c.T_ss, c.swing_apex);
-    walk_ref(Rr, st + 24, st + 36, land_RF, j, c.T_ss, c.swing_apex);
+    walk_ref(Lr, st, st + 12, land_LF, j, c.T_ss, apex);
+    walk_ref(Rr, st + 24, st + 36, land_RF, j, c.T_ss, apex);
     double* tab = tables + (size_t)stage_slot(a, j) * L.max_stage_doubles;
     if (c.off_lf >= 0) for (int e = 0; e < 12; ++e) tab[c.off_lf + e] = Lr[e];
     if (c.off_rf >= 0) for (int e = 0; e < 12; ++e) tab[c.off_rf + e] = Rr[e];

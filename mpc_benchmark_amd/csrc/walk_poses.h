@@ -8,11 +8,13 @@
 // tables mi / md of another handle) and one applies the foothold rules to the robot's plan; then a thread per knot forms the references of both
 // feet and stores the translation at the three places of every foot whose contact state in the knot's own table is on — ring-indexed as the
 // stage tables are, BEFORE the rotation of this tick.  The threads of knots 0 and 1 also keep the two reference samples of both feet.
+// cmd: nullptr or the [B][16] command table of include/mpc_walk_commands.h, staged as in k_walk_refs.
 __global__ void __launch_bounds__(128) k_walk_poses(SolverArgs a, const int32_t* mi, const double* md, const double* x, int nx, mpc_walk_poses_config c,
-                                                    double* state, double* samples, int takeoff_RF, int takeoff_LF, int land_RF, int land_LF, int replanning) {
+                                                    double* state, double* samples, int takeoff_RF, int takeoff_LF, int land_RF, int land_LF, int replanning,
+                                                    const double* cmd) {
   const Layout& L = a.L;
   const int b = blockIdx.x, tid = threadIdx.x, N = L.N;
-  __shared__ double st[48], meas[24];
+  __shared__ double st[48], meas[24], cw[MPC_WALK_COMMAND_WIDTH];
   double* gst = state + (size_t)b * 48;
   if (replanning) {
     if (tid < 2) {
@@ -21,19 +23,25 @@ __global__ void __launch_bounds__(128) k_walk_poses(SolverArgs a, const int32_t*
       walk_pose_store(meas + 12 * tid, R, p);
     }
     if (tid >= 64 && tid < 112) st[tid - 64] = gst[tid - 64];
+    else if (cmd && tid >= 112) cw[tid - 112] = cmd[(size_t)b * MPC_WALK_COMMAND_WIDTH + (tid - 112)];
     __syncthreads();
-    if (tid == 0) walk_plan(st, meas, meas + 12, takeoff_RF, takeoff_LF, land_RF, land_LF, c.T_ds, c.t_left, c.t_right, c.rot_diff, c.floor_z);
+    if (tid == 0) {
+      if (cmd) walk_plan(st, meas, meas + 12, takeoff_RF, takeoff_LF, land_RF, land_LF, c.T_ds, cw, cw + 3, cw + 6, c.floor_z);
+      else walk_plan(st, meas, meas + 12, takeoff_RF, takeoff_LF, land_RF, land_LF, c.T_ds, c.t_left, c.t_right, c.rot_diff, c.floor_z);
+    }
     __syncthreads();
     if (tid < 48) gst[tid] = st[tid];
   } else {
     if (tid < 48) st[tid] = gst[tid];
+    else if (cmd && tid < 48 + MPC_WALK_COMMAND_WIDTH) cw[tid - 48] = cmd[(size_t)b * MPC_WALK_COMMAND_WIDTH + (tid - 48)];
     __syncthreads();
   }
+  const double apex = cmd ? cw[15] : c.swing_apex;
   double* tables = const_cast<double*>(a.inst_params) + (size_t)b * (N + 1) * L.max_stage_doubles;
   for (int j = tid; j < N; j += blockDim.x) {
     double ref[2][12];
-    walk_ref(ref[0], st, st + 12, land_LF, j, c.T_ss, c.swing_apex);
-    walk_ref(ref[1], st + 24, st + 36, land_RF, j, c.T_ss, c.swing_apex);
+    walk_ref(ref[0], st, st + 12, land_LF, j, c.T_ss, apex);
+    walk_ref(ref[1], st + 24, st + 36, land_RF, j, c.T_ss, apex);
     double* tab = tables + (size_t)stage_slot(a, j) * L.max_stage_doubles;
     for (int i = 0; i < 2; ++i) {
       if (tab[c.state_offs[2 * i]] == 0.0) continue;  // a foot that does not stand in this knot's stage keeps its pose (centroidal_talos.py:376, 381)
@@ -76,6 +84,7 @@ int mpc_walk_poses_init(mpc_solver* s, mpc_solver* model, const mpc_walk_poses_c
     copy_sync(s, s->d_poses_state, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice);
     copy_sync(s, s->d_poses_samples, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice);  // (the same layout: both samples at the initial footholds)
     s->poses_on = true;
+    s->poses_cmd_on = false;  // (include/mpc_walk_commands.h: a new configuration starts without a table)
   })
 }
 
@@ -102,10 +111,13 @@ int mpc_walk_poses_update(mpc_solver* s, mpc_solver* model, const double* x, mpc
       if (!scr || !*kept) throw std::runtime_error("walk_poses_update: the QP handle keeps no measurement (mpc_qp_ikid_low_level_steps first, or pass x)");
       d_x = scr;
     } else throw std::runtime_error("walk_poses_update: measured states are needed (x, or the QP handle that keeps them)");
+    if (forward && s->poses_cmd_on)
+      throw std::runtime_error("walk_poses_update: forward is refused while a command table is set (mpc_walk_poses_set_commands: every robot walks its own row; set the stopped rows instead)");
     if (forward) { std::memcpy(c.t_left, forward, 24); std::memcpy(c.t_right, forward + 3, 24); c.swing_apex = forward[6]; }
     const bool replanning = land_LF < 0 || land_RF < 0 || (takeoff_RF >= 0 && takeoff_RF < c.T_ds) || (takeoff_LF >= 0 && takeoff_LF < c.T_ds);
     hipLaunchKernelGGL(k_walk_poses, dim3(L.B), dim3(128), 0, s->stream, s->args(), (const int32_t*)model->d_model_i, (const double*)model->d_model_d, d_x, (int)nx,
-                       c, s->d_poses_state, s->d_poses_samples, (int)takeoff_RF, (int)takeoff_LF, (int)land_RF, (int)land_LF, replanning ? 1 : 0);
+                       c, s->d_poses_state, s->d_poses_samples, (int)takeoff_RF, (int)takeoff_LF, (int)land_RF, (int)land_LF, replanning ? 1 : 0,
+                       (const double*)(s->poses_cmd_on ? s->d_poses_cmd : nullptr));
     HIP_OK(hipGetLastError());
     // every knot's references were rewritten: records kept for tick reuse are stale, and the host mirror of the written ranges no longer says what the
     // device holds (poisoned once per slot until a host patch or a stage upload rewrites it, as in mpc_walk_update)

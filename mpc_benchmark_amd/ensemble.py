@@ -119,7 +119,7 @@ class EnsembleMPC:
         import copy
         walk = None
         if self._walk is not None:
-            walk = copy.deepcopy({k: self._walk[k] for k in ("lists", "traj", "x_measured", "last", "replanning", "batch", "x_measured_all", "last_all", "feet_all") if k in self._walk})
+            walk = copy.deepcopy({k: self._walk[k] for k in ("lists", "traj", "x_measured", "last", "replanning", "batch", "x_measured_all", "last_all", "feet_all", "commands") if k in self._walk})
             if self._walk.get("device"):
                 walk["device_plan"] = self.native.walk_get_state()
             if self._walk.get("poses") == "device":
@@ -137,7 +137,11 @@ class EnsembleMPC:
         if self._walk is not None and walk is not None:
             walk = copy.deepcopy(walk)
             plan, poses_plan = walk.pop("device_plan", None), walk.pop("device_poses_plan", None)
+            now = self._walk.get("commands")
             self._walk.update(walk)
+            saved = self._walk.get("commands")
+            if (saved is None) != (now is None) or (saved is not None and not np.array_equal(saved, now)):
+                self._apply_walk_commands(saved)   # (the command table is not part of mpc_get_state: the device gets the episode's again)
             if plan is not None:
                 self.native.walk_set_state(plan)
             if poses_plan is not None:
@@ -281,7 +285,7 @@ class EnsembleMPC:
 
     # -- the reference loop's per-tick problem updates on the shared stage tables ---------------------------------
     def enable_walk(self, swing_apex=0.15, x_forward=None, y_forward=0.0, foot_yaw=0.0, y_gap=0.18, z_height=0.0, per_instance=False, generator="host", floor=False,
-                    model_handle=None):
+                    model_handle=None, commands=None):
         """From now on every tick does what the loop bodies of the scripts do to the problem before solving (fulldynamic_talos.py:444-510,
         kinodynamic_talos.py:361-409, centroidal_talos.py:357-384): ``FootTrajectory.updateTrajectory`` from the measured foot poses, the
         references written into every stage of the horizon (``setReference`` on the two foot-placement costs — integer keys 3 / 4 or the
@@ -319,7 +323,16 @@ class EnsembleMPC:
         An ensemble that feeds the solver's own prediction back has no ground; the full-dynamics script aims the left foot 1 cm below the right one's
         height at every step (fulldynamic_talos.py:449, ``forward_z_left``), which a floor stops and a prediction does not: without this the footholds of
         the benchmark ensemble sink 5 - 6 cm over the schedule's seven swings and the instances lost late in the schedule are lost on those stretched
-        legs.  The mirror loops (a simulator with a floor measures their states) do not need it."""
+        legs.  The mirror loops (a simulator with a floor measures their states) do not need it.
+
+        ``commands`` (with ``per_instance=True``): a (B, 16) table of ``references.walk_commands`` — robot b walks with the step offsets, the foot yaw
+        per step and the swing apex of row b instead of ``x_forward`` ... ``swing_apex`` (include/mpc_walk_commands.h; DESIGN.md "A walk command per
+        robot").  The host generator takes it on either library, for whole-body and contact-pose problems; ``generator="device"`` uploads it once
+        (HIP library only).  The step timing stays the schedule's, shared by the robots.  Where the scripts call ``updateForward(0, 0, ...)`` once the
+        walk is over, the table becomes ``references.stopped_commands(table, forward_z_left)``.  The base height of the posture reference follows the
+        feet when any row climbs (as with ``z_height != 0``); ``floor=True`` needs rows without a z offset.  ``set_walk_commands`` changes the table
+        mid-walk, ``walk_commands`` returns the one in force.  The table is not part of ``native.get_state()``: a caller that restores such a
+        checkpoint restores its table (``save_episode`` / ``restart_episode`` do)."""
         from . import references as refgen
         from .robot import minipin as pin
         pd, N = self.pd, self.problem.num_steps
@@ -329,8 +342,19 @@ class EnsembleMPC:
         if per_instance and generator == "device" and spec["kind"] == "contact_poses" and not hasattr(self.lib, "mpc_walk_poses_init"):
             raise RuntimeError("mpc_walk_poses_init is not exported by this library (%s): the device generator of the contact-pose references is HIP only "
                                "(libmpc_hip.so, include/mpc_walk_poses.h)" % self.native.backend)
+        cmd = None
+        if commands is not None:
+            if not per_instance:
+                raise ValueError("commands: a walk command per robot needs per_instance=True (the shared stage tables cannot carry per-robot references)")
+            cmd = refgen.check_commands(commands, self.batch, "enable_walk: commands")
+            if floor is not False and floor is not None and np.any(cmd[:, [2, 5]] != 0.0):
+                raise ValueError("floor=True: per-instance references on flat ground (every row of commands with z offsets of 0)")
+            sym = "mpc_walk_poses_set_commands" if spec["kind"] == "contact_poses" else "mpc_walk_set_commands"
+            if generator == "device" and not hasattr(self.lib, sym):
+                raise RuntimeError("%s is not exported by this library (%s): a walk command per robot on the device generator is HIP only "
+                                   "(libmpc_hip.so, include/mpc_walk_commands.h)" % (sym, self.native.backend))
         self._walk_args = dict(swing_apex=swing_apex, x_forward=x_forward, y_forward=y_forward, foot_yaw=foot_yaw, y_gap=y_gap, z_height=z_height, per_instance=per_instance,
-                               generator=generator, floor=floor, model_handle=model_handle)
+                               generator=generator, floor=floor, model_handle=model_handle, commands=cmd)
         if floor is not False and floor is not None and (not per_instance or z_height != 0.0):
             raise ValueError("floor=True: per-instance references on flat ground")
         if generator not in ("host", "device") or (generator == "device" and not per_instance):
@@ -351,6 +375,8 @@ class EnsembleMPC:
             "data": rb.model.createData(), "pin": pin, "refgen": refgen, "spec": spec, "kind": spec["kind"],
             "step": dict(swing_apex=swing_apex, x_forward=x_forward, y_forward=y_forward, y_gap=y_gap, z_height=z_height),
             "x_measured": np.array(self.x0[0]), "patched": 0, "patches": 0, "last": None, "feet": None,
+            "commands": cmd,  # the table in force (None: the shared command), equal to the device's with generator="device"
+            "z_follow": bool(z_height != 0.0 or (cmd is not None and np.any(cmd[:, [2, 5]] != 0.0))),  # the posture reference's base height follows the feet
             "floor_z": (None if floor is False or floor is None else float(min(lf.translation[2], rf.translation[2])) if floor is True else float(floor)),  # (a number: that height — tests)
         }
         nterm = len(self.problem.term_cost.components)
@@ -390,11 +416,13 @@ class EnsembleMPC:
             cfg.t_left[:], cfg.t_right[:] = list(gen.translationLeft), list(gen.translationRight)
             cfg.rot_diff[:] = list(np.asarray(gen.rotationDiff, dtype=float).reshape(-1))
             cfg.com0[:] = list(np.asarray(rb.com0, dtype=float))
-            cfg.feet_z0, cfg.xref_z0, cfg.z_follow = float(w["feet_z0"]), float(self.pd.x0[2]), (1.0 if z_height != 0.0 else 0.0)
+            cfg.feet_z0, cfg.xref_z0, cfg.z_follow = float(w["feet_z0"]), float(self.pd.x0[2]), (1.0 if w["z_follow"] else 0.0)
             flat = lambda M: list(np.concatenate([np.asarray(M.rotation, dtype=float).reshape(-1), np.asarray(M.translation, dtype=float)]))
             cfg.lf0[:], cfg.rf0[:] = flat(lf), flat(rf)
             cfg.floor_z = w["floor_z"] if w["floor_z"] is not None else -1e308
             self.native.walk_init(cfg)
+            if cmd is not None:
+                self.native.walk_set_commands(cmd)
             w["device"] = True
         elif per_instance:
             B = self.batch
@@ -403,6 +431,7 @@ class EnsembleMPC:
             (LR, Lp), (RR, Rp) = bc(lf), bc(rf)
             w["batch"] = refgen.FootTrajectoryBatch(LR, Lp, RR, Rp, T_SS, T_DS, N, swing_apex, x_forward, y_forward, foot_yaw, y_gap, z_height)
             w["batch"].floor_z = w["floor_z"]
+            w["batch"].set_commands(cmd)
             w["x_measured_all"] = np.array(self.x0, dtype=float)
             i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
             # index arrays of the patches of one tick: per instance the N left-foot and N right-foot references, then (after the cycle) its terminal targets
@@ -419,7 +448,58 @@ class EnsembleMPC:
         kinodynamic_talos.py:368-370, centroidal_talos.py:365-366)"""
         rule, p = self._walk["spec"]["forward_rule"], self._walk["step"]
         if rule(takeoff_RF, takeoff_LF, land_RF, land_LF):
+            if self._walk["commands"] is not None:
+                return self._walk_stop_commands()
             gen.updateForward(0, 0, p["y_gap"], p["y_forward"], self._walk["spec"]["forward_z_left"], 0, p["swing_apex"])
+
+    # -- a walk command per robot (include/mpc_walk_commands.h) ---------------------------------------------------------------
+    def _apply_walk_commands(self, cmd):
+        """the table (None: the shared command) to whichever generators this walk runs: the numpy one, and the device's by one upload"""
+        w = self._walk
+        w["commands"] = cmd
+        if "batch" in w:
+            w["batch"].set_commands(cmd)
+        if w.get("device"):
+            self.native.walk_set_commands(cmd)
+        if w.get("poses") == "device":
+            self.native.walk_poses_set_commands(cmd)
+
+    def _walk_stop_commands(self):
+        """the scripts' ``updateForward(0, 0, ...)`` with a table: ``references.stopped_commands`` of the table in force.  The rule fires on every tick
+        once the walk is over; the stopped table equals itself stopped, so it travels once."""
+        w = self._walk
+        stopped = w["refgen"].stopped_commands(w["commands"], w["spec"]["forward_z_left"])
+        if not np.array_equal(stopped, w["commands"]):
+            self._apply_walk_commands(stopped)
+
+    def set_walk_commands(self, commands):
+        """Another command table mid-walk ((B, 16), ``references.walk_commands``; None: every robot walks the shared command of ``enable_walk``
+        again).  Footholds are planned with it from the next replanning tick on, the swing curves follow the new apex from the next tick on
+        (include/mpc_walk_commands.h).  Whether the posture reference's base height follows the feet was decided by ``enable_walk``: rows that climb
+        need a walk that was enabled with climbing rows (or ``z_height``)."""
+        w = self._walk
+        if w is None or not ("batch" in w or w.get("device")):
+            raise ValueError("set_walk_commands: enable_walk(per_instance=True) first")
+        cmd = None
+        if commands is not None:
+            cmd = w["refgen"].check_commands(commands, self.batch, "set_walk_commands")
+            climbs = bool(np.any(cmd[:, [2, 5]] != 0.0))
+            if climbs and (not w["z_follow"] or w["floor_z"] is not None):
+                raise ValueError("set_walk_commands: rows with a z offset need a walk enabled for steps that climb (enable_walk(commands=...) with such rows "
+                                 "or z_height != 0, and no floor)")
+        self._apply_walk_commands(cmd)
+        self._walk_args["commands"] = cmd
+
+    def walk_commands(self):
+        """The table in force, (B, 16), or None when every robot walks the shared command (read back from the device with ``generator="device"``)."""
+        w = self._walk
+        if w is None or w.get("commands") is None:
+            return None
+        if w.get("device"):
+            return self.native.walk_get_commands()
+        if w.get("poses") == "device":
+            return self.native.walk_poses_get_commands()
+        return w["commands"].copy()
 
     def _walk_references(self):
         w, N = self._walk, self.problem.num_steps
@@ -430,7 +510,10 @@ class EnsembleMPC:
         if w.get("device"):  # the generator runs in the library: only the countdowns (and the scripts' updateForward rule) are host work
             takeoff_RF, takeoff_LF, land_RF, land_LF = refgen.update_timings(land_LFs, land_RFs, takeoff_LFs, takeoff_RFs)
             forward = None
-            if w["spec"]["forward_rule"](takeoff_RF, takeoff_LF, land_RF, land_LF):
+            if w["commands"] is not None:  # (the library refuses `forward` while a table is set)
+                if w["spec"]["forward_rule"](takeoff_RF, takeoff_LF, land_RF, land_LF):
+                    self._walk_stop_commands()
+            elif w["spec"]["forward_rule"](takeoff_RF, takeoff_LF, land_RF, land_LF):
                 p = w["step"]
                 forward = ([0.0, p["y_gap"], w["spec"]["forward_z_left"]], [0.0, -p["y_gap"] - p["y_forward"], 0.0], p["swing_apex"])
             self.native.walk_update(takeoff_RF, takeoff_LF, land_RF, land_LF, forward)
@@ -445,7 +528,7 @@ class EnsembleMPC:
             Lb, Rb = w["batch"].updateTrajectory(takeoff_RF, takeoff_LF, land_RF, land_LF, LR, Lp, RR, Rp)
             vals = np.ascontiguousarray(np.concatenate([Lb, Rb], axis=1)).reshape(-1)
             self.native.update_instance_params_arrays(*w["idx"], vals)
-            if w["step"]["z_height"] != 0.0:  # stairs: the posture reference climbs with the feet
+            if w["z_follow"]:  # stairs: the posture reference climbs with the feet
                 zref = self.pd.x0[2] + 0.5 * (Lb[:, :, 11] + Rb[:, :, 11]) - w["feet_z0"]
                 self.native.update_instance_params_arrays(*w["zidx"], np.ascontiguousarray(zref).reshape(-1))
             w["last_all"] = (Lb[:, -1].copy(), Rb[:, -1].copy())
@@ -508,6 +591,7 @@ class EnsembleMPC:
         w["batch"] = refgen.FootTrajectoryBatch(LR, Lp, RR, Rp, gen.T_ss, gen.T_ds, N, p["swing_apex"], p["x_forward"], p["y_forward"], self._walk_args["foot_yaw"],
                                                 p["y_gap"], p["z_height"])
         w["batch"].floor_z = w["floor_z"]
+        w["batch"].set_commands(w["commands"])
         w["poses"] = generator
         if generator != "device":
             return
@@ -530,6 +614,8 @@ class EnsembleMPC:
         cfg.lf0[:], cfg.rf0[:] = flat(lf), flat(rf)
         cfg.floor_z = w["floor_z"] if w["floor_z"] is not None else -1e308
         self.native.walk_poses_init(model_handle, cfg)
+        if w["commands"] is not None:
+            self.native.walk_poses_set_commands(w["commands"])
         w["model_handle"] = model_handle
         w["xik_from"] = None   # a QP handle whose device loop kept the measurement (pipeline.CentroidalPipeline): the kernel reads it there
 
@@ -558,7 +644,10 @@ class EnsembleMPC:
         X = w["x_measured_all"]
         if w["poses"] == "device":
             forward = None
-            if w["spec"]["forward_rule"](takeoff_RF, takeoff_LF, land_RF, land_LF):
+            if w["commands"] is not None:  # (the library refuses `forward` while a table is set)
+                if w["spec"]["forward_rule"](takeoff_RF, takeoff_LF, land_RF, land_LF):
+                    self._walk_stop_commands()
+            elif w["spec"]["forward_rule"](takeoff_RF, takeoff_LF, land_RF, land_LF):
                 p = w["step"]
                 forward = ([0.0, p["y_gap"], w["spec"]["forward_z_left"]], [0.0, -p["y_gap"] - p["y_forward"], 0.0], p["swing_apex"])
             self.native.walk_poses_update(w["model_handle"], X, w["xik_from"], takeoff_RF, takeoff_LF, land_RF, land_LF, forward)
@@ -596,7 +685,7 @@ class EnsembleMPC:
             L_last, R_last = w["last_all"]
             com = np.tile(self.pd.robot.com0, (self.batch, 1))
             com[:, :2] = 0.5 * (L_last[:, 9:11] + R_last[:, 9:11])
-            if w["step"]["z_height"] != 0.0:
+            if w["z_follow"]:
                 com[:, 2] += 0.5 * (L_last[:, 11] + R_last[:, 11]) - w["feet_z0"]
             vals = np.ascontiguousarray(np.concatenate([com, L_last, R_last] if feet else [com], axis=1)).reshape(-1)
             self.native.update_instance_params_arrays(*w["tidx"], vals)

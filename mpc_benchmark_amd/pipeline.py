@@ -33,7 +33,11 @@ include/mpc_qp_contacts.h; HIP library only); ``tick(host_glue=True)`` reads the
 ``terrain`` (all three pipelines, with ``contact_rule`` only): None, the ground is the plane; or boxes ``(n, 5)`` for every robot / ``(B, n, 5)`` per
 robot under the rule (mpc_sim_terrain, include/mpc_sim_terrain.h; ``contact_rule.stairs`` lays the reference's staircase).  Nothing else about a
 tick changes: the planner keeps the schedule's footholds, the low-level QPs the contact set ``contact_source`` names (by default the schedule's
-``contact_state``); the plant decides where a foot is caught."""
+``contact_state``); the plant decides where a foot is caught.
+
+``walk=dict(per_instance=True, commands=table)`` (all three pipelines): a walk command per robot, a (B, 16) table of ``references.walk_commands`` that
+``EnsembleMPC.enable_walk`` takes (include/mpc_walk_commands.h) — one robot per step length, turn rate or lateral step in one ensemble.  The table is
+checked when the pipeline is built; ``pipeline.mpc.set_walk_commands`` changes it mid-walk."""
 from __future__ import annotations
 
 import numpy as np
@@ -136,6 +140,18 @@ def _checked_terrain(name, terrain, contact_rule, batch):
     return _contact_rule.terrain_boxes(terrain, batch)
 
 
+def _checked_walk(name, walk, batch):
+    """``walk`` of a pipeline: the ``commands`` table in it is checked before any library call (shape, finite values, ``per_instance=True``)"""
+    if walk is None or walk.get("commands") is None:
+        return walk
+    from . import references as refgen
+    if not walk.get("per_instance"):
+        raise ValueError("%s: walk commands need walk=dict(per_instance=True, commands=...) (the shared stage tables cannot carry per-robot references)" % name)
+    walk = dict(walk)
+    walk["commands"] = refgen.check_commands(walk["commands"], batch, "%s: walk commands" % name)
+    return walk
+
+
 def _enable_contact_rule(sim, tables, robot, cfg, terrain=None):
     """``contact_rule`` of a pipeline: stage 0 of the simulator is the double-support stage once, and the rule is on from the initial footholds
     (the ground plane at the lower one unless ``cfg`` names ``ground_z``), over ``terrain`` if there is one."""
@@ -229,6 +245,7 @@ class KinodynamicPipeline(_QpContactSource):
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("KinodynamicPipeline", contact_source, contact_rule)
         self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
+        walk = _checked_walk("KinodynamicPipeline", walk, self.batch)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
         rb = problem_def.robot
@@ -413,6 +430,7 @@ class CentroidalPipeline(_QpContactSource):
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("CentroidalPipeline", contact_source, contact_rule)
         self.terrain = _checked_terrain("CentroidalPipeline", terrain, contact_rule, self.batch)
+        walk = _checked_walk("CentroidalPipeline", walk, self.batch)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
         rb = problem_def.robot
@@ -584,6 +602,7 @@ class FullDynamicPipeline:
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes (module docstring of pipeline.py)."""
         self.terrain = _checked_terrain("FullDynamicPipeline", terrain, contact_rule, int(batch))
+        walk = _checked_walk("FullDynamicPipeline", walk, int(batch))
         if ens_kw.get("closed_loop") is not None:
             raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
                              "EnsembleMPC(closed_loop=...) would simulate a second time)")

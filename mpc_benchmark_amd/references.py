@@ -286,6 +286,59 @@ class FootTrajectory:
         return out
 
 
+# ---- a walk command per robot (include/mpc_walk_commands.h) --------------------------------------------------------------------------
+WALK_COMMAND_WIDTH = 16   # t_left[3] | t_right[3] | rot_diff[9] row-major | swing_apex
+
+
+def check_commands(cmd, batch=None, who="commands"):
+    """``cmd`` as a contiguous (B, 16) float64 copy; ValueError for another shape, another B than ``batch`` or non-finite values."""
+    c = np.array(cmd, dtype=np.float64, order="C")
+    if c.ndim != 2 or c.shape[1] != WALK_COMMAND_WIDTH:
+        raise ValueError("%s: a table of shape (B, %d) expected, got %s" % (who, WALK_COMMAND_WIDTH, c.shape))
+    if batch is not None and c.shape[0] != int(batch):
+        raise ValueError("%s: %d rows for %d robots" % (who, c.shape[0], int(batch)))
+    if not np.all(np.isfinite(c)):
+        raise ValueError("%s: non-finite values" % who)
+    return c
+
+
+def walk_commands(batch, x_forward, y_forward=0.0, foot_yaw=0.0, y_gap=0.18, z_height=0.0, swing_apex=0.15):
+    """The command table of ``batch`` robots, (B, 16) float64: row b = t_left[3] | t_right[3] | rot_diff[9] row-major | swing_apex of a walk with robot
+    b's step length ``x_forward``, lateral step ``y_forward``, foot yaw per step ``foot_yaw``, foot gap ``y_gap``, height per step ``z_height`` and
+    swing apex.  Every argument is a scalar (every robot's) or (B,).  The values are formed by the expressions of ``FootTrajectory.__init__``, one
+    robot at a time: a row made from the arguments of a shared walk holds the bits of that walk's configuration."""
+    B = int(batch)
+    if B < 1:
+        raise ValueError("walk_commands: batch must be positive")
+    cols = []
+    for name, v in (("x_forward", x_forward), ("y_forward", y_forward), ("foot_yaw", foot_yaw), ("y_gap", y_gap), ("z_height", z_height), ("swing_apex", swing_apex)):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 1 and a.shape[0] != B:
+            raise ValueError("walk_commands: %s has %d entries for %d robots" % (name, a.shape[0], B))
+        if a.ndim > 1:
+            raise ValueError("walk_commands: %s must be a scalar or of shape (%d,), got %s" % (name, B, a.shape))
+        if not np.all(np.isfinite(a)):
+            raise ValueError("walk_commands: %s has non-finite values" % name)
+        cols.append(np.broadcast_to(a, (B,)))
+    out = np.empty((B, WALK_COMMAND_WIDTH))
+    for b in range(B):
+        x, yf, yaw, yg, z, apex = (float(c[b]) for c in cols)
+        out[b, 0:3] = np.array([x, yg, z], dtype=float)
+        out[b, 3:6] = np.array([x, -yg - yf, z], dtype=float)
+        out[b, 6:15] = yaw_rotation(yaw).reshape(-1)
+        out[b, 15] = apex
+    return out
+
+
+def stopped_commands(cmd, z_left):
+    """``updateForward(0, 0, y_gap, y_forward, z_left, 0, swing_apex)`` — what the scripts call once the walk is over — for every row of a table: the
+    x of both offsets becomes 0, the left z ``z_left``, the right z 0; the y components, rot_diff and the apex stay.  -> a new (B, 16) table."""
+    out = check_commands(cmd, who="stopped_commands")
+    out[:, 0], out[:, 3] = 0.0, 0.0
+    out[:, 2], out[:, 5] = float(z_left), 0.0
+    return out
+
+
 # ---- the same generator for B robots at once (ensembles with per-instance references) ---------------------------------------------
 def _yaw_rotation_batch(yaw):
     c, s = np.cos(yaw), np.sin(yaw)
@@ -329,8 +382,26 @@ class FootTrajectoryBatch:
         self.sR, self.fR = (RF_R.copy(), RF_p.copy()), (RF_R.copy(), RF_p.copy())
         self.T_ds, self.T_ss, self.nsteps, self.swing_apex = T_ds, T_ss, nsteps, swing_apex
         self.floor_z = None  # EnsembleMPC.enable_walk(floor=...): no foothold is planned below this height (mpc_walk_config.floor_z)
+        self.commands = None  # set_commands: (B, 16), a walk command per robot
+
+    def set_commands(self, cmd):
+        """A walk command per robot (``walk_commands``; include/mpc_walk_commands.h): from now on robot b's footholds are planned with the offsets
+        and the rot_diff of row b and its swing curve has row b's apex — ``tL`` / ``tR`` (B, 3), ``rotationDiff`` (B, 3, 3) and ``swing_apex`` (B,) are
+        taken from a copy of the table.  Footholds already planned stay until the rules plan again.  None: back to the shared command the generator had."""
+        if cmd is None:
+            if self.commands is not None:
+                self.tL, self.tR, self.rotationDiff, self.swing_apex = self._shared
+                self.commands = None
+            return
+        c = check_commands(cmd, self.sL[0].shape[0], "set_commands")
+        if self.commands is None:
+            self._shared = (self.tL, self.tR, self.rotationDiff, self.swing_apex)
+        self.commands = c
+        self.tL, self.tR, self.rotationDiff, self.swing_apex = c[:, 0:3], c[:, 3:6], c[:, 6:15].reshape(-1, 3, 3), c[:, 15]
 
     def updateForward(self, x_f_left, x_f_right, y_gap, y_forward, z_height_left, z_height_right, swing_apex):
+        if self.commands is not None:
+            raise ValueError("updateForward: this generator holds a command per robot (set_commands); set references.stopped_commands(cmd, z_left) instead")
         self.tR = np.array([x_f_right, -y_gap - y_forward, z_height_right], dtype=float)
         self.tL = np.array([x_f_left, y_gap, z_height_left], dtype=float)
         self.swing_apex = swing_apex
@@ -341,7 +412,10 @@ class FootTrajectoryBatch:
 
     def _beside(self, pose, offset, rotate):
         R, p = pose
-        p2 = p + np.einsum("bij,j->bi", _yaw_rotation_batch(self._yaw(R)), offset)
+        if offset.ndim == 2:  # (set_commands: robot b's own offset, and below its own rotationDiff [B, 3, 3])
+            p2 = p + np.einsum("bij,bj->bi", _yaw_rotation_batch(self._yaw(R)), offset)
+        else:
+            p2 = p + np.einsum("bij,j->bi", _yaw_rotation_batch(self._yaw(R)), offset)
         if self.floor_z is not None:
             p2[:, 2] = np.maximum(p2[:, 2], self.floor_z)
         R2 = (self.rotationDiff @ R) if rotate else R.copy()
