@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 
+from . import actuator_model as _actuator_model
 from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
 
@@ -159,6 +160,14 @@ _SIM_CONTACTS_SIGNATURES = {
     "mpc_sim_contacts_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_actuators.h: exported by the HIP library alone, bound when present (``NativeSolver.actuators`` / ``read_actuators`` / ``set_actuators``)
+_SIM_ACTUATORS_SIGNATURES = {
+    "mpc_sim_actuators": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
+    "mpc_sim_actuators_read": (C.c_int, [C.c_void_p, _DP, _DP]),
+    "mpc_sim_actuators_set": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_actuators_width": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_sim_terrain.h: exported by the HIP library alone, bound when present (``NativeSolver.terrain`` / ``read_terrain`` / ``terrain_height``)
 class MpcSimTerrainConfig(C.Structure):
     _fields_ = [("n_boxes", C.c_int32), ("per_robot", C.c_int32)]
@@ -208,7 +217,7 @@ def bind_library(path):
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
+            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -453,6 +462,59 @@ class NativeSolver:
         if r.shape != (self.dims.batch, _contact_rule.WIDTH):
             raise ValueError("set_contacts: rows of shape (%d, %d) expected, got %s" % (self.dims.batch, _contact_rule.WIDTH, r.shape))
         self._check(fn(self._h, _dp(r)), "mpc_sim_contacts_set")
+
+    # -- include/mpc_sim_actuators.h (HIP library only): the per-robot actuator model of the torque-driven simulator steps -----------------------
+    def _sim_actuators(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the actuator model of torque-driven simulator steps is HIP only "
+                               "(libmpc_hip.so, include/mpc_sim_actuators.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def actuators(self, params, limit=None, friction_shape=None):
+        """Pass the torque of every torque-driven simulator step of this handle through every robot's own actuator model on the device before the
+        dynamics integrate it (mpc_sim_actuators; ``actuator_model`` is the definition).  ``params``: (B, 8) rows, one row of 8 for every robot, or
+        a dict by ``actuator_model.FIELDS`` name of scalars or (B,) arrays (missing fields: the identity value); turns the model on and resets
+        its state rows.  ``limit`` (nu,): the effort limits, needed when a row has ``sat`` > 0; ``friction_shape`` (nu,) or None (ones).  None turns
+        the model off."""
+        fn = self._sim_actuators("mpc_sim_actuators")
+        if params is None:
+            self._check(fn(self._h, None, None, None), "mpc_sim_actuators")
+            return
+        d = self.dims
+        p = _f64(_actuator_model.rows(params, d.batch))
+        vec = []
+        for name, a in (("limit", limit), ("friction_shape", friction_shape)):
+            if a is not None:
+                a = _f64(a)
+                if a.shape != (d.nu,):
+                    raise ValueError("actuators: %s of shape (%d,) expected, got %s" % (name, d.nu, a.shape))
+            vec.append(a)
+        self._check(fn(self._h, _dp(p), _dp(vec[0]), _dp(vec[1])), "mpc_sim_actuators")
+
+    def read_actuators(self, raw=False):
+        """The state rows of the actuator model (mpc_sim_actuators_read) -> dict of arrays by ``actuator_model.unpack`` (``ring`` (B, 16, nu), ``y``,
+        ``applied`` (B, nu), ``head``, ``count`` (B,)) plus ``params`` (B, 8), the rows in force; ``raw``: the (B, 18 nu + 2) state rows themselves."""
+        fn = self._sim_actuators("mpc_sim_actuators_read")
+        w = self._sim_actuators("mpc_sim_actuators_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_actuators_width")
+        d = self.dims
+        out, par = np.zeros((d.batch, w)), np.zeros((d.batch, _actuator_model.PARAMS))
+        self._check(fn(self._h, _dp(par), _dp(out)), "mpc_sim_actuators_read")
+        if raw:
+            return out
+        r = _actuator_model.unpack(out, d.nu)
+        r["params"] = par
+        return r
+
+    def set_actuators(self, state):
+        """Impose the state rows of the actuator model (mpc_sim_actuators_set): (B, 18 nu + 2), e.g. ``read_actuators(raw=True)`` of an earlier point."""
+        fn = self._sim_actuators("mpc_sim_actuators_set")
+        r = _f64(state)
+        d = self.dims
+        if r.shape != (d.batch, _actuator_model.width(d.nu)):
+            raise ValueError("set_actuators: state rows of shape (%d, %d) expected, got %s" % (d.batch, _actuator_model.width(d.nu), r.shape))
+        self._check(fn(self._h, _dp(r)), "mpc_sim_actuators_set")
 
     # -- include/mpc_sim_terrain.h (HIP library only): the box terrain under the contact rule ------------------------------------------------------
     def _sim_terrain(self, name):

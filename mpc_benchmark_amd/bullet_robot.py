@@ -16,6 +16,8 @@ and deterministically; it is not a physics engine.  ``device_contacts=True`` (HI
 placements, and a catch needs no new model.  ``createStairs(pose_stairs, height_step)`` (the reference's three boxes) and ``setTerrain(boxes)`` put a
 box terrain under the rule, host or device: a foot is caught on the highest box top under the ORIGIN of its sole frame (``contact_rule.terrain_height``);
 risers, soles hanging over an edge and slopes are not modelled.  ``addStairs`` (a URDF in the reference) stays unavailable.
+``actuators=`` / ``setActuators(params, limit=None, friction_shape=None)`` (HIP library only) put the actuator model of ``actuator_model`` between
+``execute(torques)`` and the dynamics (mpc_sim_actuators, include/mpc_sim_actuators.h): delay, gain error, lag, saturation, joint friction.
 
 Differences from PyBullet worth knowing: ``measureState`` returns the base velocity in the LOCAL frame of the base (Pinocchio's
 convention, which is what the scripts assume when they copy it into the state, talos_utils.py:337-348); PyBullet reports it in the
@@ -44,7 +46,7 @@ class BulletRobot:
 
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
                  inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
-                 device_contacts=False):
+                 device_contacts=False, actuators=None):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -57,6 +59,7 @@ class BulletRobot:
         self.release_force = float(release_force)  # N: the ground "pulls" when the normal force is below minus this
         self.device_contacts = bool(device_contacts)  # the contact rule on the device (in_contact and the rest are read back after every step)
         self.terrain = None  # boxes (n, 5) under the contact rule (setTerrain / createStairs); None: the plane z = ground_z
+        self._actuators = None if actuators is None else (actuators, None, None)  # (params, limit, friction_shape) of setActuators, armed at initializeJoints
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
         self._native = None
@@ -102,6 +105,8 @@ class BulletRobot:
                                    "release_steps": self.release_steps})
             if self.terrain is not None:
                 self._native.terrain(self.terrain)
+        if self._actuators is not None:
+            self.setActuators(*self._actuators)
 
     def _contact_models(self):
         m = self.model
@@ -294,6 +299,21 @@ class BulletRobot:
             self.terrain = b
         if self.device_contacts and self._native is not None:  # (the rule is on since initializeJoints)
             self._native.terrain(self.terrain)
+
+    def setActuators(self, params, limit=None, friction_shape=None):
+        """The actuator model between ``execute(torques)`` and the dynamics (``actuator_model``; HIP library only): ``params`` one row of 8, (1, 8), or a
+        dict by field name (missing fields: the identity value); ``limit``: the effort limits of the controlled joints (default: the model's);
+        None: off.  Arms and resets the model; before ``initializeJoints`` it is kept for then."""
+        self._actuators = None if params is None else (params, limit, friction_shape)
+        if self._native is None:
+            return
+        if params is None:
+            if hasattr(self._native.lib, "mpc_sim_actuators"):
+                self._native.actuators(None)
+            return
+        if limit is None:
+            limit = np.asarray(self.model.effortLimit, dtype=float)[6:]
+        self._native.actuators(params, limit=limit, friction_shape=friction_shape)
 
     def createStairs(self, pose_stairs, height_step):
         """bullet_robot.py:275-340 of the reference: three steps of half extents 0.2 x 0.5 x height_step / 2, each 0.3 m further and height_step higher,

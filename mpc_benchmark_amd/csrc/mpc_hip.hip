@@ -33,6 +33,7 @@
 #include "sim_record.h"
 #include "sim_metrics.h"
 #include "sim_contacts.h"
+#include "sim_actuators.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
 #include "../../include/mpc_walk_poses.h"
@@ -149,6 +150,9 @@ struct mpc_solver {
   double* d_ter = nullptr;
   mpc_sim_terrain_config ter_cfg = {};
   std::vector<double> h_ter;
+  // include/mpc_sim_actuators.h: the actuator model (nullptr: off), one allocation: params [B][8] | limit [nu] | friction shape [nu] | state rows [B][18 nu + 2]
+  double* d_act = nullptr;
+  std::vector<double> h_act;  // params | limit | shape as they are in force
   // per-slot invalidation (mpc_update_stage_params*): slots whose parameters changed since the last pass was enqueued ; dirty_all:
   // an update on a horizon too long for the mask of SolverArgs
   std::vector<uint8_t> slot_dirty;
@@ -940,7 +944,7 @@ void mpc_destroy(mpc_solver* s) {
   for (int i = 0; i < mpc_solver::ASYNC_DEPTH; ++i) if (s->h_xnext[i]) (void)hipHostFree(s->h_xnext[i]);
   if (s->d_patch) (void)hipFree(s->d_patch);
   for (void* p : s->allocs) (void)hipFree(p);
-  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec, s->d_met, s->d_con, s->d_ter}) if (p) (void)hipFree(p);
+  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec, s->d_met, s->d_con, s->d_ter, s->d_act}) if (p) (void)hipFree(p);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1449,6 +1453,22 @@ static void sim_contacts_reset(mpc_solver* s) {
   copy_sync(s, s->d_con, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
 }
 
+static size_t sim_actuators_width(const Layout& L) { return (size_t)(MPC_SIM_ACTUATORS_RING + 2) * L.m + 2; }
+static double* sim_actuators_rows(const mpc_solver* s) { return s->d_act + (size_t)s->L.B * MPC_SIM_ACTUATORS_PARAMS + 2 * (size_t)s->L.m; }
+// before a simulator step of length dt_step on stream st (after the controller wrote the step's torque into d_simu, before the dynamics): the actuator
+// model (sim_actuators.h), when it is on, turns the command into the applied torque in place
+static void sim_actuators_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
+  if (!s->d_act) return;
+  const Layout& L = s->L;
+  SimActuatorsArgs a;
+  a.nv = L.n / 2; a.nq = L.nx - L.n / 2; a.nu = L.m;
+  a.x = s->d_x0; a.tau = s->d_simu;
+  a.params = s->d_act; a.limit = s->d_act + (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS; a.shape = a.limit + L.m;
+  a.rows = sim_actuators_rows(s); a.dt = dt_step;
+  hipLaunchKernelGGL(k_sim_actuators, dim3((unsigned)L.B), dim3(SIM_ACT_THREADS), 0, st, a);
+  HIP_OK(hipGetLastError());
+}
+
 int mpc_sim_set_push(mpc_solver* s, const double* f_ext, int32_t width) {
   MPC_TRY(s, {
     sim_check(s, "sim_set_push");
@@ -1708,6 +1728,99 @@ int32_t mpc_sim_contacts_width(mpc_solver* s) {
   }
 }
 
+// ---- include/mpc_sim_actuators.h: the per-robot actuator model of the torque-driven simulator steps ------------------------------------------
+int mpc_sim_actuators(mpc_solver* s, const double* params, const double* limit, const double* friction_shape) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_actuators");
+    const Layout& L = s->L;
+    const size_t nu = L.m, np = (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS;
+    std::vector<double> h;
+    if (params) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
+      h.assign(np + 2 * nu, 0.0);
+      bool any_sat = false;
+      for (int b = 0; b < L.B; ++b) {
+        const double* r = params + (size_t)b * MPC_SIM_ACTUATORS_PARAMS;
+        const std::string row = "sim_actuators: row " + std::to_string(b);
+        for (int e = 0; e < MPC_SIM_ACTUATORS_PARAMS; ++e)
+          if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+        if (r[0] != std::floor(r[0]) || r[0] < 0.0 || r[0] > MPC_SIM_ACTUATORS_RING - 1)
+          throw std::runtime_error(row + ": delay must be an integer value in [0, " + std::to_string(MPC_SIM_ACTUATORS_RING - 1) + "]");
+        if (!(r[1] > 0.0)) throw std::runtime_error(row + ": scale must be > 0");
+        for (int e = 2; e < 7; ++e)
+          if (r[e] < 0.0) throw std::runtime_error(row + ": time_constant, damping, coulomb, v_eps and sat must be >= 0");
+        if (r[4] > 0.0 && !(r[5] > 0.0)) throw std::runtime_error(row + ": coulomb > 0 needs v_eps > 0");
+        if (r[6] > 0.0) any_sat = true;
+        std::copy(r, r + MPC_SIM_ACTUATORS_PARAMS, h.begin() + (size_t)b * MPC_SIM_ACTUATORS_PARAMS);
+        h[(size_t)b * MPC_SIM_ACTUATORS_PARAMS + 7] = 0.0;
+      }
+      if (any_sat && !limit) throw std::runtime_error("sim_actuators: a row with sat > 0 needs the effort limits (limit must not be null)");
+      for (size_t j = 0; j < nu; ++j) {
+        const double l = limit ? limit[j] : 0.0, f = friction_shape ? friction_shape[j] : 1.0;
+        if (!std::isfinite(l) || l < 0.0 || !std::isfinite(f) || f < 0.0)
+          throw std::runtime_error("sim_actuators: limit and friction_shape must be finite and >= 0");
+        h[np + j] = l;
+        h[np + nu + j] = f;
+      }
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (s->d_act) { HIP_OK(hipFree(s->d_act)); s->d_act = nullptr; }
+    s->h_act.clear();
+    if (params) {
+      const size_t rows = (size_t)L.B * sim_actuators_width(L);
+      void* p = nullptr;
+      HIP_OK(hipMalloc(&p, (h.size() + rows) * sizeof(double)));
+      s->d_act = (double*)p;
+      s->h_act = h;
+      h.resize(h.size() + rows, 0.0);  // (the state rows after a reset: all 0)
+      copy_sync(s, s->d_act, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
+  })
+}
+
+int mpc_sim_actuators_read(mpc_solver* s, double* params, double* state) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_actuators_read");
+    if (!s->d_act) throw std::runtime_error("sim_actuators_read: the actuator model is off on this handle (turn it on with mpc_sim_actuators)");
+    const Layout& L = s->L;
+    if (params) std::copy(s->h_act.begin(), s->h_act.begin() + (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS, params);
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (state) copy_sync(s, state, sim_actuators_rows(s), (size_t)L.B * sim_actuators_width(L) * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int mpc_sim_actuators_set(mpc_solver* s, const double* state) {
+  MPC_TRY(s, {
+    if (!state) throw std::runtime_error("sim_actuators_set: state must not be null");
+    sim_check(s, "sim_actuators_set");
+    if (!s->d_act) throw std::runtime_error("sim_actuators_set: the actuator model is off on this handle (turn it on with mpc_sim_actuators)");
+    const Layout& L = s->L;
+    const size_t W = sim_actuators_width(L);
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = state + (size_t)b * W;
+      const std::string row = "sim_actuators_set: row " + std::to_string(b);
+      for (size_t e = 0; e < W; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      const double head = r[W - 2], count = r[W - 1];
+      if (head != std::floor(head) || head < 0.0 || head >= MPC_SIM_ACTUATORS_RING)
+        throw std::runtime_error(row + ": head must be an integer value in [0, " + std::to_string(MPC_SIM_ACTUATORS_RING) + ")");
+      if (count < 0.0) throw std::runtime_error(row + ": count must be >= 0");
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, sim_actuators_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+int32_t mpc_sim_actuators_width(mpc_solver* s) {
+  if (!s) return -1;
+  try {
+    sim_check(s, "sim_actuators_width");
+    return (int32_t)sim_actuators_width(s->L);
+  } catch (const std::exception& e) {
+    s->err = e.what();
+    return -1;
+  }
+}
+
 int32_t mpc_sim_record_width(mpc_solver* s) {
   if (!s) return -1;
   try {
@@ -1732,6 +1845,7 @@ int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32
     if (x) copy_sync(s, s->d_x0, x, (size_t)L.B * L.nx * sizeof(double), hipMemcpyHostToDevice);
     copy_sync(s, s->d_simu, tau, (size_t)L.B * L.m * sizeof(double), hipMemcpyHostToDevice);
     sim_metrics_begin(s, s->stream);
+    sim_actuators_enqueue(s, s->stream, substeps * dt);
     launch_eval_multibody(s->stream, s->args(), s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, sim_push(s), true,
                           s->d_simu, sim_wrench_out(s, wrenches != nullptr), sim_push_width(s), sim_contacts_rows(s));
     HIP_OK(hipGetLastError());
@@ -1812,6 +1926,7 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
       qp_id_enqueue(qp, S, kd);
       qp_launch_solve(qp, S);
       hipLaunchKernelGGL(k_pipe_torque, dim3((unsigned)B), dim3(64), 0, st, p);
+      sim_actuators_enqueue(sim, st, dt);
       launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
                             sim_wrench_out(sim, false), sim_push_width(sim), sim_contacts_rows(sim));
       HIP_OK(hipGetLastError());
@@ -1910,6 +2025,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
       qp_ikid_enqueue(qp, S);
       qp_launch_solve(qp, S);
       hipLaunchKernelGGL(k_pipe_ikid_torque, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+      sim_actuators_enqueue(sim, st, dt);
       launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
                             sim_wrench_out(sim, false), sim_push_width(sim), sim_contacts_rows(sim));
       HIP_OK(hipGetLastError());
@@ -1969,6 +2085,7 @@ int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double
     for (int step = 0; step < steps; ++step) {
       if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(sim->d_xlast, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(k_pipe_state_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
+      sim_actuators_enqueue(sim, st, dt);
       launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
                             sim_wrench_out(sim, wrenches != nullptr), sim_push_width(sim), sim_contacts_rows(sim));
       HIP_OK(hipGetLastError());

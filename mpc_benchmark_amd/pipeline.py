@@ -37,12 +37,20 @@ tick changes: the planner keeps the schedule's footholds, the low-level QPs the 
 
 ``walk=dict(per_instance=True, commands=table)`` (all three pipelines): a walk command per robot, a (B, 16) table of ``references.walk_commands`` that
 ``EnsembleMPC.enable_walk`` takes (include/mpc_walk_commands.h) — one robot per step length, turn rate or lateral step in one ensemble.  The table is
-checked when the pipeline is built; ``pipeline.mpc.set_walk_commands`` changes it mid-walk."""
+checked when the pipeline is built; ``pipeline.mpc.set_walk_commands`` changes it mid-walk.
+
+``actuators`` (all three pipelines): None, the simulator integrates the torque the controller computed; or the parameter rows of the per-robot actuator
+model (``actuator_model``: transport delay, gain error, first-order lag, saturation, joint friction; (B, 8), one row of 8 for every robot, or a dict by
+field name of scalars or (B,) arrays, which may also carry ``limit`` and ``friction_shape``), armed on the simulator handle when the pipeline is built
+(mpc_sim_actuators, include/mpc_sim_actuators.h; HIP library only).  ``limit`` defaults to the model's effort limits.  ``torques`` is then the APPLIED
+torque of the last step on both forms of a tick (the device loop returns it; the host glue reads it back after each step), and so are the record's
+torque columns and the metrics' power and energy.  ``set_actuators`` changes or removes the model later."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _capi as K
+from . import actuator_model as _actuator_model
 from . import contact_rule as _contact_rule
 from . import qp_utils
 from .aligator import _core as core
@@ -186,6 +194,33 @@ def stairs_under_walk(robot, x_forward, z_height, y_gap=0.18, n_steps=3, half_ex
     return boxes, holds
 
 
+class _Actuators:
+    """``actuators`` of the three pipelines (module docstring): the model is armed on the simulator handle; the host glue reads the applied torque back."""
+    _actuators_on = False
+
+    def set_actuators(self, params, limit=None, friction_shape=None):
+        """Arm (and reset) the per-robot actuator model on ``self.sim``: ``params`` in the forms of ``NativeSolver.actuators``, a dict may also carry
+        ``limit`` and ``friction_shape``; ``limit`` defaults to the model's effort limits.  None turns the model off."""
+        if params is None:
+            if self._actuators_on:
+                self.sim.actuators(None)
+            self._actuators_on = False
+            return
+        if isinstance(params, dict):
+            params = dict(params)
+            limit = params.pop("limit", limit)
+            friction_shape = params.pop("friction_shape", friction_shape)
+        if limit is None:
+            limit = np.asarray(self.model.effortLimit, dtype=float)[6:]
+        self.sim.actuators(_actuator_model.rows(params, self.batch), limit=limit, friction_shape=friction_shape)
+        self._actuators_on = True
+
+    def _applied_torques(self):
+        """host glue, after a simulator step: with the model on ``torques`` is what the step integrated, as on the device loop"""
+        if self._actuators_on:
+            self.torques = self.sim.read_actuators()["applied"].copy()
+
+
 class _QpContactSource:
     """``contact_source`` of the two pipelines with a low-level QP (module docstring): the checks, the host-glue form of the selection (the numpy mirror
     ``contact_rule.qp_contact_states`` on the rows read before every step) and ``qp_contacts``."""
@@ -236,12 +271,12 @@ class _QpContactSource:
         return dict(used=used, counts=counts)
 
 
-class KinodynamicPipeline(_QpContactSource):
+class KinodynamicPipeline(_QpContactSource, _Actuators):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
-                 terrain=None, contact_source="schedule", **ens_kw):
+                 terrain=None, contact_source="schedule", actuators=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
-        ``contact_source``: "schedule", "plant" or "both" (module docstring)."""
+        ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model (module docstring)."""
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("KinodynamicPipeline", contact_source, contact_rule)
         self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
@@ -260,6 +295,8 @@ class KinodynamicPipeline(_QpContactSource):
         self.qp.enable_device_assembly()
         self.umax = np.asarray(m.effortLimit, dtype=float)[6:]
         self._build_simulator()
+        if actuators is not None:
+            self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
         self.x_prev = self.x.copy()                      # the measurement of the tick before (the solve's initial condition)
         self.torques = np.zeros((self.batch, m.nv - 6))
@@ -318,6 +355,7 @@ class KinodynamicPipeline(_QpContactSource):
         tau = np.clip(tau, -self.umax, self.umax)
         self.x = self.sim.simulate_torque(x, tau, 1, self.sim_dt)
         self.torques, self.forces = tau, f_new
+        self._applied_torques()
         return tau
 
     def low_level_loop(self, cs):
@@ -389,7 +427,7 @@ def posture_gains(nv):
     return G, 2 * np.sqrt(G)
 
 
-class CentroidalPipeline(_QpContactSource):
+class CentroidalPipeline(_QpContactSource, _Actuators):
     """The centroidal control pipeline of centroidal_talos.py:353-468 for an ensemble of robots, every stage on the solver library:
 
         MPC tick (centroidal OCP, x = [com ; h_lin ; h_ang], one ProxDDP iteration)
@@ -421,11 +459,12 @@ class CentroidalPipeline(_QpContactSource):
     G_FOOT, G_ROT = 400.0, 10.0                        # g_p, g_b (:305-307)
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
-                 sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", **ens_kw):
+                 sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
-        dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both" (module docstring)."""
+        dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model
+        (module docstring)."""
         from .ensemble import ensemble_initial_states
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("CentroidalPipeline", contact_source, contact_rule)
@@ -460,6 +499,8 @@ class CentroidalPipeline(_QpContactSource):
         if self.contact_rule is not None:
             _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule, self.terrain)
         self._set_sim_contacts((True, True))   # (the schedule starts in double support)
+        if actuators is not None:
+            self.set_actuators(actuators)
         self.torques = np.zeros((self.batch, m.nv - 6))
         self.forces = np.zeros((self.batch, 12))
         self.ik = None                 # the task errors of the last period
@@ -523,6 +564,7 @@ class CentroidalPipeline(_QpContactSource):
         _, f_new, tau = self.qp.solve_batch_device_ik(x, ik, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
         self.x = self.sim.simulate_torque(x, tau, 1, self.sim_dt)
         self.torques, self.forces = tau, f_new
+        self._applied_torques()
         return new_x
 
     def low_level_loop(self, cs, refs):
@@ -580,7 +622,7 @@ class CentroidalPipeline(_QpContactSource):
 
 
 # -- the full-dynamics pipeline ---------------------------------------------------------------------------------------------------------
-class FullDynamicPipeline:
+class FullDynamicPipeline(_Actuators):
     """The full-dynamics control pipeline of fulldynamic_talos.py:437-550 for an ensemble of robots, every stage on the solver library:
 
         MPC tick (full-dynamics OCP, one ProxDDP iteration)                                                    fulldynamic_talos.py:536-541
@@ -597,10 +639,12 @@ class FullDynamicPipeline:
     contact set of ``contact_state``).  ``library``: the HIP library by default; the device loop (``low_level_loop``,
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
-    def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, **ens_kw):
+    def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
+                 **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
-        the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes (module docstring of pipeline.py)."""
+        the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
+        actuator model (module docstring of pipeline.py)."""
         self.terrain = _checked_terrain("FullDynamicPipeline", terrain, contact_rule, int(batch))
         walk = _checked_walk("FullDynamicPipeline", walk, int(batch))
         if ens_kw.get("closed_loop") is not None:
@@ -620,6 +664,8 @@ class FullDynamicPipeline:
         self._sim_mask = None
         if self.contact_rule is not None:
             _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule, self.terrain)
+        if actuators is not None:
+            self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
         self.x_prev = self.x.copy()                      # the measurement of the period before (the solve's initial condition)
         self.torques = np.zeros((self.batch, m.nv - 6))
@@ -663,6 +709,7 @@ class FullDynamicPipeline:
         tau = self.us0 - np.einsum("bij,bj->bi", self.K0, d)
         self.x, wr = self.sim.simulate_torque(x, tau, 1, self.sim_dt, wrenches=True)
         self.torques, self.wrenches = tau, wr
+        self._applied_torques()
         return tau
 
     def low_level_loop(self, cs):
