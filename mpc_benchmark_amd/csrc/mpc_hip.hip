@@ -67,6 +67,35 @@ static void lds_attr_max(const void* fn, int bytes) {
 // (28 dofs), full dynamics   4: the same, kinodynamic.  The stage kernel has its own list (eval_multibody.hip).
 #define MPC_FIXED_MODELS(X) X(1, 76, 32, 1, 1, 80, 32) X(2, 76, 44, 3, 0, 80, 48) X(3, 56, 22, 3, 1, 64, 32) X(4, 56, 34, 3, 1, 64, 48)
 
+// The plant: state of the torque-driven simulator steps (mpc_simulate_torque and the device loops of the three pipelines; host code: sim_host.h)
+struct SimPlant {
+  double* d_simu = nullptr;  // [B][nu] torques, [B][12] wrenches of mpc_simulate_torque
+  double* d_simwr = nullptr;
+  double* d_xlast = nullptr;  // [B][nx] the states before the last period of mpc_feedback_low_level_steps
+  // include/mpc_sim_ext.h: the push armed for the torque-driven steps (push_width 0: none) and the record ring [rec_cap][B][rec]
+  double* d_push = nullptr;  // [B][6]
+  int push_width = 0;
+  double* d_rec = nullptr;
+  int rec_cap = 0, rec_count = 0;
+  // include/mpc_sim_metrics.h: the metric rows (nullptr: metrics off), [B][W] rows | [B] frozen flags | [B][nx] the state the next step starts from
+  double* d_met = nullptr;
+  mpc_sim_metrics_config met_cfg = {};
+  // include/mpc_sim_contacts.h: the rows of the contact rule (nullptr: rule off, stage 0 decides the contacts), [B][W]
+  double* d_con = nullptr;
+  mpc_sim_contacts_config con_cfg = {};
+  // include/mpc_sim_terrain.h: the boxes under the contact rule (nullptr: the plane; also with zero boxes), [n] or [B][n] boxes; h_ter as they were given
+  double* d_ter = nullptr;
+  mpc_sim_terrain_config ter_cfg = {};
+  std::vector<double> h_ter;
+  // include/mpc_sim_actuators.h: the actuator model (nullptr: off), one allocation: params [B][8] | limit [nu] | friction shape [nu] | state rows [B][18 nu + 2]
+  double* d_act = nullptr;
+  std::vector<double> h_act;  // params | limit | shape as they are in force
+  // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
+  void free_owned() {
+    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+  }
+};
+
 struct mpc_solver {
   mpc_dims dims{};
   mpc_options opt{};
@@ -132,27 +161,7 @@ struct mpc_solver {
   size_t poses_x_cap = 0;
   int since_change = 1 << 20;      // mpc_cycle calls since the appended stage last changed its contact pattern (corrector_window)
   bool refine_now = false;         // ... and this run refines the warm start of the appended knot after k_begin_run
-  double* d_simu = nullptr;  // [B][nu] torques, [B][12] wrenches of mpc_simulate_torque
-  double* d_simwr = nullptr;
-  double* d_xlast = nullptr;  // [B][nx] the states before the last period of mpc_feedback_low_level_steps
-  // include/mpc_sim_ext.h: the push armed for the torque-driven steps (push_width 0: none) and the record ring [rec_cap][B][rec]
-  double* d_push = nullptr;  // [B][6]
-  int push_width = 0;
-  double* d_rec = nullptr;
-  int rec_cap = 0, rec_count = 0;
-  // include/mpc_sim_metrics.h: the metric rows (nullptr: metrics off), [B][W] rows | [B] frozen flags | [B][nx] the state the next step starts from
-  double* d_met = nullptr;
-  mpc_sim_metrics_config met_cfg = {};
-  // include/mpc_sim_contacts.h: the rows of the contact rule (nullptr: rule off, stage 0 decides the contacts), [B][W]
-  double* d_con = nullptr;
-  mpc_sim_contacts_config con_cfg = {};
-  // include/mpc_sim_terrain.h: the boxes under the contact rule (nullptr: the plane; also with zero boxes), [n] or [B][n] boxes; h_ter as they were given
-  double* d_ter = nullptr;
-  mpc_sim_terrain_config ter_cfg = {};
-  std::vector<double> h_ter;
-  // include/mpc_sim_actuators.h: the actuator model (nullptr: off), one allocation: params [B][8] | limit [nu] | friction shape [nu] | state rows [B][18 nu + 2]
-  double* d_act = nullptr;
-  std::vector<double> h_act;  // params | limit | shape as they are in force
+  SimPlant plant;  // the torque-driven simulator steps on this handle (sim_host.h)
   // per-slot invalidation (mpc_update_stage_params*): slots whose parameters changed since the last pass was enqueued ; dirty_all:
   // an update on a horizon too long for the mask of SolverArgs
   std::vector<uint8_t> slot_dirty;
@@ -944,7 +953,8 @@ void mpc_destroy(mpc_solver* s) {
   for (int i = 0; i < mpc_solver::ASYNC_DEPTH; ++i) if (s->h_xnext[i]) (void)hipHostFree(s->h_xnext[i]);
   if (s->d_patch) (void)hipFree(s->d_patch);
   for (void* p : s->allocs) (void)hipFree(p);
-  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf, s->d_rec, s->d_met, s->d_con, s->d_ter, s->d_act}) if (p) (void)hipFree(p);
+  for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf}) if (p) (void)hipFree(p);
+  s->plant.free_owned();
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1342,764 +1352,6 @@ int mpc_simulate(mpc_solver* s, int32_t substeps, double dt) {
 
 int mpc_simulate_push(mpc_solver* s, int32_t substeps, double dt, const double* f_ext) {
   MPC_TRY(s, { simulate_impl(s, substeps, dt, f_ext); })
-}
-
-// ---- include/mpc_sim_ext.h: push and record of the torque-driven simulator steps --------------------------------------------------------------
-// the handle of mpc_simulate_torque: whole-body, nu = nv - 6.  (Its stage 0 may be set later, as the pipelines do per contact state: the contact dynamics
-// are checked by the simulator steps themselves.)
-static void sim_check(mpc_solver* s, const char* what) {
-  const Layout& L = s->L;
-  if (L.space != MPC_SPACE_MULTIBODY || L.m != L.n / 2 - 6 || L.nx != L.n / 2 + (L.n / 2 + 1))
-    throw std::runtime_error(std::string(what) + ": the simulator handle must be a whole-body handle with nu = nv - 6 (the handle of mpc_simulate_torque)");
-}
-static const double* sim_push(const mpc_solver* s) { return s->push_width ? s->d_push : nullptr; }
-static int sim_push_width(const mpc_solver* s) { return s->push_width ? s->push_width : 3; }
-static double* sim_wrench_out(const mpc_solver* s, bool wanted) { return (wanted || s->rec_cap > 0 || s->d_met || s->d_con) ? s->d_simwr : nullptr; }
-// every one of the `steps` simulator steps about to be enqueued gets its record slot, or the call fails before anything is enqueued
-static void sim_record_reserve(const mpc_solver* s, int steps) {
-  if (s->rec_cap > 0 && s->rec_count + steps > s->rec_cap)
-    throw std::runtime_error("sim_record: the record ring is full (" + std::to_string(s->rec_count) + " of " + std::to_string(s->rec_cap) + " steps held, " +
-                             std::to_string(steps) + " more asked for): read it with mpc_sim_record_read or enlarge it with mpc_sim_record");
-}
-// after a simulator step on stream st: its record (sim_record.h), when recording is on
-static void sim_record_enqueue(mpc_solver* s, hipStream_t st) {
-  if (s->rec_cap <= 0) return;
-  const Layout& L = s->L;
-  SimRecordArgs r;
-  r.mi = s->d_model_i; r.md = s->d_model_d; r.nv = L.n / 2; r.nq = L.nx - L.n / 2;
-  r.x = s->d_x0; r.tau = s->d_simu; r.wr = s->d_simwr; r.push = sim_push(s); r.push_width = s->push_width;
-  r.out = s->d_rec + (size_t)s->rec_count * L.B * sim_record_width(L.nx, L.m);
-  hipLaunchKernelGGL(k_sim_record, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, r);
-  HIP_OK(hipGetLastError());
-  s->rec_count++;
-}
-// before the first simulator step of a call, on its stream (after the state is uploaded): the state that step starts from, for its joint power
-static void sim_metrics_begin(mpc_solver* s, hipStream_t st) {
-  if (!s->d_met) return;
-  const Layout& L = s->L;
-  HIP_OK(hipMemcpyAsync(s->d_met + (size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1), s->d_x0, (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-}
-// the terrain of the contact rule as the kernels take it (sim_terrain.h): boxes nullptr without one
-static SimTerrain sim_terrain_args(const mpc_solver* s) {
-  SimTerrain t;
-  t.boxes = s->d_con ? s->d_ter : nullptr;
-  t.n = s->ter_cfg.n_boxes;
-  t.stride = s->ter_cfg.per_robot ? s->ter_cfg.n_boxes * MPC_SIM_TERRAIN_BOX_WIDTH : 0;
-  return t;
-}
-// after a simulator step of length dt on stream st: its metrics (sim_metrics.h), when they are on
-static void sim_metrics_enqueue(mpc_solver* s, hipStream_t st, double dt) {
-  if (!s->d_met) return;
-  const Layout& L = s->L;
-  SimMetricsArgs m;
-  m.mi = s->d_model_i; m.md = s->d_model_d; m.nv = L.n / 2; m.nq = L.nx - L.n / 2;
-  m.x = s->d_x0; m.tau = s->d_simu; m.wr = s->d_simwr; m.dt = dt; m.cfg = s->met_cfg;
-  m.acc = s->d_met; m.frozen = s->d_met + (size_t)L.B * MPC_SIM_METRICS_WIDTH; m.xs = m.frozen + L.B;
-  m.ter = sim_terrain_args(s); m.con = s->d_con; m.ground_z = s->con_cfg.ground_z;
-  hipLaunchKernelGGL(k_sim_metrics, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, m);
-  HIP_OK(hipGetLastError());
-}
-// the rows after a reset: nothing accumulated, no fall, nothing latched (the margin's minimum, the heights and the centres of mass NaN); not frozen
-static void sim_metrics_reset(mpc_solver* s) {
-  const Layout& L = s->L;
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  std::vector<double> h((size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1), 0.0);
-  for (int b = 0; b < L.B; ++b) {
-    double* r = h.data() + (size_t)b * MPC_SIM_METRICS_WIDTH;
-    r[6] = nan;
-    r[11] = -1.0;
-    for (int i = 12; i < MPC_SIM_METRICS_WIDTH; ++i) r[i] = nan;
-  }
-  copy_sync(s, s->d_met, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-}
-// with the contact rule on, stage 0 must be the double-support stage: the rule picks each robot's contacts out of its two (checked by every
-// stepping call before anything is enqueued)
-static void sim_contacts_check(const mpc_solver* s, const char* what) {
-  if (!s->d_con) return;
-  const int32_t* d = s->h_desc.data() + (size_t)slot_of(s, 0) * s->L.max_stage_ints;
-  if (d[0] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER || d[1] != 2 || !((d[2] == 0 && d[3] == 1) || (d[2] == 1 && d[3] == 0)))
-    throw std::runtime_error(std::string(what) + ": the contact rule is on (mpc_sim_contacts), so stage 0 of the simulator handle must be the double-support "
-                             "stage (contact dynamics of contacts 0 and 1)");
-}
-static const double* sim_contacts_rows(const mpc_solver* s) { return s->d_con; }
-// after a simulator step on stream st (after its record and metrics): the contact rule (sim_contacts.h), when it is on
-static void sim_contacts_enqueue(mpc_solver* s, hipStream_t st) {
-  if (!s->d_con) return;
-  const Layout& L = s->L;
-  SimContactsArgs c;
-  c.mi = s->d_model_i; c.md = s->d_model_d; c.nv = L.n / 2; c.nq = L.nx - L.n / 2;
-  c.x = s->d_x0; c.wr = s->d_simwr; c.cfg = s->con_cfg; c.rows = s->d_con; c.ter = sim_terrain_args(s);
-  hipLaunchKernelGGL(k_sim_contacts, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, c);
-  HIP_OK(hipGetLastError());
-}
-// the rows after a reset: both soles in contact at the model's ground-side placements (contacts 0 and 1), nothing counted
-static void sim_contacts_reset(mpc_solver* s) {
-  const Layout& L = s->L;
-  const int nj = s->h_model_i[0], nframes = s->h_model_i[3];
-  const size_t off = MPC_MODEL_HEADER_DOUBLES + (size_t)MPC_MODEL_JOINT_DOUBLES * nj + (size_t)MPC_MODEL_FRAME_DOUBLES * nframes;
-  double cm[2 * MPC_MODEL_CONTACT_DOUBLES];
-  copy_sync(s, cm, s->d_model_d + off, sizeof(cm), hipMemcpyDeviceToHost);
-  std::vector<double> h((size_t)L.B * MPC_SIM_CONTACTS_WIDTH, 0.0);
-  for (int b = 0; b < L.B; ++b) {
-    double* r = h.data() + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
-    for (int i = 0; i < 2; ++i) {
-      const double* c = cm + MPC_MODEL_CONTACT_DOUBLES * i;
-      r[i] = 1.0;
-      r[6 + i] = c[23];                                          // z_prev: the anchor's height
-      for (int e = 0; e < 12; ++e) r[8 + 12 * i + e] = c[12 + e];  // R2 (9), p2 (3)
-      r[36 + i] = r[38 + i] = -1.0;
-    }
-  }
-  copy_sync(s, s->d_con, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-}
-
-static size_t sim_actuators_width(const Layout& L) { return (size_t)(MPC_SIM_ACTUATORS_RING + 2) * L.m + 2; }
-static double* sim_actuators_rows(const mpc_solver* s) { return s->d_act + (size_t)s->L.B * MPC_SIM_ACTUATORS_PARAMS + 2 * (size_t)s->L.m; }
-// before a simulator step of length dt_step on stream st (after the controller wrote the step's torque into d_simu, before the dynamics): the actuator
-// model (sim_actuators.h), when it is on, turns the command into the applied torque in place
-static void sim_actuators_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
-  if (!s->d_act) return;
-  const Layout& L = s->L;
-  SimActuatorsArgs a;
-  a.nv = L.n / 2; a.nq = L.nx - L.n / 2; a.nu = L.m;
-  a.x = s->d_x0; a.tau = s->d_simu;
-  a.params = s->d_act; a.limit = s->d_act + (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS; a.shape = a.limit + L.m;
-  a.rows = sim_actuators_rows(s); a.dt = dt_step;
-  hipLaunchKernelGGL(k_sim_actuators, dim3((unsigned)L.B), dim3(SIM_ACT_THREADS), 0, st, a);
-  HIP_OK(hipGetLastError());
-}
-
-int mpc_sim_set_push(mpc_solver* s, const double* f_ext, int32_t width) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_set_push");
-    if (!f_ext) { s->push_width = 0; return 0; }
-    if (width != 3 && width != 6) throw std::runtime_error("sim_set_push: width must be 3 (force at the base origin) or 6 (force, world point)");
-    const Layout& L = s->L;
-    if (!s->d_push) s->d_push = s->alloc<double>((size_t)L.B * 6);
-    // (a small synchronous upload: the push changes a few times per run, not part of the steady loop)
-    copy_sync(s, s->d_push, f_ext, (size_t)L.B * width * sizeof(double), hipMemcpyHostToDevice);
-    s->push_width = width;
-  })
-}
-
-int mpc_sim_record(mpc_solver* s, int32_t cap) {
-  MPC_TRY(s, {
-    if (cap < 0) throw std::runtime_error("sim_record: cap must be >= 0 (0: recording off)");
-    sim_check(s, "sim_record");
-    const Layout& L = s->L;
-    if (cap > 0 && (s->h_model_i.size() < 5 || s->h_model_i[4] < 2))
-      throw std::runtime_error("sim_record: the model of the simulator handle must hold the two sole contacts (contacts 0 and 1)");
-    if (cap > 0 && L.nj > CG_MAX_NJ) throw std::runtime_error("sim_record: more moving joints than the record kernel holds (64)");
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (s->d_rec) { HIP_OK(hipFree(s->d_rec)); s->d_rec = nullptr; }
-    s->rec_cap = s->rec_count = 0;
-    if (cap > 0) {
-      void* p = nullptr;
-      HIP_OK(hipMalloc(&p, (size_t)cap * L.B * sim_record_width(L.nx, L.m) * sizeof(double)));
-      s->d_rec = (double*)p;
-      s->rec_cap = cap;
-      if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
-      HIP_OK(hipStreamSynchronize(s->stream));
-    }
-  })
-}
-
-int mpc_sim_record_read(mpc_solver* s, double* out, int32_t* count) {
-  MPC_TRY(s, {
-    if (!count) throw std::runtime_error("sim_record_read: count must not be null");
-    sim_check(s, "sim_record_read");
-    HIP_OK(hipStreamSynchronize(s->stream));
-    *count = s->rec_count;
-    if (out) {
-      const Layout& L = s->L;
-      if (s->rec_count > 0) copy_sync(s, out, s->d_rec, (size_t)s->rec_count * L.B * sim_record_width(L.nx, L.m) * sizeof(double), hipMemcpyDeviceToHost);
-      s->rec_count = 0;
-    }
-  })
-}
-
-int mpc_sim_metrics(mpc_solver* s, const mpc_sim_metrics_config* cfg) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_metrics");
-    const Layout& L = s->L;
-    if (cfg) {
-      if (s->h_model_i.size() < 5 || s->h_model_i[4] < 2)
-        throw std::runtime_error("sim_metrics: the model of the simulator handle must hold the two sole contacts (contacts 0 and 1)");
-      if (L.nj > CG_MAX_NJ) throw std::runtime_error("sim_metrics: more moving joints than the metrics kernel holds (64)");
-      for (double v : {cfg->min_force, cfg->half_length, cfg->half_width, cfg->fall_drop, cfg->sole_lift})
-        if (!std::isfinite(v) || v < 0.0) throw std::runtime_error("sim_metrics: every field of the configuration must be finite and >= 0");
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (s->d_met) { HIP_OK(hipFree(s->d_met)); s->d_met = nullptr; }
-    if (cfg) {
-      void* p = nullptr;
-      HIP_OK(hipMalloc(&p, (size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1 + L.nx) * sizeof(double)));
-      s->d_met = (double*)p;
-      s->met_cfg = *cfg;
-      if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
-      sim_metrics_reset(s);
-    }
-  })
-}
-
-int mpc_sim_metrics_read(mpc_solver* s, double* out, int32_t reset) {
-  MPC_TRY(s, {
-    if (!out) throw std::runtime_error("sim_metrics_read: out must not be null");
-    sim_check(s, "sim_metrics_read");
-    if (!s->d_met) throw std::runtime_error("sim_metrics_read: metrics are off on this handle (turn them on with mpc_sim_metrics)");
-    HIP_OK(hipStreamSynchronize(s->stream));
-    copy_sync(s, out, s->d_met, (size_t)s->L.B * MPC_SIM_METRICS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
-    if (reset) sim_metrics_reset(s);
-  })
-}
-
-int32_t mpc_sim_metrics_width(mpc_solver* s) {
-  if (!s) return -1;
-  try {
-    sim_check(s, "sim_metrics_width");
-    return MPC_SIM_METRICS_WIDTH;
-  } catch (const std::exception& e) {
-    s->err = e.what();
-    return -1;
-  }
-}
-
-static void sim_terrain_drop(mpc_solver* s) {
-  if (s->d_ter) { HIP_OK(hipFree(s->d_ter)); s->d_ter = nullptr; }
-  s->ter_cfg = {};
-  s->h_ter.clear();
-}
-
-int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_contacts");
-    const Layout& L = s->L;
-    if (cfg) {
-      if (s->h_model_i.size() < 5 || s->h_model_i[4] < 2)
-        throw std::runtime_error("sim_contacts: the model of the simulator handle must hold the two sole contacts (contacts 0 and 1)");
-      if (L.nj > CG_MAX_NJ) throw std::runtime_error("sim_contacts: more moving joints than the contact-rule kernel holds (64)");
-      if (!std::isfinite(cfg->ground_z) || !std::isfinite(cfg->ground_tol) || !std::isfinite(cfg->release_force))
-        throw std::runtime_error("sim_contacts: ground_z, ground_tol and release_force must be finite");
-      if (cfg->ground_tol < 0.0 || cfg->release_force < 0.0) throw std::runtime_error("sim_contacts: ground_tol and release_force must be >= 0");
-      if (cfg->release_steps < 1) throw std::runtime_error("sim_contacts: release_steps must be >= 1");
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (s->d_con) { HIP_OK(hipFree(s->d_con)); s->d_con = nullptr; }
-    if (!cfg) sim_terrain_drop(s);  // (the terrain goes with the rows; a reset keeps it)
-    if (cfg) {
-      void* p = nullptr;
-      HIP_OK(hipMalloc(&p, (size_t)L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double)));
-      s->d_con = (double*)p;
-      s->con_cfg = *cfg;
-      s->con_cfg.reserved = 0;
-      if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
-      sim_contacts_reset(s);
-    }
-  })
-}
-
-int mpc_sim_contacts_set(mpc_solver* s, const double* rows) {
-  MPC_TRY(s, {
-    if (!rows) throw std::runtime_error("sim_contacts_set: rows must not be null");
-    sim_check(s, "sim_contacts_set");
-    if (!s->d_con) throw std::runtime_error("sim_contacts_set: the contact rule is off on this handle (turn it on with mpc_sim_contacts)");
-    const Layout& L = s->L;
-    for (int b = 0; b < L.B; ++b) {
-      const double* r = rows + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
-      const std::string row = "sim_contacts_set: row " + std::to_string(b);
-      for (int e = 0; e < MPC_SIM_CONTACTS_WIDTH; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-      for (int e = 0; e < 4; ++e)
-        if (r[e] != 0.0 && r[e] != 1.0) throw std::runtime_error(row + ": in_contact and lifted must be 0 or 1");
-      if (r[0] == 0.0 && r[1] == 0.0) throw std::runtime_error(row + " has no sole in contact (flight phases are not simulated)");
-      for (int e : {4, 5, 32, 33, 34, 35, 40})
-        if (r[e] < 0.0) throw std::runtime_error(row + ": pulling, the counts and steps must be >= 0");
-      for (int i = 0; i < 2; ++i) {
-        const double* R = r + 8 + 12 * i;
-        double dev = 0.0;
-        for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) {
-          double d = (a == c) ? -1.0 : 0.0;
-          for (int k = 0; k < 3; ++k) d += R[3 * k + a] * R[3 * k + c];
-          dev = std::fmax(dev, std::fabs(d));
-        }
-        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-        if (dev > 1e-9 || det < 0.0) throw std::runtime_error(row + ": the anchor of sole " + std::to_string(i) + " is not a rotation");
-      }
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    copy_sync(s, s->d_con, rows, (size_t)L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyHostToDevice);
-  })
-}
-
-int mpc_sim_contacts_read(mpc_solver* s, double* rows) {
-  MPC_TRY(s, {
-    if (!rows) throw std::runtime_error("sim_contacts_read: rows must not be null");
-    sim_check(s, "sim_contacts_read");
-    if (!s->d_con) throw std::runtime_error("sim_contacts_read: the contact rule is off on this handle (turn it on with mpc_sim_contacts)");
-    HIP_OK(hipStreamSynchronize(s->stream));
-    copy_sync(s, rows, s->d_con, (size_t)s->L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
-  })
-}
-
-int mpc_sim_terrain(mpc_solver* s, const mpc_sim_terrain_config* cfg, const double* boxes) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_terrain");
-    if (!s->d_con) throw std::runtime_error("sim_terrain: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
-    const Layout& L = s->L;
-    size_t count = 0;
-    if (cfg) {
-      if (cfg->n_boxes < 0 || cfg->n_boxes > MPC_SIM_TERRAIN_MAX_BOXES)
-        throw std::runtime_error("sim_terrain: n_boxes must be 0 .. " + std::to_string(MPC_SIM_TERRAIN_MAX_BOXES));
-      if (cfg->per_robot != 0 && cfg->per_robot != 1) throw std::runtime_error("sim_terrain: per_robot must be 0 or 1");
-      if (cfg->n_boxes > 0 && !boxes) throw std::runtime_error("sim_terrain: boxes must not be null with n_boxes > 0");
-      count = (size_t)(cfg->per_robot ? L.B : 1) * cfg->n_boxes;
-      for (size_t k = 0; k < count; ++k) {
-        const double* bx = boxes + k * MPC_SIM_TERRAIN_BOX_WIDTH;
-        for (int e = 0; e < MPC_SIM_TERRAIN_BOX_WIDTH; ++e)
-          if (!std::isfinite(bx[e])) throw std::runtime_error("sim_terrain: box " + std::to_string(k) + " holds a non-finite number");
-        if (bx[0] > bx[1] || bx[2] > bx[3]) throw std::runtime_error("sim_terrain: box " + std::to_string(k) + " has x_lo > x_hi or y_lo > y_hi");
-      }
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    sim_terrain_drop(s);
-    if (cfg) {
-      s->ter_cfg = *cfg;
-      s->h_ter.assign(boxes, boxes + count * MPC_SIM_TERRAIN_BOX_WIDTH);
-      if (count > 0) {  // (zero boxes: the plane, by the old path)
-        std::vector<double> h(s->h_ter);
-        for (size_t k = 0; k < count; ++k) h[k * MPC_SIM_TERRAIN_BOX_WIDTH + 4] += 0.0;  // (a top of -0 counts as +0, as in the numpy definition)
-        void* p = nullptr;
-        HIP_OK(hipMalloc(&p, h.size() * sizeof(double)));
-        s->d_ter = (double*)p;
-        copy_sync(s, s->d_ter, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-      }
-    }
-  })
-}
-
-int mpc_sim_terrain_read(mpc_solver* s, mpc_sim_terrain_config* cfg, double* boxes) {
-  MPC_TRY(s, {
-    if (!cfg) throw std::runtime_error("sim_terrain_read: cfg must not be null");
-    sim_check(s, "sim_terrain_read");
-    if (!s->d_con) throw std::runtime_error("sim_terrain_read: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
-    *cfg = s->ter_cfg;
-    if (boxes) std::copy(s->h_ter.begin(), s->h_ter.end(), boxes);
-  })
-}
-
-int mpc_sim_terrain_height(mpc_solver* s, const double* xy, int32_t n, double* h) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_terrain_height");
-    if (!s->d_con) throw std::runtime_error("sim_terrain_height: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
-    if (n < 0) throw std::runtime_error("sim_terrain_height: n must be >= 0");
-    if (n > 0 && (!xy || !h)) throw std::runtime_error("sim_terrain_height: xy and h must not be null");
-    const Layout& L = s->L;
-    const size_t np = (size_t)L.B * n;
-    for (size_t i = 0; i < 2 * np; ++i)
-      if (!std::isfinite(xy[i])) throw std::runtime_error("sim_terrain_height: xy holds a non-finite number");
-    if (n > 0) {
-      void* p = nullptr;
-      HIP_OK(hipMalloc(&p, 3 * np * sizeof(double)));
-      double* d_xy = (double*)p;
-      try {
-        copy_sync(s, d_xy, xy, 2 * np * sizeof(double), hipMemcpyHostToDevice);
-        SimTerrainHeightArgs a;
-        a.t = sim_terrain_args(s); a.ground_z = s->con_cfg.ground_z; a.xy = d_xy; a.n = n; a.h = d_xy + 2 * np;
-        hipLaunchKernelGGL(k_sim_terrain_height, dim3((unsigned)L.B), dim3(64), 0, s->stream, a);
-        HIP_OK(hipGetLastError());
-        copy_sync(s, h, a.h, np * sizeof(double), hipMemcpyDeviceToHost);
-      } catch (...) {
-        (void)hipFree(p);
-        throw;
-      }
-      HIP_OK(hipFree(p));
-    }
-  })
-}
-
-int32_t mpc_sim_contacts_width(mpc_solver* s) {
-  if (!s) return -1;
-  try {
-    sim_check(s, "sim_contacts_width");
-    return MPC_SIM_CONTACTS_WIDTH;
-  } catch (const std::exception& e) {
-    s->err = e.what();
-    return -1;
-  }
-}
-
-// ---- include/mpc_sim_actuators.h: the per-robot actuator model of the torque-driven simulator steps ------------------------------------------
-int mpc_sim_actuators(mpc_solver* s, const double* params, const double* limit, const double* friction_shape) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_actuators");
-    const Layout& L = s->L;
-    const size_t nu = L.m, np = (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS;
-    std::vector<double> h;
-    if (params) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
-      h.assign(np + 2 * nu, 0.0);
-      bool any_sat = false;
-      for (int b = 0; b < L.B; ++b) {
-        const double* r = params + (size_t)b * MPC_SIM_ACTUATORS_PARAMS;
-        const std::string row = "sim_actuators: row " + std::to_string(b);
-        for (int e = 0; e < MPC_SIM_ACTUATORS_PARAMS; ++e)
-          if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-        if (r[0] != std::floor(r[0]) || r[0] < 0.0 || r[0] > MPC_SIM_ACTUATORS_RING - 1)
-          throw std::runtime_error(row + ": delay must be an integer value in [0, " + std::to_string(MPC_SIM_ACTUATORS_RING - 1) + "]");
-        if (!(r[1] > 0.0)) throw std::runtime_error(row + ": scale must be > 0");
-        for (int e = 2; e < 7; ++e)
-          if (r[e] < 0.0) throw std::runtime_error(row + ": time_constant, damping, coulomb, v_eps and sat must be >= 0");
-        if (r[4] > 0.0 && !(r[5] > 0.0)) throw std::runtime_error(row + ": coulomb > 0 needs v_eps > 0");
-        if (r[6] > 0.0) any_sat = true;
-        std::copy(r, r + MPC_SIM_ACTUATORS_PARAMS, h.begin() + (size_t)b * MPC_SIM_ACTUATORS_PARAMS);
-        h[(size_t)b * MPC_SIM_ACTUATORS_PARAMS + 7] = 0.0;
-      }
-      if (any_sat && !limit) throw std::runtime_error("sim_actuators: a row with sat > 0 needs the effort limits (limit must not be null)");
-      for (size_t j = 0; j < nu; ++j) {
-        const double l = limit ? limit[j] : 0.0, f = friction_shape ? friction_shape[j] : 1.0;
-        if (!std::isfinite(l) || l < 0.0 || !std::isfinite(f) || f < 0.0)
-          throw std::runtime_error("sim_actuators: limit and friction_shape must be finite and >= 0");
-        h[np + j] = l;
-        h[np + nu + j] = f;
-      }
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (s->d_act) { HIP_OK(hipFree(s->d_act)); s->d_act = nullptr; }
-    s->h_act.clear();
-    if (params) {
-      const size_t rows = (size_t)L.B * sim_actuators_width(L);
-      void* p = nullptr;
-      HIP_OK(hipMalloc(&p, (h.size() + rows) * sizeof(double)));
-      s->d_act = (double*)p;
-      s->h_act = h;
-      h.resize(h.size() + rows, 0.0);  // (the state rows after a reset: all 0)
-      copy_sync(s, s->d_act, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-    }
-  })
-}
-
-int mpc_sim_actuators_read(mpc_solver* s, double* params, double* state) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_actuators_read");
-    if (!s->d_act) throw std::runtime_error("sim_actuators_read: the actuator model is off on this handle (turn it on with mpc_sim_actuators)");
-    const Layout& L = s->L;
-    if (params) std::copy(s->h_act.begin(), s->h_act.begin() + (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS, params);
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (state) copy_sync(s, state, sim_actuators_rows(s), (size_t)L.B * sim_actuators_width(L) * sizeof(double), hipMemcpyDeviceToHost);
-  })
-}
-
-int mpc_sim_actuators_set(mpc_solver* s, const double* state) {
-  MPC_TRY(s, {
-    if (!state) throw std::runtime_error("sim_actuators_set: state must not be null");
-    sim_check(s, "sim_actuators_set");
-    if (!s->d_act) throw std::runtime_error("sim_actuators_set: the actuator model is off on this handle (turn it on with mpc_sim_actuators)");
-    const Layout& L = s->L;
-    const size_t W = sim_actuators_width(L);
-    for (int b = 0; b < L.B; ++b) {
-      const double* r = state + (size_t)b * W;
-      const std::string row = "sim_actuators_set: row " + std::to_string(b);
-      for (size_t e = 0; e < W; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-      const double head = r[W - 2], count = r[W - 1];
-      if (head != std::floor(head) || head < 0.0 || head >= MPC_SIM_ACTUATORS_RING)
-        throw std::runtime_error(row + ": head must be an integer value in [0, " + std::to_string(MPC_SIM_ACTUATORS_RING) + ")");
-      if (count < 0.0) throw std::runtime_error(row + ": count must be >= 0");
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    copy_sync(s, sim_actuators_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
-  })
-}
-
-int32_t mpc_sim_actuators_width(mpc_solver* s) {
-  if (!s) return -1;
-  try {
-    sim_check(s, "sim_actuators_width");
-    return (int32_t)sim_actuators_width(s->L);
-  } catch (const std::exception& e) {
-    s->err = e.what();
-    return -1;
-  }
-}
-
-int32_t mpc_sim_record_width(mpc_solver* s) {
-  if (!s) return -1;
-  try {
-    sim_check(s, "sim_record_width");
-    return sim_record_width(s->L.nx, s->L.m);
-  } catch (const std::exception& e) {
-    s->err = e.what();
-    return -1;
-  }
-}
-
-int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32_t substeps, double dt, double* wrenches) {
-  MPC_TRY(s, {
-    if (substeps <= 0 || !(dt > 0.0)) throw std::runtime_error("simulate: substeps and dt must be positive");
-    if (!tau) throw std::runtime_error("simulate_torque: tau must not be null");
-    if (s->L.space != MPC_SPACE_MULTIBODY || s->h_desc[(size_t)slot_of(s, 0) * s->L.max_stage_ints] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER)
-      throw std::runtime_error("simulate: only contact-constrained whole-body dynamics are supported");
-    const Layout& L = s->L;
-    sim_record_reserve(s, 1);
-    sim_contacts_check(s, "simulate_torque");
-    if (!s->d_simu) { s->d_simu = s->alloc<double>((size_t)L.B * L.m); s->d_simwr = s->alloc<double>((size_t)L.B * 12); }
-    if (x) copy_sync(s, s->d_x0, x, (size_t)L.B * L.nx * sizeof(double), hipMemcpyHostToDevice);
-    copy_sync(s, s->d_simu, tau, (size_t)L.B * L.m * sizeof(double), hipMemcpyHostToDevice);
-    sim_metrics_begin(s, s->stream);
-    sim_actuators_enqueue(s, s->stream, substeps * dt);
-    launch_eval_multibody(s->stream, s->args(), s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, sim_push(s), true,
-                          s->d_simu, sim_wrench_out(s, wrenches != nullptr), sim_push_width(s), sim_contacts_rows(s));
-    HIP_OK(hipGetLastError());
-    sim_record_enqueue(s, s->stream);
-    sim_metrics_enqueue(s, s->stream, substeps * dt);
-    sim_contacts_enqueue(s, s->stream);
-    if (wrenches) copy_sync(s, wrenches, s->d_simwr, (size_t)L.B * 12 * sizeof(double), hipMemcpyDeviceToHost);
-    s->perfect_feedback = false;
-  })
-}
-
-// include/mpc_qp_contacts.h: a loop call on a QP handle whose contact source is not the schedule.  The checks (throws), then the arguments of
-// k_pipe_contact_states: the caller's contact_states go to the schedule buffer and q.cs becomes an output of that kernel, once per step.
-static PipeContactsArgs pipe_contacts_args(const char* who, const QpContactSource& qc, const mpc_solver* sim, int nk, int B, int32_t* cs) {
-  if (nk != 2) throw std::runtime_error(std::string(who) + ": a contact source other than the schedule needs two contacts (nk = 2: the soles of mpc_sim_contacts)");
-  if (!sim_contacts_rows(sim))
-    throw std::runtime_error(std::string(who) + ": a contact source other than the schedule needs the contact rule on the simulator handle (mpc_sim_contacts first)");
-  PipeContactsArgs c;
-  c.rows = sim_contacts_rows(sim); c.width = MPC_SIM_CONTACTS_WIDTH; c.B = B; c.source = qc.source;
-  c.sched = qc.sched; c.cs = cs; c.used = qc.used; c.counts = qc.counts;
-  return c;
-}
-static void pipe_contacts_enqueue(const PipeContactsArgs& c, hipStream_t st) {
-  hipLaunchKernelGGL(k_pipe_contact_states, dim3((unsigned)((2 * c.B + 63) / 64)), dim3(64), 0, st, c);
-}
-
-// include/mpc_qp_abi.h: the low-level loop of the kinodynamic pipeline with nothing but the kernels between its stages.  Everything is enqueued on
-// the QP handle's stream (the plan and the simulator are idle: their streams are drained first); one synchronisation at the end.
-int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solver* plan, mpc_solver* sim, int32_t nk, const int32_t* frames,
-                           const double* weights, const double* cone, double kd, const int32_t* contact_states, const double* tau_max,
-                           const double* x, int32_t steps, double dt, double* x_prev, double* x_out, double* tau, double* forces, mpc_qp_info* info) {
-  if (!qp) return -2;
-  try {
-    if (!S || !plan || !sim || !contact_states || !tau_max) throw std::runtime_error("qp_low_level_steps: null argument");
-    if (steps <= 0 || !(dt > 0.0)) throw std::runtime_error("qp_low_level_steps: steps and dt must be positive");
-    const QpContactSource qc = qp_contact_source(qp);
-    const bool from_plant = qc.source != MPC_QP_CONTACTS_SCHEDULE;
-    if (from_plant) (void)pipe_contacts_args("qp_low_level_steps", qc, sim, nk, 0, nullptr);  // (the checks, before anything is allocated for another nk)
-    qp_id_prepare(qp, nk, frames, weights, cone);
-    const QpIdBuffers q = qp_id_buffers(qp);
-    const Layout& P = plan->L;
-    const Layout& Z = sim->L;
-    const int nx = q.nq + q.nv, nu = q.nv - 6, nf = 6 * nk;
-    if (plan->dims.device != q.device || sim->dims.device != q.device) throw std::runtime_error("qp_low_level_steps: the three handles must live on one device");
-    if (P.B != q.B || Z.B != q.B) throw std::runtime_error("qp_low_level_steps: the three handles must have the same batch size");
-    if (P.space != MPC_SPACE_MULTIBODY || P.nx != nx || P.n != 2 * q.nv || P.m != nf + nu || P.n > PIPE_MAX_N)
-      throw std::runtime_error("qp_low_level_steps: the plan must be a multibody problem with nx = nq + nv and controls (6 nk contact wrench components, nv - 6 joint accelerations)");
-    if (Z.space != MPC_SPACE_MULTIBODY || Z.nx != nx || Z.m != nu ||
-        sim->h_desc[(size_t)slot_of(sim, 0) * Z.max_stage_ints] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER)
-      throw std::runtime_error("qp_low_level_steps: the simulator handle must hold whole-body contact dynamics with nu = nv - 6 (the handle of mpc_simulate_torque)");
-    if (plan->async_pending > 0) throw std::runtime_error("qp_low_level_steps: the plan has ticks in flight (mpc_wait first)");
-    sim_record_reserve(sim, steps);
-    sim_contacts_check(sim, "qp_low_level_steps");
-    HIP_OK(hipStreamSynchronize(plan->stream));
-    HIP_OK(hipStreamSynchronize(sim->stream));
-    if (!sim->d_simu) { sim->d_simu = sim->alloc<double>((size_t)Z.B * Z.m); sim->d_simwr = sim->alloc<double>((size_t)Z.B * 12); HIP_OK(hipStreamSynchronize(sim->stream)); }
-    const size_t B = q.B;
-    double* scr = qp_scratch(qp, B * nx + B * nf + nu);  // x before the last period | forces + df | tau_max
-    double *d_xprev = scr, *d_fnew = scr + B * nx, *d_taumax = d_fnew + B * nf;
-    hipStream_t st = q.stream;
-    if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
-    sim_metrics_begin(sim, st);
-    HIP_OK(hipMemcpyAsync(from_plant ? qc.sched : q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_taumax, tau_max, nu * sizeof(double), hipMemcpyHostToDevice, st));
-    PipeContactsArgs pc = {};
-    if (from_plant) pc = pipe_contacts_args("qp_low_level_steps", qc, sim, nk, (int)B, q.cs);
-    PipeArgs p;
-    p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains; p.knots = plan->d_knots;
-    p.N = P.N; p.nx = nx; p.nq = q.nq; p.nv = q.nv; p.n = P.n; p.m = P.m; p.gain_stride = P.gain_stride; p.oK = P.oK; p.knot_stride = P.knot_stride; p.oXD = P.oXD;
-    p.slot0 = plan->khead % P.N;
-    p.x = sim->d_x0; p.xrob = q.xrob; p.acc = q.acc; p.f = q.f; p.sol = q.sol; p.nk = nk; p.qn = q.n; p.tau_max = d_taumax; p.sim_u = sim->d_simu; p.f_new = d_fnew;
-    p.used = from_plant ? qc.used : nullptr;
-    const SolverArgs za = sim->args();
-    for (int step = 0; step < steps; ++step) {
-      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(d_xprev, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(k_pipe_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
-      if (from_plant) pipe_contacts_enqueue(pc, st);  // (the rows as the rule left them after the step before: the state this QP is solved at)
-      qp_id_enqueue(qp, S, kd);
-      qp_launch_solve(qp, S);
-      hipLaunchKernelGGL(k_pipe_torque, dim3((unsigned)B), dim3(64), 0, st, p);
-      sim_actuators_enqueue(sim, st, dt);
-      launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
-                            sim_wrench_out(sim, false), sim_push_width(sim), sim_contacts_rows(sim));
-      HIP_OK(hipGetLastError());
-      sim_record_enqueue(sim, st);
-      sim_metrics_enqueue(sim, st, dt);
-      sim_contacts_enqueue(sim, st);
-    }
-    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (forces) HIP_OK(hipMemcpyAsync(forces, d_fnew, B * nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (info) HIP_OK(hipMemcpyAsync(info, q.info, B * sizeof(mpc_qp_info), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    sim->perfect_feedback = false;
-    return 0;
-  } catch (const std::exception& e) {
-    qp_set_error(qp, e.what());
-    return -1;
-  }
-}
-
-// include/mpc_qp_abi.h: the low-level loop of the centroidal pipeline (centroidal_talos.py:408-447) with nothing but the kernels between its stages:
-// the task errors once, then per step the centroidal state of the measurement and the feedback forces, the IK + ID QP and the simulator step.  Everything
-// is enqueued on the QP handle's stream (the plan and the simulator are idle: their streams are drained first); one synchronisation at the end.
-int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solver* plan, mpc_solver* sim, int32_t nk, const int32_t* frames,
-                                int32_t base_frame, int32_t torso_frame, const double* weights, const double* gains, const double* cone, const double* l_box,
-                                const double* u_box, const double* x_posture, const double* foot_refs, double ref_dt, const int32_t* contact_states,
-                                const double* x, const double* x_ik, int32_t steps, double dt, double* x_prev, double* c_prev, double* x_out, double* tau,
-                                double* forces, mpc_qp_info* info, double* ik_out) {
-  if (!qp) return -2;
-  try {
-    if (!S || !plan || !sim || !frames || !weights || !gains || !cone || !l_box || !u_box || !x_posture || !contact_states)
-      throw std::runtime_error("qp_ikid_low_level_steps: null argument");
-    // foot_refs = NULL: the samples the plan's own generator keeps on the device (mpc_walk_poses_update) ; without one that is the null argument it was
-    if (!foot_refs && !plan->poses_on) throw std::runtime_error("qp_ikid_low_level_steps: null argument");
-    if (steps <= 0 || !(dt > 0.0) || !(ref_dt > 0.0)) throw std::runtime_error("qp_ikid_low_level_steps: steps, dt and ref_dt must be positive");
-    if (nk != 2) throw std::runtime_error("qp_ikid_low_level_steps: two contacts (nk = 2) expected");
-    const QpContactSource qc = qp_contact_source(qp);
-    const bool from_plant = qc.source != MPC_QP_CONTACTS_SCHEDULE;
-    if (from_plant) (void)pipe_contacts_args("qp_ikid_low_level_steps", qc, sim, nk, 0, nullptr);
-    qp_ikid_prepare(qp, nk, frames, base_frame, torso_frame, weights, gains, cone, l_box, u_box);
-    const QpIdBuffers q = qp_id_buffers(qp);
-    const Layout& P = plan->L;
-    const Layout& Z = sim->L;
-    const int nx = q.nq + q.nv, nu = q.nv - 6, nf = 6 * nk, nik = CG_IK_DOUBLES(q.nv);
-    if (plan->dims.device != q.device || sim->dims.device != q.device) throw std::runtime_error("qp_ikid_low_level_steps: the three handles must live on one device");
-    if (P.B != q.B || Z.B != q.B) throw std::runtime_error("qp_ikid_low_level_steps: the three handles must have the same batch size");
-    if (P.space != MPC_SPACE_VECTOR || P.nx != CG_NC || P.n != CG_NC || P.m != nf)
-      throw std::runtime_error("qp_ikid_low_level_steps: the plan must be a centroidal problem (vector space, nx = 9) with controls of 6 nk contact wrench components");
-    if (Z.space != MPC_SPACE_MULTIBODY || Z.nx != nx || Z.m != nu ||
-        sim->h_desc[(size_t)slot_of(sim, 0) * Z.max_stage_ints] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER)
-      throw std::runtime_error("qp_ikid_low_level_steps: the simulator handle must hold whole-body contact dynamics with nu = nv - 6 (the handle of mpc_simulate_torque)");
-    if (q.nj > CG_MAX_NJ) throw std::runtime_error("qp_ikid_low_level_steps: more moving joints than the glue kernels hold (64)");
-    if (plan->async_pending > 0) throw std::runtime_error("qp_ikid_low_level_steps: the plan has ticks in flight (mpc_wait first)");
-    sim_record_reserve(sim, steps);
-    sim_contacts_check(sim, "qp_ikid_low_level_steps");
-    HIP_OK(hipStreamSynchronize(plan->stream));
-    HIP_OK(hipStreamSynchronize(sim->stream));
-    if (!sim->d_simu) { sim->d_simu = sim->alloc<double>((size_t)Z.B * Z.m); sim->d_simwr = sim->alloc<double>((size_t)Z.B * 12); HIP_OK(hipStreamSynchronize(sim->stream)); }
-    const size_t B = q.B;
-    bool* kept = nullptr;
-    // x before the last step (kept for the next call) | its new_x | forces + df | x_posture | foot references
-    double* scr = qp_ikid_scratch(qp, B * nx + B * CG_NC + B * nf + nx + B * 48, &kept);
-    double *d_xprev = scr, *d_cprev = d_xprev + B * nx, *d_fnew = d_cprev + B * CG_NC, *d_xpost = d_fnew + B * nf, *d_refs = d_xpost + nx;
-    if (!x_ik && !*kept) throw std::runtime_error("qp_ikid_low_level_steps: x_ik is NULL and no earlier call kept a measurement");
-    hipStream_t st = q.stream;
-    if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
-    sim_metrics_begin(sim, st);
-    if (x_ik) HIP_OK(hipMemcpyAsync(d_xprev, x_ik, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(from_plant ? qc.sched : q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    PipeContactsArgs pc = {};
-    if (from_plant) pc = pipe_contacts_args("qp_ikid_low_level_steps", qc, sim, nk, (int)B, q.cs);
-    HIP_OK(hipMemcpyAsync(d_xpost, x_posture, nx * sizeof(double), hipMemcpyHostToDevice, st));
-    if (foot_refs) HIP_OK(hipMemcpyAsync(d_refs, foot_refs, B * 48 * sizeof(double), hipMemcpyHostToDevice, st));
-    else HIP_OK(hipMemcpyAsync(d_refs, plan->d_poses_samples, B * 48 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    IkidGlueArgs g = {};
-    g.mi = q.mi; g.md = q.md; g.nq = q.nq; g.nv = q.nv;
-    g.xs = plan->d_xs; g.us = plan->d_us; g.gains = plan->d_gains; g.knots = plan->d_knots;
-    g.N = P.N; g.m = P.m; g.gain_stride = P.gain_stride; g.oK = P.oK; g.knot_stride = P.knot_stride; g.oXD = P.oXD;
-    g.slot0 = plan->khead % P.N;
-    g.x_ik = d_xprev; g.x_post = d_xpost; g.refs = d_refs; g.ref_dt = ref_dt;
-    g.fr[0] = frames[0]; g.fr[1] = frames[1]; g.fr[2] = base_frame; g.fr[3] = torso_frame;
-    g.ik = q.ik;
-    g.x = sim->d_x0; g.xrob = q.xrob; g.f = q.f; g.c_prev = d_cprev;
-    g.sol = q.sol; g.nk = nk; g.qn = q.n; g.sim_u = sim->d_simu; g.f_new = d_fnew;
-    g.used = from_plant ? qc.used : nullptr;
-    hipLaunchKernelGGL(k_ikid_task_errors, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
-    HIP_OK(hipGetLastError());
-    if (ik_out) HIP_OK(hipMemcpyAsync(ik_out, q.ik, B * nik * sizeof(double), hipMemcpyDeviceToHost, st));
-    const SolverArgs za = sim->args();
-    for (int step = 0; step < steps; ++step) {
-      g.last = (step == steps - 1);
-      if (g.last) HIP_OK(hipMemcpyAsync(d_xprev, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(k_pipe_centroidal_feedback, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
-      if (from_plant) pipe_contacts_enqueue(pc, st);  // (the rows as the rule left them after the step before: the state this QP is solved at)
-      qp_ikid_enqueue(qp, S);
-      qp_launch_solve(qp, S);
-      hipLaunchKernelGGL(k_pipe_ikid_torque, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
-      sim_actuators_enqueue(sim, st, dt);
-      launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
-                            sim_wrench_out(sim, false), sim_push_width(sim), sim_contacts_rows(sim));
-      HIP_OK(hipGetLastError());
-      sim_record_enqueue(sim, st);
-      sim_metrics_enqueue(sim, st, dt);
-      sim_contacts_enqueue(sim, st);
-    }
-    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (c_prev) HIP_OK(hipMemcpyAsync(c_prev, d_cprev, B * CG_NC * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (forces) HIP_OK(hipMemcpyAsync(forces, d_fnew, B * nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (info) HIP_OK(hipMemcpyAsync(info, q.info, B * sizeof(mpc_qp_info), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    *kept = true;
-    sim->perfect_feedback = false;
-    return 0;
-  } catch (const std::exception& e) {
-    qp_set_error(qp, e.what());
-    return -1;
-  }
-}
-
-// include/mpc_feedback_pipeline.h: the low-level loop of the full-dynamics pipeline (fulldynamic_talos.py:512-530) with one kernel between the plan and
-// the simulator step.  Everything is enqueued on the simulator handle's stream (the plan's is drained first); one synchronisation at the end.  Errors
-// are reported on the plan's handle.
-int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double* x, int32_t steps, double dt, double* x_prev, double* x_out, double* tau,
-                                 double* wrenches) {
-  MPC_TRY(plan, {
-    if (!plan || !sim) throw std::runtime_error("feedback_low_level_steps: null handle");
-    if (steps <= 0 || !(dt > 0.0)) throw std::runtime_error("feedback_low_level_steps: steps and dt must be positive");
-    if (plan->dims.device != sim->dims.device) throw std::runtime_error("feedback_low_level_steps: the two handles must live on one device");
-    const Layout& P = plan->L;
-    const Layout& Z = sim->L;
-    if (P.B != Z.B) throw std::runtime_error("feedback_low_level_steps: the two handles must have the same batch size");
-    sim_check(sim, "feedback_low_level_steps");
-    if (sim->h_desc[(size_t)slot_of(sim, 0) * Z.max_stage_ints] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER)
-      throw std::runtime_error("feedback_low_level_steps: the simulator handle must hold whole-body contact dynamics (stage 0 of the handle of mpc_simulate_torque)");
-    if (P.space != MPC_SPACE_MULTIBODY || P.nx != Z.nx || P.n != Z.n || P.m != Z.m || P.n > PIPE_MAX_N)
-      throw std::runtime_error("feedback_low_level_steps: the plan must be a multibody problem with the simulator's nx and joint-torque controls (m = nu = nv - 6)");
-    if (plan->async_pending > 0) throw std::runtime_error("feedback_low_level_steps: the plan has ticks in flight (mpc_wait first)");
-    sim_record_reserve(sim, steps);
-    sim_contacts_check(sim, "feedback_low_level_steps");
-    HIP_OK(hipStreamSynchronize(plan->stream));
-    const size_t B = Z.B;
-    const int nx = Z.nx, nu = Z.m;
-    if (!sim->d_simu) { sim->d_simu = sim->alloc<double>(B * nu); sim->d_simwr = sim->alloc<double>(B * 12); }
-    if (x_prev && !sim->d_xlast) sim->d_xlast = sim->alloc<double>(B * nx);
-    hipStream_t st = sim->stream;
-    if (x) HIP_OK(hipMemcpyAsync(sim->d_x0, x, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
-    sim_metrics_begin(sim, st);
-    FdPipeArgs p;
-    p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains;
-    p.N = P.N; p.nx = nx; p.nv = Z.n / 2; p.nq = nx - Z.n / 2; p.n = P.n; p.m = nu; p.gain_stride = P.gain_stride; p.oK = P.oK;
-    p.x = sim->d_x0; p.sim_u = sim->d_simu;
-    const SolverArgs za = sim->args();
-    for (int step = 0; step < steps; ++step) {
-      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(sim->d_xlast, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(k_pipe_state_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
-      sim_actuators_enqueue(sim, st, dt);
-      launch_eval_multibody(st, za, sim->LT, sim->d_tknots, sim->d_mbwork, sim->mb_work_stride, true, 0, 1, 1, dt, false, sim_push(sim), true, sim->d_simu,
-                            sim_wrench_out(sim, wrenches != nullptr), sim_push_width(sim), sim_contacts_rows(sim));
-      HIP_OK(hipGetLastError());
-      sim_record_enqueue(sim, st);
-      sim_metrics_enqueue(sim, st, dt);
-      sim_contacts_enqueue(sim, st);
-    }
-    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, sim->d_xlast, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (wrenches) HIP_OK(hipMemcpyAsync(wrenches, sim->d_simwr, B * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    sim->perfect_feedback = false;
-  })
 }
 
 int mpc_get_x0(mpc_solver* s, double* x0) {
@@ -2509,3 +1761,5 @@ int mpc_debug_get(mpc_solver* s, const char* name, int32_t b, int32_t k, double*
 
 #include "walk_poses.h"
 #include "walk_commands.h"
+#include "sim_host.h"
+#include "pipeline_loops.h"

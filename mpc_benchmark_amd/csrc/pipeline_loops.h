@@ -1,0 +1,221 @@
+// pipeline_loops.h — the device loops of the three control pipelines: per period the controller's kernels, then one step of the plant (sim_host.h
+// sim_step_enqueue), with nothing but kernels in between.  mpc_qp_low_level_steps (kinodynamic, include/mpc_qp_abi.h), mpc_qp_ikid_low_level_steps
+// (centroidal, the same header) and mpc_feedback_low_level_steps (full dynamics, include/mpc_feedback_pipeline.h).  Included at the end of mpc_hip.hip,
+// after sim_host.h.
+#pragma once
+
+// include/mpc_qp_contacts.h: a loop call on a QP handle whose contact source is not the schedule.  The checks (throws), then the arguments of
+// k_pipe_contact_states: the caller's contact_states go to the schedule buffer and q.cs becomes an output of that kernel, once per step.
+static PipeContactsArgs pipe_contacts_args(const char* who, const QpContactSource& qc, const mpc_solver* sim, int nk, int B, int32_t* cs) {
+  if (nk != 2) throw std::runtime_error(std::string(who) + ": a contact source other than the schedule needs two contacts (nk = 2: the soles of mpc_sim_contacts)");
+  if (!sim->plant.d_con)
+    throw std::runtime_error(std::string(who) + ": a contact source other than the schedule needs the contact rule on the simulator handle (mpc_sim_contacts first)");
+  PipeContactsArgs c;
+  c.rows = sim->plant.d_con; c.width = MPC_SIM_CONTACTS_WIDTH; c.B = B; c.source = qc.source;
+  c.sched = qc.sched; c.cs = cs; c.used = qc.used; c.counts = qc.counts;
+  return c;
+}
+// (before the QP of a step: the rows as the contact rule left them after the step before are the state this QP is solved at)
+static void pipe_contacts_enqueue(const PipeContactsArgs& c, hipStream_t st) {
+  hipLaunchKernelGGL(k_pipe_contact_states, dim3((unsigned)((2 * c.B + 63) / 64)), dim3(64), 0, st, c);
+}
+
+extern "C" {
+
+// include/mpc_qp_abi.h: the low-level loop of the kinodynamic pipeline with nothing but the kernels between its stages.  Everything is enqueued on
+// the QP handle's stream (the plan and the simulator are idle: their streams are drained first); one synchronisation at the end.
+int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solver* plan, mpc_solver* sim, int32_t nk, const int32_t* frames,
+                           const double* weights, const double* cone, double kd, const int32_t* contact_states, const double* tau_max,
+                           const double* x, int32_t steps, double dt, double* x_prev, double* x_out, double* tau, double* forces, mpc_qp_info* info) {
+  if (!qp) return -2;
+  try {
+    if (!S || !plan || !sim || !contact_states || !tau_max) throw std::runtime_error("qp_low_level_steps: null argument");
+    if (steps <= 0 || !(dt > 0.0)) throw std::runtime_error("qp_low_level_steps: steps and dt must be positive");
+    const QpContactSource qc = qp_contact_source(qp);
+    const bool from_plant = qc.source != MPC_QP_CONTACTS_SCHEDULE;
+    if (from_plant) (void)pipe_contacts_args("qp_low_level_steps", qc, sim, nk, 0, nullptr);  // (the checks, before anything is allocated for another nk)
+    qp_id_prepare(qp, nk, frames, weights, cone);
+    const QpIdBuffers q = qp_id_buffers(qp);
+    const Layout& P = plan->L;
+    const Layout& Z = sim->L;
+    const int nx = q.nq + q.nv, nu = q.nv - 6, nf = 6 * nk;
+    if (plan->dims.device != q.device || sim->dims.device != q.device) throw std::runtime_error("qp_low_level_steps: the three handles must live on one device");
+    if (P.B != q.B || Z.B != q.B) throw std::runtime_error("qp_low_level_steps: the three handles must have the same batch size");
+    if (P.space != MPC_SPACE_MULTIBODY || P.nx != nx || P.n != 2 * q.nv || P.m != nf + nu || P.n > PIPE_MAX_N)
+      throw std::runtime_error("qp_low_level_steps: the plan must be a multibody problem with nx = nq + nv and controls (6 nk contact wrench components, nv - 6 joint accelerations)");
+    if (Z.nx != nx || Z.m != nu) throw std::runtime_error("qp_low_level_steps: the simulator handle must have the QP's model (nx = nq + nv, nu = nv - 6)");
+    if (plan->async_pending > 0) throw std::runtime_error("qp_low_level_steps: the plan has ticks in flight (mpc_wait first)");
+    sim_steps_check(sim, "qp_low_level_steps", SIM_STAGE0, steps);
+    HIP_OK(hipStreamSynchronize(plan->stream));
+    HIP_OK(hipStreamSynchronize(sim->stream));
+    const size_t B = q.B;
+    double* scr = qp_scratch(qp, B * nx + B * nf + nu);  // x before the last period | forces + df | tau_max
+    double *d_xprev = scr, *d_fnew = scr + B * nx, *d_taumax = d_fnew + B * nf;
+    hipStream_t st = q.stream;
+    sim_steps_begin(sim, st, x);
+    HIP_OK(hipMemcpyAsync(from_plant ? qc.sched : q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_taumax, tau_max, nu * sizeof(double), hipMemcpyHostToDevice, st));
+    PipeContactsArgs pc = {};
+    if (from_plant) pc = pipe_contacts_args("qp_low_level_steps", qc, sim, nk, (int)B, q.cs);
+    PipeArgs p;
+    p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains; p.knots = plan->d_knots;
+    p.N = P.N; p.nx = nx; p.nq = q.nq; p.nv = q.nv; p.n = P.n; p.m = P.m; p.gain_stride = P.gain_stride; p.oK = P.oK; p.knot_stride = P.knot_stride; p.oXD = P.oXD;
+    p.slot0 = plan->khead % P.N;
+    p.x = sim->d_x0; p.xrob = q.xrob; p.acc = q.acc; p.f = q.f; p.sol = q.sol; p.nk = nk; p.qn = q.n; p.tau_max = d_taumax; p.sim_u = sim->plant.d_simu; p.f_new = d_fnew;
+    p.used = from_plant ? qc.used : nullptr;
+    const SolverArgs za = sim->args();
+    for (int step = 0; step < steps; ++step) {
+      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(d_xprev, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(k_pipe_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
+      if (from_plant) pipe_contacts_enqueue(pc, st);
+      qp_id_enqueue(qp, S, kd);
+      qp_launch_solve(qp, S);
+      hipLaunchKernelGGL(k_pipe_torque, dim3((unsigned)B), dim3(64), 0, st, p);
+      sim_step_enqueue(sim, st, za, 1, dt, false);
+    }
+    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->plant.d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (forces) HIP_OK(hipMemcpyAsync(forces, d_fnew, B * nf * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (info) HIP_OK(hipMemcpyAsync(info, q.info, B * sizeof(mpc_qp_info), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    sim->perfect_feedback = false;
+    return 0;
+  } catch (const std::exception& e) {
+    qp_set_error(qp, e.what());
+    return -1;
+  }
+}
+
+// include/mpc_qp_abi.h: the low-level loop of the centroidal pipeline (centroidal_talos.py:408-447) with nothing but the kernels between its stages:
+// the task errors once, then per step the centroidal state of the measurement and the feedback forces, the IK + ID QP and the simulator step.  Everything
+// is enqueued on the QP handle's stream (the plan and the simulator are idle: their streams are drained first); one synchronisation at the end.
+int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solver* plan, mpc_solver* sim, int32_t nk, const int32_t* frames,
+                                int32_t base_frame, int32_t torso_frame, const double* weights, const double* gains, const double* cone, const double* l_box,
+                                const double* u_box, const double* x_posture, const double* foot_refs, double ref_dt, const int32_t* contact_states,
+                                const double* x, const double* x_ik, int32_t steps, double dt, double* x_prev, double* c_prev, double* x_out, double* tau,
+                                double* forces, mpc_qp_info* info, double* ik_out) {
+  if (!qp) return -2;
+  try {
+    if (!S || !plan || !sim || !frames || !weights || !gains || !cone || !l_box || !u_box || !x_posture || !contact_states)
+      throw std::runtime_error("qp_ikid_low_level_steps: null argument");
+    // foot_refs = NULL: the samples the plan's own generator keeps on the device (mpc_walk_poses_update) ; without one that is the null argument it was
+    if (!foot_refs && !plan->poses_on) throw std::runtime_error("qp_ikid_low_level_steps: null argument");
+    if (steps <= 0 || !(dt > 0.0) || !(ref_dt > 0.0)) throw std::runtime_error("qp_ikid_low_level_steps: steps, dt and ref_dt must be positive");
+    if (nk != 2) throw std::runtime_error("qp_ikid_low_level_steps: two contacts (nk = 2) expected");
+    const QpContactSource qc = qp_contact_source(qp);
+    const bool from_plant = qc.source != MPC_QP_CONTACTS_SCHEDULE;
+    if (from_plant) (void)pipe_contacts_args("qp_ikid_low_level_steps", qc, sim, nk, 0, nullptr);
+    qp_ikid_prepare(qp, nk, frames, base_frame, torso_frame, weights, gains, cone, l_box, u_box);
+    const QpIdBuffers q = qp_id_buffers(qp);
+    const Layout& P = plan->L;
+    const Layout& Z = sim->L;
+    const int nx = q.nq + q.nv, nu = q.nv - 6, nf = 6 * nk, nik = CG_IK_DOUBLES(q.nv);
+    if (plan->dims.device != q.device || sim->dims.device != q.device) throw std::runtime_error("qp_ikid_low_level_steps: the three handles must live on one device");
+    if (P.B != q.B || Z.B != q.B) throw std::runtime_error("qp_ikid_low_level_steps: the three handles must have the same batch size");
+    if (P.space != MPC_SPACE_VECTOR || P.nx != CG_NC || P.n != CG_NC || P.m != nf)
+      throw std::runtime_error("qp_ikid_low_level_steps: the plan must be a centroidal problem (vector space, nx = 9) with controls of 6 nk contact wrench components");
+    if (Z.nx != nx || Z.m != nu) throw std::runtime_error("qp_ikid_low_level_steps: the simulator handle must have the QP's model (nx = nq + nv, nu = nv - 6)");
+    if (q.nj > CG_MAX_NJ) throw std::runtime_error("qp_ikid_low_level_steps: more moving joints than the glue kernels hold (64)");
+    if (plan->async_pending > 0) throw std::runtime_error("qp_ikid_low_level_steps: the plan has ticks in flight (mpc_wait first)");
+    sim_steps_check(sim, "qp_ikid_low_level_steps", SIM_STAGE0, steps);
+    HIP_OK(hipStreamSynchronize(plan->stream));
+    HIP_OK(hipStreamSynchronize(sim->stream));
+    const size_t B = q.B;
+    bool* kept = nullptr;
+    // x before the last step (kept for the next call) | its new_x | forces + df | x_posture | foot references
+    double* scr = qp_ikid_scratch(qp, B * nx + B * CG_NC + B * nf + nx + B * 48, &kept);
+    double *d_xprev = scr, *d_cprev = d_xprev + B * nx, *d_fnew = d_cprev + B * CG_NC, *d_xpost = d_fnew + B * nf, *d_refs = d_xpost + nx;
+    if (!x_ik && !*kept) throw std::runtime_error("qp_ikid_low_level_steps: x_ik is NULL and no earlier call kept a measurement");
+    hipStream_t st = q.stream;
+    sim_steps_begin(sim, st, x);
+    if (x_ik) HIP_OK(hipMemcpyAsync(d_xprev, x_ik, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(from_plant ? qc.sched : q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    PipeContactsArgs pc = {};
+    if (from_plant) pc = pipe_contacts_args("qp_ikid_low_level_steps", qc, sim, nk, (int)B, q.cs);
+    HIP_OK(hipMemcpyAsync(d_xpost, x_posture, nx * sizeof(double), hipMemcpyHostToDevice, st));
+    if (foot_refs) HIP_OK(hipMemcpyAsync(d_refs, foot_refs, B * 48 * sizeof(double), hipMemcpyHostToDevice, st));
+    else HIP_OK(hipMemcpyAsync(d_refs, plan->d_poses_samples, B * 48 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    IkidGlueArgs g = {};
+    g.mi = q.mi; g.md = q.md; g.nq = q.nq; g.nv = q.nv;
+    g.xs = plan->d_xs; g.us = plan->d_us; g.gains = plan->d_gains; g.knots = plan->d_knots;
+    g.N = P.N; g.m = P.m; g.gain_stride = P.gain_stride; g.oK = P.oK; g.knot_stride = P.knot_stride; g.oXD = P.oXD;
+    g.slot0 = plan->khead % P.N;
+    g.x_ik = d_xprev; g.x_post = d_xpost; g.refs = d_refs; g.ref_dt = ref_dt;
+    g.fr[0] = frames[0]; g.fr[1] = frames[1]; g.fr[2] = base_frame; g.fr[3] = torso_frame;
+    g.ik = q.ik;
+    g.x = sim->d_x0; g.xrob = q.xrob; g.f = q.f; g.c_prev = d_cprev;
+    g.sol = q.sol; g.nk = nk; g.qn = q.n; g.sim_u = sim->plant.d_simu; g.f_new = d_fnew;
+    g.used = from_plant ? qc.used : nullptr;
+    hipLaunchKernelGGL(k_ikid_task_errors, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+    HIP_OK(hipGetLastError());
+    if (ik_out) HIP_OK(hipMemcpyAsync(ik_out, q.ik, B * nik * sizeof(double), hipMemcpyDeviceToHost, st));
+    const SolverArgs za = sim->args();
+    for (int step = 0; step < steps; ++step) {
+      g.last = (step == steps - 1);
+      if (g.last) HIP_OK(hipMemcpyAsync(d_xprev, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(k_pipe_centroidal_feedback, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+      if (from_plant) pipe_contacts_enqueue(pc, st);
+      qp_ikid_enqueue(qp, S);
+      qp_launch_solve(qp, S);
+      hipLaunchKernelGGL(k_pipe_ikid_torque, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+      sim_step_enqueue(sim, st, za, 1, dt, false);
+    }
+    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (c_prev) HIP_OK(hipMemcpyAsync(c_prev, d_cprev, B * CG_NC * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->plant.d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (forces) HIP_OK(hipMemcpyAsync(forces, d_fnew, B * nf * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (info) HIP_OK(hipMemcpyAsync(info, q.info, B * sizeof(mpc_qp_info), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    *kept = true;
+    sim->perfect_feedback = false;
+    return 0;
+  } catch (const std::exception& e) {
+    qp_set_error(qp, e.what());
+    return -1;
+  }
+}
+
+// include/mpc_feedback_pipeline.h: the low-level loop of the full-dynamics pipeline (fulldynamic_talos.py:512-530) with one kernel between the plan and
+// the simulator step.  Everything is enqueued on the simulator handle's stream (the plan's is drained first); one synchronisation at the end.  Errors
+// are reported on the plan's handle.
+int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double* x, int32_t steps, double dt, double* x_prev, double* x_out, double* tau,
+                                 double* wrenches) {
+  MPC_TRY(plan, {
+    if (!plan || !sim) throw std::runtime_error("feedback_low_level_steps: null handle");
+    if (steps <= 0 || !(dt > 0.0)) throw std::runtime_error("feedback_low_level_steps: steps and dt must be positive");
+    if (plan->dims.device != sim->dims.device) throw std::runtime_error("feedback_low_level_steps: the two handles must live on one device");
+    const Layout& P = plan->L;
+    const Layout& Z = sim->L;
+    if (P.B != Z.B) throw std::runtime_error("feedback_low_level_steps: the two handles must have the same batch size");
+    if (P.space != MPC_SPACE_MULTIBODY || P.nx != Z.nx || P.n != Z.n || P.m != Z.m || P.n > PIPE_MAX_N)
+      throw std::runtime_error("feedback_low_level_steps: the plan must be a multibody problem with the simulator's nx and joint-torque controls (m = nu = nv - 6)");
+    if (plan->async_pending > 0) throw std::runtime_error("feedback_low_level_steps: the plan has ticks in flight (mpc_wait first)");
+    sim_steps_check(sim, "feedback_low_level_steps", SIM_NU | SIM_STAGE0, steps);
+    HIP_OK(hipStreamSynchronize(plan->stream));
+    const size_t B = Z.B;
+    const int nx = Z.nx, nu = Z.m;
+    if (x_prev && !sim->plant.d_xlast) sim->plant.d_xlast = sim->alloc<double>(B * nx);
+    hipStream_t st = sim->stream;
+    sim_steps_begin(sim, st, x);
+    FdPipeArgs p;
+    p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains;
+    p.N = P.N; p.nx = nx; p.nv = Z.n / 2; p.nq = nx - Z.n / 2; p.n = P.n; p.m = nu; p.gain_stride = P.gain_stride; p.oK = P.oK;
+    p.x = sim->d_x0; p.sim_u = sim->plant.d_simu;
+    const SolverArgs za = sim->args();
+    for (int step = 0; step < steps; ++step) {
+      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(sim->plant.d_xlast, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(k_pipe_state_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
+      sim_step_enqueue(sim, st, za, 1, dt, wrenches != nullptr);
+    }
+    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, sim->plant.d_xlast, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->plant.d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (wrenches) HIP_OK(hipMemcpyAsync(wrenches, sim->plant.d_simwr, B * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    sim->perfect_feedback = false;
+  })
+}
+
+}  // extern "C"

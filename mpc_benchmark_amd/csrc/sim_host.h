@@ -1,0 +1,506 @@
+// sim_host.h — host side of the torque-driven simulator (the plant): mpc_simulate_torque and the entry points of include/mpc_sim_ext.h (push, record),
+// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h and mpc_sim_actuators.h.  Its state is mpc_solver::plant (SimPlant); its kernels are in
+// sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h and sim_actuators.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
+// loops of the three pipelines in pipeline_loops.h — goes through sim_steps_check, sim_steps_begin and sim_step_enqueue: an extension of the simulator
+// is added there, once.  Included at the end of mpc_hip.hip (mpc_solver, MPC_TRY, copy_sync, slot_of).
+#pragma once
+
+// Which handles an entry point takes.  Every simulator handle is a whole-body handle; SIM_NU: with nu = nv - 6 (the handle of mpc_simulate_torque) ;
+// SIM_STAGE0: whose stage 0 holds contact dynamics (what a step integrates: the pipelines set stage 0 per contact state, so only the stepping calls ask)
+enum : int { SIM_NU = 1, SIM_STAGE0 = 2 };
+static void sim_check(const mpc_solver* s, const char* who, int need = SIM_NU) {
+  const Layout& L = s->L;
+  bool ok = L.space == MPC_SPACE_MULTIBODY;
+  if (need & SIM_NU) ok = ok && L.m == L.n / 2 - 6 && L.nx == L.n / 2 + (L.n / 2 + 1);
+  if (need & SIM_STAGE0) ok = ok && s->h_desc[(size_t)slot_of(s, 0) * L.max_stage_ints] == MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER;
+  if (!ok)
+    throw std::runtime_error(std::string(who) + ": the simulator handle must be a whole-body handle" + ((need & SIM_NU) ? " with nu = nv - 6" : "") +
+                             ((need & SIM_STAGE0) ? " and contact dynamics in stage 0" : "") + " (the handle of mpc_simulate_torque)");
+}
+// the kernels of the record, the metrics and the contact rule read the two sole contacts of the model and hold at most CG_MAX_NJ moving joints
+static void sim_model_check(const mpc_solver* s, const char* who) {
+  if (s->h_model_i.size() < 5 || s->h_model_i[4] < 2)
+    throw std::runtime_error(std::string(who) + ": the model of the simulator handle must hold the two sole contacts (contacts 0 and 1)");
+  if (s->L.nj > CG_MAX_NJ) throw std::runtime_error(std::string(who) + ": more moving joints than the simulator's kernels hold (" + std::to_string(CG_MAX_NJ) + ")");
+}
+// the torques and wrenches of a step.  alloc zero-fills on the handle's own stream: it is drained here, so that the buffers may be used from any stream at
+// once (the loops of the QP pipelines step the plant on the QP handle's)
+static void sim_ensure(mpc_solver* s) {
+  if (s->plant.d_simu) return;
+  s->plant.d_simu = s->alloc<double>((size_t)s->L.B * s->L.m);
+  s->plant.d_simwr = s->alloc<double>((size_t)s->L.B * 12);
+  HIP_OK(hipStreamSynchronize(s->stream));
+}
+// a buffer the plant owns (SimPlant::free_owned) is replaced by one of `count` doubles, 0: dropped; nothing in flight on the handle's stream reads the old one
+static void sim_realloc(mpc_solver* s, double*& buf, size_t count) {
+  HIP_OK(hipStreamSynchronize(s->stream));
+  if (buf) { HIP_OK(hipFree(buf)); buf = nullptr; }
+  if (count) { void* p = nullptr; HIP_OK(hipMalloc(&p, count * sizeof(double))); buf = (double*)p; }
+}
+// the *_width entry points: the width on a simulator handle, -1 otherwise
+template <class F> static int32_t sim_width(mpc_solver* s, const char* who, F&& width) {
+  if (!s) return -1;
+  try {
+    sim_check(s, who);
+    return (int32_t)width();
+  } catch (const std::exception& e) {
+    s->err = e.what();
+    return -1;
+  }
+}
+
+// the record of the step just enqueued on stream st (sim_record.h), when recording is on
+static void sim_record_enqueue(mpc_solver* s, hipStream_t st) {
+  SimPlant& p = s->plant;
+  if (p.rec_cap <= 0) return;
+  const Layout& L = s->L;
+  SimRecordArgs r;
+  r.mi = s->d_model_i; r.md = s->d_model_d; r.nv = L.n / 2; r.nq = L.nx - L.n / 2;
+  r.x = s->d_x0; r.tau = p.d_simu; r.wr = p.d_simwr; r.push = p.push_width ? p.d_push : nullptr; r.push_width = p.push_width;
+  r.out = p.d_rec + (size_t)p.rec_count * L.B * sim_record_width(L.nx, L.m);
+  hipLaunchKernelGGL(k_sim_record, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, r);
+  HIP_OK(hipGetLastError());
+  p.rec_count++;
+}
+// the terrain of the contact rule as the kernels take it (sim_terrain.h): boxes nullptr without one
+static SimTerrain sim_terrain_args(const mpc_solver* s) {
+  const SimPlant& p = s->plant;
+  SimTerrain t;
+  t.boxes = p.d_con ? p.d_ter : nullptr;
+  t.n = p.ter_cfg.n_boxes;
+  t.stride = p.ter_cfg.per_robot ? p.ter_cfg.n_boxes * MPC_SIM_TERRAIN_BOX_WIDTH : 0;
+  return t;
+}
+// the metrics of the step of length dt just enqueued on stream st (sim_metrics.h), when they are on
+static void sim_metrics_enqueue(mpc_solver* s, hipStream_t st, double dt) {
+  const SimPlant& p = s->plant;
+  if (!p.d_met) return;
+  const Layout& L = s->L;
+  SimMetricsArgs m;
+  m.mi = s->d_model_i; m.md = s->d_model_d; m.nv = L.n / 2; m.nq = L.nx - L.n / 2;
+  m.x = s->d_x0; m.tau = p.d_simu; m.wr = p.d_simwr; m.dt = dt; m.cfg = p.met_cfg;
+  m.acc = p.d_met; m.frozen = p.d_met + (size_t)L.B * MPC_SIM_METRICS_WIDTH; m.xs = m.frozen + L.B;
+  m.ter = sim_terrain_args(s); m.con = p.d_con; m.ground_z = p.con_cfg.ground_z;
+  hipLaunchKernelGGL(k_sim_metrics, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, m);
+  HIP_OK(hipGetLastError());
+}
+// the rows after a reset: nothing accumulated, no fall, nothing latched (the margin's minimum, the heights and the centres of mass NaN); not frozen
+static void sim_metrics_reset(mpc_solver* s) {
+  const Layout& L = s->L;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<double> h((size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1), 0.0);
+  for (int b = 0; b < L.B; ++b) {
+    double* r = h.data() + (size_t)b * MPC_SIM_METRICS_WIDTH;
+    r[6] = nan;
+    r[11] = -1.0;
+    for (int i = 12; i < MPC_SIM_METRICS_WIDTH; ++i) r[i] = nan;
+  }
+  copy_sync(s, s->plant.d_met, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+}
+// the contact rule after the step just enqueued on stream st (sim_contacts.h), when it is on
+static void sim_contacts_enqueue(mpc_solver* s, hipStream_t st) {
+  const SimPlant& p = s->plant;
+  if (!p.d_con) return;
+  const Layout& L = s->L;
+  SimContactsArgs c;
+  c.mi = s->d_model_i; c.md = s->d_model_d; c.nv = L.n / 2; c.nq = L.nx - L.n / 2;
+  c.x = s->d_x0; c.wr = p.d_simwr; c.cfg = p.con_cfg; c.rows = p.d_con; c.ter = sim_terrain_args(s);
+  hipLaunchKernelGGL(k_sim_contacts, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, c);
+  HIP_OK(hipGetLastError());
+}
+// the rows after a reset: both soles in contact at the model's ground-side placements (contacts 0 and 1), nothing counted
+static void sim_contacts_reset(mpc_solver* s) {
+  const Layout& L = s->L;
+  const int nj = s->h_model_i[0], nframes = s->h_model_i[3];
+  const size_t off = MPC_MODEL_HEADER_DOUBLES + (size_t)MPC_MODEL_JOINT_DOUBLES * nj + (size_t)MPC_MODEL_FRAME_DOUBLES * nframes;
+  double cm[2 * MPC_MODEL_CONTACT_DOUBLES];
+  copy_sync(s, cm, s->d_model_d + off, sizeof(cm), hipMemcpyDeviceToHost);
+  std::vector<double> h((size_t)L.B * MPC_SIM_CONTACTS_WIDTH, 0.0);
+  for (int b = 0; b < L.B; ++b) {
+    double* r = h.data() + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
+    for (int i = 0; i < 2; ++i) {
+      const double* c = cm + MPC_MODEL_CONTACT_DOUBLES * i;
+      r[i] = 1.0;
+      r[6 + i] = c[23];                                          // z_prev: the anchor's height
+      for (int e = 0; e < 12; ++e) r[8 + 12 * i + e] = c[12 + e];  // R2 (9), p2 (3)
+      r[36 + i] = r[38 + i] = -1.0;
+    }
+  }
+  copy_sync(s, s->plant.d_con, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+}
+
+static size_t sim_actuators_width(const Layout& L) { return (size_t)(MPC_SIM_ACTUATORS_RING + 2) * L.m + 2; }
+static double* sim_actuators_rows(const mpc_solver* s) { return s->plant.d_act + (size_t)s->L.B * MPC_SIM_ACTUATORS_PARAMS + 2 * (size_t)s->L.m; }
+// the actuator model of the step of length dt_step about to be enqueued on stream st (sim_actuators.h), when it is on
+static void sim_actuators_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
+  const SimPlant& p = s->plant;
+  if (!p.d_act) return;
+  const Layout& L = s->L;
+  SimActuatorsArgs a;
+  a.nv = L.n / 2; a.nq = L.nx - L.n / 2; a.nu = L.m;
+  a.x = s->d_x0; a.tau = p.d_simu;
+  a.params = p.d_act; a.limit = p.d_act + (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS; a.shape = a.limit + L.m;
+  a.rows = sim_actuators_rows(s); a.dt = dt_step;
+  hipLaunchKernelGGL(k_sim_actuators, dim3((unsigned)L.B), dim3(SIM_ACT_THREADS), 0, st, a);
+  HIP_OK(hipGetLastError());
+}
+
+// A call that steps the plant `steps` times, part one: everything that can fail, before anything is enqueued.  `need`: sim_check.
+static void sim_steps_check(mpc_solver* s, const char* who, int need, int steps) {
+  const SimPlant& p = s->plant;
+  sim_check(s, who, need);
+  if (p.rec_cap > 0 && p.rec_count + steps > p.rec_cap)  // (every step gets its record slot)
+    throw std::runtime_error("sim_record: the record ring is full (" + std::to_string(p.rec_count) + " of " + std::to_string(p.rec_cap) + " steps held, " +
+                             std::to_string(steps) + " more asked for): read it with mpc_sim_record_read or enlarge it with mpc_sim_record");
+  const int32_t* d = s->h_desc.data() + (size_t)slot_of(s, 0) * s->L.max_stage_ints;
+  if (p.d_con && (d[0] != MPC_DYN_MULTIBODY_CONSTRAINT_SEMIEULER || d[1] != 2 || !((d[2] == 0 && d[3] == 1) || (d[2] == 1 && d[3] == 0))))
+    throw std::runtime_error(std::string(who) + ": the contact rule is on (mpc_sim_contacts), so stage 0 of the simulator handle must be the double-support "
+                             "stage (contact dynamics of contacts 0 and 1): the rule picks each robot's contacts out of its two");
+  sim_ensure(s);
+}
+// ... part two, on the stream st the steps will be enqueued on: the state they start from (x NULL: the one the handle holds), which the metrics keep
+// for the joint power of the first step
+static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
+  const Layout& L = s->L;
+  if (x) HIP_OK(hipMemcpyAsync(s->d_x0, x, (size_t)L.B * L.nx * sizeof(double), hipMemcpyHostToDevice, st));
+  if (s->plant.d_met)
+    HIP_OK(hipMemcpyAsync(s->plant.d_met + (size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1), s->d_x0, (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+}
+// One step of the plant on stream st: `substeps` integration steps of length dt under the torque the caller put into plant.d_simu.  The order is the
+// contract of the extensions.  The actuator model first: it turns the command into the applied torque in place, over the whole step (substeps * dt),
+// and everything after it sees the applied torque.  Then the dynamics, with the armed push and the contacts the rule's rows held when the step BEFORE
+// ended (the rows the low-level QPs of pipeline_loops.h read for this step); wrenches are written when the caller, the record, the metrics or the rule
+// want them.  Then the record and the metrics of the step: the new state, the applied torque, its wrenches, the rows it was integrated with.  The
+// contact rule last: it rewrites the rows for the NEXT step from the new state and this step's wrenches.
+static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& args, int substeps, double dt, bool want_wrenches) {
+  const SimPlant& p = s->plant;
+  sim_actuators_enqueue(s, st, substeps * dt);
+  launch_eval_multibody(st, args, s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, p.push_width ? p.d_push : nullptr, true,
+                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con) ? p.d_simwr : nullptr, p.push_width ? p.push_width : 3, p.d_con);
+  HIP_OK(hipGetLastError());
+  sim_record_enqueue(s, st);
+  sim_metrics_enqueue(s, st, substeps * dt);
+  sim_contacts_enqueue(s, st);
+}
+
+extern "C" {
+
+// ---- include/mpc_sim_ext.h: push and record -----------------------------------------------------------------------------------------------
+int mpc_sim_set_push(mpc_solver* s, const double* f_ext, int32_t width) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_set_push");
+    if (!f_ext) { s->plant.push_width = 0; return 0; }
+    if (width != 3 && width != 6) throw std::runtime_error("sim_set_push: width must be 3 (force at the base origin) or 6 (force, world point)");
+    const Layout& L = s->L;
+    if (!s->plant.d_push) s->plant.d_push = s->alloc<double>((size_t)L.B * 6);
+    // (a small synchronous upload: the push changes a few times per run, not part of the steady loop)
+    copy_sync(s, s->plant.d_push, f_ext, (size_t)L.B * width * sizeof(double), hipMemcpyHostToDevice);
+    s->plant.push_width = width;
+  })
+}
+
+int mpc_sim_record(mpc_solver* s, int32_t cap) {
+  MPC_TRY(s, {
+    if (cap < 0) throw std::runtime_error("sim_record: cap must be >= 0 (0: recording off)");
+    sim_check(s, "sim_record");
+    const Layout& L = s->L;
+    if (cap > 0) sim_model_check(s, "sim_record");
+    s->plant.rec_cap = s->plant.rec_count = 0;
+    sim_realloc(s, s->plant.d_rec, (size_t)cap * L.B * sim_record_width(L.nx, L.m));
+    s->plant.rec_cap = cap;
+    if (cap > 0) sim_ensure(s);
+  })
+}
+
+int mpc_sim_record_read(mpc_solver* s, double* out, int32_t* count) {
+  MPC_TRY(s, {
+    if (!count) throw std::runtime_error("sim_record_read: count must not be null");
+    sim_check(s, "sim_record_read");
+    HIP_OK(hipStreamSynchronize(s->stream));
+    *count = s->plant.rec_count;
+    if (out) {
+      const Layout& L = s->L;
+      if (s->plant.rec_count > 0) copy_sync(s, out, s->plant.d_rec, (size_t)s->plant.rec_count * L.B * sim_record_width(L.nx, L.m) * sizeof(double), hipMemcpyDeviceToHost);
+      s->plant.rec_count = 0;
+    }
+  })
+}
+
+int32_t mpc_sim_record_width(mpc_solver* s) { return sim_width(s, "sim_record_width", [&] { return sim_record_width(s->L.nx, s->L.m); }); }
+
+// ---- include/mpc_sim_metrics.h ---------------------------------------------------------------------------------------------------------------
+int mpc_sim_metrics(mpc_solver* s, const mpc_sim_metrics_config* cfg) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_metrics");
+    const Layout& L = s->L;
+    if (cfg) {
+      sim_model_check(s, "sim_metrics");
+      for (double v : {cfg->min_force, cfg->half_length, cfg->half_width, cfg->fall_drop, cfg->sole_lift})
+        if (!std::isfinite(v) || v < 0.0) throw std::runtime_error("sim_metrics: every field of the configuration must be finite and >= 0");
+    }
+    sim_realloc(s, s->plant.d_met, cfg ? (size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1 + L.nx) : 0);
+    if (cfg) {
+      s->plant.met_cfg = *cfg;
+      sim_ensure(s);
+      sim_metrics_reset(s);
+    }
+  })
+}
+
+int mpc_sim_metrics_read(mpc_solver* s, double* out, int32_t reset) {
+  MPC_TRY(s, {
+    if (!out) throw std::runtime_error("sim_metrics_read: out must not be null");
+    sim_check(s, "sim_metrics_read");
+    if (!s->plant.d_met) throw std::runtime_error("sim_metrics_read: metrics are off on this handle (turn them on with mpc_sim_metrics)");
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, out, s->plant.d_met, (size_t)s->L.B * MPC_SIM_METRICS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
+    if (reset) sim_metrics_reset(s);
+  })
+}
+
+int32_t mpc_sim_metrics_width(mpc_solver* s) { return sim_width(s, "sim_metrics_width", [&] { return MPC_SIM_METRICS_WIDTH; }); }
+
+// ---- include/mpc_sim_contacts.h, include/mpc_sim_terrain.h: the contact rule and the terrain under it -----------------------------------------
+static void sim_terrain_drop(mpc_solver* s) {
+  sim_realloc(s, s->plant.d_ter, 0);
+  s->plant.ter_cfg = {};
+  s->plant.h_ter.clear();
+}
+
+int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_contacts");
+    const Layout& L = s->L;
+    if (cfg) {
+      sim_model_check(s, "sim_contacts");
+      if (!std::isfinite(cfg->ground_z) || !std::isfinite(cfg->ground_tol) || !std::isfinite(cfg->release_force))
+        throw std::runtime_error("sim_contacts: ground_z, ground_tol and release_force must be finite");
+      if (cfg->ground_tol < 0.0 || cfg->release_force < 0.0) throw std::runtime_error("sim_contacts: ground_tol and release_force must be >= 0");
+      if (cfg->release_steps < 1) throw std::runtime_error("sim_contacts: release_steps must be >= 1");
+    }
+    sim_realloc(s, s->plant.d_con, cfg ? (size_t)L.B * MPC_SIM_CONTACTS_WIDTH : 0);
+    if (!cfg) sim_terrain_drop(s);  // (the terrain goes with the rows; a reset keeps it)
+    if (cfg) {
+      s->plant.con_cfg = *cfg;
+      s->plant.con_cfg.reserved = 0;
+      sim_ensure(s);
+      sim_contacts_reset(s);
+    }
+  })
+}
+
+int mpc_sim_contacts_set(mpc_solver* s, const double* rows) {
+  MPC_TRY(s, {
+    if (!rows) throw std::runtime_error("sim_contacts_set: rows must not be null");
+    sim_check(s, "sim_contacts_set");
+    if (!s->plant.d_con) throw std::runtime_error("sim_contacts_set: the contact rule is off on this handle (turn it on with mpc_sim_contacts)");
+    const Layout& L = s->L;
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = rows + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
+      const std::string row = "sim_contacts_set: row " + std::to_string(b);
+      for (int e = 0; e < MPC_SIM_CONTACTS_WIDTH; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      for (int e = 0; e < 4; ++e)
+        if (r[e] != 0.0 && r[e] != 1.0) throw std::runtime_error(row + ": in_contact and lifted must be 0 or 1");
+      if (r[0] == 0.0 && r[1] == 0.0) throw std::runtime_error(row + " has no sole in contact (flight phases are not simulated)");
+      for (int e : {4, 5, 32, 33, 34, 35, 40})
+        if (r[e] < 0.0) throw std::runtime_error(row + ": pulling, the counts and steps must be >= 0");
+      for (int i = 0; i < 2; ++i) {
+        const double* R = r + 8 + 12 * i;
+        double dev = 0.0;
+        for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) {
+          double d = (a == c) ? -1.0 : 0.0;
+          for (int k = 0; k < 3; ++k) d += R[3 * k + a] * R[3 * k + c];
+          dev = std::fmax(dev, std::fabs(d));
+        }
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (dev > 1e-9 || det < 0.0) throw std::runtime_error(row + ": the anchor of sole " + std::to_string(i) + " is not a rotation");
+      }
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, s->plant.d_con, rows, (size_t)L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+int mpc_sim_contacts_read(mpc_solver* s, double* rows) {
+  MPC_TRY(s, {
+    if (!rows) throw std::runtime_error("sim_contacts_read: rows must not be null");
+    sim_check(s, "sim_contacts_read");
+    if (!s->plant.d_con) throw std::runtime_error("sim_contacts_read: the contact rule is off on this handle (turn it on with mpc_sim_contacts)");
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, rows, s->plant.d_con, (size_t)s->L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int mpc_sim_terrain(mpc_solver* s, const mpc_sim_terrain_config* cfg, const double* boxes) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_terrain");
+    if (!s->plant.d_con) throw std::runtime_error("sim_terrain: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    const Layout& L = s->L;
+    size_t count = 0;
+    if (cfg) {
+      if (cfg->n_boxes < 0 || cfg->n_boxes > MPC_SIM_TERRAIN_MAX_BOXES)
+        throw std::runtime_error("sim_terrain: n_boxes must be 0 .. " + std::to_string(MPC_SIM_TERRAIN_MAX_BOXES));
+      if (cfg->per_robot != 0 && cfg->per_robot != 1) throw std::runtime_error("sim_terrain: per_robot must be 0 or 1");
+      if (cfg->n_boxes > 0 && !boxes) throw std::runtime_error("sim_terrain: boxes must not be null with n_boxes > 0");
+      count = (size_t)(cfg->per_robot ? L.B : 1) * cfg->n_boxes;
+      for (size_t k = 0; k < count; ++k) {
+        const double* bx = boxes + k * MPC_SIM_TERRAIN_BOX_WIDTH;
+        for (int e = 0; e < MPC_SIM_TERRAIN_BOX_WIDTH; ++e)
+          if (!std::isfinite(bx[e])) throw std::runtime_error("sim_terrain: box " + std::to_string(k) + " holds a non-finite number");
+        if (bx[0] > bx[1] || bx[2] > bx[3]) throw std::runtime_error("sim_terrain: box " + std::to_string(k) + " has x_lo > x_hi or y_lo > y_hi");
+      }
+    }
+    sim_terrain_drop(s);
+    if (cfg) {
+      s->plant.ter_cfg = *cfg;
+      s->plant.h_ter.assign(boxes, boxes + count * MPC_SIM_TERRAIN_BOX_WIDTH);
+      if (count > 0) {  // (zero boxes: the plane, by the old path)
+        std::vector<double> h(s->plant.h_ter);
+        for (size_t k = 0; k < count; ++k) h[k * MPC_SIM_TERRAIN_BOX_WIDTH + 4] += 0.0;  // (a top of -0 counts as +0, as in the numpy definition)
+        sim_realloc(s, s->plant.d_ter, h.size());
+        copy_sync(s, s->plant.d_ter, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+      }
+    }
+  })
+}
+
+int mpc_sim_terrain_read(mpc_solver* s, mpc_sim_terrain_config* cfg, double* boxes) {
+  MPC_TRY(s, {
+    if (!cfg) throw std::runtime_error("sim_terrain_read: cfg must not be null");
+    sim_check(s, "sim_terrain_read");
+    if (!s->plant.d_con) throw std::runtime_error("sim_terrain_read: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    *cfg = s->plant.ter_cfg;
+    if (boxes) std::copy(s->plant.h_ter.begin(), s->plant.h_ter.end(), boxes);
+  })
+}
+
+int mpc_sim_terrain_height(mpc_solver* s, const double* xy, int32_t n, double* h) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_terrain_height");
+    if (!s->plant.d_con) throw std::runtime_error("sim_terrain_height: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    if (n < 0) throw std::runtime_error("sim_terrain_height: n must be >= 0");
+    if (n > 0 && (!xy || !h)) throw std::runtime_error("sim_terrain_height: xy and h must not be null");
+    const Layout& L = s->L;
+    const size_t np = (size_t)L.B * n;
+    for (size_t i = 0; i < 2 * np; ++i)
+      if (!std::isfinite(xy[i])) throw std::runtime_error("sim_terrain_height: xy holds a non-finite number");
+    if (n > 0) {
+      void* p = nullptr;
+      HIP_OK(hipMalloc(&p, 3 * np * sizeof(double)));
+      double* d_xy = (double*)p;
+      try {
+        copy_sync(s, d_xy, xy, 2 * np * sizeof(double), hipMemcpyHostToDevice);
+        SimTerrainHeightArgs a;
+        a.t = sim_terrain_args(s); a.ground_z = s->plant.con_cfg.ground_z; a.xy = d_xy; a.n = n; a.h = d_xy + 2 * np;
+        hipLaunchKernelGGL(k_sim_terrain_height, dim3((unsigned)L.B), dim3(64), 0, s->stream, a);
+        HIP_OK(hipGetLastError());
+        copy_sync(s, h, a.h, np * sizeof(double), hipMemcpyDeviceToHost);
+      } catch (...) {
+        (void)hipFree(p);
+        throw;
+      }
+      HIP_OK(hipFree(p));
+    }
+  })
+}
+
+int32_t mpc_sim_contacts_width(mpc_solver* s) { return sim_width(s, "sim_contacts_width", [&] { return MPC_SIM_CONTACTS_WIDTH; }); }
+
+// ---- include/mpc_sim_actuators.h: the per-robot actuator model of the torque-driven simulator steps ------------------------------------------
+int mpc_sim_actuators(mpc_solver* s, const double* params, const double* limit, const double* friction_shape) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_actuators");
+    const Layout& L = s->L;
+    const size_t nu = L.m, np = (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS;
+    std::vector<double> h;
+    if (params) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
+      h.assign(np + 2 * nu, 0.0);
+      bool any_sat = false;
+      for (int b = 0; b < L.B; ++b) {
+        const double* r = params + (size_t)b * MPC_SIM_ACTUATORS_PARAMS;
+        const std::string row = "sim_actuators: row " + std::to_string(b);
+        for (int e = 0; e < MPC_SIM_ACTUATORS_PARAMS; ++e)
+          if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+        if (r[0] != std::floor(r[0]) || r[0] < 0.0 || r[0] > MPC_SIM_ACTUATORS_RING - 1)
+          throw std::runtime_error(row + ": delay must be an integer value in [0, " + std::to_string(MPC_SIM_ACTUATORS_RING - 1) + "]");
+        if (!(r[1] > 0.0)) throw std::runtime_error(row + ": scale must be > 0");
+        for (int e = 2; e < 7; ++e)
+          if (r[e] < 0.0) throw std::runtime_error(row + ": time_constant, damping, coulomb, v_eps and sat must be >= 0");
+        if (r[4] > 0.0 && !(r[5] > 0.0)) throw std::runtime_error(row + ": coulomb > 0 needs v_eps > 0");
+        if (r[6] > 0.0) any_sat = true;
+        std::copy(r, r + MPC_SIM_ACTUATORS_PARAMS, h.begin() + (size_t)b * MPC_SIM_ACTUATORS_PARAMS);
+        h[(size_t)b * MPC_SIM_ACTUATORS_PARAMS + 7] = 0.0;
+      }
+      if (any_sat && !limit) throw std::runtime_error("sim_actuators: a row with sat > 0 needs the effort limits (limit must not be null)");
+      for (size_t j = 0; j < nu; ++j) {
+        const double l = limit ? limit[j] : 0.0, f = friction_shape ? friction_shape[j] : 1.0;
+        if (!std::isfinite(l) || l < 0.0 || !std::isfinite(f) || f < 0.0)
+          throw std::runtime_error("sim_actuators: limit and friction_shape must be finite and >= 0");
+        h[np + j] = l;
+        h[np + nu + j] = f;
+      }
+    }
+    const size_t rows = (size_t)L.B * sim_actuators_width(L);
+    sim_realloc(s, s->plant.d_act, params ? h.size() + rows : 0);
+    s->plant.h_act = h;
+    if (params) {
+      h.resize(h.size() + rows, 0.0);  // (the state rows after a reset: all 0)
+      copy_sync(s, s->plant.d_act, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
+  })
+}
+
+int mpc_sim_actuators_read(mpc_solver* s, double* params, double* state) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_actuators_read");
+    if (!s->plant.d_act) throw std::runtime_error("sim_actuators_read: the actuator model is off on this handle (turn it on with mpc_sim_actuators)");
+    const Layout& L = s->L;
+    if (params) std::copy(s->plant.h_act.begin(), s->plant.h_act.begin() + (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS, params);
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (state) copy_sync(s, state, sim_actuators_rows(s), (size_t)L.B * sim_actuators_width(L) * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int mpc_sim_actuators_set(mpc_solver* s, const double* state) {
+  MPC_TRY(s, {
+    if (!state) throw std::runtime_error("sim_actuators_set: state must not be null");
+    sim_check(s, "sim_actuators_set");
+    if (!s->plant.d_act) throw std::runtime_error("sim_actuators_set: the actuator model is off on this handle (turn it on with mpc_sim_actuators)");
+    const Layout& L = s->L;
+    const size_t W = sim_actuators_width(L);
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = state + (size_t)b * W;
+      const std::string row = "sim_actuators_set: row " + std::to_string(b);
+      for (size_t e = 0; e < W; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      const double head = r[W - 2], count = r[W - 1];
+      if (head != std::floor(head) || head < 0.0 || head >= MPC_SIM_ACTUATORS_RING)
+        throw std::runtime_error(row + ": head must be an integer value in [0, " + std::to_string(MPC_SIM_ACTUATORS_RING) + ")");
+      if (count < 0.0) throw std::runtime_error(row + ": count must be >= 0");
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, sim_actuators_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+int32_t mpc_sim_actuators_width(mpc_solver* s) { return sim_width(s, "sim_actuators_width", [&] { return sim_actuators_width(s->L); }); }
+
+// ---- include/mpc_abi.h: one step under the caller's torques -------------------------------------------------------------------------------------
+int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32_t substeps, double dt, double* wrenches) {
+  MPC_TRY(s, {
+    if (substeps <= 0 || !(dt > 0.0)) throw std::runtime_error("simulate_torque: substeps and dt must be positive");
+    if (!tau) throw std::runtime_error("simulate_torque: tau must not be null");
+    const Layout& L = s->L;
+    sim_steps_check(s, "simulate_torque", SIM_STAGE0, 1);
+    // (synchronous uploads: the caller's arrays are free when the call returns)
+    if (x) copy_sync(s, s->d_x0, x, (size_t)L.B * L.nx * sizeof(double), hipMemcpyHostToDevice);
+    copy_sync(s, s->plant.d_simu, tau, (size_t)L.B * L.m * sizeof(double), hipMemcpyHostToDevice);
+    sim_steps_begin(s, s->stream, nullptr);
+    sim_step_enqueue(s, s->stream, s->args(), substeps, dt, wrenches != nullptr);
+    if (wrenches) copy_sync(s, wrenches, s->plant.d_simwr, (size_t)L.B * 12 * sizeof(double), hipMemcpyDeviceToHost);
+    s->perfect_feedback = false;
+  })
+}
+
+}  // extern "C"
