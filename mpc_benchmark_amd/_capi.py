@@ -13,6 +13,7 @@ import os
 import numpy as np
 
 from . import actuator_model as _actuator_model
+from . import sensor_model as _sensor_model
 from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
 
@@ -168,6 +169,14 @@ _SIM_ACTUATORS_SIGNATURES = {
     "mpc_sim_actuators_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_sensors.h: exported by the HIP library alone, bound when present (``NativeSolver.sensors`` / ``read_sensors`` / ``set_sensors``)
+_SIM_SENSORS_SIGNATURES = {
+    "mpc_sim_sensors": (C.c_int, [C.c_void_p, _DP, _DP]),
+    "mpc_sim_sensors_read": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
+    "mpc_sim_sensors_set": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_sensors_width": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_sim_terrain.h: exported by the HIP library alone, bound when present (``NativeSolver.terrain`` / ``read_terrain`` / ``terrain_height``)
 class MpcSimTerrainConfig(C.Structure):
     _fields_ = [("n_boxes", C.c_int32), ("per_robot", C.c_int32)]
@@ -217,7 +226,7 @@ def bind_library(path):
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
+            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -515,6 +524,59 @@ class NativeSolver:
         if r.shape != (d.batch, _actuator_model.width(d.nu)):
             raise ValueError("set_actuators: state rows of shape (%d, %d) expected, got %s" % (d.batch, _actuator_model.width(d.nu), r.shape))
         self._check(fn(self._h, _dp(r)), "mpc_sim_actuators_set")
+
+    # -- include/mpc_sim_sensors.h (HIP library only): the per-robot sensor model between the torque-driven simulator steps and the controllers -----
+    def _sim_sensors(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the sensor model of torque-driven simulator steps is HIP only "
+                               "(libmpc_hip.so, include/mpc_sim_sensors.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def sensors(self, params, x0=None):
+        """Follow every torque-driven simulator step of this handle with every robot's own measurement event on the device: the controllers of the
+        device loops then read the measurement, not the true state (mpc_sim_sensors; ``sensor_model`` is the definition).  ``params``: (B, 16) rows,
+        one row of 16 for every robot, or a dict by ``sensor_model.FIELDS`` name of scalars or (B,) arrays (missing fields 0: the identity); turns the
+        model on, resets its state rows and takes the first measurement, of ``x0`` (B, nx): the true states the simulator starts from.  None turns
+        the model off."""
+        fn = self._sim_sensors("mpc_sim_sensors")
+        if params is None:
+            self._check(fn(self._h, None, None), "mpc_sim_sensors")
+            return
+        d = self.dims
+        p = _f64(_sensor_model.rows(params, d.batch))
+        if x0 is None:
+            raise ValueError("sensors: x0 (B, nx), the states the first measurement is taken of, is needed with params")
+        xa = np.ascontiguousarray(np.broadcast_to(_f64(x0).reshape(-1, d.nx), (d.batch, d.nx)))
+        self._check(fn(self._h, _dp(p), _dp(xa)), "mpc_sim_sensors")
+
+    def read_sensors(self, raw=False):
+        """The sensor model as it stands (mpc_sim_sensors_read) -> dict: ``x`` (B, nx) the measurement the controllers read, ``params`` (B, 16) the
+        rows in force, and the state rows by ``sensor_model.unpack`` (``ring`` (B, 16, nx), ``meas`` (B, nx), ``vf``, ``qm_prev`` (B, nu), ``head``,
+        ``count`` (B,)); ``raw``: the (B, 17 nx + 2 nu + 2) state rows themselves."""
+        fn = self._sim_sensors("mpc_sim_sensors_read")
+        w = self._sim_sensors("mpc_sim_sensors_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_sensors_width")
+        d = self.dims
+        out, par, xm = np.zeros((d.batch, w)), np.zeros((d.batch, _sensor_model.PARAMS)), np.zeros((d.batch, d.nx))
+        self._check(fn(self._h, _dp(par), _dp(out), _dp(xm)), "mpc_sim_sensors_read")
+        if raw:
+            return out
+        r = _sensor_model.unpack(out, d.ndx // 2)
+        r["params"], r["x"] = par, xm
+        return r
+
+    def set_sensors(self, state):
+        """Impose the state rows of the sensor model (mpc_sim_sensors_set): (B, 17 nx + 2 nu + 2), e.g. ``read_sensors(raw=True)`` of an earlier point."""
+        fn = self._sim_sensors("mpc_sim_sensors_set")
+        w = self._sim_sensors("mpc_sim_sensors_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_sensors_width")
+        r = _f64(state)
+        d = self.dims
+        if r.shape != (d.batch, w):
+            raise ValueError("set_sensors: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
+        self._check(fn(self._h, _dp(r)), "mpc_sim_sensors_set")
 
     # -- include/mpc_sim_terrain.h (HIP library only): the box terrain under the contact rule ------------------------------------------------------
     def _sim_terrain(self, name):

@@ -18,6 +18,9 @@ box terrain under the rule, host or device: a foot is caught on the highest box 
 risers, soles hanging over an edge and slopes are not modelled.  ``addStairs`` (a URDF in the reference) stays unavailable.
 ``actuators=`` / ``setActuators(params, limit=None, friction_shape=None)`` (HIP library only) put the actuator model of ``actuator_model`` between
 ``execute(torques)`` and the dynamics (mpc_sim_actuators, include/mpc_sim_actuators.h): delay, gain error, lag, saturation, joint friction.
+``sensors=`` / ``setSensors(params)`` (HIP library only) put the sensor model of ``sensor_model`` between the dynamics and ``measureState()``
+(mpc_sim_sensors, include/mpc_sim_sensors.h): latency, encoder resolution, calibration offsets, noise, finite-difference velocities.  ``x``, the
+contact rule and ``history`` stay the true state; ``measureState()`` returns the measurement.
 
 Differences from PyBullet worth knowing: ``measureState`` returns the base velocity in the LOCAL frame of the base (Pinocchio's
 convention, which is what the scripts assume when they copy it into the state, talos_utils.py:337-348); PyBullet reports it in the
@@ -46,7 +49,7 @@ class BulletRobot:
 
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
                  inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
-                 device_contacts=False, actuators=None):
+                 device_contacts=False, actuators=None, sensors=None):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -60,6 +63,7 @@ class BulletRobot:
         self.device_contacts = bool(device_contacts)  # the contact rule on the device (in_contact and the rest are read back after every step)
         self.terrain = None  # boxes (n, 5) under the contact rule (setTerrain / createStairs); None: the plane z = ground_z
         self._actuators = None if actuators is None else (actuators, None, None)  # (params, limit, friction_shape) of setActuators, armed at initializeJoints
+        self._sensors = sensors  # params of setSensors, armed at initializeJoints
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
         self._native = None
@@ -107,6 +111,8 @@ class BulletRobot:
                 self._native.terrain(self.terrain)
         if self._actuators is not None:
             self.setActuators(*self._actuators)
+        if self._sensors is not None:
+            self.setSensors(self._sensors)
 
     def _contact_models(self):
         m = self.model
@@ -240,19 +246,22 @@ class BulletRobot:
     def measureState(self):
         """-> (q, v) of the COMPLETE model (bullet_robot.py:172-196): locked joints at their initial positions, zero velocity."""
         m = self.model
+        x = self.x if (self._sensors is None or self._native is None) else self._native.read_sensors()["x"][0]  # (setSensors: the measurement)
         q, v = self.q_complete.copy(), self.v_complete.copy()
-        q[:7] = self.x[:7]
-        v[:6] = self.x[m.nq:m.nq + 6]
+        q[:7] = x[:7]
+        v[:6] = x[m.nq:m.nq + 6]
         for src, dst in self._qmap:
-            q[src] = self.x[dst]
+            q[src] = x[dst]
         for src, dst in self._vmap:
-            v[src] = self.x[m.nq + dst]
+            v[src] = x[m.nq + dst]
         return q, v
 
     def resetState(self, q0Start):
         m = self.model
         self.x[:m.nq] = np.asarray(q0Start, dtype=float)[:m.nq]
         self.x[m.nq:] = 0.0
+        if self._sensors is not None and self._native is not None:  # (an imposed state: the sensor model is armed again, on it)
+            self.setSensors(self._sensors)
 
     def apply_force(self, force, position):
         """PyBullet's applyExternalForce(robot, -1, force, position, WORLD_FRAME): a world-frame force on the base link at a world point, acting
@@ -314,6 +323,19 @@ class BulletRobot:
         if limit is None:
             limit = np.asarray(self.model.effortLimit, dtype=float)[6:]
         self._native.actuators(params, limit=limit, friction_shape=friction_shape)
+
+    def setSensors(self, params):
+        """The sensor model between the dynamics and ``measureState()`` (``sensor_model``; HIP library only): ``params`` one row of 16, (1, 16), or a
+        dict by field name (missing fields 0: the identity); None: off.  Arms and resets the model at the current true state; before
+        ``initializeJoints`` it is kept for then."""
+        self._sensors = params
+        if self._native is None:
+            return
+        if params is None:
+            if hasattr(self._native.lib, "mpc_sim_sensors"):
+                self._native.sensors(None)
+            return
+        self._native.sensors(params, self.x)
 
     def createStairs(self, pose_stairs, height_step):
         """bullet_robot.py:275-340 of the reference: three steps of half extents 0.2 x 0.5 x height_step / 2, each 0.3 m further and height_step higher,

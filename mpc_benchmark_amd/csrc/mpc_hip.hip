@@ -34,6 +34,7 @@
 #include "sim_metrics.h"
 #include "sim_contacts.h"
 #include "sim_actuators.h"
+#include "sim_sensors.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
 #include "../../include/mpc_walk_poses.h"
@@ -90,9 +91,13 @@ struct SimPlant {
   // include/mpc_sim_actuators.h: the actuator model (nullptr: off), one allocation: params [B][8] | limit [nu] | friction shape [nu] | state rows [B][18 nu + 2]
   double* d_act = nullptr;
   std::vector<double> h_act;  // params | limit | shape as they are in force
+  // include/mpc_sim_sensors.h: the sensor model (nullptr: off), one allocation: params [B][16] | the measurement the controllers read [B][nx] | staging of
+  // the states to arm on [B][nx] | state rows [B][17 nx + 2 nu + 2]
+  double* d_sen = nullptr;
+  std::vector<double> h_sen;  // params as they are in force
   // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
   void free_owned() {
-    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen}) if (*p) { (void)hipFree(*p); *p = nullptr; }
   }
 };
 

@@ -1,7 +1,8 @@
 // pipeline_loops.h — the device loops of the three control pipelines: per period the controller's kernels, then one step of the plant (sim_host.h
 // sim_step_enqueue), with nothing but kernels in between.  mpc_qp_low_level_steps (kinodynamic, include/mpc_qp_abi.h), mpc_qp_ikid_low_level_steps
-// (centroidal, the same header) and mpc_feedback_low_level_steps (full dynamics, include/mpc_feedback_pipeline.h).  Included at the end of mpc_hip.hip,
-// after sim_host.h.
+// (centroidal, the same header) and mpc_feedback_low_level_steps (full dynamics, include/mpc_feedback_pipeline.h).  The controllers read sim_measured(sim): the measurement of
+// the sensor model when it is on (include/mpc_sim_sensors.h), the true state otherwise; x_out, the record, the metrics and the contact rule are the
+// true state's.  Included at the end of mpc_hip.hip, after sim_host.h.
 #pragma once
 
 // include/mpc_qp_contacts.h: a loop call on a QP handle whose contact source is not the schedule.  The checks (throws), then the arguments of
@@ -61,11 +62,11 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
     p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains; p.knots = plan->d_knots;
     p.N = P.N; p.nx = nx; p.nq = q.nq; p.nv = q.nv; p.n = P.n; p.m = P.m; p.gain_stride = P.gain_stride; p.oK = P.oK; p.knot_stride = P.knot_stride; p.oXD = P.oXD;
     p.slot0 = plan->khead % P.N;
-    p.x = sim->d_x0; p.xrob = q.xrob; p.acc = q.acc; p.f = q.f; p.sol = q.sol; p.nk = nk; p.qn = q.n; p.tau_max = d_taumax; p.sim_u = sim->plant.d_simu; p.f_new = d_fnew;
+    p.x = sim_measured(sim); p.xrob = q.xrob; p.acc = q.acc; p.f = q.f; p.sol = q.sol; p.nk = nk; p.qn = q.n; p.tau_max = d_taumax; p.sim_u = sim->plant.d_simu; p.f_new = d_fnew;
     p.used = from_plant ? qc.used : nullptr;
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
-      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(d_xprev, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(d_xprev, sim_measured(sim), B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(k_pipe_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
       if (from_plant) pipe_contacts_enqueue(pc, st);
       qp_id_enqueue(qp, S, kd);
@@ -144,7 +145,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     g.x_ik = d_xprev; g.x_post = d_xpost; g.refs = d_refs; g.ref_dt = ref_dt;
     g.fr[0] = frames[0]; g.fr[1] = frames[1]; g.fr[2] = base_frame; g.fr[3] = torso_frame;
     g.ik = q.ik;
-    g.x = sim->d_x0; g.xrob = q.xrob; g.f = q.f; g.c_prev = d_cprev;
+    g.x = sim_measured(sim); g.xrob = q.xrob; g.f = q.f; g.c_prev = d_cprev;
     g.sol = q.sol; g.nk = nk; g.qn = q.n; g.sim_u = sim->plant.d_simu; g.f_new = d_fnew;
     g.used = from_plant ? qc.used : nullptr;
     hipLaunchKernelGGL(k_ikid_task_errors, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
@@ -153,7 +154,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
       g.last = (step == steps - 1);
-      if (g.last) HIP_OK(hipMemcpyAsync(d_xprev, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (g.last) HIP_OK(hipMemcpyAsync(d_xprev, sim_measured(sim), B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(k_pipe_centroidal_feedback, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
       if (from_plant) pipe_contacts_enqueue(pc, st);
       qp_ikid_enqueue(qp, S);
@@ -202,10 +203,10 @@ int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double
     FdPipeArgs p;
     p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains;
     p.N = P.N; p.nx = nx; p.nv = Z.n / 2; p.nq = nx - Z.n / 2; p.n = P.n; p.m = nu; p.gain_stride = P.gain_stride; p.oK = P.oK;
-    p.x = sim->d_x0; p.sim_u = sim->plant.d_simu;
+    p.x = sim_measured(sim); p.sim_u = sim->plant.d_simu;
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
-      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(sim->plant.d_xlast, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(sim->plant.d_xlast, sim_measured(sim), B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(k_pipe_state_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
       sim_step_enqueue(sim, st, za, 1, dt, wrenches != nullptr);
     }

@@ -1,6 +1,6 @@
 // sim_host.h — host side of the torque-driven simulator (the plant): mpc_simulate_torque and the entry points of include/mpc_sim_ext.h (push, record),
-// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h and mpc_sim_actuators.h.  Its state is mpc_solver::plant (SimPlant); its kernels are in
-// sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h and sim_actuators.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
+// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h and mpc_sim_sensors.h.  Its state is mpc_solver::plant (SimPlant); its kernels
+// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h and sim_sensors.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
 // loops of the three pipelines in pipeline_loops.h — goes through sim_steps_check, sim_steps_begin and sim_step_enqueue: an extension of the simulator
 // is added there, once.  Included at the end of mpc_hip.hip (mpc_solver, MPC_TRY, copy_sync, slot_of).
 #pragma once
@@ -145,6 +145,24 @@ static void sim_actuators_enqueue(mpc_solver* s, hipStream_t st, double dt_step)
   HIP_OK(hipGetLastError());
 }
 
+static size_t sim_sensors_width(const Layout& L) { return (size_t)(MPC_SIM_SENSORS_RING + 1) * L.nx + 2 * (size_t)L.m + 2; }
+static double* sim_sensors_meas(const mpc_solver* s) { return s->plant.d_sen + (size_t)s->L.B * MPC_SIM_SENSORS_PARAMS; }
+static double* sim_sensors_stage(const mpc_solver* s) { return sim_sensors_meas(s) + (size_t)s->L.B * s->L.nx; }
+static double* sim_sensors_rows(const mpc_solver* s) { return sim_sensors_stage(s) + (size_t)s->L.B * s->L.nx; }
+// the state the controllers read, [B][nx]: the measurement of the sensor model when it is on, the true state otherwise
+static const double* sim_measured(const mpc_solver* s) { return s->plant.d_sen ? sim_sensors_meas(s) : s->d_x0; }
+// the measurement event of the true states x, produced by a step of length dt_step, on stream st (sim_sensors.h), when the model is on
+static void sim_sensors_enqueue(mpc_solver* s, hipStream_t st, const double* x, double dt_step) {
+  const SimPlant& p = s->plant;
+  if (!p.d_sen) return;
+  const Layout& L = s->L;
+  SimSensorsArgs a;
+  a.nv = L.n / 2; a.nq = L.nx - L.n / 2; a.nu = L.m;
+  a.x = x; a.params = p.d_sen; a.xm = sim_sensors_meas(s); a.rows = sim_sensors_rows(s); a.dt = dt_step;
+  hipLaunchKernelGGL(k_sim_sensors, dim3((unsigned)L.B), dim3(SIM_SEN_THREADS), sim_sensors_lds_bytes(a.nv), st, a);
+  HIP_OK(hipGetLastError());
+}
+
 // A call that steps the plant `steps` times, part one: everything that can fail, before anything is enqueued.  `need`: sim_check.
 static void sim_steps_check(mpc_solver* s, const char* who, int need, int steps) {
   const SimPlant& p = s->plant;
@@ -171,7 +189,8 @@ static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
 // and everything after it sees the applied torque.  Then the dynamics, with the armed push and the contacts the rule's rows held when the step BEFORE
 // ended (the rows the low-level QPs of pipeline_loops.h read for this step); wrenches are written when the caller, the record, the metrics or the rule
 // want them.  Then the record and the metrics of the step: the new state, the applied torque, its wrenches, the rows it was integrated with.  The
-// contact rule last: it rewrites the rows for the NEXT step from the new state and this step's wrenches.
+// contact rule: it rewrites the rows for the NEXT step from the new state and this step's wrenches.  The sensor model last: the measurement event of
+// the new state, over the whole step; nothing of this step reads it, the controllers of the next step do (sim_measured).
 static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& args, int substeps, double dt, bool want_wrenches) {
   const SimPlant& p = s->plant;
   sim_actuators_enqueue(s, st, substeps * dt);
@@ -181,6 +200,7 @@ static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& ar
   sim_record_enqueue(s, st);
   sim_metrics_enqueue(s, st, substeps * dt);
   sim_contacts_enqueue(s, st);
+  sim_sensors_enqueue(s, st, s->d_x0, substeps * dt);
 }
 
 extern "C" {
@@ -485,6 +505,84 @@ int mpc_sim_actuators_set(mpc_solver* s, const double* state) {
 }
 
 int32_t mpc_sim_actuators_width(mpc_solver* s) { return sim_width(s, "sim_actuators_width", [&] { return sim_actuators_width(s->L); }); }
+
+// ---- include/mpc_sim_sensors.h: the per-robot sensor model between the simulator steps and the controllers -----------------------------------
+int mpc_sim_sensors(mpc_solver* s, const double* params, const double* x0) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_sensors");
+    const Layout& L = s->L;
+    const size_t np = (size_t)L.B * MPC_SIM_SENSORS_PARAMS, nxs = (size_t)L.B * L.nx;
+    if (params) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
+      for (int b = 0; b < L.B; ++b) {
+        const double* r = params + (size_t)b * MPC_SIM_SENSORS_PARAMS;
+        const std::string row = "sim_sensors: row " + std::to_string(b);
+        for (int e = 0; e < MPC_SIM_SENSORS_PARAMS; ++e)
+          if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+        if (r[0] != std::floor(r[0]) || r[0] < 0.0 || r[0] > MPC_SIM_SENSORS_RING - 1)
+          throw std::runtime_error(row + ": delay must be an integer value in [0, " + std::to_string(MPC_SIM_SENSORS_RING - 1) + "]");
+        for (int e : {1, 2, 3, 4, 5, 6, 7, 8, 10})
+          if (r[e] < 0.0) throw std::runtime_error(row + ": the noise levels (sigma_*), quantum, q_bias and v_time_constant must be >= 0");
+        if (r[9] != 0.0 && r[9] != 1.0) throw std::runtime_error(row + ": v_from_q must be 0 or 1");
+        if (r[11] != std::floor(r[11]) || r[11] < 0.0 || r[11] >= 4294967296.0) throw std::runtime_error(row + ": seed must be an integer value in [0, 2^32)");
+        for (int e = 12; e < MPC_SIM_SENSORS_PARAMS; ++e)
+          if (r[e] != 0.0) throw std::runtime_error(row + ": the reserved entries must be 0");
+      }
+      if (!x0) throw std::runtime_error("sim_sensors: x0 must not be null (the first measurement is taken of it)");
+      for (size_t e = 0; e < nxs; ++e)
+        if (!std::isfinite(x0[e])) throw std::runtime_error("sim_sensors: x0 holds a non-finite entry");
+    }
+    sim_realloc(s, s->plant.d_sen, params ? np + 2 * nxs + (size_t)L.B * sim_sensors_width(L) : 0);
+    s->plant.h_sen.clear();
+    if (params) {
+      s->plant.h_sen.assign(params, params + np);
+      // the rows after a reset: all 0, then the arming event (count 1) on x0
+      HIP_OK(hipMemsetAsync(s->plant.d_sen, 0, (np + 2 * nxs + (size_t)L.B * sim_sensors_width(L)) * sizeof(double), s->stream));
+      copy_sync(s, s->plant.d_sen, params, np * sizeof(double), hipMemcpyHostToDevice);
+      copy_sync(s, sim_sensors_stage(s), x0, nxs * sizeof(double), hipMemcpyHostToDevice);
+      sim_sensors_enqueue(s, s->stream, sim_sensors_stage(s), 0.0);
+      HIP_OK(hipStreamSynchronize(s->stream));
+    }
+  })
+}
+
+int mpc_sim_sensors_read(mpc_solver* s, double* params, double* state, double* x_meas) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_sensors_read");
+    if (!s->plant.d_sen) throw std::runtime_error("sim_sensors_read: the sensor model is off on this handle (turn it on with mpc_sim_sensors)");
+    const Layout& L = s->L;
+    if (params) std::copy(s->plant.h_sen.begin(), s->plant.h_sen.end(), params);
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (state) copy_sync(s, state, sim_sensors_rows(s), (size_t)L.B * sim_sensors_width(L) * sizeof(double), hipMemcpyDeviceToHost);
+    if (x_meas) copy_sync(s, x_meas, sim_sensors_meas(s), (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int mpc_sim_sensors_set(mpc_solver* s, const double* state) {
+  MPC_TRY(s, {
+    if (!state) throw std::runtime_error("sim_sensors_set: state must not be null");
+    sim_check(s, "sim_sensors_set");
+    if (!s->plant.d_sen) throw std::runtime_error("sim_sensors_set: the sensor model is off on this handle (turn it on with mpc_sim_sensors)");
+    const Layout& L = s->L;
+    const size_t W = sim_sensors_width(L), o_meas = (size_t)MPC_SIM_SENSORS_RING * L.nx;
+    std::vector<double> xm((size_t)L.B * L.nx);
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = state + (size_t)b * W;
+      const std::string row = "sim_sensors_set: row " + std::to_string(b);
+      for (size_t e = 0; e < W; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      const double head = r[W - 2], count = r[W - 1];
+      if (head != std::floor(head) || head < 0.0 || head >= MPC_SIM_SENSORS_RING)
+        throw std::runtime_error(row + ": head must be an integer value in [0, " + std::to_string(MPC_SIM_SENSORS_RING) + ")");
+      if (count < 1.0) throw std::runtime_error(row + ": count must be >= 1 (a measurement is always held)");
+      std::copy(r + o_meas, r + o_meas + L.nx, xm.begin() + (size_t)b * L.nx);
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, sim_sensors_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
+    copy_sync(s, sim_sensors_meas(s), xm.data(), xm.size() * sizeof(double), hipMemcpyHostToDevice);  // (the controllers read the rows' measurement)
+  })
+}
+
+int32_t mpc_sim_sensors_width(mpc_solver* s) { return sim_width(s, "sim_sensors_width", [&] { return sim_sensors_width(s->L); }); }
 
 // ---- include/mpc_abi.h: one step under the caller's torques -------------------------------------------------------------------------------------
 int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32_t substeps, double dt, double* wrenches) {

@@ -44,7 +44,16 @@ model (``actuator_model``: transport delay, gain error, first-order lag, saturat
 field name of scalars or (B,) arrays, which may also carry ``limit`` and ``friction_shape``), armed on the simulator handle when the pipeline is built
 (mpc_sim_actuators, include/mpc_sim_actuators.h; HIP library only).  ``limit`` defaults to the model's effort limits.  ``torques`` is then the APPLIED
 torque of the last step on both forms of a tick (the device loop returns it; the host glue reads it back after each step), and so are the record's
-torque columns and the metrics' power and energy.  ``set_actuators`` changes or removes the model later."""
+torque columns and the metrics' power and energy.  ``set_actuators`` changes or removes the model later.
+
+``sensors`` (all three pipelines): None, the controllers read the simulator's exact state; or the parameter rows of the per-robot sensor model
+(``sensor_model``: latency, encoder resolution, calibration offsets, joint and floating-base noise, finite-difference joint velocities, their low-pass;
+(B, 16), one row of 16 for every robot, or a dict by field name of scalars or (B,) arrays), armed on the simulator handle at the pipeline's true
+states (mpc_sim_sensors, include/mpc_sim_sensors.h; HIP library only).  ``x`` stays the TRUE state, and the plant, its record, its metrics, its contact
+rule and the QPs' contact source keep it; ``x_meas`` is the measurement.  The feedback laws, the low-level QPs and the task errors work at the
+measurement, and ``x_prev`` / ``c_prev`` (the next solve's initial condition, the state the walk references are planned from) are measured ones, on
+both forms of a tick: the device loops read the measurement where the kernel left it, the host glue reads it back before each step.
+``set_sensors`` changes or removes the model later (it arms at the current ``x``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -53,6 +62,7 @@ from . import _capi as K
 from . import actuator_model as _actuator_model
 from . import contact_rule as _contact_rule
 from . import qp_utils
+from . import sensor_model as _sensor_model
 from .aligator import _core as core
 from .aligator import dynamics as _dyn
 from .aligator import manifolds as _manifolds
@@ -195,8 +205,26 @@ def stairs_under_walk(robot, x_forward, z_height, y_gap=0.18, n_steps=3, half_ex
 
 
 class _Actuators:
-    """``actuators`` of the three pipelines (module docstring): the model is armed on the simulator handle; the host glue reads the applied torque back."""
+    """``actuators`` and ``sensors`` of the three pipelines (module docstring): the models are armed on the simulator handle; the host glue reads the
+    applied torque back after a step and the measurement before one."""
     _actuators_on = False
+    _sensors_on = False
+
+    def set_sensors(self, params):
+        """Arm (and reset) the per-robot sensor model on ``self.sim`` at the current true states ``self.x``: ``params`` in the forms of
+        ``NativeSolver.sensors``.  None turns the model off."""
+        if params is None:
+            if self._sensors_on:
+                self.sim.sensors(None)
+            self._sensors_on = False
+            return
+        self.sim.sensors(_sensor_model.rows(params, self.batch), self.x)
+        self._sensors_on = True
+
+    @property
+    def x_meas(self):
+        """the state the controllers read: the measurement of the sensor model, ``x`` itself without one"""
+        return self.sim.read_sensors()["x"] if self._sensors_on else self.x
 
     def set_actuators(self, params, limit=None, friction_shape=None):
         """Arm (and reset) the per-robot actuator model on ``self.sim``: ``params`` in the forms of ``NativeSolver.actuators``, a dict may also carry
@@ -273,10 +301,11 @@ class _QpContactSource:
 
 class KinodynamicPipeline(_QpContactSource, _Actuators):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
-                 terrain=None, contact_source="schedule", actuators=None, **ens_kw):
+                 terrain=None, contact_source="schedule", actuators=None, sensors=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
-        ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model (module docstring)."""
+        ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model, ``sensors``: None or the rows of the
+        sensor model (module docstring)."""
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("KinodynamicPipeline", contact_source, contact_rule)
         self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
@@ -298,7 +327,9 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         if actuators is not None:
             self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
-        self.x_prev = self.x.copy()                      # the measurement of the tick before (the solve's initial condition)
+        if sensors is not None:
+            self.set_sensors(sensors)
+        self.x_prev = self.x_meas.copy()                 # the measurement of the tick before (the solve's initial condition)
         self.torques = np.zeros((self.batch, m.nv - 6))
         self.forces = np.zeros((self.batch, 12))
         self._plan_stale = True
@@ -346,14 +377,14 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         if self._plan_stale:
             self._fetch()
         nq, nv = self.nq, self.nv
-        x = self.x
+        x = self.x_meas
         d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], self.xs0[:, :nq]), self.xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
         a0 = self.xdot0[:, nv:].copy()
         a0[:, 6:] = self.us0[:, 12:] - np.einsum("bij,bj->bi", self.K0[:, 12:], d)
         forces = self.us0[:, :12] - np.einsum("bij,bj->bi", self.K0[:, :12], d)
         a_new, f_new, tau = self.qp.solve_batch_device(x, a0, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
         tau = np.clip(tau, -self.umax, self.umax)
-        self.x = self.sim.simulate_torque(x, tau, 1, self.sim_dt)
+        self.x = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt)
         self.torques, self.forces = tau, f_new
         self._applied_torques()
         return tau
@@ -381,7 +412,7 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
                 if self._plan_stale:
                     self._fetch()
                 for _ in range(self.substeps):
-                    x_last = self.x.copy()   # (the script's x_measured is read BEFORE the last execute of the tick)
+                    x_last = self.x_meas.copy()   # (the script's x_measured is read BEFORE the last execute of the tick)
                     used = self._host_contact_set(cs)
                     self.low_level_step(used)
                     if self.contact_source != "schedule":
@@ -459,12 +490,13 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
     G_FOOT, G_ROT = 400.0, 10.0                        # g_p, g_b (:305-307)
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
-                 sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, **ens_kw):
+                 sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, sensors=None,
+                 **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
-        dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model
-        (module docstring)."""
+        dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model,
+        ``sensors``: None or the rows of the sensor model (module docstring)."""
         from .ensemble import ensemble_initial_states
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("CentroidalPipeline", contact_source, contact_rule)
@@ -501,6 +533,9 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
         self._set_sim_contacts((True, True))   # (the schedule starts in double support)
         if actuators is not None:
             self.set_actuators(actuators)
+        if sensors is not None:
+            self.set_sensors(sensors)
+            self.x_prev = self.x_meas.copy()
         self.torques = np.zeros((self.batch, m.nv - 6))
         self.forces = np.zeros((self.batch, 12))
         self.ik = None                 # the task errors of the last period
@@ -558,11 +593,11 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
         robot or (B, 2) per robot).  -> new_x of the measurement the step started from."""
         if self._plan_stale:
             self._fetch()
-        x = self.x
+        x = self.x_meas
         new_x = centroidal_state(self.model, x)
         forces = self.us0 - np.einsum("bij,bj->bi", self.K0, self.xs0 - new_x)   # us[0] - K_0 difference(new_x, xs[0])
         _, f_new, tau = self.qp.solve_batch_device_ik(x, ik, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
-        self.x = self.sim.simulate_torque(x, tau, 1, self.sim_dt)
+        self.x = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt)
         self.torques, self.forces = tau, f_new
         self._applied_torques()
         return new_x
@@ -603,7 +638,7 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
                     self._fetch()
                 self.ik = self.qp.task_errors(self.x_prev, self.x_posture, refs, self.ref_dt, self.dH)
                 for _ in range(self.substeps):
-                    x_last = self.x.copy()   # (the script's x_measured is read BEFORE the last execute of the period)
+                    x_last = self.x_meas.copy()   # (the script's x_measured is read BEFORE the last execute of the period)
                     used = self._host_contact_set(cs)
                     c_last = self.low_level_step(used, self.ik)
                     if self.contact_source != "schedule":
@@ -640,11 +675,11 @@ class FullDynamicPipeline(_Actuators):
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
-                 **ens_kw):
+                 sensors=None, **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
-        actuator model (module docstring of pipeline.py)."""
+        actuator model, ``sensors``: None or the rows of the sensor model (module docstring of pipeline.py)."""
         self.terrain = _checked_terrain("FullDynamicPipeline", terrain, contact_rule, int(batch))
         walk = _checked_walk("FullDynamicPipeline", walk, int(batch))
         if ens_kw.get("closed_loop") is not None:
@@ -667,7 +702,9 @@ class FullDynamicPipeline(_Actuators):
         if actuators is not None:
             self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
-        self.x_prev = self.x.copy()                      # the measurement of the period before (the solve's initial condition)
+        if sensors is not None:
+            self.set_sensors(sensors)
+        self.x_prev = self.x_meas.copy()                 # the measurement of the period before (the solve's initial condition)
         self.torques = np.zeros((self.batch, m.nv - 6))
         self.wrenches = np.zeros((self.batch, 2, 6))     # contact wrenches of the last simulator step (LOCAL frame of the sole)
         self._plan_stale = True
@@ -704,10 +741,10 @@ class FullDynamicPipeline(_Actuators):
         if self._plan_stale:
             self._fetch()
         nq = self.nq
-        x = self.x
+        x = self.x_meas
         d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], self.xs0[:, :nq]), self.xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
         tau = self.us0 - np.einsum("bij,bj->bi", self.K0, d)
-        self.x, wr = self.sim.simulate_torque(x, tau, 1, self.sim_dt, wrenches=True)
+        self.x, wr = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt, wrenches=True)
         self.torques, self.wrenches = tau, wr
         self._applied_torques()
         return tau
@@ -733,7 +770,7 @@ class FullDynamicPipeline(_Actuators):
                 if self._plan_stale:
                     self._fetch()
                 for _ in range(self.substeps):
-                    x_last = self.x.copy()   # (x_measured_prev is read BEFORE the last execute of the period)
+                    x_last = self.x_meas.copy()   # (x_measured_prev is read BEFORE the last execute of the period)
                     self.low_level_step(cs)
             else:
                 x_last = self.low_level_loop(cs)
