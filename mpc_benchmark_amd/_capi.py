@@ -14,6 +14,7 @@ import numpy as np
 
 from . import actuator_model as _actuator_model
 from . import sensor_model as _sensor_model
+from . import state_estimator as _state_estimator
 from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
 
@@ -177,6 +178,14 @@ _SIM_SENSORS_SIGNATURES = {
     "mpc_sim_sensors_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_estimator.h: exported by the HIP library alone, bound when present (``NativeSolver.estimator`` / ``read_estimator`` / ``set_estimator``)
+_SIM_ESTIMATOR_SIGNATURES = {
+    "mpc_sim_estimator": (C.c_int, [C.c_void_p, _DP, _DP]),
+    "mpc_sim_estimator_read": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
+    "mpc_sim_estimator_set": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_estimator_width": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_sim_terrain.h: exported by the HIP library alone, bound when present (``NativeSolver.terrain`` / ``read_terrain`` / ``terrain_height``)
 class MpcSimTerrainConfig(C.Structure):
     _fields_ = [("n_boxes", C.c_int32), ("per_robot", C.c_int32)]
@@ -226,7 +235,7 @@ def bind_library(path):
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
+            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_ESTIMATOR_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -577,6 +586,59 @@ class NativeSolver:
         if r.shape != (d.batch, w):
             raise ValueError("set_sensors: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
         self._check(fn(self._h, _dp(r)), "mpc_sim_sensors_set")
+
+    # -- include/mpc_sim_estimator.h (HIP library only): the per-robot base-state estimator between the sensor model and the controllers -------------
+    def _sim_estimator(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the base-state estimator of torque-driven simulator steps is HIP only "
+                               "(libmpc_hip.so, include/mpc_sim_estimator.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def estimator(self, params, x0=None):
+        """Follow every torque-driven simulator step of this handle with every robot's own estimation event on the device: the controllers of the
+        device loops then read the estimate — the measured state with the base position and linear velocity blended with leg odometry — not the
+        measurement (mpc_sim_estimator; ``state_estimator`` is the definition).  Needs the contact rule (``contacts``).  ``params``: (B, 16) rows, one
+        row of 16 for every robot, or a dict by ``state_estimator.FIELDS`` name of scalars or (B,) arrays (missing fields 0: the identity); turns the
+        estimator on, resets its state rows and arms on ``x0`` (B, nx): the first MEASURED states.  None turns the estimator off."""
+        fn = self._sim_estimator("mpc_sim_estimator")
+        if params is None:
+            self._check(fn(self._h, None, None), "mpc_sim_estimator")
+            return
+        d = self.dims
+        p = _f64(_state_estimator.rows(params, d.batch))
+        if x0 is None:
+            raise ValueError("estimator: x0 (B, nx), the measured states the arming event is run on, is needed with params")
+        xa = np.ascontiguousarray(np.broadcast_to(_f64(x0).reshape(-1, d.nx), (d.batch, d.nx)))
+        self._check(fn(self._h, _dp(p), _dp(xa)), "mpc_sim_estimator")
+
+    def read_estimator(self, raw=False):
+        """The estimator as it stands (mpc_sim_estimator_read) -> dict: ``x`` (B, nx) the estimate the controllers read, ``params`` (B, 16) the rows
+        in force, and the state rows by ``state_estimator.unpack`` (``est`` (B, nx), ``held`` (B, 2), ``anchor`` (B, 2, 3), ``stats`` (B, 8),
+        ``count`` (B,)); ``raw``: the (B, nx + 17) state rows themselves."""
+        fn = self._sim_estimator("mpc_sim_estimator_read")
+        w = self._sim_estimator("mpc_sim_estimator_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_estimator_width")
+        d = self.dims
+        out, par, xe = np.zeros((d.batch, w)), np.zeros((d.batch, _state_estimator.PARAMS)), np.zeros((d.batch, d.nx))
+        self._check(fn(self._h, _dp(par), _dp(out), _dp(xe)), "mpc_sim_estimator_read")
+        if raw:
+            return out
+        r = _state_estimator.unpack(out, d.ndx // 2)
+        r["params"], r["x"] = par, xe
+        return r
+
+    def set_estimator(self, state):
+        """Impose the state rows of the estimator (mpc_sim_estimator_set): (B, nx + 17), e.g. ``read_estimator(raw=True)`` of an earlier point."""
+        fn = self._sim_estimator("mpc_sim_estimator_set")
+        w = self._sim_estimator("mpc_sim_estimator_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_estimator_width")
+        r = _f64(state)
+        d = self.dims
+        if r.shape != (d.batch, w):
+            raise ValueError("set_estimator: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
+        self._check(fn(self._h, _dp(r)), "mpc_sim_estimator_set")
 
     # -- include/mpc_sim_terrain.h (HIP library only): the box terrain under the contact rule ------------------------------------------------------
     def _sim_terrain(self, name):

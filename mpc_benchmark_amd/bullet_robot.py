@@ -21,6 +21,9 @@ risers, soles hanging over an edge and slopes are not modelled.  ``addStairs`` (
 ``sensors=`` / ``setSensors(params)`` (HIP library only) put the sensor model of ``sensor_model`` between the dynamics and ``measureState()``
 (mpc_sim_sensors, include/mpc_sim_sensors.h): latency, encoder resolution, calibration offsets, noise, finite-difference velocities.  ``x``, the
 contact rule and ``history`` stay the true state; ``measureState()`` returns the measurement.
+``estimator=`` / ``setEstimator(params)`` (HIP library only, with ``device_contacts=True``) put the base-state estimator of ``state_estimator`` after
+the sensors (mpc_sim_estimator, include/mpc_sim_estimator.h): the base position and linear velocity by leg odometry through the soles the rule
+holds, blended with the measurement; ``measureState()`` then returns the estimate.
 
 Differences from PyBullet worth knowing: ``measureState`` returns the base velocity in the LOCAL frame of the base (Pinocchio's
 convention, which is what the scripts assume when they copy it into the state, talos_utils.py:337-348); PyBullet reports it in the
@@ -49,7 +52,7 @@ class BulletRobot:
 
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
                  inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
-                 device_contacts=False, actuators=None, sensors=None):
+                 device_contacts=False, actuators=None, sensors=None, estimator=None):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -64,6 +67,7 @@ class BulletRobot:
         self.terrain = None  # boxes (n, 5) under the contact rule (setTerrain / createStairs); None: the plane z = ground_z
         self._actuators = None if actuators is None else (actuators, None, None)  # (params, limit, friction_shape) of setActuators, armed at initializeJoints
         self._sensors = sensors  # params of setSensors, armed at initializeJoints
+        self._estimator = estimator  # params of setEstimator, armed at initializeJoints after the sensors
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
         self._native = None
@@ -113,6 +117,8 @@ class BulletRobot:
             self.setActuators(*self._actuators)
         if self._sensors is not None:
             self.setSensors(self._sensors)
+        elif self._estimator is not None:
+            self.setEstimator(self._estimator)
 
     def _contact_models(self):
         m = self.model
@@ -246,7 +252,9 @@ class BulletRobot:
     def measureState(self):
         """-> (q, v) of the COMPLETE model (bullet_robot.py:172-196): locked joints at their initial positions, zero velocity."""
         m = self.model
-        x = self.x if (self._sensors is None or self._native is None) else self._native.read_sensors()["x"][0]  # (setSensors: the measurement)
+        x = self._sensed()
+        if self._estimator is not None and self._native is not None:  # (setEstimator: the estimate)
+            x = self._native.read_estimator()["x"][0]
         q, v = self.q_complete.copy(), self.v_complete.copy()
         q[:7] = x[:7]
         v[:6] = x[m.nq:m.nq + 6]
@@ -256,12 +264,18 @@ class BulletRobot:
             v[src] = x[m.nq + dst]
         return q, v
 
+    def _sensed(self):
+        """what the sensors deliver: the measurement of the sensor model (setSensors), the true state without one"""
+        return self.x if (self._sensors is None or self._native is None) else self._native.read_sensors()["x"][0]
+
     def resetState(self, q0Start):
         m = self.model
         self.x[:m.nq] = np.asarray(q0Start, dtype=float)[:m.nq]
         self.x[m.nq:] = 0.0
         if self._sensors is not None and self._native is not None:  # (an imposed state: the sensor model is armed again, on it)
             self.setSensors(self._sensors)
+        elif self._estimator is not None and self._native is not None:  # (... and so is the estimator, after the sensors)
+            self.setEstimator(self._estimator)
 
     def apply_force(self, force, position):
         """PyBullet's applyExternalForce(robot, -1, force, position, WORLD_FRAME): a world-frame force on the base link at a world point, acting
@@ -334,8 +348,25 @@ class BulletRobot:
         if params is None:
             if hasattr(self._native.lib, "mpc_sim_sensors"):
                 self._native.sensors(None)
+            if self._estimator is not None:  # (the estimator reads the true state from here on: armed again, on it)
+                self.setEstimator(self._estimator)
             return
         self._native.sensors(params, self.x)
+        if self._estimator is not None:  # (the estimator arms after the sensors, on their first measurement)
+            self.setEstimator(self._estimator)
+
+    def setEstimator(self, params):
+        """The base-state estimator between the sensors and ``measureState()`` (``state_estimator``; HIP library only, needs
+        ``device_contacts=True``): ``params`` one row of 16, (1, 16), or a dict by field name (``w_p``, ``w_v``; missing fields 0: the identity); None:
+        off.  Arms and resets the estimator at the current measurement; before ``initializeJoints`` it is kept for then."""
+        self._estimator = params
+        if self._native is None:
+            return
+        if params is None:
+            if hasattr(self._native.lib, "mpc_sim_estimator"):
+                self._native.estimator(None)
+            return
+        self._native.estimator(params, self._sensed())
 
     def createStairs(self, pose_stairs, height_step):
         """bullet_robot.py:275-340 of the reference: three steps of half extents 0.2 x 0.5 x height_step / 2, each 0.3 m further and height_step higher,

@@ -35,6 +35,7 @@
 #include "sim_contacts.h"
 #include "sim_actuators.h"
 #include "sim_sensors.h"
+#include "sim_estimator.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
 #include "../../include/mpc_walk_poses.h"
@@ -95,9 +96,13 @@ struct SimPlant {
   // the states to arm on [B][nx] | state rows [B][17 nx + 2 nu + 2]
   double* d_sen = nullptr;
   std::vector<double> h_sen;  // params as they are in force
+  // include/mpc_sim_estimator.h: the base-state estimator (nullptr: off), one allocation: params [B][16] | the estimate the controllers read [B][nx] |
+  // staging of the states to arm on [B][nx] | state rows [B][nx + 17]
+  double* d_est = nullptr;
+  std::vector<double> h_est;  // params as they are in force
   // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
   void free_owned() {
-    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est}) if (*p) { (void)hipFree(*p); *p = nullptr; }
   }
 };
 

@@ -1,6 +1,6 @@
 // sim_host.h — host side of the torque-driven simulator (the plant): mpc_simulate_torque and the entry points of include/mpc_sim_ext.h (push, record),
-// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h and mpc_sim_sensors.h.  Its state is mpc_solver::plant (SimPlant); its kernels
-// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h and sim_sensors.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
+// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h and mpc_sim_estimator.h.  Its state is mpc_solver::plant (SimPlant); its kernels
+// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h and sim_estimator.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
 // loops of the three pipelines in pipeline_loops.h — goes through sim_steps_check, sim_steps_begin and sim_step_enqueue: an extension of the simulator
 // is added there, once.  Included at the end of mpc_hip.hip (mpc_solver, MPC_TRY, copy_sync, slot_of).
 #pragma once
@@ -149,8 +149,14 @@ static size_t sim_sensors_width(const Layout& L) { return (size_t)(MPC_SIM_SENSO
 static double* sim_sensors_meas(const mpc_solver* s) { return s->plant.d_sen + (size_t)s->L.B * MPC_SIM_SENSORS_PARAMS; }
 static double* sim_sensors_stage(const mpc_solver* s) { return sim_sensors_meas(s) + (size_t)s->L.B * s->L.nx; }
 static double* sim_sensors_rows(const mpc_solver* s) { return sim_sensors_stage(s) + (size_t)s->L.B * s->L.nx; }
-// the state the controllers read, [B][nx]: the measurement of the sensor model when it is on, the true state otherwise
-static const double* sim_measured(const mpc_solver* s) { return s->plant.d_sen ? sim_sensors_meas(s) : s->d_x0; }
+// what the sensors deliver, [B][nx]: the measurement of the sensor model when it is on, the true state otherwise
+static const double* sim_sensed(const mpc_solver* s) { return s->plant.d_sen ? sim_sensors_meas(s) : s->d_x0; }
+static double* sim_estimator_est(const mpc_solver* s) { return s->plant.d_est + (size_t)s->L.B * MPC_SIM_ESTIMATOR_PARAMS; }
+static double* sim_estimator_stage(const mpc_solver* s) { return sim_estimator_est(s) + (size_t)s->L.B * s->L.nx; }
+static double* sim_estimator_rows(const mpc_solver* s) { return sim_estimator_stage(s) + (size_t)s->L.B * s->L.nx; }
+static size_t sim_estimator_width(const Layout& L) { return (size_t)L.nx + MPC_SIM_ESTIMATOR_TAIL; }
+// the state the controllers read, [B][nx]: the estimate of the base-state estimator when it is on, what the sensors deliver otherwise
+static const double* sim_measured(const mpc_solver* s) { return s->plant.d_est ? sim_estimator_est(s) : sim_sensed(s); }
 // the measurement event of the true states x, produced by a step of length dt_step, on stream st (sim_sensors.h), when the model is on
 static void sim_sensors_enqueue(mpc_solver* s, hipStream_t st, const double* x, double dt_step) {
   const SimPlant& p = s->plant;
@@ -161,6 +167,23 @@ static void sim_sensors_enqueue(mpc_solver* s, hipStream_t st, const double* x, 
   a.x = x; a.params = p.d_sen; a.xm = sim_sensors_meas(s); a.rows = sim_sensors_rows(s); a.dt = dt_step;
   hipLaunchKernelGGL(k_sim_sensors, dim3((unsigned)L.B), dim3(SIM_SEN_THREADS), sim_sensors_lds_bytes(a.nv), st, a);
   HIP_OK(hipGetLastError());
+}
+
+// the estimation event of the measured states xm and the true states xt on stream st (sim_estimator.h), when the estimator is on: it reads the rows
+// of the contact rule as they stand on the stream
+static void sim_estimator_enqueue(mpc_solver* s, hipStream_t st, const double* xm, const double* xt) {
+  const SimPlant& p = s->plant;
+  if (!p.d_est) return;
+  const Layout& L = s->L;
+  SimEstimatorArgs a;
+  a.mi = s->d_model_i; a.md = s->d_model_d; a.nv = L.n / 2; a.nq = L.nx - L.n / 2;
+  a.xm = xm; a.xt = xt; a.con = p.d_con; a.params = p.d_est; a.xe = sim_estimator_est(s); a.rows = sim_estimator_rows(s);
+  hipLaunchKernelGGL(k_sim_estimator, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, a);
+  HIP_OK(hipGetLastError());
+}
+static void sim_estimator_drop(mpc_solver* s) {
+  sim_realloc(s, s->plant.d_est, 0);
+  s->plant.h_est.clear();
 }
 
 // A call that steps the plant `steps` times, part one: everything that can fail, before anything is enqueued.  `need`: sim_check.
@@ -190,7 +213,8 @@ static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
 // ended (the rows the low-level QPs of pipeline_loops.h read for this step); wrenches are written when the caller, the record, the metrics or the rule
 // want them.  Then the record and the metrics of the step: the new state, the applied torque, its wrenches, the rows it was integrated with.  The
 // contact rule: it rewrites the rows for the NEXT step from the new state and this step's wrenches.  The sensor model last: the measurement event of
-// the new state, over the whole step; nothing of this step reads it, the controllers of the next step do (sim_measured).
+// the new state, over the whole step.  The base-state estimator after it: the estimation event of that measurement (the true state without a
+// sensor model) and of the rows the contact rule just wrote; nothing of this step reads either, the controllers of the next step do (sim_measured).
 static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& args, int substeps, double dt, bool want_wrenches) {
   const SimPlant& p = s->plant;
   sim_actuators_enqueue(s, st, substeps * dt);
@@ -201,6 +225,7 @@ static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& ar
   sim_metrics_enqueue(s, st, substeps * dt);
   sim_contacts_enqueue(s, st);
   sim_sensors_enqueue(s, st, s->d_x0, substeps * dt);
+  sim_estimator_enqueue(s, st, sim_sensed(s), s->d_x0);
 }
 
 extern "C" {
@@ -299,7 +324,10 @@ int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
       if (cfg->release_steps < 1) throw std::runtime_error("sim_contacts: release_steps must be >= 1");
     }
     sim_realloc(s, s->plant.d_con, cfg ? (size_t)L.B * MPC_SIM_CONTACTS_WIDTH : 0);
-    if (!cfg) sim_terrain_drop(s);  // (the terrain goes with the rows; a reset keeps it)
+    if (!cfg) {  // (the terrain and the estimator go with the rows; a reset keeps them)
+      sim_terrain_drop(s);
+      sim_estimator_drop(s);
+    }
     if (cfg) {
       s->plant.con_cfg = *cfg;
       s->plant.con_cfg.reserved = 0;
@@ -583,6 +611,83 @@ int mpc_sim_sensors_set(mpc_solver* s, const double* state) {
 }
 
 int32_t mpc_sim_sensors_width(mpc_solver* s) { return sim_width(s, "sim_sensors_width", [&] { return sim_sensors_width(s->L); }); }
+
+// ---- include/mpc_sim_estimator.h: the per-robot base-state estimator between the sensor model and the controllers ----------------------------
+int mpc_sim_estimator(mpc_solver* s, const double* params, const double* x0) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_estimator");
+    const Layout& L = s->L;
+    const size_t np = (size_t)L.B * MPC_SIM_ESTIMATOR_PARAMS, nxs = (size_t)L.B * L.nx;
+    if (params) {  // (every check before anything changes: a bad call leaves the previous configuration in force)
+      sim_model_check(s, "sim_estimator");
+      if (L.nx > SIM_EST_MAX_NX) throw std::runtime_error("sim_estimator: a longer state than the estimator's kernel holds (" + std::to_string(SIM_EST_MAX_NX) + ")");
+      for (int b = 0; b < L.B; ++b) {
+        const double* r = params + (size_t)b * MPC_SIM_ESTIMATOR_PARAMS;
+        const std::string row = "sim_estimator: row " + std::to_string(b);
+        for (int e = 0; e < MPC_SIM_ESTIMATOR_PARAMS; ++e)
+          if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+        for (int e = 0; e < 2; ++e)
+          if (r[e] < 0.0 || r[e] > 1.0) throw std::runtime_error(row + ": the weights w_p and w_v must be in [0, 1]");
+        for (int e = 2; e < MPC_SIM_ESTIMATOR_PARAMS; ++e)
+          if (r[e] != 0.0) throw std::runtime_error(row + ": the reserved entries must be 0");
+      }
+      if (!x0) throw std::runtime_error("sim_estimator: x0 must not be null (the arming event is run on it)");
+      for (size_t e = 0; e < nxs; ++e)
+        if (!std::isfinite(x0[e])) throw std::runtime_error("sim_estimator: x0 holds a non-finite entry");
+      if (!s->plant.d_con) throw std::runtime_error("sim_estimator: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    }
+    const size_t total = np + 2 * nxs + (size_t)L.B * sim_estimator_width(L);
+    sim_realloc(s, s->plant.d_est, params ? total : 0);
+    s->plant.h_est.clear();
+    if (params) {
+      s->plant.h_est.assign(params, params + np);
+      // the rows after a reset: all 0, then the arming event (count 1) on x0
+      HIP_OK(hipMemsetAsync(s->plant.d_est, 0, total * sizeof(double), s->stream));
+      copy_sync(s, s->plant.d_est, params, np * sizeof(double), hipMemcpyHostToDevice);
+      copy_sync(s, sim_estimator_stage(s), x0, nxs * sizeof(double), hipMemcpyHostToDevice);
+      sim_estimator_enqueue(s, s->stream, sim_estimator_stage(s), sim_estimator_stage(s));
+      HIP_OK(hipStreamSynchronize(s->stream));
+    }
+  })
+}
+
+int mpc_sim_estimator_read(mpc_solver* s, double* params, double* state, double* x_est) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_estimator_read");
+    if (!s->plant.d_est) throw std::runtime_error("sim_estimator_read: the estimator is off on this handle (turn it on with mpc_sim_estimator)");
+    const Layout& L = s->L;
+    if (params) std::copy(s->plant.h_est.begin(), s->plant.h_est.end(), params);
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (state) copy_sync(s, state, sim_estimator_rows(s), (size_t)L.B * sim_estimator_width(L) * sizeof(double), hipMemcpyDeviceToHost);
+    if (x_est) copy_sync(s, x_est, sim_estimator_est(s), (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int mpc_sim_estimator_set(mpc_solver* s, const double* state) {
+  MPC_TRY(s, {
+    if (!state) throw std::runtime_error("sim_estimator_set: state must not be null");
+    sim_check(s, "sim_estimator_set");
+    if (!s->plant.d_est) throw std::runtime_error("sim_estimator_set: the estimator is off on this handle (turn it on with mpc_sim_estimator)");
+    const Layout& L = s->L;
+    const size_t W = sim_estimator_width(L);
+    std::vector<double> xe((size_t)L.B * L.nx);
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = state + (size_t)b * W;
+      const std::string row = "sim_estimator_set: row " + std::to_string(b);
+      for (size_t e = 0; e < W; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      for (int i = 0; i < 2; ++i)
+        if (r[L.nx + i] != 0.0 && r[L.nx + i] != 1.0) throw std::runtime_error(row + ": held must be 0 or 1");
+      if (r[W - 1] < 1.0) throw std::runtime_error(row + ": count must be >= 1 (an estimate is always held)");
+      std::copy(r, r + L.nx, xe.begin() + (size_t)b * L.nx);
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, sim_estimator_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
+    copy_sync(s, sim_estimator_est(s), xe.data(), xe.size() * sizeof(double), hipMemcpyHostToDevice);  // (the controllers read the rows' estimate)
+  })
+}
+
+int32_t mpc_sim_estimator_width(mpc_solver* s) { return sim_width(s, "sim_estimator_width", [&] { return sim_estimator_width(s->L); }); }
 
 // ---- include/mpc_abi.h: one step under the caller's torques -------------------------------------------------------------------------------------
 int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32_t substeps, double dt, double* wrenches) {

@@ -53,7 +53,15 @@ states (mpc_sim_sensors, include/mpc_sim_sensors.h; HIP library only).  ``x`` st
 rule and the QPs' contact source keep it; ``x_meas`` is the measurement.  The feedback laws, the low-level QPs and the task errors work at the
 measurement, and ``x_prev`` / ``c_prev`` (the next solve's initial condition, the state the walk references are planned from) are measured ones, on
 both forms of a tick: the device loops read the measurement where the kernel left it, the host glue reads it back before each step.
-``set_sensors`` changes or removes the model later (it arms at the current ``x``)."""
+``set_sensors`` changes or removes the model later (it arms at the current ``x``).
+
+``estimator`` (all three pipelines, with ``contact_rule``): None, the controllers read what the sensors deliver; or the parameter rows of the per-robot
+base-state estimator (``state_estimator``: ``w_p``, ``w_v``, the weights of leg odometry through the soles the contact rule holds in the base position
+and the base linear velocity; (B, 16), one row of 16 for every robot, or a dict by field name of scalars or (B,) arrays), armed on the simulator
+handle after the sensors, at ``x_meas`` (mpc_sim_estimator, include/mpc_sim_estimator.h; HIP library only).  ``x`` stays the TRUE state, ``x_meas``
+the sensor measurement, ``x_est`` is the estimate: what the feedback laws, the low-level QPs and the task errors work at and what ``x_prev`` /
+``c_prev`` hold, on both forms of a tick (the host glue reads ``x_est`` back before each step and applies nothing else).  ``set_estimator`` changes or
+removes the estimator later (it arms at the current ``x_meas``); ``set_sensors`` arms it again, after the sensors."""
 from __future__ import annotations
 
 import numpy as np
@@ -63,6 +71,7 @@ from . import actuator_model as _actuator_model
 from . import contact_rule as _contact_rule
 from . import qp_utils
 from . import sensor_model as _sensor_model
+from . import state_estimator as _state_estimator
 from .aligator import _core as core
 from .aligator import dynamics as _dyn
 from .aligator import manifolds as _manifolds
@@ -205,10 +214,11 @@ def stairs_under_walk(robot, x_forward, z_height, y_gap=0.18, n_steps=3, half_ex
 
 
 class _Actuators:
-    """``actuators`` and ``sensors`` of the three pipelines (module docstring): the models are armed on the simulator handle; the host glue reads the
-    applied torque back after a step and the measurement before one."""
+    """``actuators``, ``sensors`` and ``estimator`` of the three pipelines (module docstring): the models are armed on the simulator handle; the host
+    glue reads the applied torque back after a step and the estimate (the measurement without an estimator) before one."""
     _actuators_on = False
     _sensors_on = False
+    _estimator_rows = None
 
     def set_sensors(self, params):
         """Arm (and reset) the per-robot sensor model on ``self.sim`` at the current true states ``self.x``: ``params`` in the forms of
@@ -217,13 +227,32 @@ class _Actuators:
             if self._sensors_on:
                 self.sim.sensors(None)
             self._sensors_on = False
+        else:
+            self.sim.sensors(_sensor_model.rows(params, self.batch), self.x)
+            self._sensors_on = True
+        if self._estimator_rows is not None:  # (the estimator arms again, after the sensors, on what they deliver now)
+            self.set_estimator(self._estimator_rows)
+
+    def set_estimator(self, params):
+        """Arm (and reset) the per-robot base-state estimator on ``self.sim`` at the current measured states ``self.x_meas``: ``params`` in the
+        forms of ``NativeSolver.estimator``; needs ``contact_rule``.  None turns the estimator off."""
+        if params is None:
+            if self._estimator_rows is not None:
+                self.sim.estimator(None)
+            self._estimator_rows = None
             return
-        self.sim.sensors(_sensor_model.rows(params, self.batch), self.x)
-        self._sensors_on = True
+        rows = _state_estimator.rows(params, self.batch)
+        self.sim.estimator(rows, self.x_meas)
+        self._estimator_rows = rows
+
+    @property
+    def x_est(self):
+        """the state the controllers read: the estimate of the base-state estimator, ``x_meas`` without one"""
+        return self.sim.read_estimator()["x"] if self._estimator_rows is not None else self.x_meas
 
     @property
     def x_meas(self):
-        """the state the controllers read: the measurement of the sensor model, ``x`` itself without one"""
+        """what the sensors deliver: the measurement of the sensor model, ``x`` itself without one"""
         return self.sim.read_sensors()["x"] if self._sensors_on else self.x
 
     def set_actuators(self, params, limit=None, friction_shape=None):
@@ -301,11 +330,11 @@ class _QpContactSource:
 
 class KinodynamicPipeline(_QpContactSource, _Actuators):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
-                 terrain=None, contact_source="schedule", actuators=None, sensors=None, **ens_kw):
+                 terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
         ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model, ``sensors``: None or the rows of the
-        sensor model (module docstring)."""
+        sensor model, ``estimator``: None or the rows of the base-state estimator (module docstring)."""
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("KinodynamicPipeline", contact_source, contact_rule)
         self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
@@ -329,7 +358,9 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
         if sensors is not None:
             self.set_sensors(sensors)
-        self.x_prev = self.x_meas.copy()                 # the measurement of the tick before (the solve's initial condition)
+        if estimator is not None:
+            self.set_estimator(estimator)
+        self.x_prev = self.x_est.copy()                  # the measurement of the tick before (the solve's initial condition)
         self.torques = np.zeros((self.batch, m.nv - 6))
         self.forces = np.zeros((self.batch, 12))
         self._plan_stale = True
@@ -377,7 +408,7 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         if self._plan_stale:
             self._fetch()
         nq, nv = self.nq, self.nv
-        x = self.x_meas
+        x = self.x_est
         d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], self.xs0[:, :nq]), self.xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
         a0 = self.xdot0[:, nv:].copy()
         a0[:, 6:] = self.us0[:, 12:] - np.einsum("bij,bj->bi", self.K0[:, 12:], d)
@@ -412,7 +443,7 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
                 if self._plan_stale:
                     self._fetch()
                 for _ in range(self.substeps):
-                    x_last = self.x_meas.copy()   # (the script's x_measured is read BEFORE the last execute of the tick)
+                    x_last = self.x_est.copy()    # (the script's x_measured is read BEFORE the last execute of the tick)
                     used = self._host_contact_set(cs)
                     self.low_level_step(used)
                     if self.contact_source != "schedule":
@@ -491,12 +522,12 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
                  sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, sensors=None,
-                 **ens_kw):
+                 estimator=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
         dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model,
-        ``sensors``: None or the rows of the sensor model (module docstring)."""
+        ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state estimator (module docstring)."""
         from .ensemble import ensemble_initial_states
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("CentroidalPipeline", contact_source, contact_rule)
@@ -535,7 +566,10 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
             self.set_actuators(actuators)
         if sensors is not None:
             self.set_sensors(sensors)
-            self.x_prev = self.x_meas.copy()
+        if estimator is not None:
+            self.set_estimator(estimator)
+        if sensors is not None or estimator is not None:
+            self.x_prev = self.x_est.copy()
         self.torques = np.zeros((self.batch, m.nv - 6))
         self.forces = np.zeros((self.batch, 12))
         self.ik = None                 # the task errors of the last period
@@ -593,7 +627,7 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
         robot or (B, 2) per robot).  -> new_x of the measurement the step started from."""
         if self._plan_stale:
             self._fetch()
-        x = self.x_meas
+        x = self.x_est
         new_x = centroidal_state(self.model, x)
         forces = self.us0 - np.einsum("bij,bj->bi", self.K0, self.xs0 - new_x)   # us[0] - K_0 difference(new_x, xs[0])
         _, f_new, tau = self.qp.solve_batch_device_ik(x, ik, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
@@ -638,7 +672,7 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
                     self._fetch()
                 self.ik = self.qp.task_errors(self.x_prev, self.x_posture, refs, self.ref_dt, self.dH)
                 for _ in range(self.substeps):
-                    x_last = self.x_meas.copy()   # (the script's x_measured is read BEFORE the last execute of the period)
+                    x_last = self.x_est.copy()    # (the script's x_measured is read BEFORE the last execute of the period)
                     used = self._host_contact_set(cs)
                     c_last = self.low_level_step(used, self.ik)
                     if self.contact_source != "schedule":
@@ -675,11 +709,12 @@ class FullDynamicPipeline(_Actuators):
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
-                 sensors=None, **ens_kw):
+                 sensors=None, estimator=None, **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
-        actuator model, ``sensors``: None or the rows of the sensor model (module docstring of pipeline.py)."""
+        actuator model, ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state
+        estimator (module docstring of pipeline.py)."""
         self.terrain = _checked_terrain("FullDynamicPipeline", terrain, contact_rule, int(batch))
         walk = _checked_walk("FullDynamicPipeline", walk, int(batch))
         if ens_kw.get("closed_loop") is not None:
@@ -704,7 +739,9 @@ class FullDynamicPipeline(_Actuators):
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
         if sensors is not None:
             self.set_sensors(sensors)
-        self.x_prev = self.x_meas.copy()                 # the measurement of the period before (the solve's initial condition)
+        if estimator is not None:
+            self.set_estimator(estimator)
+        self.x_prev = self.x_est.copy()                  # the measurement of the period before (the solve's initial condition)
         self.torques = np.zeros((self.batch, m.nv - 6))
         self.wrenches = np.zeros((self.batch, 2, 6))     # contact wrenches of the last simulator step (LOCAL frame of the sole)
         self._plan_stale = True
@@ -741,7 +778,7 @@ class FullDynamicPipeline(_Actuators):
         if self._plan_stale:
             self._fetch()
         nq = self.nq
-        x = self.x_meas
+        x = self.x_est
         d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], self.xs0[:, :nq]), self.xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
         tau = self.us0 - np.einsum("bij,bj->bi", self.K0, d)
         self.x, wr = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt, wrenches=True)
@@ -770,7 +807,7 @@ class FullDynamicPipeline(_Actuators):
                 if self._plan_stale:
                     self._fetch()
                 for _ in range(self.substeps):
-                    x_last = self.x_meas.copy()   # (x_measured_prev is read BEFORE the last execute of the period)
+                    x_last = self.x_est.copy()    # (x_measured_prev is read BEFORE the last execute of the period)
                     self.low_level_step(cs)
             else:
                 x_last = self.low_level_loop(cs)
