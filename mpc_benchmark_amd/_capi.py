@@ -15,6 +15,7 @@ import numpy as np
 from . import actuator_model as _actuator_model
 from . import sensor_model as _sensor_model
 from . import state_estimator as _state_estimator
+from . import foot_sensors as _foot_sensors
 from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
 
@@ -186,6 +187,16 @@ _SIM_ESTIMATOR_SIGNATURES = {
     "mpc_sim_estimator_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_foot_sensors.h: exported by the HIP library alone, bound when present (``NativeSolver.foot_sensors`` / ``read_foot_sensors`` /
+# ``set_foot_sensors`` / ``foot_sensors_feed``)
+_SIM_FOOT_SENSORS_SIGNATURES = {
+    "mpc_sim_foot_sensors": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_foot_sensors_read": (C.c_int, [C.c_void_p, _DP, _DP]),
+    "mpc_sim_foot_sensors_set": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_foot_sensors_width": (C.c_int32, [C.c_void_p]),
+    "mpc_sim_foot_sensors_feed": (C.c_int, [C.c_void_p, C.c_int32]),
+}
+
 # include/mpc_sim_terrain.h: exported by the HIP library alone, bound when present (``NativeSolver.terrain`` / ``read_terrain`` / ``terrain_height``)
 class MpcSimTerrainConfig(C.Structure):
     _fields_ = [("n_boxes", C.c_int32), ("per_robot", C.c_int32)]
@@ -235,7 +246,7 @@ def bind_library(path):
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_ESTIMATOR_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
+            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_ESTIMATOR_SIGNATURES.items()) + list(_SIM_FOOT_SENSORS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -639,6 +650,62 @@ class NativeSolver:
         if r.shape != (d.batch, w):
             raise ValueError("set_estimator: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
         self._check(fn(self._h, _dp(r)), "mpc_sim_estimator_set")
+
+    # -- include/mpc_sim_foot_sensors.h (HIP library only): the per-robot foot force sensors and the contact detector ------------------------------
+    def _sim_foot_sensors(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the foot force sensors of torque-driven simulator steps are HIP only "
+                               "(libmpc_hip.so, include/mpc_sim_foot_sensors.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def foot_sensors(self, params):
+        """Follow every torque-driven simulator step of this handle with every robot's own detection event on the device: the step's contact wrenches
+        are measured and a threshold detector decides which soles the robot takes to stand (mpc_sim_foot_sensors; ``foot_sensors`` is the
+        definition).  Needs the contact rule (``contacts``).  ``params``: (B, 16) rows, one row of 16 for every robot, or a dict by
+        ``foot_sensors.FIELDS`` name of scalars or (B,) arrays (missing fields as in ``foot_sensors.EXACT``); turns the model on and arms it on the
+        rule's ``in_contact`` pairs.  None turns the model off and clears the feed."""
+        fn = self._sim_foot_sensors("mpc_sim_foot_sensors")
+        if params is None:
+            self._check(fn(self._h, None), "mpc_sim_foot_sensors")
+            return
+        p = _f64(_foot_sensors.rows(params, self.dims.batch))
+        self._check(fn(self._h, _dp(p)), "mpc_sim_foot_sensors")
+
+    def read_foot_sensors(self, raw=False):
+        """The detector as it stands (mpc_sim_foot_sensors_read) -> dict: ``params`` (B, 16) the rows in force, and the state rows by
+        ``foot_sensors.unpack`` (``det`` (B, 2), ``above``, ``below``, ``wf`` (B, 12), ``wm`` (B, 12), ``counts`` (B, 2, 4), ``ring`` (B, 16, 12),
+        ``head``, ``count``); ``raw``: the (B, 232) state rows themselves."""
+        fn = self._sim_foot_sensors("mpc_sim_foot_sensors_read")
+        w = self._sim_foot_sensors("mpc_sim_foot_sensors_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_foot_sensors_width")
+        d = self.dims
+        out, par = np.zeros((d.batch, w)), np.zeros((d.batch, _foot_sensors.PARAMS))
+        self._check(fn(self._h, _dp(par), _dp(out)), "mpc_sim_foot_sensors_read")
+        if raw:
+            return out
+        r = _foot_sensors.unpack(out)
+        r["params"] = par
+        return r
+
+    def set_foot_sensors(self, state):
+        """Impose the state rows of the detector (mpc_sim_foot_sensors_set): (B, 232), e.g. ``read_foot_sensors(raw=True)`` of an earlier point."""
+        fn = self._sim_foot_sensors("mpc_sim_foot_sensors_set")
+        w = self._sim_foot_sensors("mpc_sim_foot_sensors_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_foot_sensors_width")
+        r = _f64(state)
+        d = self.dims
+        if r.shape != (d.batch, w):
+            raise ValueError("set_foot_sensors: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
+        self._check(fn(self._h, _dp(r)), "mpc_sim_foot_sensors_set")
+
+    def foot_sensors_feed(self, consumers):
+        """Who works from the detected pair instead of the contact rule's (mpc_sim_foot_sensors_feed): a subset of ``("estimator", "qp")``, None or
+        ``()`` for nobody (the default), or the bit mask itself.  Sticky until the model is turned off."""
+        fn = self._sim_foot_sensors("mpc_sim_foot_sensors_feed")
+        mask = int(consumers) if isinstance(consumers, (int, np.integer)) else _foot_sensors.feed_mask(consumers)
+        self._check(fn(self._h, mask), "mpc_sim_foot_sensors_feed")
 
     # -- include/mpc_sim_terrain.h (HIP library only): the box terrain under the contact rule ------------------------------------------------------
     def _sim_terrain(self, name):

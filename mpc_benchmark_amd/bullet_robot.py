@@ -24,6 +24,9 @@ contact rule and ``history`` stay the true state; ``measureState()`` returns the
 ``estimator=`` / ``setEstimator(params)`` (HIP library only, with ``device_contacts=True``) put the base-state estimator of ``state_estimator`` after
 the sensors (mpc_sim_estimator, include/mpc_sim_estimator.h): the base position and linear velocity by leg odometry through the soles the rule
 holds, blended with the measurement; ``measureState()`` then returns the estimate.
+``foot_sensors=`` / ``setFootSensors(params, detected_contacts=())`` (HIP library only, with ``device_contacts=True``) measure the contact wrenches of
+every step and run the contact detector of ``foot_sensors`` on them (mpc_sim_foot_sensors, include/mpc_sim_foot_sensors.h); ``detectedContacts()``
+is the pair the robot takes to stand, and ``detected_contacts=("estimator",)`` lets the estimator work from it.  ``in_contact`` stays the plant's.
 
 Differences from PyBullet worth knowing: ``measureState`` returns the base velocity in the LOCAL frame of the base (Pinocchio's
 convention, which is what the scripts assume when they copy it into the state, talos_utils.py:337-348); PyBullet reports it in the
@@ -52,7 +55,7 @@ class BulletRobot:
 
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
                  inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
-                 device_contacts=False, actuators=None, sensors=None, estimator=None):
+                 device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -68,6 +71,7 @@ class BulletRobot:
         self._actuators = None if actuators is None else (actuators, None, None)  # (params, limit, friction_shape) of setActuators, armed at initializeJoints
         self._sensors = sensors  # params of setSensors, armed at initializeJoints
         self._estimator = estimator  # params of setEstimator, armed at initializeJoints after the sensors
+        self._foot_sensors = None if foot_sensors is None else (foot_sensors, ())  # (params, detected_contacts) of setFootSensors, armed at initializeJoints
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
         self._native = None
@@ -115,6 +119,8 @@ class BulletRobot:
                 self._native.terrain(self.terrain)
         if self._actuators is not None:
             self.setActuators(*self._actuators)
+        if self._foot_sensors is not None:  # (before the estimator: its arming event already reads the pair it will be fed)
+            self.setFootSensors(*self._foot_sensors)
         if self._sensors is not None:
             self.setSensors(self._sensors)
         elif self._estimator is not None:
@@ -367,6 +373,27 @@ class BulletRobot:
                 self._native.estimator(None)
             return
         self._native.estimator(params, self._sensed())
+
+    def setFootSensors(self, params, detected_contacts=()):
+        """The foot force sensors and the contact detector after every step (``foot_sensors``; HIP library only, needs ``device_contacts=True``):
+        ``params`` one row of 16, (1, 16), or a dict by field name (missing fields as in ``foot_sensors.EXACT``); None: off.  ``detected_contacts``:
+        () or ("estimator",): the estimator works from the detected pair.  Arms the detector on the rule's ``in_contact`` pair; before
+        ``initializeJoints`` it is kept for then."""
+        self._foot_sensors = None if params is None else (params, tuple(detected_contacts))
+        if self._native is None:
+            return
+        if params is None:
+            if hasattr(self._native.lib, "mpc_sim_foot_sensors"):
+                self._native.foot_sensors(None)
+            return
+        self._native.foot_sensors(params)
+        self._native.foot_sensors_feed(tuple(detected_contacts))
+
+    def detectedContacts(self):
+        """[left, right] the contacts the detector of ``setFootSensors`` reports; ``in_contact`` without one"""
+        if self._foot_sensors is None or self._native is None:
+            return list(self.in_contact)
+        return [bool(v) for v in self._native.read_foot_sensors()["det"][0]]
 
     def createStairs(self, pose_stairs, height_step):
         """bullet_robot.py:275-340 of the reference: three steps of half extents 0.2 x 0.5 x height_step / 2, each 0.3 m further and height_step higher,

@@ -36,6 +36,7 @@
 #include "sim_actuators.h"
 #include "sim_sensors.h"
 #include "sim_estimator.h"
+#include "sim_foot_sensors.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
 #include "../../include/mpc_walk_poses.h"
@@ -100,9 +101,14 @@ struct SimPlant {
   // staging of the states to arm on [B][nx] | state rows [B][nx + 17]
   double* d_est = nullptr;
   std::vector<double> h_est;  // params as they are in force
+  // include/mpc_sim_foot_sensors.h: the foot force sensors and the contact detector (nullptr: off), one allocation: params [B][16] | state rows [B][232];
+  // fs_feed: who works from the detected pair (the MPC_SIM_FOOT_SENSORS_FEED_* bits)
+  double* d_fs = nullptr;
+  std::vector<double> h_fs;  // params as they are in force
+  int fs_feed = 0;
   // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
   void free_owned() {
-    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est, &d_fs}) if (*p) { (void)hipFree(*p); *p = nullptr; }
   }
 };
 

@@ -12,7 +12,8 @@ static PipeContactsArgs pipe_contacts_args(const char* who, const QpContactSourc
   if (!sim->plant.d_con)
     throw std::runtime_error(std::string(who) + ": a contact source other than the schedule needs the contact rule on the simulator handle (mpc_sim_contacts first)");
   PipeContactsArgs c;
-  c.rows = sim->plant.d_con; c.width = MPC_SIM_CONTACTS_WIDTH; c.B = B; c.source = qc.source;
+  const SimContactRows cr = sim_contact_rows(sim, MPC_SIM_FOOT_SENSORS_FEED_QP);  // (the detected pair when the contact detector feeds the QPs)
+  c.rows = cr.rows; c.width = cr.width; c.B = B; c.source = qc.source;
   c.sched = qc.sched; c.cs = cs; c.used = qc.used; c.counts = qc.counts;
   return c;
 }

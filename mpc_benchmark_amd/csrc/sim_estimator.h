@@ -20,7 +20,8 @@ struct SimEstimatorArgs {
   int nq, nv;
   const double* xm;      // [B][nq + nv] the measured states
   const double* xt;      // [B][nq + nv] the true states (statistics only)
-  const double* con;     // [B][MPC_SIM_CONTACTS_WIDTH] the rows of the contact rule after the step (entries 0, 1: in_contact)
+  const double* con;     // [B][con_width] the rows of the contact rule after the step (entries 0, 1: in_contact), or the rows of the contact
+  int con_width;         // detector after this step's detection event (entries 0, 1: det) when it feeds the estimator (mpc_sim_foot_sensors_feed)
   const double* params;  // [B][MPC_SIM_ESTIMATOR_PARAMS]
   double* xe;            // [B][nq + nv] out: the estimate the controllers read
   double* rows;          // [B][nx + 17]: est[nx] | held[2] | anchor[2][3] | stats[8] | count
@@ -51,7 +52,7 @@ __global__ void __launch_bounds__(CG_THREADS) k_sim_estimator(SimEstimatorArgs a
   double* row = a.rows + (size_t)b * (nx + MPC_SIM_ESTIMATOR_TAIL);
   if (tid == 0) {
     const double* p = a.params + (size_t)b * MPC_SIM_ESTIMATOR_PARAMS;
-    const double* c = a.con + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
+    const double* c = a.con + (size_t)b * a.con_width;
     const double* xt = a.xt + (size_t)b * nx;
     double *held = row + nx, *anchor = held + 2, *stats = anchor + 6, *cnt = stats + 8;
     const double w_p = p[0], w_v = p[1], count = cnt[0] + 1.0;

@@ -1,6 +1,6 @@
 // sim_host.h — host side of the torque-driven simulator (the plant): mpc_simulate_torque and the entry points of include/mpc_sim_ext.h (push, record),
-// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h and mpc_sim_estimator.h.  Its state is mpc_solver::plant (SimPlant); its kernels
-// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h and sim_estimator.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
+// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h, mpc_sim_estimator.h and mpc_sim_foot_sensors.h.  Its state is mpc_solver::plant (SimPlant); its kernels
+// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h, sim_estimator.h and sim_foot_sensors.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
 // loops of the three pipelines in pipeline_loops.h — goes through sim_steps_check, sim_steps_begin and sim_step_enqueue: an extension of the simulator
 // is added there, once.  Included at the end of mpc_hip.hip (mpc_solver, MPC_TRY, copy_sync, slot_of).
 #pragma once
@@ -169,15 +169,58 @@ static void sim_sensors_enqueue(mpc_solver* s, hipStream_t st, const double* x, 
   HIP_OK(hipGetLastError());
 }
 
+static double* sim_foot_sensors_rows(const mpc_solver* s) { return s->plant.d_fs + (size_t)s->L.B * MPC_SIM_FOOT_SENSORS_PARAMS; }
+// the rows a consumer of contact flags indexes by 0 and 1, and their width: the state rows of the contact detector when it feeds that consumer
+// (mpc_sim_foot_sensors_feed: one MPC_SIM_FOOT_SENSORS_FEED_* bit), the rows of the contact rule otherwise
+struct SimContactRows { const double* rows; int width; };
+static SimContactRows sim_contact_rows(const mpc_solver* s, int consumer) {
+  const SimPlant& p = s->plant;
+  if (p.d_fs && (p.fs_feed & consumer)) return {sim_foot_sensors_rows(s), MPC_SIM_FOOT_SENSORS_WIDTH};
+  return {p.d_con, MPC_SIM_CONTACTS_WIDTH};
+}
+// the detection event of the wrenches of the step of length dt_step just enqueued on stream st (sim_foot_sensors.h), when the model is on
+static void sim_foot_sensors_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
+  const SimPlant& p = s->plant;
+  if (!p.d_fs) return;
+  SimFootSensorsArgs a;
+  a.wr = p.d_simwr; a.con = p.d_con; a.params = p.d_fs; a.rows = sim_foot_sensors_rows(s); a.dt = dt_step;
+  hipLaunchKernelGGL(k_sim_foot_sensors, dim3((unsigned)s->L.B), dim3(SIM_FS_THREADS), 0, st, a);
+  HIP_OK(hipGetLastError());
+}
+// the state rows after arming: det = the in_contact pair of the contact rule's rows (`con` the rows on the host, NULL: read from the device),
+// everything else 0.  Host work, not part of the steady loop
+static void sim_foot_sensors_arm(mpc_solver* s, const double* con) {
+  if (!s->plant.d_fs) return;
+  const Layout& L = s->L;
+  std::vector<double> c;
+  if (!con) {
+    c.resize((size_t)L.B * MPC_SIM_CONTACTS_WIDTH);
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, c.data(), s->plant.d_con, c.size() * sizeof(double), hipMemcpyDeviceToHost);
+    con = c.data();
+  }
+  std::vector<double> h((size_t)L.B * MPC_SIM_FOOT_SENSORS_WIDTH, 0.0);
+  for (int b = 0; b < L.B; ++b)
+    for (int i = 0; i < 2; ++i) h[(size_t)b * MPC_SIM_FOOT_SENSORS_WIDTH + i] = con[(size_t)b * MPC_SIM_CONTACTS_WIDTH + i] != 0.0 ? 1.0 : 0.0;
+  HIP_OK(hipStreamSynchronize(s->stream));
+  copy_sync(s, sim_foot_sensors_rows(s), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+}
+static void sim_foot_sensors_drop(mpc_solver* s) {
+  sim_realloc(s, s->plant.d_fs, 0);
+  s->plant.h_fs.clear();
+  s->plant.fs_feed = 0;
+}
+
 // the estimation event of the measured states xm and the true states xt on stream st (sim_estimator.h), when the estimator is on: it reads the rows
-// of the contact rule as they stand on the stream
+// of the contact rule, or of the contact detector when that feeds it (sim_contact_rows), as they stand on the stream
 static void sim_estimator_enqueue(mpc_solver* s, hipStream_t st, const double* xm, const double* xt) {
   const SimPlant& p = s->plant;
   if (!p.d_est) return;
   const Layout& L = s->L;
   SimEstimatorArgs a;
   a.mi = s->d_model_i; a.md = s->d_model_d; a.nv = L.n / 2; a.nq = L.nx - L.n / 2;
-  a.xm = xm; a.xt = xt; a.con = p.d_con; a.params = p.d_est; a.xe = sim_estimator_est(s); a.rows = sim_estimator_rows(s);
+  const SimContactRows cr = sim_contact_rows(s, MPC_SIM_FOOT_SENSORS_FEED_ESTIMATOR);
+  a.xm = xm; a.xt = xt; a.con = cr.rows; a.con_width = cr.width; a.params = p.d_est; a.xe = sim_estimator_est(s); a.rows = sim_estimator_rows(s);
   hipLaunchKernelGGL(k_sim_estimator, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
 }
@@ -214,17 +257,21 @@ static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
 // want them.  Then the record and the metrics of the step: the new state, the applied torque, its wrenches, the rows it was integrated with.  The
 // contact rule: it rewrites the rows for the NEXT step from the new state and this step's wrenches.  The sensor model last: the measurement event of
 // the new state, over the whole step.  The base-state estimator after it: the estimation event of that measurement (the true state without a
-// sensor model) and of the rows the contact rule just wrote; nothing of this step reads either, the controllers of the next step do (sim_measured).
+// sensor model) and of the rows the contact rule just wrote; nothing of this step reads either, the controllers of the next step do (sim_measured).  Between the two, the foot force sensors and
+// the contact detector: the detection event of this step's wrenches (which the dynamics then always write), so that an estimator fed by detection reads
+// the pair this step's event left, and the low-level QPs of the next step the same pair.  In one line: actuator model -> dynamics -> record -> metrics
+// -> contact rule -> sensors -> foot sensors -> estimator.
 static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& args, int substeps, double dt, bool want_wrenches) {
   const SimPlant& p = s->plant;
   sim_actuators_enqueue(s, st, substeps * dt);
   launch_eval_multibody(st, args, s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, p.push_width ? p.d_push : nullptr, true,
-                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con) ? p.d_simwr : nullptr, p.push_width ? p.push_width : 3, p.d_con);
+                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con || p.d_fs) ? p.d_simwr : nullptr, p.push_width ? p.push_width : 3, p.d_con);
   HIP_OK(hipGetLastError());
   sim_record_enqueue(s, st);
   sim_metrics_enqueue(s, st, substeps * dt);
   sim_contacts_enqueue(s, st);
   sim_sensors_enqueue(s, st, s->d_x0, substeps * dt);
+  sim_foot_sensors_enqueue(s, st, substeps * dt);
   sim_estimator_enqueue(s, st, sim_sensed(s), s->d_x0);
 }
 
@@ -324,15 +371,17 @@ int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
       if (cfg->release_steps < 1) throw std::runtime_error("sim_contacts: release_steps must be >= 1");
     }
     sim_realloc(s, s->plant.d_con, cfg ? (size_t)L.B * MPC_SIM_CONTACTS_WIDTH : 0);
-    if (!cfg) {  // (the terrain and the estimator go with the rows; a reset keeps them)
+    if (!cfg) {  // (the terrain, the estimator and the contact detector go with the rows; a reset keeps them)
       sim_terrain_drop(s);
       sim_estimator_drop(s);
+      sim_foot_sensors_drop(s);
     }
     if (cfg) {
       s->plant.con_cfg = *cfg;
       s->plant.con_cfg.reserved = 0;
       sim_ensure(s);
       sim_contacts_reset(s);
+      sim_foot_sensors_arm(s, nullptr);  // (the contact detector starts again from the rows just reset)
     }
   })
 }
@@ -367,6 +416,7 @@ int mpc_sim_contacts_set(mpc_solver* s, const double* rows) {
     }
     HIP_OK(hipStreamSynchronize(s->stream));
     copy_sync(s, s->plant.d_con, rows, (size_t)L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyHostToDevice);
+    sim_foot_sensors_arm(s, rows);  // (... and from rows imposed)
   })
 }
 
@@ -688,6 +738,93 @@ int mpc_sim_estimator_set(mpc_solver* s, const double* state) {
 }
 
 int32_t mpc_sim_estimator_width(mpc_solver* s) { return sim_width(s, "sim_estimator_width", [&] { return sim_estimator_width(s->L); }); }
+
+// ---- include/mpc_sim_foot_sensors.h: the per-robot foot force sensors and the contact detector ----------------------------------------------------
+int mpc_sim_foot_sensors(mpc_solver* s, const double* params) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_foot_sensors");
+    const Layout& L = s->L;
+    const size_t np = (size_t)L.B * MPC_SIM_FOOT_SENSORS_PARAMS;
+    if (!params) {
+      sim_foot_sensors_drop(s);
+      return 0;
+    }
+    for (int b = 0; b < L.B; ++b) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
+      const double* r = params + (size_t)b * MPC_SIM_FOOT_SENSORS_PARAMS;
+      const std::string row = "sim_foot_sensors: row " + std::to_string(b);
+      for (int e = 0; e < MPC_SIM_FOOT_SENSORS_PARAMS; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      if (r[0] != std::floor(r[0]) || r[0] < 0.0 || r[0] > MPC_SIM_FOOT_SENSORS_RING - 1)
+        throw std::runtime_error(row + ": delay must be an integer value in [0, " + std::to_string(MPC_SIM_FOOT_SENSORS_RING - 1) + "]");
+      for (int e = 1; e < 6; ++e)
+        if (r[e] < 0.0) throw std::runtime_error(row + ": sigma_f, sigma_m, bias_f, bias_m and time_constant must be >= 0");
+      if (r[7] > r[6]) throw std::runtime_error(row + ": f_off must be <= f_on");
+      for (int e = 8; e < 10; ++e)
+        if (r[e] != std::floor(r[e]) || r[e] < 1.0) throw std::runtime_error(row + ": on_steps and off_steps must be integer values >= 1");
+      if (r[10] != std::floor(r[10]) || r[10] < 0.0 || r[10] >= 4294967296.0) throw std::runtime_error(row + ": seed must be an integer value in [0, 2^32)");
+      for (int e = 11; e < MPC_SIM_FOOT_SENSORS_PARAMS; ++e)
+        if (r[e] != 0.0) throw std::runtime_error(row + ": the reserved entries must be 0");
+    }
+    if (!s->plant.d_con) throw std::runtime_error("sim_foot_sensors: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    sim_realloc(s, s->plant.d_fs, np + (size_t)L.B * MPC_SIM_FOOT_SENSORS_WIDTH);
+    s->plant.h_fs.assign(params, params + np);
+    sim_ensure(s);
+    copy_sync(s, s->plant.d_fs, params, np * sizeof(double), hipMemcpyHostToDevice);
+    sim_foot_sensors_arm(s, nullptr);
+  })
+}
+
+int mpc_sim_foot_sensors_read(mpc_solver* s, double* params, double* state) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_foot_sensors_read");
+    if (!s->plant.d_fs) throw std::runtime_error("sim_foot_sensors_read: the foot sensors are off on this handle (turn them on with mpc_sim_foot_sensors)");
+    if (params) std::copy(s->plant.h_fs.begin(), s->plant.h_fs.end(), params);
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (state) copy_sync(s, state, sim_foot_sensors_rows(s), (size_t)s->L.B * MPC_SIM_FOOT_SENSORS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int mpc_sim_foot_sensors_set(mpc_solver* s, const double* state) {
+  MPC_TRY(s, {
+    if (!state) throw std::runtime_error("sim_foot_sensors_set: state must not be null");
+    sim_check(s, "sim_foot_sensors_set");
+    if (!s->plant.d_fs) throw std::runtime_error("sim_foot_sensors_set: the foot sensors are off on this handle (turn them on with mpc_sim_foot_sensors)");
+    const Layout& L = s->L;
+    const size_t W = MPC_SIM_FOOT_SENSORS_WIDTH;
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = state + (size_t)b * W;
+      const std::string row = "sim_foot_sensors_set: row " + std::to_string(b);
+      for (size_t e = 0; e < W; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      for (int i = 0; i < 2; ++i)
+        if (r[i] != 0.0 && r[i] != 1.0) throw std::runtime_error(row + ": det must be 0 or 1");
+      if (r[0] == 0.0 && r[1] == 0.0) throw std::runtime_error(row + " has no sole detected (the detector never reports an empty set)");
+      for (int e = SIM_FS_O_ABOVE; e < SIM_FS_O_WF; ++e)
+        if (r[e] < 0.0) throw std::runtime_error(row + ": the counters above and below must be >= 0");
+      for (int e = SIM_FS_O_COUNTS; e < SIM_FS_O_RING; ++e)
+        if (r[e] < 0.0) throw std::runtime_error(row + ": the confusion counts must be >= 0");
+      const double head = r[W - 2], count = r[W - 1];
+      if (head != std::floor(head) || head < 0.0 || head >= MPC_SIM_FOOT_SENSORS_RING)
+        throw std::runtime_error(row + ": head must be an integer value in [0, " + std::to_string(MPC_SIM_FOOT_SENSORS_RING) + ")");
+      if (count < 0.0) throw std::runtime_error(row + ": count must be >= 0");
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, sim_foot_sensors_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+int32_t mpc_sim_foot_sensors_width(mpc_solver* s) { return sim_width(s, "sim_foot_sensors_width", [&] { return MPC_SIM_FOOT_SENSORS_WIDTH; }); }
+
+int mpc_sim_foot_sensors_feed(mpc_solver* s, int32_t consumers) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_foot_sensors_feed");
+    if (!s->plant.d_fs) throw std::runtime_error("sim_foot_sensors_feed: the foot sensors are off on this handle (turn them on with mpc_sim_foot_sensors)");
+    if (consumers & ~(MPC_SIM_FOOT_SENSORS_FEED_ESTIMATOR | MPC_SIM_FOOT_SENSORS_FEED_QP))
+      throw std::runtime_error("sim_foot_sensors_feed: unknown consumer bit in " + std::to_string(consumers) + " (1: the estimator, 2: the low-level QPs)");
+    HIP_OK(hipStreamSynchronize(s->stream));
+    s->plant.fs_feed = consumers;
+  })
+}
 
 // ---- include/mpc_abi.h: one step under the caller's torques -------------------------------------------------------------------------------------
 int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32_t substeps, double dt, double* wrenches) {

@@ -61,7 +61,18 @@ and the base linear velocity; (B, 16), one row of 16 for every robot, or a dict 
 handle after the sensors, at ``x_meas`` (mpc_sim_estimator, include/mpc_sim_estimator.h; HIP library only).  ``x`` stays the TRUE state, ``x_meas``
 the sensor measurement, ``x_est`` is the estimate: what the feedback laws, the low-level QPs and the task errors work at and what ``x_prev`` /
 ``c_prev`` hold, on both forms of a tick (the host glue reads ``x_est`` back before each step and applies nothing else).  ``set_estimator`` changes or
-removes the estimator later (it arms at the current ``x_meas``); ``set_sensors`` arms it again, after the sensors."""
+removes the estimator later (it arms at the current ``x_meas``); ``set_sensors`` arms it again, after the sensors.
+
+``foot_sensors`` (all three pipelines, with ``contact_rule``): None, nobody measures the contact wrenches; or the parameter rows of the per-robot foot
+force sensors and contact detector (``foot_sensors``: latency, noise, offsets, a low-pass, thresholds with hysteresis and debounce; (B, 16), one row
+of 16 for every robot, or a dict by field name of scalars or (B,) arrays), armed on the simulator handle on the rule's ``in_contact`` pairs
+(mpc_sim_foot_sensors, include/mpc_sim_foot_sensors.h; HIP library only).  On its own the model only observes: ``detected`` is the pair every robot
+takes to stand, ``sim.read_foot_sensors()["counts"]`` the confusion against the plant.  ``detected_contacts``: a subset of ``("estimator", "qp")``
+naming who works from the detected pair instead of the plant's: the events of the base-state estimator, and the "plant" rows of ``contact_source``
+(``"qp"``: ``KinodynamicPipeline`` and ``CentroidalPipeline`` with a ``contact_source`` other than ``"schedule"``; ``qp_contacts()`` then counts plan
+against detection).  The selection is made on the device on both forms of a tick for the estimator (its kernel runs inside every simulator step);
+for the QPs ``tick()`` selects on the device and ``tick(host_glue=True)`` reads the detector rows back before each step.  The plant, its record, its
+metrics and its contact rule keep the truth.  ``set_foot_sensors`` changes or removes the model later."""
 from __future__ import annotations
 
 import numpy as np
@@ -69,6 +80,7 @@ import numpy as np
 from . import _capi as K
 from . import actuator_model as _actuator_model
 from . import contact_rule as _contact_rule
+from . import foot_sensors as _foot_sensors
 from . import qp_utils
 from . import sensor_model as _sensor_model
 from . import state_estimator as _state_estimator
@@ -219,6 +231,47 @@ class _Actuators:
     _actuators_on = False
     _sensors_on = False
     _estimator_rows = None
+    _foot_rows = None
+    _detected_contacts = ()
+
+    def _check_detected(self, name, foot_sensors, detected_contacts, contact_rule, contact_source=None):
+        """``foot_sensors`` / ``detected_contacts`` of a pipeline, checked before any library call -> the consumers as a tuple"""
+        names = () if detected_contacts is None else ((detected_contacts,) if isinstance(detected_contacts, str) else tuple(detected_contacts))
+        _foot_sensors.feed_mask(names)
+        if foot_sensors is not None and contact_rule is None:
+            raise ValueError("%s: foot_sensors needs contact_rule (the detector is armed on the rows of the unilateral contact rule; contact_rule={} "
+                             "turns it on)" % name)
+        if names and foot_sensors is None:
+            raise ValueError("%s: detected_contacts=%r needs foot_sensors (the rows of the detector)" % (name, names))
+        if "qp" in names and contact_source in (None, "schedule"):
+            raise ValueError("%s: detected_contacts \"qp\" needs a low-level QP with contact_source \"plant\" or \"both\" (the detected pair takes the "
+                             "place of the plant's rows there)" % name)
+        return tuple(n for n in _foot_sensors.CONSUMERS if n in names)
+
+    def set_foot_sensors(self, params, detected_contacts=None):
+        """Arm (and reset) the per-robot foot force sensors and contact detector on ``self.sim``: ``params`` in the forms of
+        ``NativeSolver.foot_sensors``; needs ``contact_rule``.  ``detected_contacts``: who works from the detected pair (None: as before).  ``params``
+        None turns the model off, and the consumers go back to the plant's pair."""
+        if params is None:
+            if self._foot_rows is not None:
+                self.sim.foot_sensors(None)
+            self._foot_rows, self._detected_contacts = None, ()
+            return
+        if detected_contacts is not None:
+            names = self._check_detected(type(self).__name__, params, detected_contacts, self.contact_rule, getattr(self, "contact_source", None))
+        else:
+            names = self._detected_contacts
+        rows = _foot_sensors.rows(params, self.batch)
+        self.sim.foot_sensors(rows)
+        self.sim.foot_sensors_feed(names)
+        self._foot_rows, self._detected_contacts = rows, names
+
+    @property
+    def detected(self):
+        """(B, 2) the pair every robot's detector reports; without ``foot_sensors`` the ``in_contact`` pair of the contact rule"""
+        if self._foot_rows is not None:
+            return self.sim.read_foot_sensors()["det"].copy()
+        return self.sim.read_contacts()["in_contact"].copy()
 
     def set_sensors(self, params):
         """Arm (and reset) the per-robot sensor model on ``self.sim`` at the current true states ``self.x``: ``params`` in the forms of
@@ -300,7 +353,7 @@ class _QpContactSource:
         if self.contact_source == "schedule":
             self._qp_used = _contact_rule.qp_contact_states("schedule", cs, np.ones((self.batch, 2)))
             return self._qp_used
-        p = self.sim.read_contacts()["in_contact"]
+        p = self.detected if "qp" in self._detected_contacts else self.sim.read_contacts()["in_contact"]   # (the detector's rows, read back)
         self._qp_used = _contact_rule.qp_contact_states(self.contact_source, cs, p)
         self._qp_counts = _contact_rule.qp_contact_counts(self._qp_counts, cs, p)
         return self._qp_used
@@ -330,13 +383,16 @@ class _QpContactSource:
 
 class KinodynamicPipeline(_QpContactSource, _Actuators):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
-                 terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, **ens_kw):
+                 terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, foot_sensors=None,
+                 detected_contacts=(), **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
         ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model, ``sensors``: None or the rows of the
-        sensor model, ``estimator``: None or the rows of the base-state estimator (module docstring)."""
+        sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the rows of the foot force sensors,
+        ``detected_contacts``: who works from the detected contacts (module docstring)."""
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("KinodynamicPipeline", contact_source, contact_rule)
+        detected_contacts = self._check_detected("KinodynamicPipeline", foot_sensors, detected_contacts, contact_rule, contact_source)
         self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
         walk = _checked_walk("KinodynamicPipeline", walk, self.batch)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
@@ -358,6 +414,8 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
         if sensors is not None:
             self.set_sensors(sensors)
+        if foot_sensors is not None:   # (before the estimator: its arming event already reads the pair it will be fed)
+            self.set_foot_sensors(foot_sensors, detected_contacts)
         if estimator is not None:
             self.set_estimator(estimator)
         self.x_prev = self.x_est.copy()                  # the measurement of the tick before (the solve's initial condition)
@@ -522,15 +580,17 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
                  sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, sensors=None,
-                 estimator=None, **ens_kw):
+                 estimator=None, foot_sensors=None, detected_contacts=(), **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
         dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model,
-        ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state estimator (module docstring)."""
+        ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the
+        rows of the foot force sensors, ``detected_contacts``: who works from the detected contacts (module docstring)."""
         from .ensemble import ensemble_initial_states
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("CentroidalPipeline", contact_source, contact_rule)
+        detected_contacts = self._check_detected("CentroidalPipeline", foot_sensors, detected_contacts, contact_rule, contact_source)
         self.terrain = _checked_terrain("CentroidalPipeline", terrain, contact_rule, self.batch)
         walk = _checked_walk("CentroidalPipeline", walk, self.batch)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
@@ -566,6 +626,8 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
             self.set_actuators(actuators)
         if sensors is not None:
             self.set_sensors(sensors)
+        if foot_sensors is not None:   # (before the estimator: its arming event already reads the pair it will be fed)
+            self.set_foot_sensors(foot_sensors, detected_contacts)
         if estimator is not None:
             self.set_estimator(estimator)
         if sensors is not None or estimator is not None:
@@ -709,12 +771,14 @@ class FullDynamicPipeline(_Actuators):
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
-                 sensors=None, estimator=None, **ens_kw):
+                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
         actuator model, ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state
-        estimator (module docstring of pipeline.py)."""
+        estimator, ``foot_sensors``: None or the rows of the foot force sensors, ``detected_contacts``: () or ("estimator",) (module docstring of
+        pipeline.py)."""
+        detected_contacts = self._check_detected("FullDynamicPipeline", foot_sensors, detected_contacts, contact_rule)
         self.terrain = _checked_terrain("FullDynamicPipeline", terrain, contact_rule, int(batch))
         walk = _checked_walk("FullDynamicPipeline", walk, int(batch))
         if ens_kw.get("closed_loop") is not None:
@@ -739,6 +803,8 @@ class FullDynamicPipeline(_Actuators):
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
         if sensors is not None:
             self.set_sensors(sensors)
+        if foot_sensors is not None:   # (before the estimator: its arming event already reads the pair it will be fed)
+            self.set_foot_sensors(foot_sensors, detected_contacts)
         if estimator is not None:
             self.set_estimator(estimator)
         self.x_prev = self.x_est.copy()                  # the measurement of the period before (the solve's initial condition)
