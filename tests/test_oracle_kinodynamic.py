@@ -1,5 +1,8 @@
-"""Pins the oracle's kinodynamic stage (kinodynamic_talos.py:107-180): finite differences of every first-order block,
-consistency of the base acceleration with the centroidal momentum balance, convergence of the cold solve."""
+"""Consistency of the oracle's kinodynamic stage (kinodynamic_talos.py:107-180): finite differences of the oracle's own
+values for every first-order block, the base acceleration against the centroidal momentum balance at the rest posture,
+convergence of the cold solve.  The VALUES of the stage (xdot, xnext, f, cost, cval with its 23 rows per contact) are
+held to an independent numpy restatement, near and far from the nominal posture, by tests/test_stage_reference.py
+(oracle, CPU port) and tests/test_gpu_stage_reference.py (HIP)."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,9 @@
-"""Pins the CPU oracle's whole-body stage evaluation (oracle/stage.hpp) by construction, since no golden
-vectors of the reference exist: central finite differences on the manifold for every
-first-order block of the LQ knot, and the algebraic identities of the constrained forward dynamics."""
+"""Consistency of the CPU oracle's whole-body stage evaluation (oracle/stage.hpp), since no golden vectors of the
+reference exist: central finite differences OF THE ORACLE'S OWN VALUES on the manifold for every
+first-order block of the LQ knot, and the algebraic identities of the constrained forward dynamics at the rest
+posture.  These say that the derivatives belong to the values; the VALUES themselves (xdot, wrench, xnext, f, cost,
+cval) are held to an independent numpy restatement of the stage, near and far from the nominal posture, by
+tests/test_stage_reference.py (oracle, CPU port) and tests/test_gpu_stage_reference.py (HIP)."""
 import numpy as np
 import pytest
 

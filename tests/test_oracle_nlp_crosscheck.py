@@ -8,6 +8,7 @@ import pytest
 from scipy.optimize import minimize
 
 from tests import _oracle
+from tests._stage_reference import centroidal_wrench_sums, centroidal_xdot
 from mpc_benchmark_amd.aligator._core import wrench_cone_matrix
 from mpc_benchmark_amd.problems import common
 from mpc_benchmark_amd.problems.centroidal import CentroidalProblem
@@ -28,17 +29,10 @@ def _nlp(cp, N):
         return xs, us
 
     def wrench_sums(x, u):
-        f = np.zeros(3); tau = np.zeros(3)
-        for i in range(2):
-            if cs[i]:
-                fi, ti = u[6 * i:6 * i + 3], u[6 * i + 3:6 * i + 6]
-                f += fi
-                tau += np.cross(p[i] - x[:3], fi) + ti
-        return f, tau
+        return centroidal_wrench_sums(x, u, cs, p)
 
-    def xdot(x, u):
-        f, tau = wrench_sums(x, u)
-        return np.concatenate((x[3:6] / m, f + m * g, tau))
+    def xdot(x, u):  # (shared with the value reference of the stage kernels, tests/_stage_reference.py)
+        return centroidal_xdot(x, u, m, g, cs, p)
 
     def cost(z):
         xs, us = split(z)
