@@ -16,6 +16,7 @@ from . import actuator_model as _actuator_model
 from . import sensor_model as _sensor_model
 from . import state_estimator as _state_estimator
 from . import foot_sensors as _foot_sensors
+from . import plant_model as _plant_model
 from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
 
@@ -197,6 +198,13 @@ _SIM_FOOT_SENSORS_SIGNATURES = {
     "mpc_sim_foot_sensors_feed": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
+# include/mpc_sim_plant.h: exported by the HIP library alone, bound when present (``NativeSolver.plant`` / ``read_plant``)
+_SIM_PLANT_SIGNATURES = {
+    "mpc_sim_plant": (C.c_int, [C.c_void_p, _DP, _DP]),
+    "mpc_sim_plant_read": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
+    "mpc_sim_plant_width": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_sim_terrain.h: exported by the HIP library alone, bound when present (``NativeSolver.terrain`` / ``read_terrain`` / ``terrain_height``)
 class MpcSimTerrainConfig(C.Structure):
     _fields_ = [("n_boxes", C.c_int32), ("per_robot", C.c_int32)]
@@ -246,7 +254,7 @@ def bind_library(path):
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_ESTIMATOR_SIGNATURES.items()) + list(_SIM_FOOT_SENSORS_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
+            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_ESTIMATOR_SIGNATURES.items()) + list(_SIM_FOOT_SENSORS_SIGNATURES.items()) + list(_SIM_PLANT_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -289,6 +297,7 @@ class NativeSolver:
     def __init__(self, lib, dims: MpcDims):
         self.lib = lib
         self.dims = dims
+        self._model_nj = None  # the joint count of the model tables in force (set_model)
         self._h = C.c_void_p()
         rc = lib.mpc_create(C.byref(dims), C.byref(self._h))
         if rc != 0:
@@ -318,6 +327,7 @@ class NativeSolver:
     def set_model(self, itab, dtab):
         itab, dtab = _i32(itab), _f64(dtab)
         self._check(self.lib.mpc_set_model(self._h, itab.ctypes.data_as(_IP), itab.size, _dp(dtab), dtab.size), "mpc_set_model")
+        self._model_nj = int(itab[0])  # (the joint count of the tables in force: ``plant`` checks the shape of ``link_scale`` with it)
 
     def set_stage(self, k, desc, params):
         desc, params = _i32(desc), _f64(params)
@@ -544,6 +554,46 @@ class NativeSolver:
         if r.shape != (d.batch, _actuator_model.width(d.nu)):
             raise ValueError("set_actuators: state rows of shape (%d, %d) expected, got %s" % (d.batch, _actuator_model.width(d.nu), r.shape))
         self._check(fn(self._h, _dp(r)), "mpc_sim_actuators_set")
+
+    # -- include/mpc_sim_plant.h (HIP library only): per-robot plant inertias of the torque-driven simulator steps ---------------------------------
+    def _sim_plant(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the plant model of torque-driven simulator steps is HIP only "
+                               "(libmpc_hip.so, include/mpc_sim_plant.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def plant(self, rows, link_scale=None):
+        """Integrate every robot of this simulator handle with its own link inertias (mpc_sim_plant; ``plant_model`` is the definition).  ``rows``:
+        (B, 16) rows, one row of 16 for every robot, or a dict by ``plant_model.FIELDS`` name of scalars or (B,) arrays (missing fields: the
+        identity value); ``link_scale``: None or (B, nj), every link's own mass factor.  Builds the per-robot model tables on the device; the
+        controllers' handles keep the nominal model.  None turns the model off."""
+        fn = self._sim_plant("mpc_sim_plant")
+        if rows is None:
+            self._check(fn(self._h, None, None), "mpc_sim_plant")
+            return
+        d = self.dims
+        p = _f64(_plant_model.rows(rows, d.batch))
+        ls = None
+        if link_scale is not None:
+            ls = _f64(link_scale)
+            nj = self._model_nj
+            if nj is None:
+                raise RuntimeError("plant: no model is set on this handle (set_model first)")
+            if ls.shape != (d.batch, nj):
+                raise ValueError("plant: link_scale of shape (%d, %d) expected, got %s" % (d.batch, nj, ls.shape))
+        self._check(fn(self._h, _dp(p), _dp(ls)), "mpc_sim_plant")
+
+    def read_plant(self):
+        """The plant model in force (mpc_sim_plant_read) -> dict: ``params`` (B, 16), ``link_scale`` (B, nj) (ones when none was given), ``tables``
+        (B, nd) the model table every robot is integrated with."""
+        fn = self._sim_plant("mpc_sim_plant_read")
+        nd = self._sim_plant("mpc_sim_plant_width")(self._h)
+        if nd < 0:
+            self._check(-1, "mpc_sim_plant_width")
+        d = self.dims
+        par, ls, tab = np.zeros((d.batch, _plant_model.PARAMS)), np.zeros((d.batch, self._model_nj)), np.zeros((d.batch, nd))
+        self._check(fn(self._h, _dp(par), _dp(ls), _dp(tab)), "mpc_sim_plant_read")
+        return {"params": par, "link_scale": ls, "tables": tab}
 
     # -- include/mpc_sim_sensors.h (HIP library only): the per-robot sensor model between the torque-driven simulator steps and the controllers -----
     def _sim_sensors(self, name):

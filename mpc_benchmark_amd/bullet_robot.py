@@ -27,6 +27,10 @@ holds, blended with the measurement; ``measureState()`` then returns the estimat
 ``foot_sensors=`` / ``setFootSensors(params, detected_contacts=())`` (HIP library only, with ``device_contacts=True``) measure the contact wrenches of
 every step and run the contact detector of ``foot_sensors`` on them (mpc_sim_foot_sensors, include/mpc_sim_foot_sensors.h); ``detectedContacts()``
 is the pair the robot takes to stand, and ``detected_contacts=("estimator",)`` lets the estimator work from it.  ``in_contact`` stays the plant's.
+``plant=`` / ``setPlant(rows, link_scale=None)`` (HIP library only) give the simulated robot other link inertias than ``model`` holds (``plant_model``:
+a payload, a mass error, a displaced centre of mass; mpc_sim_plant, include/mpc_sim_plant.h).  ``model`` stays the nominal one, what a controller is
+built from; ``plantModel()`` is what is integrated.  The host contact rule lowers the model again at every catch: the library rebuilds the plant's
+table from the rows in force.
 
 Differences from PyBullet worth knowing: ``measureState`` returns the base velocity in the LOCAL frame of the base (Pinocchio's
 convention, which is what the scripts assume when they copy it into the state, talos_utils.py:337-348); PyBullet reports it in the
@@ -55,7 +59,7 @@ class BulletRobot:
 
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
                  inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
-                 device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None):
+                 device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None, plant=None):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -72,6 +76,7 @@ class BulletRobot:
         self._sensors = sensors  # params of setSensors, armed at initializeJoints
         self._estimator = estimator  # params of setEstimator, armed at initializeJoints after the sensors
         self._foot_sensors = None if foot_sensors is None else (foot_sensors, ())  # (params, detected_contacts) of setFootSensors, armed at initializeJoints
+        self._plant = None if plant is None else (plant, None)  # (rows, link_scale) of setPlant, armed at initializeJoints
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
         self._native = None
@@ -117,6 +122,8 @@ class BulletRobot:
                                    "release_steps": self.release_steps})
             if self.terrain is not None:
                 self._native.terrain(self.terrain)
+        if self._plant is not None:
+            self.setPlant(*self._plant)
         if self._actuators is not None:
             self.setActuators(*self._actuators)
         if self._foot_sensors is not None:  # (before the estimator: its arming event already reads the pair it will be fed)
@@ -343,6 +350,35 @@ class BulletRobot:
         if limit is None:
             limit = np.asarray(self.model.effortLimit, dtype=float)[6:]
         self._native.actuators(params, limit=limit, friction_shape=friction_shape)
+
+    def setPlant(self, rows, link_scale=None):
+        """The plant's own link inertias (``plant_model``; HIP library only): ``rows`` one row of 16, (1, 16), or a dict by field name (missing fields:
+        the identity value); ``link_scale``: None or (1, nj) / (nj,), every link's own mass factor; None: off.  Body indices are table joint indices
+        of the REDUCED model (``model.names[j + 1]``).  Checked here before any library call; before ``initializeJoints`` it is kept for then."""
+        self._plant = None if rows is None else (rows, link_scale)
+        if self._native is None:
+            return
+        if rows is None:
+            if hasattr(self._native.lib, "mpc_sim_plant"):
+                self._native.plant(None)
+            return
+        rows, link_scale = self._checked_plant()
+        self._native.plant(rows, link_scale=link_scale)
+
+    def _checked_plant(self):
+        from . import plant_model as _plant_model
+        rows, link_scale = self._plant
+        nj = self.model.njoints - 1
+        if link_scale is not None:
+            link_scale = np.asarray(link_scale, dtype=float).reshape(1, -1)
+        return _plant_model.validate(_plant_model.rows(rows, 1), nj, link_scale)
+
+    def plantModel(self):
+        """the ``minipin.Model`` the simulator integrates: ``model`` with the inertias of ``setPlant`` (``model`` itself without one)"""
+        if self._plant is None:
+            return self.model
+        from . import plant_model as _plant_model
+        return _plant_model.models(self.model, *self._checked_plant())[0]
 
     def setSensors(self, params):
         """The sensor model between the dynamics and ``measureState()`` (``sensor_model``; HIP library only): ``params`` one row of 16, (1, 16), or a

@@ -307,6 +307,9 @@ cand_loop:  // (TRIAL == 1 with mb.ncand_loop: next backtracking candidate of th
 
   const int32_t* mi = a.model_i;
   const double* md = a.model_d;
+  if constexpr (TRIAL == 2) {  // the plant model (include/mpc_sim_plant.h): robot b is integrated with its own table
+    if (mb.sim_model) md = mb.sim_model + (size_t)b * mb.sim_model_stride;
+  }
   const int nframes = mi[3];
   const int32_t* mj = mi + MPC_MODEL_HEADER_WORDS;
   const int32_t* mframe = mj + MPC_MODEL_JOINT_WORDS * nj;

@@ -128,6 +128,8 @@ struct MbArgs {
   double* sim_wrench;     // TRIAL == 2: contact wrenches of the last sub-step [B][2][6], or nullptr
   const double* sim_contacts;  // TRIAL == 2: the rows of the contact rule [B][MPC_SIM_CONTACTS_WIDTH] (include/mpc_sim_contacts.h), or nullptr:
                                // each robot integrates the contacts of stage 0 its row holds, at the row's anchors
+  const double* sim_model;     // TRIAL == 2: the per-robot model tables [B][sim_model_stride] of the plant model (include/mpc_sim_plant.h), or
+  size_t sim_model_stride;     // nullptr: every robot is integrated with the handle's one table
 };
 
 
@@ -135,5 +137,5 @@ struct MbArgs {
 void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
                            bool trial, int cand0 = 0, int ncand = 1, int sim_substeps = 0, double sim_dt = 0.0, bool with_derivs = false,
                            const double* f_ext = nullptr, bool contact_dyn = true, const double* sim_u = nullptr, double* sim_wrench = nullptr,
-                           int f_ext_width = 3, const double* sim_contacts = nullptr);
+                           int f_ext_width = 3, const double* sim_contacts = nullptr, const double* sim_model = nullptr, size_t sim_model_stride = 0);
 const void* eval_multibody_kernel(int trial);  // entry point of k_eval_multibody<trial> (occupancy tooling)

@@ -37,6 +37,7 @@
 #include "sim_sensors.h"
 #include "sim_estimator.h"
 #include "sim_foot_sensors.h"
+#include "sim_plant.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
 #include "../../include/mpc_walk_poses.h"
@@ -106,9 +107,15 @@ struct SimPlant {
   double* d_fs = nullptr;
   std::vector<double> h_fs;  // params as they are in force
   int fs_feed = 0;
+  // include/mpc_sim_plant.h: the per-robot plant inertias (nullptr: off, every robot is integrated with the handle's one table), one allocation:
+  // params [B][16] | link_scale [B][nj] | tables [B][plant_nd]
+  double* d_plant = nullptr;
+  std::vector<double> h_plant;  // params | link_scale (ones when none was given) as they are in force
+  size_t plant_nd = 0;          // doubles of one robot's table: the handle's model_nd when the tables were built
+  size_t plant_off = 0;         // doubles before the tables: B (16 + nj) with the joint count the rows were armed on
   // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
   void free_owned() {
-    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est, &d_fs}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est, &d_fs, &d_plant}) if (*p) { (void)hipFree(*p); *p = nullptr; }
   }
 };
 
@@ -139,6 +146,7 @@ struct mpc_solver {
   std::vector<double> h_params;            // host mirror of the stage parameters (an unchanged stage is not uploaded again)
   std::vector<int32_t> h_len;              // per slot: n_desc, n_params of the mirror (0, 0 = nothing uploaded yet)
   std::vector<int> h_model_i;
+  size_t model_nd = 0;  // doubles of d_model_d
   bool have_model = false;
   size_t mb_work_stride = 0;
   bool perfect_feedback = false;
@@ -675,6 +683,7 @@ static void launch_shift(mpc_solver* s) {
 }
 
 static int slot_of(const mpc_solver* s, int k) { return k < s->L.N ? (s->head + k) % s->L.N : s->L.N; }
+static void sim_plant_build(mpc_solver* s);  // sim_host.h: mpc_set_model rebuilds the per-robot tables of an armed plant model
 
 // ---- kernel sequences -----------------------------------------------------------------------------
 static void launch_eval(mpc_solver* s, bool trial, int cand0 = 0, int ncand = 1, bool with_derivs = false) {
@@ -996,6 +1005,14 @@ int mpc_set_model(mpc_solver* s, const int32_t* itab, int32_t n_i, const double*
     if (n_i < MPC_MODEL_HEADER_WORDS + MPC_MODEL_JOINT_WORDS * nj + nf + ncn ||
         n_d < MPC_MODEL_HEADER_DOUBLES + MPC_MODEL_JOINT_DOUBLES * nj + MPC_MODEL_FRAME_DOUBLES * nf + MPC_MODEL_CONTACT_DOUBLES * ncn)
       throw std::runtime_error("model table size mismatch");
+    if (s->plant.d_plant && nj != s->L.nj)  // (before anything changes: the rows in force name joints of the model they were armed on)
+      throw std::runtime_error("set_model: the plant model is on (mpc_sim_plant) and its rows were armed on a model of " + std::to_string(s->L.nj) +
+                               " joints; this one has " + std::to_string(nj) + ": turn the plant model off first");
+    if (s->dims.space == MPC_SPACE_MULTIBODY) {  // (every check of the tables before anything changes: a refused model leaves the one in force, and the
+                                                 // per-robot tables an armed plant model built from it, whole)
+      if (itab[2] * 2 != s->L.n || itab[1] + itab[2] != s->L.nx) throw std::runtime_error("model dimensions do not match the state space");
+      check_multibody_model(itab, n_i);
+    }
     HIP_OK(hipStreamSynchronize(s->stream));
     // device copy of the int table = the caller's table followed by the 64-bit tree masks the whole-body kernel walks
     // (ancestors of a body, bodies of its subtree, dofs on its root path), two int32 words each
@@ -1034,10 +1051,9 @@ int mpc_set_model(mpc_solver* s, const int32_t* itab, int32_t n_i, const double*
     copy_sync(s, s->d_model_i, ext.data(), ext.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     copy_sync(s, s->d_model_d, dtab, n_d * sizeof(double), hipMemcpyHostToDevice);
     s->h_model_i.assign(itab, itab + n_i);
+    s->model_nd = (size_t)n_d;
     s->L.nj = nj; s->LT.nj = nj; s->LT.model_mask_off = s->L.model_mask_off;
     if (s->dims.space == MPC_SPACE_MULTIBODY) {
-      if (itab[2] * 2 != s->L.n || itab[1] + itab[2] != s->L.nx) throw std::runtime_error("model dimensions do not match the state space");
-      check_multibody_model(itab, n_i);
       if (!s->d_mbwork) {
         s->mb_work_stride = multibody_work_doubles(s->L);
         s->d_mbwork = s->alloc<double>((size_t)s->L.B * (s->L.N + 2) * s->mb_work_stride + 8);  // one slot more per instance: the speculative knot
@@ -1046,6 +1062,7 @@ int mpc_set_model(mpc_solver* s, const int32_t* itab, int32_t n_i, const double*
     }
     s->have_model = true;
     HIP_OK(hipStreamSynchronize(s->stream));
+    sim_plant_build(s);  // (the plant model, when it is on: every robot's table again, from the rows in force)
   })
 }
 

@@ -1,6 +1,6 @@
 // sim_host.h — host side of the torque-driven simulator (the plant): mpc_simulate_torque and the entry points of include/mpc_sim_ext.h (push, record),
-// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h, mpc_sim_estimator.h and mpc_sim_foot_sensors.h.  Its state is mpc_solver::plant (SimPlant); its kernels
-// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h, sim_estimator.h and sim_foot_sensors.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
+// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h, mpc_sim_estimator.h, mpc_sim_foot_sensors.h and mpc_sim_plant.h.  Its state is mpc_solver::plant (SimPlant); its kernels
+// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h, sim_estimator.h, sim_foot_sensors.h and sim_plant.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
 // loops of the three pipelines in pipeline_loops.h — goes through sim_steps_check, sim_steps_begin and sim_step_enqueue: an extension of the simulator
 // is added there, once.  Included at the end of mpc_hip.hip (mpc_solver, MPC_TRY, copy_sync, slot_of).
 #pragma once
@@ -49,13 +49,19 @@ template <class F> static int32_t sim_width(mpc_solver* s, const char* who, F&& 
   }
 }
 
+// the model tables the plant is integrated and recorded with (include/mpc_sim_plant.h): robot b's own table at sim_plant_md + b * sim_plant_stride
+// while the plant model is on, the handle's one table (stride 0) otherwise.  Everything else keeps s->d_model_d, the controllers' belief
+static double* sim_plant_tables(const mpc_solver* s) { return s->plant.d_plant + s->plant.plant_off; }
+static const double* sim_plant_md(const mpc_solver* s) { return s->plant.d_plant ? sim_plant_tables(s) : s->d_model_d; }
+static size_t sim_plant_stride(const mpc_solver* s) { return s->plant.d_plant ? s->plant.plant_nd : 0; }
+
 // the record of the step just enqueued on stream st (sim_record.h), when recording is on
 static void sim_record_enqueue(mpc_solver* s, hipStream_t st) {
   SimPlant& p = s->plant;
   if (p.rec_cap <= 0) return;
   const Layout& L = s->L;
   SimRecordArgs r;
-  r.mi = s->d_model_i; r.md = s->d_model_d; r.nv = L.n / 2; r.nq = L.nx - L.n / 2;
+  r.mi = s->d_model_i; r.md = sim_plant_md(s); r.md_stride = sim_plant_stride(s); r.nv = L.n / 2; r.nq = L.nx - L.n / 2;
   r.x = s->d_x0; r.tau = p.d_simu; r.wr = p.d_simwr; r.push = p.push_width ? p.d_push : nullptr; r.push_width = p.push_width;
   r.out = p.d_rec + (size_t)p.rec_count * L.B * sim_record_width(L.nx, L.m);
   hipLaunchKernelGGL(k_sim_record, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, r);
@@ -77,7 +83,7 @@ static void sim_metrics_enqueue(mpc_solver* s, hipStream_t st, double dt) {
   if (!p.d_met) return;
   const Layout& L = s->L;
   SimMetricsArgs m;
-  m.mi = s->d_model_i; m.md = s->d_model_d; m.nv = L.n / 2; m.nq = L.nx - L.n / 2;
+  m.mi = s->d_model_i; m.md = sim_plant_md(s); m.md_stride = sim_plant_stride(s); m.nv = L.n / 2; m.nq = L.nx - L.n / 2;
   m.x = s->d_x0; m.tau = p.d_simu; m.wr = p.d_simwr; m.dt = dt; m.cfg = p.met_cfg;
   m.acc = p.d_met; m.frozen = p.d_met + (size_t)L.B * MPC_SIM_METRICS_WIDTH; m.xs = m.frozen + L.B;
   m.ter = sim_terrain_args(s); m.con = p.d_con; m.ground_z = p.con_cfg.ground_z;
@@ -229,6 +235,27 @@ static void sim_estimator_drop(mpc_solver* s) {
   s->plant.h_est.clear();
 }
 
+// the plant model's tables, built from the rows in force (h_plant) and the handle's nominal table: when the model is armed, and when mpc_set_model
+// replaced the nominal table of an armed handle (the joint count is then unchanged; the table may have grown by a frame).  Synchronous: the tables
+// may be read from any stream at once (the loops of the QP pipelines step the plant on the QP handle's).  Host work, not part of the steady loop
+static void sim_plant_build(mpc_solver* s) {
+  SimPlant& p = s->plant;
+  if (!p.d_plant) return;
+  const Layout& L = s->L;
+  const size_t head = p.plant_off;
+  if (p.plant_nd != s->model_nd) {
+    sim_realloc(s, p.d_plant, head + (size_t)L.B * s->model_nd);
+    p.plant_nd = s->model_nd;
+  }
+  copy_sync(s, p.d_plant, p.h_plant.data(), head * sizeof(double), hipMemcpyHostToDevice);
+  SimPlantArgs a;
+  a.md = s->d_model_d; a.nd = (int)p.plant_nd; a.nj = L.nj;
+  a.params = p.d_plant; a.link_scale = p.d_plant + (size_t)L.B * MPC_SIM_PLANT_PARAMS; a.tables = sim_plant_tables(s);
+  hipLaunchKernelGGL(k_sim_plant_models, dim3((unsigned)L.B), dim3(SIM_PLANT_THREADS), 0, s->stream, a);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(s->stream));
+}
+
 // A call that steps the plant `steps` times, part one: everything that can fail, before anything is enqueued.  `need`: sim_check.
 static void sim_steps_check(mpc_solver* s, const char* who, int need, int steps) {
   const SimPlant& p = s->plant;
@@ -260,12 +287,14 @@ static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
 // sensor model) and of the rows the contact rule just wrote; nothing of this step reads either, the controllers of the next step do (sim_measured).  Between the two, the foot force sensors and
 // the contact detector: the detection event of this step's wrenches (which the dynamics then always write), so that an estimator fed by detection reads
 // the pair this step's event left, and the low-level QPs of the next step the same pair.  In one line: actuator model -> dynamics -> record -> metrics
-// -> contact rule -> sensors -> foot sensors -> estimator.
+// -> contact rule -> sensors -> foot sensors -> estimator.  The plant model (include/mpc_sim_plant.h) launches nothing here: the dynamics, the record and
+// the metrics read robot b's own model table, built when the model was armed.
 static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& args, int substeps, double dt, bool want_wrenches) {
   const SimPlant& p = s->plant;
   sim_actuators_enqueue(s, st, substeps * dt);
   launch_eval_multibody(st, args, s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, p.push_width ? p.d_push : nullptr, true,
-                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con || p.d_fs) ? p.d_simwr : nullptr, p.push_width ? p.push_width : 3, p.d_con);
+                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con || p.d_fs) ? p.d_simwr : nullptr, p.push_width ? p.push_width : 3, p.d_con,
+                        p.d_plant ? sim_plant_tables(s) : nullptr, sim_plant_stride(s));
   HIP_OK(hipGetLastError());
   sim_record_enqueue(s, st);
   sim_metrics_enqueue(s, st, substeps * dt);
@@ -824,6 +853,70 @@ int mpc_sim_foot_sensors_feed(mpc_solver* s, int32_t consumers) {
     HIP_OK(hipStreamSynchronize(s->stream));
     s->plant.fs_feed = consumers;
   })
+}
+
+// ---- include/mpc_sim_plant.h: per-robot plant inertias ------------------------------------------------------------------------------------------
+int mpc_sim_plant(mpc_solver* s, const double* params, const double* link_scale) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_plant");
+    const Layout& L = s->L;
+    if (!params) {
+      sim_realloc(s, s->plant.d_plant, 0);
+      s->plant.h_plant.clear();
+      s->plant.plant_nd = s->plant.plant_off = 0;
+      return 0;
+    }
+    // (every check before anything changes: a bad row leaves the previous configuration in force)
+    if (!s->have_model || !s->d_model_d || s->h_model_i.empty()) throw std::runtime_error("sim_plant: no model is set on this handle (mpc_set_model first)");
+    const int nj = L.nj;
+    const size_t np = (size_t)L.B * MPC_SIM_PLANT_PARAMS;
+    std::vector<double> h(np + (size_t)L.B * nj, 1.0);
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = params + (size_t)b * MPC_SIM_PLANT_PARAMS;
+      const std::string row = "sim_plant: row " + std::to_string(b);
+      for (int e = 0; e < MPC_SIM_PLANT_PARAMS; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      if (!(r[0] > 0.0) || !(r[1] > 0.0)) throw std::runtime_error(row + ": mass_scale and inertia_scale must be > 0");
+      if (r[7] < 0.0) throw std::runtime_error(row + ": payload_mass must be >= 0");
+      for (int e : {2, 6})
+        if (r[e] != std::floor(r[e]) || r[e] < 0.0 || r[e] > nj - 1)
+          throw std::runtime_error(row + ": shift_body and payload_body must be integer values in [0, " + std::to_string(nj - 1) + "] (table joint indices)");
+      for (int e = 11; e < MPC_SIM_PLANT_PARAMS; ++e)
+        if (r[e] != 0.0) throw std::runtime_error(row + ": the reserved entries must be 0");
+      std::copy(r, r + MPC_SIM_PLANT_PARAMS, h.begin() + (size_t)b * MPC_SIM_PLANT_PARAMS);
+    }
+    if (link_scale)
+      for (size_t e = 0; e < (size_t)L.B * nj; ++e) {
+        if (!std::isfinite(link_scale[e]) || !(link_scale[e] > 0.0))
+          throw std::runtime_error("sim_plant: link_scale must be finite and > 0 (robot " + std::to_string(e / nj) + ", joint " + std::to_string(e % nj) + ")");
+        h[np + e] = link_scale[e];
+      }
+    sim_realloc(s, s->plant.d_plant, h.size() + (size_t)L.B * s->model_nd);
+    s->plant.plant_nd = s->model_nd;
+    s->plant.plant_off = h.size();
+    s->plant.h_plant = h;
+    sim_plant_build(s);
+  })
+}
+
+int mpc_sim_plant_read(mpc_solver* s, double* params, double* link_scale, double* tables) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_plant_read");
+    if (!s->plant.d_plant) throw std::runtime_error("sim_plant_read: the plant model is off on this handle (turn it on with mpc_sim_plant)");
+    const Layout& L = s->L;
+    const size_t np = (size_t)L.B * MPC_SIM_PLANT_PARAMS;
+    if (params) std::copy(s->plant.h_plant.begin(), s->plant.h_plant.begin() + np, params);
+    if (link_scale) std::copy(s->plant.h_plant.begin() + np, s->plant.h_plant.end(), link_scale);
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (tables) copy_sync(s, tables, sim_plant_tables(s), (size_t)L.B * s->plant.plant_nd * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int32_t mpc_sim_plant_width(mpc_solver* s) {
+  return sim_width(s, "sim_plant_width", [&] {
+    if (!s->have_model || !s->d_model_d) throw std::runtime_error("sim_plant_width: no model is set on this handle (mpc_set_model first)");
+    return s->model_nd;
+  });
 }
 
 // ---- include/mpc_abi.h: one step under the caller's torques -------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 struct SimMetricsArgs {
   const int32_t* mi;    // model tables of the simulator handle (contacts 0 and 1: the two soles)
   const double* md;
+  size_t md_stride;     // 0: one table for every robot; the plant model on (include/mpc_sim_plant.h): robot b's own table at md + b * md_stride
   int nq, nv;
   const double* x;      // [B][nq + nv] the states after the step
   const double* tau;    // [B][nv - 6] the joint torques of the step
@@ -55,12 +56,13 @@ __global__ void __launch_bounds__(CG_THREADS) k_sim_metrics(SimMetricsArgs a) {
     return;
   }
   for (int i = tid; i < nx; i += CG_THREADS) xs[i] = x[i];
-  cg_kinematics(a.mi, a.md, nq, x, K, tid);
-  cg_centroidal(a.mi, a.md, K, body, cx, tid);
+  const double* md = a.md + (size_t)b * a.md_stride;
+  cg_kinematics(a.mi, md, nq, x, K, tid);
+  cg_centroidal(a.mi, md, K, body, cx, tid);
   if (tid < 2) {
     M3 Rc;
     V3 pc;
-    sim_sole_placement(a.mi, a.md, K, tid, Rc, pc);
+    sim_sole_placement(a.mi, md, K, tid, Rc, pc);
     for (int e = 0; e < 9; ++e) sole[tid][e] = Rc.m[e];
     sole[tid][9] = pc.x; sole[tid][10] = pc.y; sole[tid][11] = pc.z;
   }

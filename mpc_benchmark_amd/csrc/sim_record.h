@@ -11,6 +11,7 @@ static inline __host__ __device__ int sim_record_width(int nx, int nu) { return 
 struct SimRecordArgs {
   const int32_t* mi;    // model tables of the simulator handle (contacts 0 and 1: the two soles)
   const double* md;
+  size_t md_stride;     // 0: one table for every robot; the plant model on (include/mpc_sim_plant.h): robot b's own table at md + b * md_stride
   int nq, nv;
   const double* x;      // [B][nq + nv] the states after the step
   const double* tau;    // [B][nv - 6] the joint torques of the step
@@ -38,8 +39,9 @@ __global__ void __launch_bounds__(CG_THREADS) k_sim_record(SimRecordArgs a) {
   __shared__ double body[10 * CG_MAX_NJ];
   __shared__ double cx[CG_NC];
   const double* x = a.x + (size_t)b * nx;
-  cg_kinematics(a.mi, a.md, a.nq, x, K, tid);
-  cg_centroidal(a.mi, a.md, K, body, cx, tid);
+  const double* md = a.md + (size_t)b * a.md_stride;
+  cg_kinematics(a.mi, md, a.nq, x, K, tid);
+  cg_centroidal(a.mi, md, K, body, cx, tid);
   double* o = a.out + (size_t)b * sim_record_width(nx, nu);
   for (int i = tid; i < nx; i += CG_THREADS) o[i] = x[i];
   o += nx;
@@ -51,7 +53,7 @@ __global__ void __launch_bounds__(CG_THREADS) k_sim_record(SimRecordArgs a) {
   if (tid < 2) {
     M3 Rc;
     V3 pc;
-    sim_sole_placement(a.mi, a.md, K, tid, Rc, pc);
+    sim_sole_placement(a.mi, md, K, tid, Rc, pc);
     double* so = o + 12 * tid;
     for (int e = 0; e < 9; ++e) so[e] = Rc.m[e];
     so[9] = pc.x; so[10] = pc.y; so[11] = pc.z;

@@ -72,7 +72,15 @@ naming who works from the detected pair instead of the plant's: the events of th
 (``"qp"``: ``KinodynamicPipeline`` and ``CentroidalPipeline`` with a ``contact_source`` other than ``"schedule"``; ``qp_contacts()`` then counts plan
 against detection).  The selection is made on the device on both forms of a tick for the estimator (its kernel runs inside every simulator step);
 for the QPs ``tick()`` selects on the device and ``tick(host_glue=True)`` reads the detector rows back before each step.  The plant, its record, its
-metrics and its contact rule keep the truth.  ``set_foot_sensors`` changes or removes the model later."""
+metrics and its contact rule keep the truth.  ``set_foot_sensors`` changes or removes the model later.
+
+``plant`` (all three pipelines): None, every robot's simulator is integrated with the inertias its MPC and its low-level QPs were built from; or the
+parameter rows of the per-robot plant model (``plant_model``: mass and inertia scales, a displaced centre of mass, a payload; (B, 16), one row of 16 for
+every robot, or a dict by field name of scalars or (B,) arrays, which may also carry ``link_scale`` (B, nj)), checked before any library call and armed
+on the simulator handle when the pipeline is built (mpc_sim_plant, include/mpc_sim_plant.h; HIP library only).  Only the plant changes: the dynamics of
+every simulator step, and the centre of mass and centroidal momentum of the record and the metrics, are those of robot b's own inertias; the MPC, the
+low-level QPs, the contact rule, the estimator and the walk generators keep the nominal model.  ``plant_models()`` returns the perturbed models;
+``set_plant`` changes or removes the model later."""
 from __future__ import annotations
 
 import numpy as np
@@ -81,6 +89,7 @@ from . import _capi as K
 from . import actuator_model as _actuator_model
 from . import contact_rule as _contact_rule
 from . import foot_sensors as _foot_sensors
+from . import plant_model as _plant_model
 from . import qp_utils
 from . import sensor_model as _sensor_model
 from . import state_estimator as _state_estimator
@@ -179,6 +188,17 @@ def _checked_terrain(name, terrain, contact_rule, batch):
     return _contact_rule.terrain_boxes(terrain, batch)
 
 
+def _checked_plant(plant, batch, problem_def):
+    """``plant`` of a pipeline: None, or (rows (B, 16), link_scale (B, nj) or None) checked before any library call (``plant_model.validate``)"""
+    if plant is None:
+        return None
+    link_scale = None
+    if isinstance(plant, dict):
+        plant = dict(plant)
+        link_scale = plant.pop("link_scale", None)
+    return _plant_model.validate(_plant_model.rows(plant, batch), problem_def.robot.model.njoints - 1, link_scale)
+
+
 def _checked_walk(name, walk, batch):
     """``walk`` of a pipeline: the ``commands`` table in it is checked before any library call (shape, finite values, ``per_instance=True``)"""
     if walk is None or walk.get("commands") is None:
@@ -233,6 +253,28 @@ class _Actuators:
     _estimator_rows = None
     _foot_rows = None
     _detected_contacts = ()
+    _plant_rows = None   # (rows (B, 16), link_scale (B, nj) or None) of the plant model in force
+
+    def set_plant(self, rows, link_scale=None):
+        """Arm the per-robot plant model on ``self.sim``: ``rows`` in the forms of ``NativeSolver.plant``, a dict may also carry ``link_scale``;
+        checked before any library call.  None turns the model off."""
+        if rows is None:
+            if self._plant_rows is not None:
+                self.sim.plant(None)
+            self._plant_rows = None
+            return
+        if isinstance(rows, dict):
+            rows = dict(rows)
+            link_scale = rows.pop("link_scale", link_scale)
+        checked = _plant_model.validate(_plant_model.rows(rows, self.batch), self.model.njoints - 1, link_scale)
+        self.sim.plant(checked[0], link_scale=checked[1])
+        self._plant_rows = checked
+
+    def plant_models(self):
+        """one ``minipin.Model`` per robot: what the simulator integrates (``plant_model.models``; the nominal model B times without ``plant``)"""
+        if self._plant_rows is None:
+            return [self.model] * self.batch
+        return _plant_model.models(self.model, *self._plant_rows)
 
     def _check_detected(self, name, foot_sensors, detected_contacts, contact_rule, contact_source=None):
         """``foot_sensors`` / ``detected_contacts`` of a pipeline, checked before any library call -> the consumers as a tuple"""
@@ -384,17 +426,18 @@ class _QpContactSource:
 class KinodynamicPipeline(_QpContactSource, _Actuators):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
                  terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, foot_sensors=None,
-                 detected_contacts=(), **ens_kw):
+                 detected_contacts=(), plant=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
         ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model, ``sensors``: None or the rows of the
         sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the rows of the foot force sensors,
-        ``detected_contacts``: who works from the detected contacts (module docstring)."""
+        ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model (module docstring)."""
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("KinodynamicPipeline", contact_source, contact_rule)
         detected_contacts = self._check_detected("KinodynamicPipeline", foot_sensors, detected_contacts, contact_rule, contact_source)
         self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
         walk = _checked_walk("KinodynamicPipeline", walk, self.batch)
+        plant = _checked_plant(plant, self.batch, problem_def)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
         rb = problem_def.robot
@@ -409,6 +452,8 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         self.qp.enable_device_assembly()
         self.umax = np.asarray(m.effortLimit, dtype=float)[6:]
         self._build_simulator()
+        if plant is not None:
+            self.set_plant(*plant)
         if actuators is not None:
             self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
@@ -580,19 +625,21 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
                  sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, sensors=None,
-                 estimator=None, foot_sensors=None, detected_contacts=(), **ens_kw):
+                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
         dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model,
         ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the
-        rows of the foot force sensors, ``detected_contacts``: who works from the detected contacts (module docstring)."""
+        rows of the foot force sensors, ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model
+        (module docstring)."""
         from .ensemble import ensemble_initial_states
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("CentroidalPipeline", contact_source, contact_rule)
         detected_contacts = self._check_detected("CentroidalPipeline", foot_sensors, detected_contacts, contact_rule, contact_source)
         self.terrain = _checked_terrain("CentroidalPipeline", terrain, contact_rule, self.batch)
         walk = _checked_walk("CentroidalPipeline", walk, self.batch)
+        plant = _checked_plant(plant, self.batch, problem_def)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
         rb = problem_def.robot
@@ -622,6 +669,8 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
         if self.contact_rule is not None:
             _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule, self.terrain)
         self._set_sim_contacts((True, True))   # (the schedule starts in double support)
+        if plant is not None:
+            self.set_plant(*plant)
         if actuators is not None:
             self.set_actuators(actuators)
         if sensors is not None:
@@ -771,13 +820,13 @@ class FullDynamicPipeline(_Actuators):
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
-                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), **ens_kw):
+                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
         actuator model, ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state
-        estimator, ``foot_sensors``: None or the rows of the foot force sensors, ``detected_contacts``: () or ("estimator",) (module docstring of
-        pipeline.py)."""
+        estimator, ``foot_sensors``: None or the rows of the foot force sensors, ``detected_contacts``: () or ("estimator",), ``plant``: None or the rows of the plant
+        model (module docstring of pipeline.py)."""
         detected_contacts = self._check_detected("FullDynamicPipeline", foot_sensors, detected_contacts, contact_rule)
         self.terrain = _checked_terrain("FullDynamicPipeline", terrain, contact_rule, int(batch))
         walk = _checked_walk("FullDynamicPipeline", walk, int(batch))
@@ -785,6 +834,7 @@ class FullDynamicPipeline(_Actuators):
             raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
                              "EnsembleMPC(closed_loop=...) would simulate a second time)")
         ens_kw.pop("closed_loop", None)
+        plant = _checked_plant(plant, int(batch), problem_def)
         self.pd, self.batch = problem_def, int(batch)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
@@ -798,6 +848,8 @@ class FullDynamicPipeline(_Actuators):
         self._sim_mask = None
         if self.contact_rule is not None:
             _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule, self.terrain)
+        if plant is not None:
+            self.set_plant(*plant)
         if actuators is not None:
             self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
