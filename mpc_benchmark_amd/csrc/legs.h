@@ -57,13 +57,16 @@ static inline constexpr LkLds make_lk_lds(int n, int m) {
   return s;
 }
 
-// grid (ceil(N / chunk), B): workgroup (ck, b) walks knots ck * chunk .. of instance b.  Reads K, k, Pt, mx, T6, Mu, Znu (gain record) and
+// The per-knot pass of one workgroup: knots kbeg .. kend - 1 of instance b.  Reads K, k, Pt, mx, T6, Mu, Znu (gain record) and
 // [A B] (knot record); writes Phi, phi for every knot and Gamma, Ku, Knup for the knots of parametric legs.  Everything the NEXT knot of
 // the chunk needs is requested into registers while this one computes (a workgroup owns its CU: 140 - 153 KB of LDS), so only the first
 // knot of a chunk waits for HBM.  MP: padded control dimension (sizes the prefetch registers).
 // FN, FM > 0: state / control dimensions as compile-time constants (see k_riccati_mfma)
+// Two kernels run it: k_leg_knot (one chunk of knots per workgroup) and k_leg_condense_tail (the last knots of the horizon as one chunk,
+// beside the condensation of the parametric legs).  prof_b, prof_k: the (instance, knot) whose phases the developer timers record
+// (negative: none).
 template <int MP, int FN = 0, int FM = 0>
-__global__ void __launch_bounds__(LK_THREADS) k_leg_knot(SolverArgs a, LkLds Srt, int chunk) {
+DEV void leg_knot_body(const SolverArgs& a, const LkLds& Srt, const int b, const int kbeg, const int kend, const int prof_b, const int prof_k) {
   constexpr bool FX = FN > 0;
   constexpr LkLds SC_ = FX ? make_lk_lds(FN, FM) : LkLds{};
   LkLds S_ = Srt;
@@ -72,14 +75,12 @@ __global__ void __launch_bounds__(LK_THREADS) k_leg_knot(SolverArgs a, LkLds Srt
   constexpr int NAB = (80 * (80 + MP) + LK_THREADS - 1) / LK_THREADS, NK = (MP * 80 + LK_THREADS - 1) / LK_THREADS;
   constexpr int NMU = (MP * MP + LK_THREADS - 1) / LK_THREADS, NZN = (16 * MP + LK_THREADS - 1) / LK_THREADS;
   const Layout& L = a.L;
-  const int b = blockIdx.y;
   int tid = threadIdx.x, lane = tid & 63;
   constexpr int nthr = LK_THREADS, nw = LK_THREADS / 64;
   int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const InstState& st = a.inst[b];
   if (st.done || st.skip_step) return;
   const int n = FX ? FN : L.n, nz = FX ? FN + FM : L.nz, np = S.np, mp = S.mp, nzp = S.nzp, lda = S.lda, ldp = S.ldp, ldm = S.ldm, nb = S.nb, nbm = S.nbm;
-  const int kbeg = blockIdx.x * chunk, kend = (kbeg + chunk < L.N) ? kbeg + chunk : L.N;
   const double mud = st.mu * a.opt.dyn_al_scale;
   extern __shared__ __attribute__((aligned(16))) double sm[];
   double *AB = sm + S.AB, *PR = sm + S.PR, *ZN = sm + S.ZN, *vec = sm + S.vec;
@@ -87,9 +88,10 @@ __global__ void __launch_bounds__(LK_THREADS) k_leg_knot(SolverArgs a, LkLds Srt
   double *TMP = sm + S.TM, *PT6 = TMP + 6 * nzp, *c6 = PT6 + 6 * np;
   double *kf = vec, *y0 = vec + mp, *z0 = y0 + np, *t6 = z0 + np, *g6 = t6 + 36, *mxs = g6 + 36;  // k (mp), B k + mx (np), (I - mu_d Pt) y0 (np), T6, T6 T6^T, mx (np)
   int* cnt = (int*)(mxs + np);  // active rows counted per wavefront (nw ints)
-  // developer phase timers (mpc_profile(3)): the workgroup of (knot 1, instance 1) -> slots 32.. of instance 1's counter block
+  // developer phase timers (mpc_profile(3)): the workgroup of (knot prof_k, instance prof_b) -> slots 32.. of that instance's counter block
+  // (k_leg_knot: knot 1 of instance 1 ; the tail role of k_leg_condense_tail is not timed: the counter blocks have no free slots for it)
   long long tk0_ = clock64();
-#define LK_PROF(slot) do { if (a.prof && k == 1 && b == 1 && tid == 0) { const long long t1_ = clock64(); a.prof[64 + 32 + (slot)] += (double)(t1_ - tk0_); tk0_ = t1_; } } while (0)
+#define LK_PROF(slot) do { if (a.prof && k == prof_k && b == prof_b && tid == 0) { const long long t1_ = clock64(); a.prof[prof_b * 64 + 32 + (slot)] += (double)(t1_ - tk0_); tk0_ = t1_; } } while (0)
 
   // ---- the operands of a knot, as the registers of the prefetch hold them ----
   double pab[NAB], pkm[NK], ptv[LK_PT], pmu[NMU], pzn[NZN], psm = 0.0, pact = 0.0;  // psm: k / T6 / mx element of this thread
@@ -326,9 +328,21 @@ __global__ void __launch_bounds__(LK_THREADS) k_leg_knot(SolverArgs a, LkLds Srt
   }
 }
 
+// grid (ceil(kmax / chunk), B): workgroup (ck, b) walks knots ck * chunk .. of instance b, below kmax (the knots from kmax on are those
+// k_leg_condense_tail walks ; kmax = N when that kernel is not in use)
+template <int MP, int FN = 0, int FM = 0>
+__global__ void __launch_bounds__(LK_THREADS) k_leg_knot(SolverArgs a, LkLds Srt, int chunk, int kmax) {
+  const int kbeg = blockIdx.x * chunk, kend = (kbeg + chunk < kmax) ? kbeg + chunk : kmax;
+  if (kbeg < kend) leg_knot_body<MP, FN, FM>(a, Srt, blockIdx.y, kbeg, kend, 1, 1);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // k_leg_condense: grid (nlegs - 1, B), leg j of instance b, backwards over its knots.  Lm (this knot's dp/dtheta) stays in LDS, Sg in the
 // accumulator registers of the matrix cores over the whole leg; Phi and Gamma of the next knot are requested while this one computes.
+// k_leg_condense_tail: grid (nlegs, B), the same for the legs j < nlegs - 1 and, in the workgroups of j = nlegs - 1, the per-knot pass
+// (leg_knot_body) over the last `tail` knots of the horizon.  The condensation holds (nlegs - 1) B compute units for the length of a leg
+// while the rest of the chip is idle, and nothing reads Phi / phi of the last leg before the forward sweep: with nlegs B workgroups on
+// the chip those knots cost no time of their own.  Which workgroup runs a body changes, the bodies and their results do not.
 // ---------------------------------------------------------------------------------------------------------------------
 struct LcLds { int np, ldp, nb; int LM, BA, BB, vec, total_bytes; unsigned mg_np, mg_ldp; };
 // Leading dimension of the three operands: every matrix-core read of this kernel takes 16 CONSECUTIVE doubles of 4 rows per instruction
@@ -351,7 +365,7 @@ static inline constexpr LcLds make_lc_lds(int n) {
 #define LC_STILES 2  // nb (nb + 1) / 2 <= 15 lower-triangle tiles of Sg
 
 template <int FN = 0>
-__global__ void __launch_bounds__(LK_THREADS) k_leg_condense(SolverArgs a, LcLds Srt) {
+DEV void leg_condense_body(const SolverArgs& a, const LcLds& Srt, const int j, const int b) {
   constexpr bool FX = FN > 0;
   constexpr LcLds SC_ = FX ? make_lc_lds(FN) : LcLds{};
   LcLds S_ = Srt;
@@ -359,7 +373,6 @@ __global__ void __launch_bounds__(LK_THREADS) k_leg_condense(SolverArgs a, LcLds
   const LcLds& S = S_;
   const Layout& L = a.L;
   constexpr int nthr = LK_THREADS, nw = LK_THREADS / 64;
-  const int j = blockIdx.x, b = blockIdx.y;
   int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const InstState& st = a.inst[b];
   if (st.done || st.skip_step) return;
@@ -478,6 +491,23 @@ __global__ void __launch_bounds__(LK_THREADS) k_leg_condense(SolverArgs a, LcLds
       }
     }
   for (int i = tid; i < n; i += nthr) lr[L.lsg + i] = sg[i];
+}
+
+template <int FN = 0>
+__global__ void __launch_bounds__(LK_THREADS) k_leg_condense(SolverArgs a, LcLds Srt) {
+  leg_condense_body<FN>(a, Srt, blockIdx.x, blockIdx.y);
+}
+
+// (a workgroup runs ONE of the two bodies from its first instruction to its last: every barrier of a body is reached by all its wavefronts ;
+// dynamic LDS: the larger of the two plans ; 1 <= tail <= N - leg_start(nlegs - 1), so the tail role never leaves the last leg)
+template <int MP, int FN = 0, int FM = 0>
+__global__ void __launch_bounds__(LK_THREADS) k_leg_condense_tail(SolverArgs a, LcLds Sc, LkLds Sk, int tail) {
+  const int j = blockIdx.x, b = blockIdx.y;
+  if (j + 1 < a.nlegs) leg_condense_body<FN>(a, Sc, j, b);
+  else {
+    const int kend = a.L.N, kbeg = kend - tail;
+    if (kbeg >= 0 && kbeg < kend) leg_knot_body<MP, FN, FM>(a, Sk, b, kbeg, kend, -1, -1);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

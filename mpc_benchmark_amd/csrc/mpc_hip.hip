@@ -227,6 +227,27 @@ struct mpc_solver {
   // developer knobs, read from the environment ONCE when the handle is created (MPC_LEGS_CHAIN, MPC_LEGS_PLAIN, MPC_TREE_SWEEPS, MPC_HIP_TRACE)
   bool env_chain = false, env_plain = false, env_reject_failed = false;
   int env_tree_sweeps = 0, env_trace = -1;
+  // k_leg_condense_tail (legs.h): the last knots of the horizon walked beside the condensation of the parametric legs.
+  // MPC_LEG_TAIL_KNOTS unset (-1): automatic, see leg_tail_knots ; 0: always the separate launches ; t > 0: t knots (at most the last leg)
+  // whatever the grid.  MPC_LEG_TAIL_CUS: the compute-unit count the automatic rule sees (tests of the fallback).
+  int env_tail_knots = -1, cu_count = 0;
+  int tail_last = 0, tail_sweeps_last = 0;          // developer probes (debug_get "leg_tail"): tail knots and sweeps of the last pass,
+  long long tail_fused = 0, tail_separate = 0;      // launches of k_leg_condense_tail / k_leg_condense so far,
+  long long leg_passes_multi = 0, leg_passes_single = 0;  // passes with legs that swept several times (no cut guess yet) / once
+  int leg_tail_knots(int J) const {
+    if (J < 2 || env_tail_knots == 0) return 0;
+    const int last = L.N - (int)((long long)(J - 1) * L.N / J);  // knots of the last leg (solver_args.h leg_start)
+    if (env_tail_knots > 0) return env_tail_knots < last ? env_tail_knots : last;
+    // automatic.  The fused grid, nlegs x B workgroups of one compute unit each, must fit the chip in one round (with more, the tail would
+    // add a round to the condensation), and k_leg_knot must need more than one round (N x B workgroups: with one round, batch 1 with 32
+    // legs, taking knots away from it gains nothing and the tail only lengthens the condensation: p50 1.114 -> 1.136 ms measured).
+    if ((long long)J * L.B > cu_count || (long long)L.N * L.B <= cu_count) return 0;
+    // A knot of the tail (stages 1 - 3 of the per-knot pass) takes about 1.2 times a knot of the condensation beside it, so the tail is
+    // 21 / 25 of a parametric leg: 64 x 4 legs, N = 100, sum of the two launches 1.221 ms with none, 1.142 / 1.126 / 1.125 / 1.140 / 1.171
+    // with 16 / 20 / 21 / 22 / 25 knots.
+    const int t = 21 * (L.N / J) / 25;
+    return t < last ? t : last;
+  }
   double* d_legbuf = nullptr;
   double* d_treebuf = nullptr;
   int leg_cap = 0;  // legs the three leg-indexed buffers (d_work, d_legbuf, d_treebuf) are sized for: they grow on demand (ensure_leg_capacity)
@@ -355,8 +376,11 @@ static void create_impl(mpc_solver* s, const mpc_dims& d) {
     e = getenv("MPC_LEGS_PLAIN"); s->env_plain = e && atoi(e) > 0;
     e = getenv("MPC_HIP_REJECT_FAILED"); s->env_reject_failed = e && atoi(e) > 0;
     e = getenv("MPC_TREE_SWEEPS"); s->env_tree_sweeps = e ? atoi(e) : 0;
-    e = getenv("MPC_HIP_TRACE"); s->env_trace = e ? atoi(e) : -1; }
+    e = getenv("MPC_HIP_TRACE"); s->env_trace = e ? atoi(e) : -1;
+    e = getenv("MPC_LEG_TAIL_KNOTS"); s->env_tail_knots = e ? (atoi(e) > 0 ? atoi(e) : 0) : -1; }
   HIP_OK(hipSetDevice(d.device));
+  HIP_OK(hipDeviceGetAttribute(&s->cu_count, hipDeviceAttributeMultiprocessorCount, d.device));
+  { const char* e = getenv("MPC_LEG_TAIL_CUS"); if (e && atoi(e) > 0) s->cu_count = atoi(e); }
   // Own non-blocking stream per handle: the shards of an ensemble on one GPU (several handles) run out of phase, the
   // sequential Riccati sweep of one shard (B workgroups) beside the wide per-knot kernels of the others.  Equal priorities:
   // alternating high / low priorities starved the low-priority shards (their tick took 16 - 21 ms against 14.5 ms).
@@ -466,10 +490,12 @@ static void create_impl(mpc_solver* s, const mpc_dims& d) {
       MPC_FIXED_MODELS(X)
 #undef X
     }
+    const int leg_tail_lds = s->lc.total_bytes > s->lk.total_bytes ? s->lc.total_bytes : s->lk.total_bytes;  // a workgroup runs either body
 #define X(ID, FN, FM, GF, ST, NPV, MPV) if (s->ric_fixed == ID) { \
       lds_attr_max((const void*)k_riccati_mfma<RIC_THREADS, 80, true, true, FN, FM, GF, ST>, s->ric.total_bytes); \
       lds_attr_max((const void*)k_leg_knot<MPV, FN, FM>, s->lk.total_bytes); \
       lds_attr_max((const void*)k_leg_condense<FN>, s->lc.total_bytes); \
+      lds_attr_max((const void*)k_leg_condense_tail<MPV, FN, FM>, leg_tail_lds); \
       lds_attr_max((const void*)k_leg_compose<NPV, FN, FM>, s->lx.total_bytes); \
       lds_attr_max((const void*)k_leg_tree_down<NPV, FN, FM>, s->lx.total_bytes); }
     MPC_FIXED_MODELS(X)
@@ -480,6 +506,9 @@ static void create_impl(mpc_solver* s, const mpc_dims& d) {
     lds_attr_max((const void*)k_leg_knot<32>, s->lk.total_bytes);
     lds_attr_max((const void*)k_leg_knot<48>, s->lk.total_bytes);
     lds_attr_max((const void*)k_leg_condense<0>, s->lc.total_bytes);
+    lds_attr_max((const void*)k_leg_condense_tail<16>, leg_tail_lds);
+    lds_attr_max((const void*)k_leg_condense_tail<32>, leg_tail_lds);
+    lds_attr_max((const void*)k_leg_condense_tail<48>, leg_tail_lds);
     lds_attr_max((const void*)k_leg_consensus<16>, s->lx.total_bytes);
     lds_attr_max((const void*)k_leg_consensus<32>, s->lx.total_bytes);
     lds_attr_max((const void*)k_leg_consensus<48>, s->lx.total_bytes);
@@ -731,6 +760,9 @@ static void launch_pass(mpc_solver* s) {
   // (the tree refreshes the guess of a cut from the node that starts there: every cut has seen the true terminal cost after one sweep per level)
   int sweeps = (J > 1 && !plain && !s->leg_guess_valid) ? (tree ? s->tree.nlev + 1 : 2) : 1;
   if (tree && !plain && s->env_tree_sweeps > sweeps) sweeps = s->env_tree_sweeps;  // developer knob: sweeps per pass
+  const int tail = s->leg_tail_knots(J);  // knots of the last leg walked by k_leg_condense_tail (0: k_leg_knot walks every knot)
+  s->tail_last = tail; s->tail_sweeps_last = sweeps;
+  if (J > 1) { if (sweeps > 1) s->leg_passes_multi++; else s->leg_passes_single++; }
   for (int sweep = 0; sweep < sweeps; ++sweep) {
   s->leg_guess_now = (J > 1 && !plain && (s->leg_guess_valid || sweep > 0)) ? 1 : 0;
   a = s->args();
@@ -762,16 +794,31 @@ static void launch_pass(mpc_solver* s) {
       // knot — the kernel is bound by its own instruction stream, not by the loads; MPC_LEG_KNOT_CHUNK for experiments)
       static const int chunk_env = getenv("MPC_LEG_KNOT_CHUNK") ? atoi(getenv("MPC_LEG_KNOT_CHUNK")) : 0;
       const int chunk = chunk_env > 0 ? chunk_env : 1;
-      const dim3 grid((L.N + chunk - 1) / chunk, L.B);
+      const int kmax = L.N - tail;  // the knots from kmax on: k_leg_condense_tail below (kmax >= leg_start(J - 1) >= 1)
+      const dim3 grid((kmax + chunk - 1) / chunk, L.B);
       if (false) {}
-#define X(ID, FN, FM, GF, ST, NPV, MPV) else if (s->ric_fixed == ID) hipLaunchKernelGGL((k_leg_knot<MPV, FN, FM>), grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk);
+#define X(ID, FN, FM, GF, ST, NPV, MPV) else if (s->ric_fixed == ID) hipLaunchKernelGGL((k_leg_knot<MPV, FN, FM>), grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk, kmax);
       MPC_FIXED_MODELS(X)
 #undef X
-      else if (s->lk.mp <= 16) hipLaunchKernelGGL(k_leg_knot<16>, grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk);
-      else if (s->lk.mp <= 32) hipLaunchKernelGGL(k_leg_knot<32>, grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk);
-      else hipLaunchKernelGGL(k_leg_knot<48>, grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk);
+      else if (s->lk.mp <= 16) hipLaunchKernelGGL(k_leg_knot<16>, grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk, kmax);
+      else if (s->lk.mp <= 32) hipLaunchKernelGGL(k_leg_knot<32>, grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk, kmax);
+      else hipLaunchKernelGGL(k_leg_knot<48>, grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk, kmax);
     });
-    s->timed(13, "k_leg_condense", [&] {
+    // (one profile slot and one name for both forms of the condensation: the per-kernel tables and the traffic table keep their rows)
+    if (tail > 0) s->timed(13, "k_leg_condense", [&] {
+      const int lds = s->lc.total_bytes > s->lk.total_bytes ? s->lc.total_bytes : s->lk.total_bytes;
+      const dim3 grid(J, L.B);
+      s->tail_fused++;
+      if (false) {}
+#define X(ID, FN, FM, GF, ST, NPV, MPV) else if (s->ric_fixed == ID) hipLaunchKernelGGL((k_leg_condense_tail<MPV, FN, FM>), grid, dim3(LK_THREADS), lds, s->stream, a, s->lc, s->lk, tail);
+      MPC_FIXED_MODELS(X)
+#undef X
+      else if (s->lk.mp <= 16) hipLaunchKernelGGL(k_leg_condense_tail<16>, grid, dim3(LK_THREADS), lds, s->stream, a, s->lc, s->lk, tail);
+      else if (s->lk.mp <= 32) hipLaunchKernelGGL(k_leg_condense_tail<32>, grid, dim3(LK_THREADS), lds, s->stream, a, s->lc, s->lk, tail);
+      else hipLaunchKernelGGL(k_leg_condense_tail<48>, grid, dim3(LK_THREADS), lds, s->stream, a, s->lc, s->lk, tail);
+    });
+    else s->timed(13, "k_leg_condense", [&] {
+      s->tail_separate++;
       if (false) {}
 #define X(ID, FN, FM, GF, ST, NPV, MPV) else if (s->ric_fixed == ID) hipLaunchKernelGGL(k_leg_condense<FN>, dim3(J - 1, L.B), dim3(LK_THREADS), s->lc.total_bytes, s->stream, a, s->lc);
       MPC_FIXED_MODELS(X)
@@ -1296,15 +1343,19 @@ int mpc_kernel_info(mpc_solver* s, int32_t idx, char* name, int32_t name_cap, in
       // (the instantiations the launch sites pick: the fixed-dimension ones when the handle's layout is one of MPC_FIXED_MODELS)
       const void* lk = s->lk.mp <= 16 ? (const void*)k_leg_knot<16> : (s->lk.mp <= 32 ? (const void*)k_leg_knot<32> : (const void*)k_leg_knot<48>);
       const void* lcd = (const void*)k_leg_condense<0>;
+      const void* lct = s->lk.mp <= 16 ? (const void*)k_leg_condense_tail<16> : (s->lk.mp <= 32 ? (const void*)k_leg_condense_tail<32> : (const void*)k_leg_condense_tail<48>);
+      const char* lct_name = "k_leg_condense_tail (condensation + the last leg's knots)";
       const char *lk_name = "k_leg_knot", *lcd_name = "k_leg_condense", *lcmp_name = "k_leg_compose (first level of the tree over the cuts)", *ltd_name = "k_leg_tree_down (last level)";
       const void *lcmp_fixed = nullptr, *ltd_fixed = nullptr;
-#define X(ID, FN, FM, GF, ST, NPV, MPV) if (s->ric_fixed == ID) { lk = (const void*)k_leg_knot<MPV, FN, FM>; lcd = (const void*)k_leg_condense<FN>; lcmp_fixed = (const void*)k_leg_compose<NPV, FN, FM>; ltd_fixed = (const void*)k_leg_tree_down<NPV, FN, FM>; \
+#define X(ID, FN, FM, GF, ST, NPV, MPV) if (s->ric_fixed == ID) { lk = (const void*)k_leg_knot<MPV, FN, FM>; lcd = (const void*)k_leg_condense<FN>; lct = (const void*)k_leg_condense_tail<MPV, FN, FM>; lct_name = "k_leg_condense_tail<" #MPV "," #FN "," #FM "> (fixed dimensions)"; lcmp_fixed = (const void*)k_leg_compose<NPV, FN, FM>; ltd_fixed = (const void*)k_leg_tree_down<NPV, FN, FM>; \
         lk_name = "k_leg_knot<" #MPV "," #FN "," #FM "> (fixed dimensions)"; lcd_name = "k_leg_condense<" #FN "> (fixed dimensions)"; \
         lcmp_name = "k_leg_compose<" #NPV "," #FN "," #FM "> (first level of the tree over the cuts, fixed dimensions)"; ltd_name = "k_leg_tree_down<" #NPV "," #FN "," #FM "> (last level, fixed dimensions)"; }
       MPC_FIXED_MODELS(X)
 #undef X
-      e.push_back({lk_name, lk, LK_THREADS, s->lk.total_bytes, (long long)L.N * L.B});
-      e.push_back({lcd_name, lcd, LK_THREADS, s->lc.total_bytes, (long long)(J - 1) * L.B});
+      const int tail = s->leg_tail_knots(J);
+      e.push_back({lk_name, lk, LK_THREADS, s->lk.total_bytes, (long long)(L.N - tail) * L.B});
+      if (tail > 0) e.push_back({lct_name, lct, LK_THREADS, s->lc.total_bytes > s->lk.total_bytes ? s->lc.total_bytes : s->lk.total_bytes, (long long)J * L.B});
+      else e.push_back({lcd_name, lcd, LK_THREADS, s->lc.total_bytes, (long long)(J - 1) * L.B});
       if (s->use_tree()) {
         const TreeDesc T = make_tree_desc(J);
         const void* lc = s->lx.np == 16 ? (const void*)k_leg_compose<16> : s->lx.np == 32 ? (const void*)k_leg_compose<32> : s->lx.np == 48 ? (const void*)k_leg_compose<48>
@@ -1774,6 +1825,8 @@ int mpc_debug_get(mpc_solver* s, const char* name, int32_t b, int32_t k, double*
       for (int i = 0; i < L.n_alpha; ++i) v.push_back(tp[(size_t)i * (L.N + 1) + k]);
       v.push_back(kn[L.oMISC + MISC_COST]); v.push_back(kn[L.oMISC + MISC_PEN]);
     }
+    else if (nm == "leg_tail") v = {(double)s->tail_last, (double)s->tail_fused, (double)s->tail_separate, (double)s->tail_sweeps_last, (double)s->eff_legs(), (double)s->cu_count,
+                                   (double)s->leg_passes_multi, (double)s->leg_passes_single};  // k_leg_condense_tail: tail knots and sweeps of the last pass, fused / separate condensation launches so far, legs, compute units, passes with several sweeps / with one
     else if (nm == "fixed_dims") v = {(double)s->ric_fixed};  // which fixed-dimension instantiations serve this handle (0: the generic kernels)
     else if (nm == "ric_prof") { dev_vec(s->d_prof + (size_t)b * 64, 64); HIP_OK(hipMemsetAsync(s->d_prof + (size_t)b * 64, 0, 64 * sizeof(double), s->stream)); HIP_OK(hipStreamSynchronize(s->stream)); }
     else if (nm == "dx") dev_vec(s->d_dxs + ((size_t)b * (L.N + 1) + k) * n, n);

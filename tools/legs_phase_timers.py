@@ -47,3 +47,5 @@ tcn = sum(pc[i] for i in cn)
 for i, nm in cn.items():
     print('COND %-44s %7.1f us/knot %5.1f%%' % (nm, pc[i] / knots / (GHZ * 1e3), 100 * pc[i] / tcn))
 print('COND total %.1f us per knot' % (tcn / knots / (GHZ * 1e3)))
+tail = int(ens.native.debug_get('leg_tail', 0)[0])
+print('TAIL %d knots of the last leg walked by k_leg_condense_tail beside the condensation (0: separate launches ; MPC_LEG_TAIL_KNOTS)' % tail)
