@@ -891,73 +891,132 @@ __global__ void __launch_bounds__(LK_THREADS) k_leg_consensus(SolverArgs a, LxLd
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// k_leg_apply: grid (N, B), block 256.  Knot k of a parametric leg with end co-state theta: p' = Lm_{k+1} theta (theta itself at
-// the last knot of the leg) ; p += Lm_k theta ; k += Ku p' ; knu[active] += Knup p' ; phi += Gamma p'.
+// k_leg_apply: grid (chunks of the parametric legs, B), block 256, LDS leg_apply_lds(n, C).  Knot k of a parametric leg with end co-state
+// theta: p' = Lm_{k+1} theta (theta itself at the last knot of the leg) ; p += Lm_k theta ; k += Ku p' ; knu[active] += Knup p' ;
+// phi += Gamma p'.  A workgroup takes C consecutive knots of one leg (the chunks do not straddle a cut): q_k = Lm_k theta for the knots
+// of the chunk and the one after it, kept in LDS, serves as the increment of p_k and as p' of knot k - 1, so that Lm is read
+// (C + 1) / C times per knot instead of twice.  C = 1: the traffic of one workgroup per knot.
+// Rows: a wavefront takes four rows at a time, matrix by matrix through the chunk, and requests the next four (with the values they
+// are added to) before it reduces the current four.  The lane's two products of a row are summed as fma(a0, x0, a1 x1), written out:
+// left to the compiler's contraction the two row passes came out in different forms, and the bits of every later tick with them.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_leg_apply(SolverArgs a) {
+#define LEG_APPLY_MAX_CHUNK 32
+static inline size_t leg_apply_lds(int n, int C) {
+  return (size_t)(C + 2) * n * sizeof(double) + (size_t)C * (4 * sizeof(unsigned long long) + 2 * sizeof(int) + 256 * sizeof(unsigned short));
+}
+// workgroups along x for chunks of C knots: every parametric leg (all but the last) is cut into its own chunks
+static inline int leg_apply_chunks(int N, int J, int C) {
+  int t = 0;
+  for (int j = 0; j + 1 < J; ++j) t += ((int)((long long)(j + 1) * N / J) - (int)((long long)j * N / J) + C - 1) / C;
+  return t;
+}
+struct LegApplyBatch { double v[4][2]; double old[4]; int kk, r0; };
+// the batches of four rows of one wavefront over `count` matrices of rows_of(kk) rows each (the wavefront that starts a matrix rotates:
+// the short last round of a matrix is not always the same wavefront's) ; load(batch) requests, reduce(batch) sums and stores
+template <class Rows, class Load, class Reduce>
+DEV void leg_apply_rows(int count, int wv, Rows&& rows_of, Load&& load, Reduce&& reduce) {
+  int kk = 0, r0 = 4 * wv;
+  auto settle = [&] { while (kk < count && r0 >= rows_of(kk)) { ++kk; r0 = 4 * ((wv + kk) & 3); } };
+  auto next = [&](LegApplyBatch& t) { r0 += 16; settle(); if (kk >= count) return false; t.kk = kk; t.r0 = r0; load(t); return true; };
+  settle();
+  if (kk >= count) return;
+  LegApplyBatch x, y;
+  x.kk = kk; x.r0 = r0; load(x);
+  for (;;) {
+    bool more = next(y);
+    reduce(x);
+    if (!more) break;
+    more = next(x);
+    reduce(y);
+    if (!more) break;
+  }
+}
+__global__ void __launch_bounds__(256) k_leg_apply(SolverArgs a, int C) {
   const Layout& L = a.L;
-  const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wv = tid >> 6, nw = nthr >> 6;
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const InstState& st = a.inst[b];
   if (st.done || st.skip_step) return;
-  const int j = leg_of_knot(a, k);
-  if (j + 1 >= a.nlegs) return;
-  const int n = L.n, ke = leg_start(a, j + 1) - 1;
-  const double* kn = knot_ptr(a, b, k);
-  double* g = gain_ptr(a, b, k);
-  const int m = (int)kn[L.oMISC + MISC_M], c = (int)kn[L.oMISC + MISC_NC];
-  const double* th_g = leg_ptr(a, b, j) + L.lth;
-  __shared__ double th[128], pn[128];
-  __shared__ int act_idx[256];
-  __shared__ int wcnt[4];
-  for (int i = tid; i < n; i += nthr) th[i] = th_g[i];
-  // active rows in order (ballot prefix; c <= 256 = block size, checked by the host)
-  const bool is_act = tid < c && kn[L.oACT + (tid < c ? tid : 0)] != 0.0;
-  const unsigned long long amask = __ballot(is_act);
-  if (lane == 0) wcnt[wv] = __popcll(amask);
-  __syncthreads();
-  int ca = 0;
-  {
-    int off = 0;
-    for (int q = 0; q < nw; ++q) { if (q < wv) off += wcnt[q]; ca += wcnt[q]; }
-    if (is_act) act_idx[off + __popcll(amask & ((1ull << lane) - 1ull))] = tid;
+  // chunk blockIdx.x: knots k0 .. k0 + cn - 1 of leg j, whose last knot is ke
+  int x = blockIdx.x, j = 0, k0 = 0, ke = -1;
+  for (; j + 1 < a.nlegs; ++j) {
+    const int s0 = leg_start(a, j), s1 = leg_start(a, j + 1), nc = (s1 - s0 + C - 1) / C;
+    if (x < nc) { k0 = s0 + x * C; ke = s1 - 1; break; }
+    x -= nc;
   }
-  // mat-vecs: a wavefront takes four rows at a time, all their loads in flight before the four reductions
+  if (ke < 0) return;
+  const int n = L.n, cn = ke - k0 + 1 < C ? ke - k0 + 1 : C;
+  const bool at_end = k0 + cn - 1 == ke;
+  const int nq = at_end ? cn : cn + 1;  // q_k = Lm_k theta for k = k0 .. k0 + nq - 1 ; at the end of the leg q_{ke + 1} = theta
+  extern __shared__ __attribute__((aligned(16))) double la_sh[];
+  double* th = la_sh;                                                                   // n
+  double* qv = th + n;                                                                  // [C + 1][n]
+  unsigned long long* amask_s = (unsigned long long*)(qv + (size_t)(C + 1) * n);        // [C][4]: active rows of every knot, one mask per wavefront
+  int* mm = (int*)(amask_s + 4 * C);                                                    // [C]: controls of every knot
+  int* cas = mm + C;                                                                    // [C]: active rows of every knot
+  unsigned short* act_idx = (unsigned short*)(cas + C);                                 // [C][256]: their row numbers in order
+  const double* th_g = leg_ptr(a, b, j) + L.lth;
+  double* g0 = gain_ptr(a, b, k0);  // (the gain records of consecutive knots are gain_stride apart)
+  const size_t gs = L.gain_stride;
+  for (int i = tid; i < n; i += 256) th[i] = th_g[i];
+  for (int kk = 0; kk < cn; ++kk) {  // (at most 256 constraint rows = block size, checked by the host)
+    const double* kn = knot_ptr(a, b, k0 + kk);
+    const int c = (int)kn[L.oMISC + MISC_NC];
+    const bool is_act = tid < c && kn[L.oACT + (tid < c ? tid : 0)] != 0.0;
+    const unsigned long long am = __ballot(is_act);
+    if (lane == 0) amask_s[4 * kk + wv] = am;
+    if (tid == 0) mm[kk] = (int)kn[L.oMISC + MISC_M];
+  }
+  __syncthreads();
+  for (int kk = 0; kk < cn; ++kk) {  // active rows in order (prefix over the ballots)
+    int off = 0, ca = 0;
+    for (int w = 0; w < 4; ++w) { const int pc = __popcll(amask_s[4 * kk + w]); if (w < wv) off += pc; ca += pc; }
+    const unsigned long long am = amask_s[4 * kk + wv];
+    if ((am >> lane) & 1ull) act_idx[256 * kk + off + __popcll(am & ((1ull << lane) - 1ull))] = (unsigned short)tid;
+    if (tid == 0) cas[kk] = ca;
+  }
   const int c0 = lane < n ? lane : 0, c1 = lane + 64 < n ? lane + 64 : 0;
   const double m0 = lane < n ? 1.0 : 0.0, m1 = lane + 64 < n ? 1.0 : 0.0;
-  if (k == ke) { for (int i = tid; i < n; i += nthr) pn[i] = th[i]; }
-  else {
-    const double* gn = gain_ptr(a, b, k + 1) + L.oLm;
+  {
     const double t0 = th[c0] * m0, t1 = th[c1] * m1;
-    for (int r0 = 4 * wv; r0 < n; r0 += 4 * nw) {
-      double v[4][2];
+    if (at_end) for (int i = tid; i < n; i += 256) qv[cn * n + i] = th[i];
+    leg_apply_rows(nq, wv, [&](int) { return n; },
+      [&](LegApplyBatch& t) {
+        const double* gn = g0 + t.kk * gs + L.oLm;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) { const int r = r0 + q < n ? r0 + q : 0; v[q][0] = gn[r * n + c0]; v[q][1] = gn[r * n + c1]; }
+        for (int q = 0; q < 4; ++q) { const int r = t.r0 + q < n ? t.r0 + q : 0; t.v[q][0] = gn[r * n + c0]; t.v[q][1] = gn[r * n + c1]; }
+      },
+      [&](const LegApplyBatch& t) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) { const double sx = wave_sum(v[q][0] * t0 + v[q][1] * t1); if (lane == 0 && r0 + q < n) pn[r0 + q] = sx; }
-    }
+        for (int q = 0; q < 4; ++q) { const double sx = wave_sum(__builtin_fma(t.v[q][0], t0, t.v[q][1] * t1)); if (lane == 0 && t.r0 + q < n) qv[t.kk * n + t.r0 + q] = sx; }
+      });
   }
   __syncthreads();
-  // rows: [0, n) p += Lm_k theta ; [n, 2n) phi += Gamma p' ; [2n, 2n + m) k += Ku p' ; then the active constraint rows: knu += Knup p'
-  const double t0 = th[c0] * m0, t1 = th[c1] * m1, q0 = pn[c0] * m0, q1 = pn[c1] * m1;
-  const int total = 2 * n + m + ca;
-  for (int r0 = 4 * wv; r0 < total; r0 += 4 * nw) {
-    double v[4][2];
-    double* dst[4];
-    bool use_th[4];
+  for (int idx = tid; idx < cn * n; idx += 256) { const int kk = idx / n; g0[kk * gs + L.op + (idx - kk * n)] += qv[idx]; }  // p += Lm_k theta
+  // rows of knot kk: [0, n) phi += Gamma p' ; [n, n + m) k += Ku p' ; then the active constraint rows: knu += Knup p' ; p' = q_{kk + 1}
+  auto dst_of = [&](int kk, int r) -> double* {
+    double* g = g0 + kk * gs;
+    const int m = mm[kk];
+    return r < n ? g + L.ophi + r : (r < n + m ? g + L.ok + (r - n) : g + L.oknu + act_idx[256 * kk + (r - n - m)]);
+  };
+  leg_apply_rows(cn, wv, [&](int kk) { return n + mm[kk] + cas[kk]; },
+    [&](LegApplyBatch& t) {
+      double* g = g0 + t.kk * gs;
+      const int m = mm[t.kk], total = n + m + cas[t.kk];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int r = r0 + q < total ? r0 + q : 0;
-      const double* row;
-      if (r < n) { row = g + L.oLm + r * n; dst[q] = g + L.op + r; use_th[q] = true; }
-      else if (r < 2 * n) { row = g + L.oGam + (r - n) * n; dst[q] = g + L.ophi + (r - n); use_th[q] = false; }
-      else if (r < 2 * n + m) { row = g + L.oKu + (r - 2 * n) * n; dst[q] = g + L.ok + (r - 2 * n); use_th[q] = false; }
-      else { row = g + L.oKnup + (r - 2 * n - m) * n; dst[q] = g + L.oknu + act_idx[r - 2 * n - m]; use_th[q] = false; }
-      v[q][0] = row[c0]; v[q][1] = row[c1];
-    }
+      for (int q = 0; q < 4; ++q) {
+        const int r = t.r0 + q < total ? t.r0 + q : 0;
+        const double* row = r < n ? g + L.oGam + r * n : (r < n + m ? g + L.oKu + (r - n) * n : g + L.oKnup + (r - n - m) * n);
+        t.v[q][0] = row[c0]; t.v[q][1] = row[c1];
+        t.old[q] = *dst_of(t.kk, r);
+      }
+    },
+    [&](const LegApplyBatch& t) {
+      const int total = n + mm[t.kk] + cas[t.kk];
+      const double q0 = qv[(t.kk + 1) * n + c0] * m0, q1 = qv[(t.kk + 1) * n + c1] * m1;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const double sx = wave_sum(use_th[q] ? v[q][0] * t0 + v[q][1] * t1 : v[q][0] * q0 + v[q][1] * q1);
-      if (lane == 0 && r0 + q < total) *dst[q] += sx;
-    }
-  }
+      for (int q = 0; q < 4; ++q) {
+        const double sx = wave_sum(__builtin_fma(t.v[q][0], q0, t.v[q][1] * q1));
+        if (lane == 0 && t.r0 + q < total) *dst_of(t.kk, t.r0 + q) = t.old[q] + sx;
+      }
+    });
 }

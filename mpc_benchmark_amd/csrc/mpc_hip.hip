@@ -248,6 +248,24 @@ struct mpc_solver {
     const int t = 21 * (L.N / J) / 25;
     return t < last ? t : last;
   }
+  // back-substitution kernels.  k_leg_apply (legs.h): knots per workgroup.  MPC_LEG_APPLY_CHUNK unset (-1): automatic, see leg_apply_chunk ;
+  // C > 0: C knots (1: one workgroup per knot, every Lm read twice).  k_duals (solver_kernels.h): MPC_DUALS_PLAIN=1 keeps the form in which
+  // every constraint row pays a global load and two reductions.  Both read ONCE, when the handle is created.
+  int env_apply_chunk = -1;
+  bool env_duals_plain = false;
+  int apply_chunk_last = 0;                                // developer probes (debug_get "backsubst"): knots per workgroup of the last k_leg_apply,
+  long long apply_chunked = 0, apply_single = 0;           // its launches with C > 1 / C = 1 so far,
+  long long duals_staged = 0, duals_plain = 0;             // launches of the two forms of k_duals so far
+  int leg_apply_chunk(int J) const {
+    int C;
+    if (env_apply_chunk > 0) C = env_apply_chunk;
+    // automatic.  A grid of one round of the chip or less (batch 1 with 32 legs of 3 knots) is bound by the latency of one workgroup, which
+    // a chunk only lengthens: one knot per workgroup there, as the tail rule above.  Otherwise 5 knots: a 25-knot leg in 5 equal chunks,
+    // Lm read 1.2 times per knot — 64 instances: 0.77 -> 0.59 GB per launch in the same 0.170 ms as C = 1 ; 256 instances: 0.614 -> 0.582 ms ;
+    // chunks that do not divide the leg, or fewer workgroups than the chip holds, are slower (profiles/backsubst_measurements.txt).
+    else C = (long long)L.N * L.B <= cu_count ? 1 : 5;
+    return C < 1 ? 1 : (C > LEG_APPLY_MAX_CHUNK ? LEG_APPLY_MAX_CHUNK : C);
+  }
   double* d_legbuf = nullptr;
   double* d_treebuf = nullptr;
   int leg_cap = 0;  // legs the three leg-indexed buffers (d_work, d_legbuf, d_treebuf) are sized for: they grow on demand (ensure_leg_capacity)
@@ -377,7 +395,9 @@ static void create_impl(mpc_solver* s, const mpc_dims& d) {
     e = getenv("MPC_HIP_REJECT_FAILED"); s->env_reject_failed = e && atoi(e) > 0;
     e = getenv("MPC_TREE_SWEEPS"); s->env_tree_sweeps = e ? atoi(e) : 0;
     e = getenv("MPC_HIP_TRACE"); s->env_trace = e ? atoi(e) : -1;
-    e = getenv("MPC_LEG_TAIL_KNOTS"); s->env_tail_knots = e ? (atoi(e) > 0 ? atoi(e) : 0) : -1; }
+    e = getenv("MPC_LEG_TAIL_KNOTS"); s->env_tail_knots = e ? (atoi(e) > 0 ? atoi(e) : 0) : -1;
+    e = getenv("MPC_LEG_APPLY_CHUNK"); s->env_apply_chunk = (e && atoi(e) > 0) ? atoi(e) : -1;
+    e = getenv("MPC_DUALS_PLAIN"); s->env_duals_plain = e && atoi(e) > 0; }
   HIP_OK(hipSetDevice(d.device));
   HIP_OK(hipDeviceGetAttribute(&s->cu_count, hipDeviceAttributeMultiprocessorCount, d.device));
   { const char* e = getenv("MPC_LEG_TAIL_CUS"); if (e && atoi(e) > 0) s->cu_count = atoi(e); }
@@ -869,7 +889,12 @@ static void launch_pass(mpc_solver* s) {
   }
   if (J > 1) {
     s->leg_guess_valid = true;
-    s->timed(15, "k_leg_apply", [&] { hipLaunchKernelGGL(k_leg_apply, dim3(L.N, L.B), dim3(256), 0, s->stream, a); });
+    s->timed(15, "k_leg_apply", [&] {
+      const int C = s->leg_apply_chunk(J);
+      s->apply_chunk_last = C;
+      if (C > 1) s->apply_chunked++; else s->apply_single++;
+      hipLaunchKernelGGL(k_leg_apply, dim3(leg_apply_chunks(L.N, J, C), L.B), dim3(256), leg_apply_lds(L.n, C), s->stream, a, C);
+    });
     s->timed(4, "k_forward", [&] {
       if (L.m <= 32) hipLaunchKernelGGL((k_forward_phi<4, 10>), dim3(L.B * J), dim3(512), 2 * L.n * sizeof(double), s->stream, a);
       else hipLaunchKernelGGL((k_forward_phi<6, 10>), dim3(L.B * J), dim3(512), 2 * L.n * sizeof(double), s->stream, a);
@@ -890,7 +915,11 @@ static void launch_pass(mpc_solver* s) {
     });
   }
   }
-  s->timed(5, "k_duals", [&] { hipLaunchKernelGGL(k_duals, dim3(L.N + 1, L.B), dim3(256), (L.nz + 3 * L.n + 16 + 3 * L.c) * sizeof(double), s->stream, a); });
+  s->timed(5, "k_duals", [&] {
+    // (LDS: the step, three vectors of n, the partial sums, then three per-row scalars of the constraint block — four in the staged form)
+    if (s->env_duals_plain) { s->duals_plain++; hipLaunchKernelGGL(k_duals<true>, dim3(L.N + 1, L.B), dim3(256), (L.nz + 3 * L.n + 16 + 3 * L.c) * sizeof(double), s->stream, a); }
+    else { s->duals_staged++; hipLaunchKernelGGL(k_duals<false>, dim3(L.N + 1, L.B), dim3(256), (L.nz + 3 * L.n + 16 + 4 * L.c) * sizeof(double), s->stream, a); }
+  });
   // linesearch: evaluate the full step first; the backtracking candidates alpha = 2^-i, i >= 1, are only
   // evaluated for instances whose full step failed the Armijo test (their workgroups exit immediately otherwise)
   // (two profile slots: with derivatives into the knot records — the launch the roofline is quoted on — or values only)
@@ -1369,14 +1398,16 @@ int mpc_kernel_info(mpc_solver* s, int32_t idx, char* name, int32_t name_cap, in
                      : s->lx.np == 64 ? (const void*)k_leg_consensus<64> : (const void*)k_leg_consensus<80>;
       e.push_back({"k_leg_consensus", lx, LK_THREADS, s->lx.total_bytes, (long long)L.B});
       }
-      e.push_back({"k_leg_apply", (const void*)k_leg_apply, 256, 0, (long long)L.N * L.B});
+      { const int C = s->leg_apply_chunk(J);
+        e.push_back({"k_leg_apply", (const void*)k_leg_apply, 256, (int)leg_apply_lds(L.n, C), (long long)leg_apply_chunks(L.N, J, C) * L.B}); }
       e.push_back({"k_forward_phi (forward sweeps of the legs)", L.m <= 32 ? (const void*)k_forward_phi<4, 10> : (const void*)k_forward_phi<6, 10>, 512, (int)(2 * L.n * sizeof(double)), (long long)L.B * J});
     } else if (s->use_mfma_riccati) {
       const void* fn = small ? (const void*)k_riccati_mfma<RIC_SMALL_THREADS, 16> : (s->ric.sq && s->ric.np <= 80) ? (const void*)k_riccati_mfma<RIC_THREADS, 80, true>
                      : s->ric.sq ? (const void*)k_riccati_mfma<RIC_THREADS, 96, true> : s->ric.np <= 80 ? (const void*)k_riccati_mfma<RIC_THREADS, 80> : (const void*)k_riccati_mfma<RIC_THREADS, 96>;
       e.push_back({"k_riccati_mfma (serial sweep)", fn, small ? RIC_SMALL_THREADS : RIC_THREADS, s->ric.total_bytes, (long long)L.B});
     } else e.push_back({"k_riccati_backward (serial sweep, no matrix cores)", (const void*)k_riccati_backward, 256, (int)s->riccati_lds(), (long long)L.B});
-    e.push_back({"k_duals", (const void*)k_duals, 256, (int)((L.nz + 3 * L.n + 16 + 3 * L.c) * sizeof(double)), (long long)(L.N + 1) * L.B});
+    if (s->env_duals_plain) e.push_back({"k_duals<true> (MPC_DUALS_PLAIN)", (const void*)k_duals<true>, 256, (int)((L.nz + 3 * L.n + 16 + 3 * L.c) * sizeof(double)), (long long)(L.N + 1) * L.B});
+    else e.push_back({"k_duals", (const void*)k_duals<false>, 256, (int)((L.nz + 3 * L.n + 16 + 4 * L.c) * sizeof(double)), (long long)(L.N + 1) * L.B});
     e.push_back({"k_lagrangian", (const void*)k_lagrangian, 64, 0, (long long)(L.N + 1) * L.B});
     if (idx < 0 || idx >= (int)e.size()) return (int)e.size();
     const Ent& k = e[idx];
@@ -1827,6 +1858,8 @@ int mpc_debug_get(mpc_solver* s, const char* name, int32_t b, int32_t k, double*
     }
     else if (nm == "leg_tail") v = {(double)s->tail_last, (double)s->tail_fused, (double)s->tail_separate, (double)s->tail_sweeps_last, (double)s->eff_legs(), (double)s->cu_count,
                                    (double)s->leg_passes_multi, (double)s->leg_passes_single};  // k_leg_condense_tail: tail knots and sweeps of the last pass, fused / separate condensation launches so far, legs, compute units, passes with several sweeps / with one
+    else if (nm == "backsubst") v = {(double)s->apply_chunk_last, (double)s->apply_chunked, (double)s->apply_single, (double)s->duals_staged, (double)s->duals_plain,
+                                    (double)leg_apply_chunks(L.N, s->eff_legs(), s->apply_chunk_last > 0 ? s->apply_chunk_last : 1)};  // k_leg_apply: knots per workgroup of the last launch, launches with C > 1 / C = 1 so far ; k_duals: launches of the staged / plain form ; workgroups along x of the last k_leg_apply
     else if (nm == "fixed_dims") v = {(double)s->ric_fixed};  // which fixed-dimension instantiations serve this handle (0: the generic kernels)
     else if (nm == "ric_prof") { dev_vec(s->d_prof + (size_t)b * 64, 64); HIP_OK(hipMemsetAsync(s->d_prof + (size_t)b * 64, 0, 64 * sizeof(double), s->stream)); HIP_OK(hipStreamSynchronize(s->stream)); }
     else if (nm == "dx") dev_vec(s->d_dxs + ((size_t)b * (L.N + 1) + k) * n, n);

@@ -502,8 +502,14 @@ __global__ void __launch_bounds__(512) k_forward_prefetch(SolverArgs a) {
 
 // ------------------------------------------------------------------------------------------------
 // P7 (cont.): multiplier steps and the merit directional derivative, parallel over knots.
-// grid (N+1, B), block 256, LDS (nz + 3 n + 16 + 3 c) doubles
+// grid (N+1, B), block 256, LDS (nz + 3 n + 16 + 4 c) doubles (PLAIN: 3 c)
+// PLAIN = false: the four per-row scalars of the constraint block are staged in LDS, and a row that contributes nothing (inactive, zero
+// projection: most rows of most knots) takes its dv and its merit term from them — no global access, no reduction.  (Requesting the
+// first four rows of P' before the row pass was tried: 102 SGPRs, 7 waves per SIMD instead of 8 — left out.)
+// PLAIN = true (MPC_DUALS_PLAIN=1): the earlier form, every row pays the load of its knu and two reductions.
+// Same sums in the same order: same bits.
 // ------------------------------------------------------------------------------------------------
+template <bool PLAIN>
 __global__ void __launch_bounds__(256) k_duals(SolverArgs a) {
   const Layout& L = a.L;
   const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wv = tid >> 6, nw = nthr >> 6;
@@ -529,10 +535,11 @@ __global__ void __launch_bounds__(256) k_duals(SolverArgs a) {
   __syncthreads();
   // per-row scalars of the constraint block (active flag, shifted value / mu, multiplier): one coalesced load per thread up front — read
   // row by row from global memory they are three dependent round trips per row, and most rows are inactive (nothing else to do)
-  double* rsc = part + nw + 2;  // [3][L.c]
+  double* rsc = part + nw + 2;  // [3][L.c] ; [4][L.c] with the affine dual gains knu beside them (not PLAIN)
   for (int i = tid; i < L.c; i += nthr) {
     const bool in = i < c;
     rsc[i] = in ? kn[L.oACT + i] : 0.0; rsc[L.c + i] = in ? kn[L.oDT + i] / mu : 0.0; rsc[2 * L.c + i] = in ? v[i] : 0.0;
+    if (!PLAIN) rsc[3 * L.c + i] = in ? g[L.oknu + i] : 0.0;
   }
   __syncthreads();
   double acc = 0.0;  // lane 0 of every wavefront accumulates the rows of that wavefront
@@ -552,8 +559,14 @@ __global__ void __launch_bounds__(256) k_duals(SolverArgs a) {
       for (int z = lane; z < n; z += 64) s += g[L.oKnu + i * n + z] * dz[z];
     if (wj != 0.0)  // an inactive row with a zero projection does not enter the slope: its Jacobian row is not read
       for (int z = lane; z < n + m; z += 64) jd += kn[L.oCD + i * nz + z] * dz[z];
-    s = wave_sum(s) + g[L.oknu + i];
-    jd = wave_sum(jd);
+    if (PLAIN) {
+      s = wave_sum(s) + g[L.oknu + i];
+      jd = wave_sum(jd);
+    } else {
+      // a row with neither term: both reductions would sum exact zeros to + 0.0, which s and jd already hold in every lane
+      if (act || wj != 0.0) { s = wave_sum(s); jd = wave_sum(jd); }
+      s = s + rsc[3 * L.c + i];
+    }
     const double dvi = s - vi;
     if (lane == 0) dv[i] = dvi;
     acc += wj * jd - mu * (vp - vi) * dvi;
