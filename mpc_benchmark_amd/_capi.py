@@ -17,6 +17,7 @@ from . import sensor_model as _sensor_model
 from . import state_estimator as _state_estimator
 from . import foot_sensors as _foot_sensors
 from . import plant_model as _plant_model
+from . import friction_model as _friction_model
 from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
 
@@ -205,6 +206,14 @@ _SIM_PLANT_SIGNATURES = {
     "mpc_sim_plant_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_friction.h: exported by the HIP library alone, bound when present (``NativeSolver.friction`` / ``read_friction`` / ``set_friction``)
+_SIM_FRICTION_SIGNATURES = {
+    "mpc_sim_friction": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_friction_read": (C.c_int, [C.c_void_p, _DP, _DP]),
+    "mpc_sim_friction_set": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_friction_width": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_sim_terrain.h: exported by the HIP library alone, bound when present (``NativeSolver.terrain`` / ``read_terrain`` / ``terrain_height``)
 class MpcSimTerrainConfig(C.Structure):
     _fields_ = [("n_boxes", C.c_int32), ("per_robot", C.c_int32)]
@@ -254,7 +263,7 @@ def bind_library(path):
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_ESTIMATOR_SIGNATURES.items()) + list(_SIM_FOOT_SENSORS_SIGNATURES.items()) + list(_SIM_PLANT_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
+            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_ESTIMATOR_SIGNATURES.items()) + list(_SIM_FOOT_SENSORS_SIGNATURES.items()) + list(_SIM_PLANT_SIGNATURES.items()) + list(_SIM_FRICTION_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -756,6 +765,54 @@ class NativeSolver:
         fn = self._sim_foot_sensors("mpc_sim_foot_sensors_feed")
         mask = int(consumers) if isinstance(consumers, (int, np.integer)) else _foot_sensors.feed_mask(consumers)
         self._check(fn(self._h, mask), "mpc_sim_foot_sensors_feed")
+
+    # -- include/mpc_sim_friction.h (HIP library only): per-robot ground friction under the soles of the torque-driven simulator steps -------------
+    def _sim_friction(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError("%s is not exported by this library (%s): the ground friction of torque-driven simulator steps is HIP only "
+                               "(libmpc_hip.so, include/mpc_sim_friction.h)" % (name, self.backend))
+        return getattr(self.lib, name)
+
+    def friction(self, params, base=None):
+        """Make every held sole of every robot of this simulator handle a Coulomb slider (mpc_sim_friction; ``friction_model`` is the definition).
+        Needs the contact rule (``contacts``).  ``params``: (B, 8) rows, one row of 8 for every robot, or a dict by ``friction_model.FIELDS`` name
+        (``mu`` / ``mu_spin``: both soles) of scalars or (B,) arrays, missing fields as in ``base`` (``friction_model.rows``); turns the model on
+        with every sole at rest.  None turns the model off."""
+        fn = self._sim_friction("mpc_sim_friction")
+        if params is None:
+            self._check(fn(self._h, None), "mpc_sim_friction")
+            return
+        p = _f64(_friction_model.rows(params, self.dims.batch, base))
+        self._check(fn(self._h, _dp(p)), "mpc_sim_friction")
+
+    def read_friction(self, raw=False):
+        """The friction model as it stands (mpc_sim_friction_read) -> dict: ``params`` (B, 8) the rows in force, and the state rows by
+        ``friction_model.unpack`` (``v`` (B, 2, 3), ``sliding``, ``slip_steps``, ``slip_dist``, ``slip_yaw``, ``peak_excess`` (B, 2), ``steps``);
+        ``raw``: the (B, 17) state rows themselves."""
+        fn = self._sim_friction("mpc_sim_friction_read")
+        w = self._sim_friction("mpc_sim_friction_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_friction_width")
+        d = self.dims
+        out, par = np.zeros((d.batch, w)), np.zeros((d.batch, _friction_model.PARAMS))
+        self._check(fn(self._h, _dp(par), _dp(out)), "mpc_sim_friction_read")
+        if raw:
+            return out
+        r = _friction_model.unpack(out)
+        r["params"] = par
+        return r
+
+    def set_friction(self, state):
+        """Impose the state rows of the friction model (mpc_sim_friction_set): (B, 17), e.g. ``read_friction(raw=True)`` of an earlier point."""
+        fn = self._sim_friction("mpc_sim_friction_set")
+        w = self._sim_friction("mpc_sim_friction_width")(self._h)
+        if w < 0:
+            self._check(-1, "mpc_sim_friction_width")
+        r = _f64(state)
+        d = self.dims
+        if r.shape != (d.batch, w):
+            raise ValueError("set_friction: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
+        self._check(fn(self._h, _dp(r)), "mpc_sim_friction_set")
 
     # -- include/mpc_sim_terrain.h (HIP library only): the box terrain under the contact rule ------------------------------------------------------
     def _sim_terrain(self, name):

@@ -31,6 +31,10 @@ is the pair the robot takes to stand, and ``detected_contacts=("estimator",)`` l
 a payload, a mass error, a displaced centre of mass; mpc_sim_plant, include/mpc_sim_plant.h).  ``model`` stays the nominal one, what a controller is
 built from; ``plantModel()`` is what is integrated.  The host contact rule lowers the model again at every catch: the library rebuilds the plant's
 table from the rows in force.
+``friction=`` / ``setFriction(rows)`` (HIP library only, with ``device_contacts=True``) make every held sole a Coulomb slider (``friction_model``;
+mpc_sim_friction, include/mpc_sim_friction.h): a sole whose tangential force leaves the cone ``mu f_z`` slips, and turns when its yaw moment leaves
+``mu_spin f_z``.  ``setFrictionCoefficients(link_id, lateral, spinning)``, the reference's knob, sets ``mu`` and ``mu_spin`` of one sole.  Without
+either every sole holds whatever force it takes, as before.
 
 Differences from PyBullet worth knowing: ``measureState`` returns the base velocity in the LOCAL frame of the base (Pinocchio's
 convention, which is what the scripts assume when they copy it into the state, talos_utils.py:337-348); PyBullet reports it in the
@@ -41,6 +45,7 @@ import numpy as np
 
 from . import _capi as K
 from . import contact_rule as _contact_rule
+from . import friction_model as _friction_model
 from .aligator import _core as core
 from .aligator import dynamics as _dyn
 from .aligator import manifolds as _manifolds
@@ -59,7 +64,7 @@ class BulletRobot:
 
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
                  inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
-                 device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None, plant=None):
+                 device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None, plant=None, friction=None):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -77,6 +82,7 @@ class BulletRobot:
         self._estimator = estimator  # params of setEstimator, armed at initializeJoints after the sensors
         self._foot_sensors = None if foot_sensors is None else (foot_sensors, ())  # (params, detected_contacts) of setFootSensors, armed at initializeJoints
         self._plant = None if plant is None else (plant, None)  # (rows, link_scale) of setPlant, armed at initializeJoints
+        self._friction = friction  # rows of setFriction, armed at initializeJoints
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
         self._native = None
@@ -124,6 +130,8 @@ class BulletRobot:
                 self._native.terrain(self.terrain)
         if self._plant is not None:
             self.setPlant(*self._plant)
+        if self._friction is not None:
+            self.setFriction(self._friction)
         if self._actuators is not None:
             self.setActuators(*self._actuators)
         if self._foot_sensors is not None:  # (before the estimator: its arming event already reads the pair it will be fed)
@@ -316,7 +324,56 @@ class BulletRobot:
         self.markers = tuple(np.array(t) for t in trans)
 
     def setFrictionCoefficients(self, link_id, lateral_friction, spinning_friction):
-        pass
+        """bullet_robot.py of the reference: ``changeDynamics(robot, link_id, lateralFriction=..., spinningFriction=...)``.  Here ``mu`` and
+        ``mu_spin`` of one sole of the friction model (``setFriction``; it is turned on with the other sole at the identity if it was off):
+        ``link_id`` 0 / 1 (left, right), or the frame id or the joint id of a sole in ``model`` once ``initializeJoints`` has built it.  Any other
+        link has no contact model here: a no-op, as before."""
+        sole = self._sole_of(link_id)
+        if sole is None:
+            return
+        rows = dict(self._friction) if isinstance(self._friction, dict) else \
+            ({} if self._friction is None else dict(zip(_friction_model.FIELDS, _friction_model.rows(self._friction, 1)[0])))
+        for short in _friction_model.BOTH:   # (a dict given with the shorthands: spelled out per sole before one sole is changed)
+            if short in rows:
+                v = rows.pop(short)
+                rows.setdefault(short + "_left", v), rows.setdefault(short + "_right", v)
+        side = ("left", "right")[sole]
+        rows["mu_" + side], rows["mu_spin_" + side] = float(lateral_friction), float(spinning_friction)
+        self.setFriction(rows)
+
+    def _sole_of(self, link_id):
+        """0 / 1 for the ids ``setFrictionCoefficients`` takes for the left / right sole, None for any other"""
+        link_id = int(link_id)
+        if link_id in (0, 1):
+            return link_id
+        if self._native is not None:
+            for i, fid in enumerate(self.frame_ids):
+                if link_id in (fid, self.model.frames[fid].parentJoint):
+                    return i
+        return None
+
+    def setFriction(self, rows):
+        """The ground friction under the soles (``friction_model``; HIP library only, needs ``device_contacts=True``): ``rows`` one row of 8, (1, 8),
+        or a dict by field name (``mu`` / ``mu_spin``: both soles; missing fields as in ``friction_model.defaults`` of this robot: coefficients
+        +inf, slider masses from its mass and posture); None: off.  Arms the model with every sole at rest; before ``initializeJoints`` it is kept
+        for then."""
+        if rows is not None and not self.device_contacts:
+            raise ValueError("setFriction: the friction model needs device_contacts=True (it slides the soles the device contact rule holds)")
+        self._friction = rows
+        if self._native is None:
+            return
+        if rows is None:
+            if hasattr(self._native.lib, "mpc_sim_friction"):
+                self._native.friction(None)
+            return
+        base = _friction_model.defaults(self.model, self.x[:self.model.nq], self.frame_ids, self.dt)
+        self._native.friction(_friction_model.validate(_friction_model.rows(rows, 1, base)))
+
+    def frictionState(self):
+        """the state rows of the friction model by ``friction_model.unpack`` (``v``, ``sliding``, ``slip_dist`` ...); None without one"""
+        if self._friction is None or self._native is None:
+            return None
+        return self._native.read_friction()
 
     def addStairs(self, path, position, orientation):
         raise NotImplementedError("headless BulletRobot: flat ground only")  # (a URDF staircase; createStairs / setTerrain lay boxes under the contact rule)

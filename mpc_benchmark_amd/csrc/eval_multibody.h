@@ -808,7 +808,18 @@ sim_u_set:
       const V3 pc = ldv3(cfr + 54 * tid + 9);
       const S6 acb = adinv(Rc, pc, sub6(ldc6(oa, nj, i), a0));
       const S6 vcb = adinv(Rc, pc, ldc6(ov, nj, i));
-      for (int r = 0; r < 6; ++r) gam[6 * tid + r] = acb.v[r] + cm[30 + r] * vcb.v[r] - cm[24 + r] * gam[6 * tid + r];
+      if constexpr (TRIAL == 2) {
+        // the friction model (include/mpc_sim_friction.h): robot b's sole is held to its slip velocity vs = (v_x, v_y, 0, 0, 0, w_z), LOCAL frame,
+        // instead of to rest (a sole that sticks, and every sole with the model off: vs = 0, and x - 0 is x in every bit)
+        double vs[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (mb.sim_friction && cid < 2) {
+          const double* fr = mb.sim_friction + (size_t)b * MPC_SIM_FRICTION_WIDTH + 3 * cid;
+          vs[0] = fr[0]; vs[1] = fr[1]; vs[5] = fr[2];
+        }
+        for (int r = 0; r < 6; ++r) gam[6 * tid + r] = acb.v[r] + cm[30 + r] * (vcb.v[r] - vs[r]) - cm[24 + r] * gam[6 * tid + r];
+      } else {
+        for (int r = 0; r < 6; ++r) gam[6 * tid + r] = acb.v[r] + cm[30 + r] * vcb.v[r] - cm[24 + r] * gam[6 * tid + r];
+      }
     }
     __syncthreads();
     // Y16 = [Jc^T | r1 | 0]  (nvp x 16): the contact columns (LOCAL frame: Ad(M_c)^-1 J) and the dynamics right-hand side r1 = B u - bias

@@ -10,7 +10,7 @@
 void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
                            bool trial, int cand0, int ncand, int sim_substeps, double sim_dt, bool with_derivs, const double* f_ext, bool contact_dyn,
                            const double* sim_u, double* sim_wrench, int f_ext_width, const double* sim_contacts, const double* sim_model,
-                           size_t sim_model_stride) {
+                           size_t sim_model_stride, const double* sim_friction) {
   const Layout& L = a.L;
   MbArgs mb;
   mb.lds = make_mb_lds(L.nj, L.n / 2, L.nx - L.n / 2, L.m, L.nz, contact_dyn);
@@ -19,6 +19,7 @@ void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout
   mb.sim_substeps = sim_substeps; mb.sim_dt = sim_dt; mb.f_ext = f_ext; mb.f_ext_width = f_ext_width; mb.sim_u = sim_u; mb.sim_wrench = sim_wrench;
   mb.sim_contacts = sim_contacts;
   mb.sim_model = sim_model; mb.sim_model_stride = sim_model_stride;
+  mb.sim_friction = sim_friction;
   mb.ncand_loop = (trial && !with_derivs && ncand > 1) ? ncand : 0;
   if (mb.lds.total_bytes > 160 * 1024) throw std::runtime_error("multibody model too large for the LDS budget of the stage kernel");
   // hipFuncSetAttribute is a per-device setting: remember what was requested on every device (a process may hold handles on several

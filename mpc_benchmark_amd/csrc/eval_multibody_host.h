@@ -4,6 +4,7 @@
 #include <stdexcept>
 #include "solver_args.h"
 #include "../../include/mpc_sim_contacts.h"
+#include "../../include/mpc_sim_friction.h"
 
 #ifndef EVAL_THREADS
 #define EVAL_THREADS 256  // threads per stage workgroup: 4 wavefronts, two workgroups per CU (measured against 512 = 8 wavefronts with a 128-VGPR cap, profiles/r03_*)
@@ -116,13 +117,18 @@ static inline size_t multibody_work_doubles(const Layout& L) {
 
 struct MbArgs {
   MbLds lds;
+  int f_ext_width;        // TRIAL == 2: the form of f_ext (below).  Kept in the tail padding of lds (an odd number of ints): see sim_friction
   double* scratch;        // per-workgroup HBM scratch
   size_t scratch_stride;  // doubles
   int ncand_loop;         // TRIAL == 1: > 0 = the workgroup walks this many candidates itself (grid z = 1)
   int sim_substeps;       // TRIAL == 2 (closed-loop simulation stand-in): integration steps ...
   double sim_dt;          // ... of this length
   const double* f_ext;    // TRIAL == 2: the push on the base per instance, or nullptr: f_ext_width 3: [B][3] world-frame force at the base origin
-  int f_ext_width;        // (mpc_simulate_push) ; 6: [B][6] = (world-frame force, fixed world point it acts at) (include/mpc_sim_ext.h)
+                          // (mpc_simulate_push) ; 6: [B][6] = (world-frame force, fixed world point it acts at) (include/mpc_sim_ext.h)
+  const double* sim_friction;  // TRIAL == 2: the state rows of the friction model [B][MPC_SIM_FRICTION_WIDTH] (include/mpc_sim_friction.h), or
+                               // nullptr: every held sole is held to rest.  It has the eight bytes f_ext_width and its padding had here: no
+                               // other member moved and the kernel argument after the struct (cand0) kept its offset, so every instantiation
+                               // but k_eval_multibody<2> compiles to the instructions it had (profiles/sim_friction.txt)
   const double* sim_u;    // TRIAL == 2: joint torques per instance [B][nu] held during the call (mpc_simulate_torque: the start state is
                           // then a.x0, no feedback law), or nullptr
   double* sim_wrench;     // TRIAL == 2: contact wrenches of the last sub-step [B][2][6], or nullptr
@@ -131,11 +137,13 @@ struct MbArgs {
   const double* sim_model;     // TRIAL == 2: the per-robot model tables [B][sim_model_stride] of the plant model (include/mpc_sim_plant.h), or
   size_t sim_model_stride;     // nullptr: every robot is integrated with the handle's one table
 };
+static_assert(sizeof(MbLds) % 8 == 4 && sizeof(MbArgs) == sizeof(MbLds) + 4 + 11 * 8, "MbArgs: f_ext_width fills the padding after lds");
 
 
 // defined in eval_multibody.hip
 void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
                            bool trial, int cand0 = 0, int ncand = 1, int sim_substeps = 0, double sim_dt = 0.0, bool with_derivs = false,
                            const double* f_ext = nullptr, bool contact_dyn = true, const double* sim_u = nullptr, double* sim_wrench = nullptr,
-                           int f_ext_width = 3, const double* sim_contacts = nullptr, const double* sim_model = nullptr, size_t sim_model_stride = 0);
+                           int f_ext_width = 3, const double* sim_contacts = nullptr, const double* sim_model = nullptr, size_t sim_model_stride = 0,
+                           const double* sim_friction = nullptr);
 const void* eval_multibody_kernel(int trial);  // entry point of k_eval_multibody<trial> (occupancy tooling)

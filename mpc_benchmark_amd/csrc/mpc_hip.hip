@@ -38,6 +38,7 @@
 #include "sim_estimator.h"
 #include "sim_foot_sensors.h"
 #include "sim_plant.h"
+#include "sim_friction.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
 #include "../../include/mpc_walk_poses.h"
@@ -113,9 +114,13 @@ struct SimPlant {
   std::vector<double> h_plant;  // params | link_scale (ones when none was given) as they are in force
   size_t plant_nd = 0;          // doubles of one robot's table: the handle's model_nd when the tables were built
   size_t plant_off = 0;         // doubles before the tables: B (16 + nj) with the joint count the rows were armed on
+  // include/mpc_sim_friction.h: the per-robot ground friction (nullptr: off, every held sole is held to rest), one allocation: params [B][8] | state
+  // rows [B][17]
+  double* d_fr = nullptr;
+  std::vector<double> h_fr;  // params as they are in force
   // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
   void free_owned() {
-    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est, &d_fs, &d_plant}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est, &d_fs, &d_plant, &d_fr}) if (*p) { (void)hipFree(*p); *p = nullptr; }
   }
 };
 

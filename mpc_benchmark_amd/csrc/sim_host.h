@@ -1,6 +1,6 @@
 // sim_host.h — host side of the torque-driven simulator (the plant): mpc_simulate_torque and the entry points of include/mpc_sim_ext.h (push, record),
-// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h, mpc_sim_estimator.h, mpc_sim_foot_sensors.h and mpc_sim_plant.h.  Its state is mpc_solver::plant (SimPlant); its kernels
-// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h, sim_estimator.h, sim_foot_sensors.h and sim_plant.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
+// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h, mpc_sim_estimator.h, mpc_sim_foot_sensors.h, mpc_sim_plant.h and mpc_sim_friction.h.  Its state is mpc_solver::plant (SimPlant); its kernels
+// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h, sim_estimator.h, sim_foot_sensors.h, sim_plant.h and sim_friction.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
 // loops of the three pipelines in pipeline_loops.h — goes through sim_steps_check, sim_steps_begin and sim_step_enqueue: an extension of the simulator
 // is added there, once.  Included at the end of mpc_hip.hip (mpc_solver, MPC_TRY, copy_sync, slot_of).
 #pragma once
@@ -230,6 +230,20 @@ static void sim_estimator_enqueue(mpc_solver* s, hipStream_t st, const double* x
   hipLaunchKernelGGL(k_sim_estimator, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
 }
+// the friction model of the step of length dt_step just enqueued on stream st, after the contact rule (sim_friction.h), when the model is on
+static double* sim_friction_rows(const mpc_solver* s) { return s->plant.d_fr + (size_t)s->L.B * MPC_SIM_FRICTION_PARAMS; }
+static void sim_friction_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
+  const SimPlant& p = s->plant;
+  if (!p.d_fr) return;
+  SimFrictionArgs a;
+  a.B = s->L.B; a.wr = p.d_simwr; a.con = p.d_con; a.params = p.d_fr; a.rows = sim_friction_rows(s); a.dt = dt_step;
+  hipLaunchKernelGGL(k_sim_friction, dim3((unsigned)((2 * s->L.B + SIM_FR_THREADS - 1) / SIM_FR_THREADS)), dim3(SIM_FR_THREADS), 0, st, a);
+  HIP_OK(hipGetLastError());
+}
+static void sim_friction_drop(mpc_solver* s) {
+  sim_realloc(s, s->plant.d_fr, 0);
+  s->plant.h_fr.clear();
+}
 static void sim_estimator_drop(mpc_solver* s) {
   sim_realloc(s, s->plant.d_est, 0);
   s->plant.h_est.clear();
@@ -286,19 +300,22 @@ static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
 // the new state, over the whole step.  The base-state estimator after it: the estimation event of that measurement (the true state without a
 // sensor model) and of the rows the contact rule just wrote; nothing of this step reads either, the controllers of the next step do (sim_measured).  Between the two, the foot force sensors and
 // the contact detector: the detection event of this step's wrenches (which the dynamics then always write), so that an estimator fed by detection reads
-// the pair this step's event left, and the low-level QPs of the next step the same pair.  In one line: actuator model -> dynamics -> record -> metrics
-// -> contact rule -> sensors -> foot sensors -> estimator.  The plant model (include/mpc_sim_plant.h) launches nothing here: the dynamics, the record and
+// the pair this step's event left, and the low-level QPs of the next step the same pair.  The friction model (include/mpc_sim_friction.h) directly
+// after the contact rule: from this step's wrenches and the flags the rule just wrote it sets the slip velocity each held sole has in the NEXT
+// step's dynamics, and advances the anchors of the soles that slid in this one.  In one line: actuator model -> dynamics -> record -> metrics
+// -> contact rule -> friction -> sensors -> foot sensors -> estimator.  The plant model (include/mpc_sim_plant.h) launches nothing here: the dynamics, the record and
 // the metrics read robot b's own model table, built when the model was armed.
 static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& args, int substeps, double dt, bool want_wrenches) {
   const SimPlant& p = s->plant;
   sim_actuators_enqueue(s, st, substeps * dt);
   launch_eval_multibody(st, args, s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, p.push_width ? p.d_push : nullptr, true,
-                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con || p.d_fs) ? p.d_simwr : nullptr, p.push_width ? p.push_width : 3, p.d_con,
-                        p.d_plant ? sim_plant_tables(s) : nullptr, sim_plant_stride(s));
+                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con || p.d_fs || p.d_fr) ? p.d_simwr : nullptr, p.push_width ? p.push_width : 3, p.d_con,
+                        p.d_plant ? sim_plant_tables(s) : nullptr, sim_plant_stride(s), p.d_fr ? sim_friction_rows(s) : nullptr);
   HIP_OK(hipGetLastError());
   sim_record_enqueue(s, st);
   sim_metrics_enqueue(s, st, substeps * dt);
   sim_contacts_enqueue(s, st);
+  sim_friction_enqueue(s, st, substeps * dt);
   sim_sensors_enqueue(s, st, s->d_x0, substeps * dt);
   sim_foot_sensors_enqueue(s, st, substeps * dt);
   sim_estimator_enqueue(s, st, sim_sensed(s), s->d_x0);
@@ -400,8 +417,9 @@ int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
       if (cfg->release_steps < 1) throw std::runtime_error("sim_contacts: release_steps must be >= 1");
     }
     sim_realloc(s, s->plant.d_con, cfg ? (size_t)L.B * MPC_SIM_CONTACTS_WIDTH : 0);
-    if (!cfg) {  // (the terrain, the estimator and the contact detector go with the rows; a reset keeps them)
+    if (!cfg) {  // (the terrain, the friction model, the estimator and the contact detector go with the rows; a reset keeps them)
       sim_terrain_drop(s);
+      sim_friction_drop(s);
       sim_estimator_drop(s);
       sim_foot_sensors_drop(s);
     }
@@ -918,6 +936,72 @@ int32_t mpc_sim_plant_width(mpc_solver* s) {
     return s->model_nd;
   });
 }
+
+// ---- include/mpc_sim_friction.h: per-robot ground friction under the soles ----------------------------------------------------------------------
+int mpc_sim_friction(mpc_solver* s, const double* params) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_friction");
+    const Layout& L = s->L;
+    const size_t np = (size_t)L.B * MPC_SIM_FRICTION_PARAMS;
+    if (!params) {
+      sim_friction_drop(s);
+      return 0;
+    }
+    for (int b = 0; b < L.B; ++b) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
+      const double* r = params + (size_t)b * MPC_SIM_FRICTION_PARAMS;
+      const std::string row = "sim_friction: row " + std::to_string(b);
+      for (int e = 0; e < 4; ++e)
+        if (std::isnan(r[e]) || r[e] < 0.0) throw std::runtime_error(row + ": mu and mu_spin must be >= 0 (+inf: the sole never slides), entry " + std::to_string(e));
+      for (int e = 4; e < MPC_SIM_FRICTION_PARAMS; ++e)
+        if (!std::isfinite(r[e]) || !(r[e] > 0.0)) throw std::runtime_error(row + ": m_slip, I_slip, v_max and w_max must be finite and > 0, entry " + std::to_string(e));
+    }
+    if (!s->plant.d_con) throw std::runtime_error("sim_friction: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    sim_realloc(s, s->plant.d_fr, np + (size_t)L.B * MPC_SIM_FRICTION_WIDTH);
+    s->plant.h_fr.assign(params, params + np);
+    sim_ensure(s);
+    std::vector<double> h(s->plant.h_fr);
+    h.resize(np + (size_t)L.B * MPC_SIM_FRICTION_WIDTH, 0.0);  // (the state rows after a reset: all 0)
+    copy_sync(s, s->plant.d_fr, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+int mpc_sim_friction_read(mpc_solver* s, double* params, double* state) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_friction_read");
+    if (!s->plant.d_fr) throw std::runtime_error("sim_friction_read: the friction model is off on this handle (turn it on with mpc_sim_friction)");
+    if (params) std::copy(s->plant.h_fr.begin(), s->plant.h_fr.end(), params);
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (state) copy_sync(s, state, sim_friction_rows(s), (size_t)s->L.B * MPC_SIM_FRICTION_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
+  })
+}
+
+int mpc_sim_friction_set(mpc_solver* s, const double* state) {
+  MPC_TRY(s, {
+    if (!state) throw std::runtime_error("sim_friction_set: state must not be null");
+    sim_check(s, "sim_friction_set");
+    if (!s->plant.d_fr) throw std::runtime_error("sim_friction_set: the friction model is off on this handle (turn it on with mpc_sim_friction)");
+    const Layout& L = s->L;
+    const size_t W = MPC_SIM_FRICTION_WIDTH;
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = state + (size_t)b * W;
+      const std::string row = "sim_friction_set: row " + std::to_string(b);
+      for (size_t e = 0; e < W; ++e)
+        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      for (int i = 0; i < 2; ++i) {
+        const double fl = r[SIM_FR_O_SLIDING + i];
+        if (fl != 0.0 && fl != 1.0) throw std::runtime_error(row + ": sliding must be 0 or 1");
+        if (fl == 0.0 && (r[3 * i] != 0.0 || r[3 * i + 1] != 0.0 || r[3 * i + 2] != 0.0))
+          throw std::runtime_error(row + ": sole " + std::to_string(i) + " holds a velocity but its sliding flag is 0");
+      }
+      for (size_t e = SIM_FR_O_STEPS; e < W; ++e)
+        if (r[e] < 0.0) throw std::runtime_error(row + ": slip_steps, slip_dist, slip_yaw, peak_excess and steps must be >= 0");
+    }
+    HIP_OK(hipStreamSynchronize(s->stream));
+    copy_sync(s, sim_friction_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+int32_t mpc_sim_friction_width(mpc_solver* s) { return sim_width(s, "sim_friction_width", [&] { return MPC_SIM_FRICTION_WIDTH; }); }
 
 // ---- include/mpc_abi.h: one step under the caller's torques -------------------------------------------------------------------------------------
 int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32_t substeps, double dt, double* wrenches) {

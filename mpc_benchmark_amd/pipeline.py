@@ -80,7 +80,14 @@ every robot, or a dict by field name of scalars or (B,) arrays, which may also c
 on the simulator handle when the pipeline is built (mpc_sim_plant, include/mpc_sim_plant.h; HIP library only).  Only the plant changes: the dynamics of
 every simulator step, and the centre of mass and centroidal momentum of the record and the metrics, are those of robot b's own inertias; the MPC, the
 low-level QPs, the contact rule, the estimator and the walk generators keep the nominal model.  ``plant_models()`` returns the perturbed models;
-``set_plant`` changes or removes the model later."""
+``set_plant`` changes or removes the model later.
+
+``friction`` (all three pipelines, with ``contact_rule``): None, every held sole transmits whatever tangential force and yaw moment it takes; or the
+parameter rows of the per-robot ground friction (``friction_model``: ``mu`` and ``mu_spin`` of each sole, the slider's masses and bounds; (B, 8), one
+row of 8 for every robot, or a dict by field name whose missing fields are the identity coefficients and ``friction_model.defaults`` of the robot),
+armed on the simulator handle when the pipeline is built (mpc_sim_friction, include/mpc_sim_friction.h; HIP library only).  Only the plant changes: a
+sole whose force leaves its cone slips.  The MPC stages and the low-level QPs keep their own cones (``mu = 0.8``).  ``friction_state()`` returns the
+slip velocities and counters; ``set_friction`` changes or removes the model later."""
 from __future__ import annotations
 
 import numpy as np
@@ -90,6 +97,7 @@ from . import actuator_model as _actuator_model
 from . import contact_rule as _contact_rule
 from . import foot_sensors as _foot_sensors
 from . import plant_model as _plant_model
+from . import friction_model as _friction_model
 from . import qp_utils
 from . import sensor_model as _sensor_model
 from . import state_estimator as _state_estimator
@@ -199,6 +207,12 @@ def _checked_plant(plant, batch, problem_def):
     return _plant_model.validate(_plant_model.rows(plant, batch), problem_def.robot.model.njoints - 1, link_scale)
 
 
+def _checked_friction(name, friction, contact_rule):
+    """``friction`` of a pipeline needs the contact rule: checked before any library call (the rows themselves when the model is armed)"""
+    if friction is not None and contact_rule is None:
+        raise ValueError("%s: friction needs contact_rule (the model slides the soles the unilateral contact rule holds; contact_rule={} turns it on)" % name)
+
+
 def _checked_walk(name, walk, batch):
     """``walk`` of a pipeline: the ``commands`` table in it is checked before any library call (shape, finite values, ``per_instance=True``)"""
     if walk is None or walk.get("commands") is None:
@@ -269,6 +283,28 @@ class _Actuators:
         checked = _plant_model.validate(_plant_model.rows(rows, self.batch), self.model.njoints - 1, link_scale)
         self.sim.plant(checked[0], link_scale=checked[1])
         self._plant_rows = checked
+
+    _friction_rows = None   # (B, 8) rows of the friction model in force
+
+    def set_friction(self, rows):
+        """Arm the per-robot ground friction on ``self.sim`` with every sole at rest: ``rows`` in the forms of ``NativeSolver.friction``, a dict's
+        missing fields from ``friction_model.defaults`` of the nominal robot; needs ``contact_rule``; checked before any library call.  None turns
+        the model off."""
+        if rows is None:
+            if self._friction_rows is not None:
+                self.sim.friction(None)
+            self._friction_rows = None
+            return
+        _checked_friction(type(self).__name__, rows, self.contact_rule)
+        rb = self.pd.robot
+        base = _friction_model.defaults(self.model, rb.x0[:self.model.nq], rb.foot_frame_ids, self.sim_dt)   # (a simulator step is one low-level period)
+        checked = _friction_model.validate(_friction_model.rows(rows, self.batch, base))
+        self.sim.friction(checked)
+        self._friction_rows = checked
+
+    def friction_state(self):
+        """the state rows of the friction model by ``friction_model.unpack`` (``v``, ``sliding``, ``slip_dist`` ...); None without ``friction``"""
+        return None if self._friction_rows is None else self.sim.read_friction()
 
     def plant_models(self):
         """one ``minipin.Model`` per robot: what the simulator integrates (``plant_model.models``; the nominal model B times without ``plant``)"""
@@ -426,17 +462,19 @@ class _QpContactSource:
 class KinodynamicPipeline(_QpContactSource, _Actuators):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
                  terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, foot_sensors=None,
-                 detected_contacts=(), plant=None, **ens_kw):
+                 detected_contacts=(), plant=None, friction=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
         ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model, ``sensors``: None or the rows of the
         sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the rows of the foot force sensors,
-        ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model (module docstring)."""
+        ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model, ``friction``: None or the rows of
+        the ground friction (module docstring)."""
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("KinodynamicPipeline", contact_source, contact_rule)
         detected_contacts = self._check_detected("KinodynamicPipeline", foot_sensors, detected_contacts, contact_rule, contact_source)
         self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
         walk = _checked_walk("KinodynamicPipeline", walk, self.batch)
+        _checked_friction("KinodynamicPipeline", friction, contact_rule)
         plant = _checked_plant(plant, self.batch, problem_def)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
@@ -454,6 +492,8 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         self._build_simulator()
         if plant is not None:
             self.set_plant(*plant)
+        if friction is not None:
+            self.set_friction(friction)
         if actuators is not None:
             self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
@@ -625,20 +665,21 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
                  sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, sensors=None,
-                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, **ens_kw):
+                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
         dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model,
         ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the
-        rows of the foot force sensors, ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model
-        (module docstring)."""
+        rows of the foot force sensors, ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model,
+        ``friction``: None or the rows of the ground friction (module docstring)."""
         from .ensemble import ensemble_initial_states
         self.pd, self.batch = problem_def, int(batch)
         self._init_contact_source("CentroidalPipeline", contact_source, contact_rule)
         detected_contacts = self._check_detected("CentroidalPipeline", foot_sensors, detected_contacts, contact_rule, contact_source)
         self.terrain = _checked_terrain("CentroidalPipeline", terrain, contact_rule, self.batch)
         walk = _checked_walk("CentroidalPipeline", walk, self.batch)
+        _checked_friction("CentroidalPipeline", friction, contact_rule)
         plant = _checked_plant(plant, self.batch, problem_def)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         self.lib = library if library is not None else K.load_hip_library()
@@ -671,6 +712,8 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
         self._set_sim_contacts((True, True))   # (the schedule starts in double support)
         if plant is not None:
             self.set_plant(*plant)
+        if friction is not None:
+            self.set_friction(friction)
         if actuators is not None:
             self.set_actuators(actuators)
         if sensors is not None:
@@ -820,16 +863,17 @@ class FullDynamicPipeline(_Actuators):
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
-                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, **ens_kw):
+                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
         actuator model, ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state
         estimator, ``foot_sensors``: None or the rows of the foot force sensors, ``detected_contacts``: () or ("estimator",), ``plant``: None or the rows of the plant
-        model (module docstring of pipeline.py)."""
+        model, ``friction``: None or the rows of the ground friction (module docstring of pipeline.py)."""
         detected_contacts = self._check_detected("FullDynamicPipeline", foot_sensors, detected_contacts, contact_rule)
         self.terrain = _checked_terrain("FullDynamicPipeline", terrain, contact_rule, int(batch))
         walk = _checked_walk("FullDynamicPipeline", walk, int(batch))
+        _checked_friction("FullDynamicPipeline", friction, contact_rule)
         if ens_kw.get("closed_loop") is not None:
             raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
                              "EnsembleMPC(closed_loop=...) would simulate a second time)")
@@ -850,6 +894,8 @@ class FullDynamicPipeline(_Actuators):
             _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule, self.terrain)
         if plant is not None:
             self.set_plant(*plant)
+        if friction is not None:
+            self.set_friction(friction)
         if actuators is not None:
             self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
