@@ -254,6 +254,24 @@ _WALK_COMMANDS_SIGNATURES = {
     "mpc_walk_poses_get_commands": (C.c_int, [C.c_void_p, _DP]),
 }
 
+# The headers the HIP library alone exports: (header, its entry points, what a library without them is told it lacks, the error that says so).
+_HIP_ONLY = (
+    ("mpc_sim_ext.h", _SIM_EXT_SIGNATURES, "the push and the record of torque-driven simulator steps are HIP only", RuntimeError),
+    ("mpc_feedback_pipeline.h", _FEEDBACK_PIPELINE_SIGNATURES, "the full-dynamics device loop is HIP only", RuntimeError),
+    ("mpc_sim_metrics.h", _SIM_METRICS_SIGNATURES, "the locomotion metrics of torque-driven simulator steps are HIP only", RuntimeError),
+    ("mpc_sim_contacts.h", _SIM_CONTACTS_SIGNATURES, "the contact rule of torque-driven simulator steps is HIP only", RuntimeError),
+    ("mpc_sim_actuators.h", _SIM_ACTUATORS_SIGNATURES, "the actuator model of torque-driven simulator steps is HIP only", RuntimeError),
+    ("mpc_sim_sensors.h", _SIM_SENSORS_SIGNATURES, "the sensor model of torque-driven simulator steps is HIP only", RuntimeError),
+    ("mpc_sim_estimator.h", _SIM_ESTIMATOR_SIGNATURES, "the base-state estimator of torque-driven simulator steps is HIP only", RuntimeError),
+    ("mpc_sim_foot_sensors.h", _SIM_FOOT_SENSORS_SIGNATURES, "the foot force sensors of torque-driven simulator steps are HIP only", RuntimeError),
+    ("mpc_sim_plant.h", _SIM_PLANT_SIGNATURES, "the plant model of torque-driven simulator steps is HIP only", RuntimeError),
+    ("mpc_sim_friction.h", _SIM_FRICTION_SIGNATURES, "the ground friction of torque-driven simulator steps is HIP only", RuntimeError),
+    ("mpc_sim_terrain.h", _SIM_TERRAIN_SIGNATURES, "the terrain of the contact rule needs the HIP library", NotImplementedError),
+    ("mpc_walk_poses.h", _WALK_POSES_SIGNATURES, "the device generator of the contact-pose references is HIP only", RuntimeError),
+    ("mpc_walk_commands.h", _WALK_COMMANDS_SIGNATURES, "a walk command per robot on the device generators needs the HIP library", NotImplementedError),
+)
+_HIP_ONLY_HEADER = {name: entry for entry in _HIP_ONLY for name in entry[1]}
+
 
 def bind_library(path):
     """dlopen ``path`` and attach the argument/return types of every entry point of mpc_abi.h."""
@@ -262,8 +280,7 @@ def bind_library(path):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in list(_SIM_EXT_SIGNATURES.items()) + list(_FEEDBACK_PIPELINE_SIGNATURES.items()) + list(_SIM_METRICS_SIGNATURES.items()) + \
-            list(_SIM_CONTACTS_SIGNATURES.items()) + list(_SIM_ACTUATORS_SIGNATURES.items()) + list(_SIM_SENSORS_SIGNATURES.items()) + list(_SIM_ESTIMATOR_SIGNATURES.items()) + list(_SIM_FOOT_SENSORS_SIGNATURES.items()) + list(_SIM_PLANT_SIGNATURES.items()) + list(_SIM_FRICTION_SIGNATURES.items()) + list(_SIM_TERRAIN_SIGNATURES.items()) + list(_WALK_POSES_SIGNATURES.items()) + list(_WALK_COMMANDS_SIGNATURES.items()):
+    for name, (res, args) in [item for _, signatures, _, _ in _HIP_ONLY for item in signatures.items()]:
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype = res
@@ -328,6 +345,47 @@ class NativeSolver:
         if rc < 0:
             raise RuntimeError("%s failed: %s" % (what, self.lib.mpc_last_error(self._h).decode(errors="replace")))
         return rc
+
+    def _hip(self, name):
+        """entry point ``name`` of a header the HIP library alone exports (``_HIP_ONLY``), or the error that names what this library lacks"""
+        if not hasattr(self.lib, name):
+            header, _, what, error = _HIP_ONLY_HEADER[name]
+            raise error("%s is not exported by this library (%s): %s (libmpc_hip.so, include/%s)" % (name, self.backend, what, header))
+        return getattr(self.lib, name)
+
+    def _width(self, name):
+        """what the width entry point ``name`` reports, or the library's error when that is -1"""
+        w = self._hip(name)(self._h)
+        if w < 0:
+            self._check(-1, name)
+        return w
+
+    def _state_rows(self, width):
+        """a zeroed (B, w) array for the rows whose width entry point ``width`` reports"""
+        return np.zeros((self.dims.batch, self._width(width)))
+
+    def _checked_rows(self, what, rows, w):
+        """``rows`` as a (B, w) float64 array, or a ValueError that begins with ``what`` (the caller and its noun)"""
+        r = _f64(rows)
+        if r.shape != (self.dims.batch, w):
+            raise ValueError("%s of shape (%d, %d) expected, got %s" % (what, self.dims.batch, w, r.shape))
+        return r
+
+    def _read_model(self, noun, model, raw, *unpack_args, x=False):
+        """``read_<noun>`` of a per-robot model: the state rows, raw or by ``model.unpack`` with the parameter rows in force as ``params`` (and,
+        for the models the controllers read through, what they deliver as ``x``)"""
+        name = "mpc_sim_%s_read" % noun
+        fn, out = self._hip(name), self._state_rows("mpc_sim_%s_width" % noun)
+        par = np.zeros((self.dims.batch, model.PARAMS))
+        xs = np.zeros((self.dims.batch, self.dims.nx)) if x else None
+        self._check(fn(self._h, _dp(par), _dp(out), *((_dp(xs),) if x else ())), name)
+        if raw:
+            return out
+        r = model.unpack(out, *unpack_args)
+        r["params"] = par
+        if x:
+            r["x"] = xs
+        return r
 
     # -- problem upload ------------------------------------------------------------------------
     def set_options(self, opt: MpcOptions):
@@ -402,16 +460,10 @@ class NativeSolver:
         return (x0, wr) if wrenches else x0
 
     # -- include/mpc_sim_ext.h (HIP library only): push and per-step record of the torque-driven simulator ----------------------------
-    def _sim_ext(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the push and the record of torque-driven simulator steps are HIP only "
-                               "(libmpc_hip.so, include/mpc_sim_ext.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def set_push(self, f_ext):
         """Arm a push for every torque-driven simulator step of this handle until re-armed (mpc_sim_set_push); None disarms.  f_ext (B, 3) or (3,):
         a world-frame force at the base origin (``simulate_push``'s convention); (B, 6) or (6,): (force, fixed world point it acts at)."""
-        fn = self._sim_ext("mpc_sim_set_push")
+        fn = self._hip("mpc_sim_set_push")
         if f_ext is None:
             self._check(fn(self._h, None, 3), "mpc_sim_set_push")
             return
@@ -424,15 +476,12 @@ class NativeSolver:
 
     def record(self, cap):
         """Record every torque-driven simulator step of this handle into a device ring of ``cap`` steps (mpc_sim_record); 0: off."""
-        self._check(self._sim_ext("mpc_sim_record")(self._h, int(cap)), "mpc_sim_record")
+        self._check(self._hip("mpc_sim_record")(self._h, int(cap)), "mpc_sim_record")
 
     def read_record(self):
         """The recorded steps, oldest first, and an empty ring (mpc_sim_record_read) -> dict of arrays shaped (steps, B, ...): x, tau,
         wrenches (2, 6) LOCAL, com (3), momentum (6: linear, angular about the com), sole_R (2, 3, 3), sole_p (2, 3), push (6: force, point)."""
-        fn = self._sim_ext("mpc_sim_record_read")
-        w = self._sim_ext("mpc_sim_record_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_record_width")
+        fn, w = self._hip("mpc_sim_record_read"), self._width("mpc_sim_record_width")
         n = C.c_int32(0)
         self._check(fn(self._h, None, C.byref(n)), "mpc_sim_record_read")
         d = self.dims
@@ -446,16 +495,10 @@ class NativeSolver:
                 "momentum": out[:, :, o + 15:o + 21], "sole_R": soles[..., :9].reshape(S, B, 2, 3, 3), "sole_p": soles[..., 9:], "push": out[:, :, o + 45:o + 51]}
 
     # -- include/mpc_sim_metrics.h (HIP library only): locomotion metrics of the torque-driven simulator steps ---------------------------------
-    def _sim_metrics(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the locomotion metrics of torque-driven simulator steps are HIP only "
-                               "(libmpc_hip.so, include/mpc_sim_metrics.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def metrics(self, cfg):
         """Accumulate the locomotion metrics of every robot on the device after every torque-driven simulator step of this handle (mpc_sim_metrics):
         ``cfg`` a dict over ``locomotion_metrics.DEFAULTS`` ({} for the defaults) turns them on and resets them; None turns them off."""
-        fn = self._sim_metrics("mpc_sim_metrics")
+        fn = self._hip("mpc_sim_metrics")
         if cfg is None:
             self._check(fn(self._h, None), "mpc_sim_metrics")
             return
@@ -465,26 +508,16 @@ class NativeSolver:
     def read_metrics(self, reset=False):
         """The metric rows since the last reset (mpc_sim_metrics_read) -> dict of (B,) arrays by ``locomotion_metrics.FIELDS`` name (``sole_z0``
         (B, 2), ``com_first`` / ``com_last`` (B, 3)).  ``reset``: then zero them; the next step latches the heights again."""
-        fn = self._sim_metrics("mpc_sim_metrics_read")
-        w = self._sim_metrics("mpc_sim_metrics_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_metrics_width")
-        out = np.zeros((self.dims.batch, w))
+        fn, out = self._hip("mpc_sim_metrics_read"), self._state_rows("mpc_sim_metrics_width")
         self._check(fn(self._h, _dp(out), int(bool(reset))), "mpc_sim_metrics_read")
         return _metrics.unpack(out)
 
     # -- include/mpc_sim_contacts.h (HIP library only): the unilateral contact rule of the torque-driven simulator steps ------------------------
-    def _sim_contacts(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the contact rule of torque-driven simulator steps is HIP only "
-                               "(libmpc_hip.so, include/mpc_sim_contacts.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def contacts(self, cfg):
         """Decide every robot's foot contacts on the device after every torque-driven simulator step of this handle (mpc_sim_contacts): ``cfg`` a
         dict over ``contact_rule.DEFAULTS`` ({} for the defaults) turns the rule on and resets it (both soles in contact at the model's anchors);
         None turns it off.  While it is on, stage 0 of this handle must be the double-support stage."""
-        fn = self._sim_contacts("mpc_sim_contacts")
+        fn = self._hip("mpc_sim_contacts")
         if cfg is None:
             self._check(fn(self._h, None), "mpc_sim_contacts")
             return
@@ -495,36 +528,23 @@ class NativeSolver:
     def read_contacts(self, raw=False):
         """The rows of the contact rule (mpc_sim_contacts_read) -> dict of arrays by ``contact_rule.FIELDS`` name (``anchor_R`` (B, 2, 3, 3),
         ``anchor_p`` (B, 2, 3)); ``raw``: the (B, WIDTH) rows themselves."""
-        fn = self._sim_contacts("mpc_sim_contacts_read")
-        w = self._sim_contacts("mpc_sim_contacts_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_contacts_width")
-        out = np.zeros((self.dims.batch, w))
+        fn, out = self._hip("mpc_sim_contacts_read"), self._state_rows("mpc_sim_contacts_width")
         self._check(fn(self._h, _dp(out)), "mpc_sim_contacts_read")
         return out if raw else _contact_rule.unpack(out)
 
     def set_contacts(self, rows):
         """Impose the rows of the contact rule (mpc_sim_contacts_set): (B, WIDTH), e.g. ``read_contacts(raw=True)`` of an earlier point."""
-        fn = self._sim_contacts("mpc_sim_contacts_set")
-        r = _f64(rows)
-        if r.shape != (self.dims.batch, _contact_rule.WIDTH):
-            raise ValueError("set_contacts: rows of shape (%d, %d) expected, got %s" % (self.dims.batch, _contact_rule.WIDTH, r.shape))
-        self._check(fn(self._h, _dp(r)), "mpc_sim_contacts_set")
+        fn = self._hip("mpc_sim_contacts_set")
+        self._check(fn(self._h, _dp(self._checked_rows("set_contacts: rows", rows, _contact_rule.WIDTH))), "mpc_sim_contacts_set")
 
     # -- include/mpc_sim_actuators.h (HIP library only): the per-robot actuator model of the torque-driven simulator steps -----------------------
-    def _sim_actuators(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the actuator model of torque-driven simulator steps is HIP only "
-                               "(libmpc_hip.so, include/mpc_sim_actuators.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def actuators(self, params, limit=None, friction_shape=None):
         """Pass the torque of every torque-driven simulator step of this handle through every robot's own actuator model on the device before the
         dynamics integrate it (mpc_sim_actuators; ``actuator_model`` is the definition).  ``params``: (B, 8) rows, one row of 8 for every robot, or
         a dict by ``actuator_model.FIELDS`` name of scalars or (B,) arrays (missing fields: the identity value); turns the model on and resets
         its state rows.  ``limit`` (nu,): the effort limits, needed when a row has ``sat`` > 0; ``friction_shape`` (nu,) or None (ones).  None turns
         the model off."""
-        fn = self._sim_actuators("mpc_sim_actuators")
+        fn = self._hip("mpc_sim_actuators")
         if params is None:
             self._check(fn(self._h, None, None, None), "mpc_sim_actuators")
             return
@@ -542,41 +562,21 @@ class NativeSolver:
     def read_actuators(self, raw=False):
         """The state rows of the actuator model (mpc_sim_actuators_read) -> dict of arrays by ``actuator_model.unpack`` (``ring`` (B, 16, nu), ``y``,
         ``applied`` (B, nu), ``head``, ``count`` (B,)) plus ``params`` (B, 8), the rows in force; ``raw``: the (B, 18 nu + 2) state rows themselves."""
-        fn = self._sim_actuators("mpc_sim_actuators_read")
-        w = self._sim_actuators("mpc_sim_actuators_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_actuators_width")
-        d = self.dims
-        out, par = np.zeros((d.batch, w)), np.zeros((d.batch, _actuator_model.PARAMS))
-        self._check(fn(self._h, _dp(par), _dp(out)), "mpc_sim_actuators_read")
-        if raw:
-            return out
-        r = _actuator_model.unpack(out, d.nu)
-        r["params"] = par
-        return r
+        return self._read_model("actuators", _actuator_model, raw, self.dims.nu)
 
     def set_actuators(self, state):
         """Impose the state rows of the actuator model (mpc_sim_actuators_set): (B, 18 nu + 2), e.g. ``read_actuators(raw=True)`` of an earlier point."""
-        fn = self._sim_actuators("mpc_sim_actuators_set")
-        r = _f64(state)
-        d = self.dims
-        if r.shape != (d.batch, _actuator_model.width(d.nu)):
-            raise ValueError("set_actuators: state rows of shape (%d, %d) expected, got %s" % (d.batch, _actuator_model.width(d.nu), r.shape))
+        fn = self._hip("mpc_sim_actuators_set")
+        r = self._checked_rows("set_actuators: state rows", state, _actuator_model.width(self.dims.nu))
         self._check(fn(self._h, _dp(r)), "mpc_sim_actuators_set")
 
     # -- include/mpc_sim_plant.h (HIP library only): per-robot plant inertias of the torque-driven simulator steps ---------------------------------
-    def _sim_plant(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the plant model of torque-driven simulator steps is HIP only "
-                               "(libmpc_hip.so, include/mpc_sim_plant.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def plant(self, rows, link_scale=None):
         """Integrate every robot of this simulator handle with its own link inertias (mpc_sim_plant; ``plant_model`` is the definition).  ``rows``:
         (B, 16) rows, one row of 16 for every robot, or a dict by ``plant_model.FIELDS`` name of scalars or (B,) arrays (missing fields: the
         identity value); ``link_scale``: None or (B, nj), every link's own mass factor.  Builds the per-robot model tables on the device; the
         controllers' handles keep the nominal model.  None turns the model off."""
-        fn = self._sim_plant("mpc_sim_plant")
+        fn = self._hip("mpc_sim_plant")
         if rows is None:
             self._check(fn(self._h, None, None), "mpc_sim_plant")
             return
@@ -595,29 +595,19 @@ class NativeSolver:
     def read_plant(self):
         """The plant model in force (mpc_sim_plant_read) -> dict: ``params`` (B, 16), ``link_scale`` (B, nj) (ones when none was given), ``tables``
         (B, nd) the model table every robot is integrated with."""
-        fn = self._sim_plant("mpc_sim_plant_read")
-        nd = self._sim_plant("mpc_sim_plant_width")(self._h)
-        if nd < 0:
-            self._check(-1, "mpc_sim_plant_width")
-        d = self.dims
-        par, ls, tab = np.zeros((d.batch, _plant_model.PARAMS)), np.zeros((d.batch, self._model_nj)), np.zeros((d.batch, nd))
+        fn, tab = self._hip("mpc_sim_plant_read"), self._state_rows("mpc_sim_plant_width")
+        par, ls = np.zeros((self.dims.batch, _plant_model.PARAMS)), np.zeros((self.dims.batch, self._model_nj))
         self._check(fn(self._h, _dp(par), _dp(ls), _dp(tab)), "mpc_sim_plant_read")
         return {"params": par, "link_scale": ls, "tables": tab}
 
     # -- include/mpc_sim_sensors.h (HIP library only): the per-robot sensor model between the torque-driven simulator steps and the controllers -----
-    def _sim_sensors(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the sensor model of torque-driven simulator steps is HIP only "
-                               "(libmpc_hip.so, include/mpc_sim_sensors.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def sensors(self, params, x0=None):
         """Follow every torque-driven simulator step of this handle with every robot's own measurement event on the device: the controllers of the
         device loops then read the measurement, not the true state (mpc_sim_sensors; ``sensor_model`` is the definition).  ``params``: (B, 16) rows,
         one row of 16 for every robot, or a dict by ``sensor_model.FIELDS`` name of scalars or (B,) arrays (missing fields 0: the identity); turns the
         model on, resets its state rows and takes the first measurement, of ``x0`` (B, nx): the true states the simulator starts from.  None turns
         the model off."""
-        fn = self._sim_sensors("mpc_sim_sensors")
+        fn = self._hip("mpc_sim_sensors")
         if params is None:
             self._check(fn(self._h, None, None), "mpc_sim_sensors")
             return
@@ -632,45 +622,21 @@ class NativeSolver:
         """The sensor model as it stands (mpc_sim_sensors_read) -> dict: ``x`` (B, nx) the measurement the controllers read, ``params`` (B, 16) the
         rows in force, and the state rows by ``sensor_model.unpack`` (``ring`` (B, 16, nx), ``meas`` (B, nx), ``vf``, ``qm_prev`` (B, nu), ``head``,
         ``count`` (B,)); ``raw``: the (B, 17 nx + 2 nu + 2) state rows themselves."""
-        fn = self._sim_sensors("mpc_sim_sensors_read")
-        w = self._sim_sensors("mpc_sim_sensors_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_sensors_width")
-        d = self.dims
-        out, par, xm = np.zeros((d.batch, w)), np.zeros((d.batch, _sensor_model.PARAMS)), np.zeros((d.batch, d.nx))
-        self._check(fn(self._h, _dp(par), _dp(out), _dp(xm)), "mpc_sim_sensors_read")
-        if raw:
-            return out
-        r = _sensor_model.unpack(out, d.ndx // 2)
-        r["params"], r["x"] = par, xm
-        return r
+        return self._read_model("sensors", _sensor_model, raw, self.dims.ndx // 2, x=True)
 
     def set_sensors(self, state):
         """Impose the state rows of the sensor model (mpc_sim_sensors_set): (B, 17 nx + 2 nu + 2), e.g. ``read_sensors(raw=True)`` of an earlier point."""
-        fn = self._sim_sensors("mpc_sim_sensors_set")
-        w = self._sim_sensors("mpc_sim_sensors_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_sensors_width")
-        r = _f64(state)
-        d = self.dims
-        if r.shape != (d.batch, w):
-            raise ValueError("set_sensors: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
-        self._check(fn(self._h, _dp(r)), "mpc_sim_sensors_set")
+        fn, w = self._hip("mpc_sim_sensors_set"), self._width("mpc_sim_sensors_width")
+        self._check(fn(self._h, _dp(self._checked_rows("set_sensors: state rows", state, w))), "mpc_sim_sensors_set")
 
     # -- include/mpc_sim_estimator.h (HIP library only): the per-robot base-state estimator between the sensor model and the controllers -------------
-    def _sim_estimator(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the base-state estimator of torque-driven simulator steps is HIP only "
-                               "(libmpc_hip.so, include/mpc_sim_estimator.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def estimator(self, params, x0=None):
         """Follow every torque-driven simulator step of this handle with every robot's own estimation event on the device: the controllers of the
         device loops then read the estimate — the measured state with the base position and linear velocity blended with leg odometry — not the
         measurement (mpc_sim_estimator; ``state_estimator`` is the definition).  Needs the contact rule (``contacts``).  ``params``: (B, 16) rows, one
         row of 16 for every robot, or a dict by ``state_estimator.FIELDS`` name of scalars or (B,) arrays (missing fields 0: the identity); turns the
         estimator on, resets its state rows and arms on ``x0`` (B, nx): the first MEASURED states.  None turns the estimator off."""
-        fn = self._sim_estimator("mpc_sim_estimator")
+        fn = self._hip("mpc_sim_estimator")
         if params is None:
             self._check(fn(self._h, None, None), "mpc_sim_estimator")
             return
@@ -685,45 +651,21 @@ class NativeSolver:
         """The estimator as it stands (mpc_sim_estimator_read) -> dict: ``x`` (B, nx) the estimate the controllers read, ``params`` (B, 16) the rows
         in force, and the state rows by ``state_estimator.unpack`` (``est`` (B, nx), ``held`` (B, 2), ``anchor`` (B, 2, 3), ``stats`` (B, 8),
         ``count`` (B,)); ``raw``: the (B, nx + 17) state rows themselves."""
-        fn = self._sim_estimator("mpc_sim_estimator_read")
-        w = self._sim_estimator("mpc_sim_estimator_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_estimator_width")
-        d = self.dims
-        out, par, xe = np.zeros((d.batch, w)), np.zeros((d.batch, _state_estimator.PARAMS)), np.zeros((d.batch, d.nx))
-        self._check(fn(self._h, _dp(par), _dp(out), _dp(xe)), "mpc_sim_estimator_read")
-        if raw:
-            return out
-        r = _state_estimator.unpack(out, d.ndx // 2)
-        r["params"], r["x"] = par, xe
-        return r
+        return self._read_model("estimator", _state_estimator, raw, self.dims.ndx // 2, x=True)
 
     def set_estimator(self, state):
         """Impose the state rows of the estimator (mpc_sim_estimator_set): (B, nx + 17), e.g. ``read_estimator(raw=True)`` of an earlier point."""
-        fn = self._sim_estimator("mpc_sim_estimator_set")
-        w = self._sim_estimator("mpc_sim_estimator_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_estimator_width")
-        r = _f64(state)
-        d = self.dims
-        if r.shape != (d.batch, w):
-            raise ValueError("set_estimator: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
-        self._check(fn(self._h, _dp(r)), "mpc_sim_estimator_set")
+        fn, w = self._hip("mpc_sim_estimator_set"), self._width("mpc_sim_estimator_width")
+        self._check(fn(self._h, _dp(self._checked_rows("set_estimator: state rows", state, w))), "mpc_sim_estimator_set")
 
     # -- include/mpc_sim_foot_sensors.h (HIP library only): the per-robot foot force sensors and the contact detector ------------------------------
-    def _sim_foot_sensors(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the foot force sensors of torque-driven simulator steps are HIP only "
-                               "(libmpc_hip.so, include/mpc_sim_foot_sensors.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def foot_sensors(self, params):
         """Follow every torque-driven simulator step of this handle with every robot's own detection event on the device: the step's contact wrenches
         are measured and a threshold detector decides which soles the robot takes to stand (mpc_sim_foot_sensors; ``foot_sensors`` is the
         definition).  Needs the contact rule (``contacts``).  ``params``: (B, 16) rows, one row of 16 for every robot, or a dict by
         ``foot_sensors.FIELDS`` name of scalars or (B,) arrays (missing fields as in ``foot_sensors.EXACT``); turns the model on and arms it on the
         rule's ``in_contact`` pairs.  None turns the model off and clears the feed."""
-        fn = self._sim_foot_sensors("mpc_sim_foot_sensors")
+        fn = self._hip("mpc_sim_foot_sensors")
         if params is None:
             self._check(fn(self._h, None), "mpc_sim_foot_sensors")
             return
@@ -734,51 +676,27 @@ class NativeSolver:
         """The detector as it stands (mpc_sim_foot_sensors_read) -> dict: ``params`` (B, 16) the rows in force, and the state rows by
         ``foot_sensors.unpack`` (``det`` (B, 2), ``above``, ``below``, ``wf`` (B, 12), ``wm`` (B, 12), ``counts`` (B, 2, 4), ``ring`` (B, 16, 12),
         ``head``, ``count``); ``raw``: the (B, 232) state rows themselves."""
-        fn = self._sim_foot_sensors("mpc_sim_foot_sensors_read")
-        w = self._sim_foot_sensors("mpc_sim_foot_sensors_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_foot_sensors_width")
-        d = self.dims
-        out, par = np.zeros((d.batch, w)), np.zeros((d.batch, _foot_sensors.PARAMS))
-        self._check(fn(self._h, _dp(par), _dp(out)), "mpc_sim_foot_sensors_read")
-        if raw:
-            return out
-        r = _foot_sensors.unpack(out)
-        r["params"] = par
-        return r
+        return self._read_model("foot_sensors", _foot_sensors, raw)
 
     def set_foot_sensors(self, state):
         """Impose the state rows of the detector (mpc_sim_foot_sensors_set): (B, 232), e.g. ``read_foot_sensors(raw=True)`` of an earlier point."""
-        fn = self._sim_foot_sensors("mpc_sim_foot_sensors_set")
-        w = self._sim_foot_sensors("mpc_sim_foot_sensors_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_foot_sensors_width")
-        r = _f64(state)
-        d = self.dims
-        if r.shape != (d.batch, w):
-            raise ValueError("set_foot_sensors: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
-        self._check(fn(self._h, _dp(r)), "mpc_sim_foot_sensors_set")
+        fn, w = self._hip("mpc_sim_foot_sensors_set"), self._width("mpc_sim_foot_sensors_width")
+        self._check(fn(self._h, _dp(self._checked_rows("set_foot_sensors: state rows", state, w))), "mpc_sim_foot_sensors_set")
 
     def foot_sensors_feed(self, consumers):
         """Who works from the detected pair instead of the contact rule's (mpc_sim_foot_sensors_feed): a subset of ``("estimator", "qp")``, None or
         ``()`` for nobody (the default), or the bit mask itself.  Sticky until the model is turned off."""
-        fn = self._sim_foot_sensors("mpc_sim_foot_sensors_feed")
+        fn = self._hip("mpc_sim_foot_sensors_feed")
         mask = int(consumers) if isinstance(consumers, (int, np.integer)) else _foot_sensors.feed_mask(consumers)
         self._check(fn(self._h, mask), "mpc_sim_foot_sensors_feed")
 
     # -- include/mpc_sim_friction.h (HIP library only): per-robot ground friction under the soles of the torque-driven simulator steps -------------
-    def _sim_friction(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the ground friction of torque-driven simulator steps is HIP only "
-                               "(libmpc_hip.so, include/mpc_sim_friction.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def friction(self, params, base=None):
         """Make every held sole of every robot of this simulator handle a Coulomb slider (mpc_sim_friction; ``friction_model`` is the definition).
         Needs the contact rule (``contacts``).  ``params``: (B, 8) rows, one row of 8 for every robot, or a dict by ``friction_model.FIELDS`` name
         (``mu`` / ``mu_spin``: both soles) of scalars or (B,) arrays, missing fields as in ``base`` (``friction_model.rows``); turns the model on
         with every sole at rest.  None turns the model off."""
-        fn = self._sim_friction("mpc_sim_friction")
+        fn = self._hip("mpc_sim_friction")
         if params is None:
             self._check(fn(self._h, None), "mpc_sim_friction")
             return
@@ -789,43 +707,19 @@ class NativeSolver:
         """The friction model as it stands (mpc_sim_friction_read) -> dict: ``params`` (B, 8) the rows in force, and the state rows by
         ``friction_model.unpack`` (``v`` (B, 2, 3), ``sliding``, ``slip_steps``, ``slip_dist``, ``slip_yaw``, ``peak_excess`` (B, 2), ``steps``);
         ``raw``: the (B, 17) state rows themselves."""
-        fn = self._sim_friction("mpc_sim_friction_read")
-        w = self._sim_friction("mpc_sim_friction_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_friction_width")
-        d = self.dims
-        out, par = np.zeros((d.batch, w)), np.zeros((d.batch, _friction_model.PARAMS))
-        self._check(fn(self._h, _dp(par), _dp(out)), "mpc_sim_friction_read")
-        if raw:
-            return out
-        r = _friction_model.unpack(out)
-        r["params"] = par
-        return r
+        return self._read_model("friction", _friction_model, raw)
 
     def set_friction(self, state):
         """Impose the state rows of the friction model (mpc_sim_friction_set): (B, 17), e.g. ``read_friction(raw=True)`` of an earlier point."""
-        fn = self._sim_friction("mpc_sim_friction_set")
-        w = self._sim_friction("mpc_sim_friction_width")(self._h)
-        if w < 0:
-            self._check(-1, "mpc_sim_friction_width")
-        r = _f64(state)
-        d = self.dims
-        if r.shape != (d.batch, w):
-            raise ValueError("set_friction: state rows of shape (%d, %d) expected, got %s" % (d.batch, w, r.shape))
-        self._check(fn(self._h, _dp(r)), "mpc_sim_friction_set")
+        fn, w = self._hip("mpc_sim_friction_set"), self._width("mpc_sim_friction_width")
+        self._check(fn(self._h, _dp(self._checked_rows("set_friction: state rows", state, w))), "mpc_sim_friction_set")
 
     # -- include/mpc_sim_terrain.h (HIP library only): the box terrain under the contact rule ------------------------------------------------------
-    def _sim_terrain(self, name):
-        if not hasattr(self.lib, name):
-            raise NotImplementedError("%s is not exported by this library (%s): the terrain of the contact rule needs the HIP library "
-                                      "(libmpc_hip.so, include/mpc_sim_terrain.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def terrain(self, boxes):
         """The ground under the contact rule of this handle (mpc_sim_terrain; the rule must be on): ``boxes`` ``(n, 5)`` for every robot or
         ``(B, n, 5)`` per robot, rows ``(x_lo, x_hi, y_lo, y_hi, z_top)``, n <= 16 (``contact_rule.terrain_height`` is the height function,
         ``contact_rule.stairs`` the reference's staircase); None: the plane z = ground_z again."""
-        fn = self._sim_terrain("mpc_sim_terrain")
+        fn = self._hip("mpc_sim_terrain")
         if boxes is None:
             self._check(fn(self._h, None, None), "mpc_sim_terrain")
             return
@@ -835,7 +729,7 @@ class NativeSolver:
 
     def read_terrain(self):
         """The terrain in force (mpc_sim_terrain_read): the boxes in the form they were given, ``(n, 5)`` or ``(B, n, 5)`` (``(0, 5)`` when none is set)."""
-        fn = self._sim_terrain("mpc_sim_terrain_read")
+        fn = self._hip("mpc_sim_terrain_read")
         cfg = MpcSimTerrainConfig()
         self._check(fn(self._h, C.byref(cfg), None), "mpc_sim_terrain_read")
         shape = ((self.dims.batch,) if cfg.per_robot else ()) + (cfg.n_boxes, _contact_rule.TERRAIN_BOX_WIDTH)
@@ -847,7 +741,7 @@ class NativeSolver:
     def terrain_height(self, xy):
         """The device's height function (mpc_sim_terrain_height): ``xy`` (B, n, 2) -> (B, n), robot b's points on robot b's terrain (``ground_z`` of the
         rule where no terrain is set): where the ground is under a planned foothold."""
-        fn = self._sim_terrain("mpc_sim_terrain_height")
+        fn = self._hip("mpc_sim_terrain_height")
         p = _f64(xy)
         if p.ndim != 3 or p.shape[0] != self.dims.batch or p.shape[2] != 2:
             raise ValueError("terrain_height: points of shape (%d, n, 2) expected, got %s" % (self.dims.batch, p.shape))
@@ -861,14 +755,11 @@ class NativeSolver:
         where its last run left them), ``sim`` the torque-driven simulator handle: per period tau = us[0] - K_0 difference(x, xs[0]), then one simulator
         step of ``dt`` under tau (the push armed on ``sim``; a record per step when ``sim`` records).  ``x`` (B, nx): the states to start from (None: the
         simulator's).  -> (x_prev: the states before the last period, x_out: after it, tau (B, nu) and contact wrenches (B, 2, 6) of the last period)."""
-        if not hasattr(self.lib, "mpc_feedback_low_level_steps"):
-            raise RuntimeError("mpc_feedback_low_level_steps is not exported by this library (%s): the full-dynamics device loop is HIP only "
-                               "(libmpc_hip.so, include/mpc_feedback_pipeline.h)" % self.backend)
-        d = sim.dims
+        fn, d = self._hip("mpc_feedback_low_level_steps"), sim.dims
         xa = None if x is None else np.ascontiguousarray(np.broadcast_to(_f64(x).reshape(-1, d.nx), (d.batch, d.nx)))
         x_prev, x_out = np.zeros((d.batch, d.nx)), np.zeros((d.batch, d.nx))
         tau, wr = np.zeros((d.batch, d.nu)), np.zeros((d.batch, 2, 6))
-        self._check(self.lib.mpc_feedback_low_level_steps(self._h, sim._h, _dp(xa), int(steps), float(dt), _dp(x_prev), _dp(x_out), _dp(tau), _dp(wr)),
+        self._check(fn(self._h, sim._h, _dp(xa), int(steps), float(dt), _dp(x_prev), _dp(x_out), _dp(tau), _dp(wr)),
                     "mpc_feedback_low_level_steps")
         return x_prev, x_out, tau, wr
 
@@ -942,20 +833,14 @@ class NativeSolver:
         self._check(self.lib.mpc_walk_set_state(self._h, plan.ctypes.data_as(_DP)), "mpc_walk_set_state")
 
     # -- include/mpc_walk_poses.h (HIP library only): the generator of the centroidal problem's contact poses, per robot ---------------------------
-    def _walk_poses(self, name):
-        if not hasattr(self.lib, name):
-            raise RuntimeError("%s is not exported by this library (%s): the device generator of the contact-pose references is HIP only "
-                               "(libmpc_hip.so, include/mpc_walk_poses.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def walk_poses_init(self, model, cfg: "MpcWalkPosesConfig"):
         """``model``: the NativeSolver handle whose model tables the forward kinematics run on (mpc_walk_poses_init)."""
-        self._check(self._walk_poses("mpc_walk_poses_init")(self._h, model._h, C.byref(cfg)), "mpc_walk_poses_init")
+        self._check(self._hip("mpc_walk_poses_init")(self._h, model._h, C.byref(cfg)), "mpc_walk_poses_init")
 
     def walk_poses_update(self, model, x, qp, takeoff_RF, takeoff_LF, land_RF, land_LF, forward=None):
         """One tick of the generator for every robot, BEFORE ``cycle``.  ``x`` (B, nq + nv): the measured states, or None and ``qp``: the QP handle
         (``_qp_capi.QpSolver``) whose centroidal device loop kept them on the device.  ``forward`` as ``walk_update``."""
-        fn = self._walk_poses("mpc_walk_poses_update")
+        fn = self._hip("mpc_walk_poses_update")
         fw = None
         if forward is not None:
             fw = _f64(np.concatenate([np.asarray(forward[0], dtype=float), np.asarray(forward[1], dtype=float), [float(forward[2])]]))
@@ -970,30 +855,24 @@ class NativeSolver:
     def walk_poses_get_state(self):
         """-> [B, 4, 12]: start / final pose of the left foot, start / final pose of the right foot (R row-major, p)."""
         out = np.zeros((self.dims.batch, 4, 12))
-        self._check(self._walk_poses("mpc_walk_poses_get_state")(self._h, _dp(out)), "mpc_walk_poses_get_state")
+        self._check(self._hip("mpc_walk_poses_get_state")(self._h, _dp(out)), "mpc_walk_poses_get_state")
         return out
 
     def walk_poses_set_state(self, plan):
         plan = _f64(plan).reshape(-1)
         if plan.size != self.dims.batch * 48:
             raise ValueError("walk_poses_set_state: a plan of shape (%d, 4, 12) expected" % self.dims.batch)
-        self._check(self._walk_poses("mpc_walk_poses_set_state")(self._h, _dp(plan)), "mpc_walk_poses_set_state")
+        self._check(self._hip("mpc_walk_poses_set_state")(self._h, _dp(plan)), "mpc_walk_poses_set_state")
 
     def walk_poses_samples(self):
         """-> [B, 2 feet, 2 samples, 12]: the reference samples of knots 0 and 1 the last update kept on the device."""
         out = np.zeros((self.dims.batch, 2, 2, 12))
-        self._check(self._walk_poses("mpc_walk_poses_get_samples")(self._h, _dp(out)), "mpc_walk_poses_get_samples")
+        self._check(self._hip("mpc_walk_poses_get_samples")(self._h, _dp(out)), "mpc_walk_poses_get_samples")
         return out
 
     # -- include/mpc_walk_commands.h (HIP library only): a walk command per robot for the two device generators -----------------------------------
-    def _walk_commands(self, name):
-        if not hasattr(self.lib, name):
-            raise NotImplementedError("%s is not exported by this library (%s): a walk command per robot on the device generators needs the HIP library "
-                                      "(libmpc_hip.so, include/mpc_walk_commands.h)" % (name, self.backend))
-        return getattr(self.lib, name)
-
     def _set_commands(self, name, cmd):
-        fn = self._walk_commands(name)
+        fn = self._hip(name)
         if cmd is None:
             self._check(fn(self._h, None), name)
             return
@@ -1003,7 +882,7 @@ class NativeSolver:
         self._check(fn(self._h, _dp(c)), name)
 
     def _get_commands(self, name):
-        fn = self._walk_commands(name)
+        fn = self._hip(name)
         out = np.zeros((self.dims.batch, WALK_COMMAND_WIDTH))
         self._check(fn(self._h, _dp(out)), name)
         return out

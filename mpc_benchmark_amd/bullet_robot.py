@@ -43,20 +43,11 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _capi as K
 from . import contact_rule as _contact_rule
 from . import friction_model as _friction_model
-from .aligator import _core as core
-from .aligator import dynamics as _dyn
-from .aligator import manifolds as _manifolds
+from . import plant_model as _plant_model
+from . import torque_simulator as _tsim
 from .robot import minipin as pin
-
-
-def _sim_options():
-    """option block of a simulator handle (never solves: only the library's own consistency checks look at it)"""
-    o = K.default_options(1e-5, 1e-8)
-    o.force_initial_condition, o.rollout_linear = 1, 1
-    return o
 
 
 class BulletRobot:
@@ -85,7 +76,8 @@ class BulletRobot:
         self._friction = friction  # rows of setFriction, armed at initializeJoints
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
-        self._native = None
+        self._native = None       # the simulator handle, and ``_sim_models``, the models armed on it (``torque_simulator.SimulatorModels``)
+        self._sim_models = None
         self._pending_force = None
         self.markers = None
         self.camera = None
@@ -121,6 +113,7 @@ class BulletRobot:
         self._lifted = [False, False]
         self._pulling = [0, 0]   # consecutive steps with a negative normal force
         self._contact_pose = [self.data.oMf[f].copy() for f in self.frame_ids]
+        self._refuse_friction_without_rule(self._friction)
         self._build_native()
         if self.device_contacts:  # stage 0 is double support once; the rule on the device picks each step's contacts
             self._upload_mask()
@@ -128,69 +121,22 @@ class BulletRobot:
                                    "release_steps": self.release_steps})
             if self.terrain is not None:
                 self._native.terrain(self.terrain)
-        if self._plant is not None:
-            self.setPlant(*self._plant)
-        if self._friction is not None:
-            self.setFriction(self._friction)
-        if self._actuators is not None:
-            self.setActuators(*self._actuators)
-        if self._foot_sensors is not None:  # (before the estimator: its arming event already reads the pair it will be fed)
-            self.setFootSensors(*self._foot_sensors)
-        if self._sensors is not None:
-            self.setSensors(self._sensors)
-        elif self._estimator is not None:
-            self.setEstimator(self._estimator)
-
-    def _contact_models(self):
-        m = self.model
-        cms = []
-        for name, fid, pose in zip(self.contact_frames, self.frame_ids, self._contact_pose):
-            cm = pin.RigidConstraintModel(pin.ContactType.CONTACT_6D, m, m.frames[fid].parentJoint, m.frames[fid].placement, 0, pose, pin.LOCAL)
-            cm.corrector.Kp[:] = (0, 0, 10, 0, 0, 0)      # fulldynamic_talos.py:93-94
-            cm.corrector.Kd[:] = (50, 50, 50, 50, 50, 50)
-            cm.name = name
-            cms.append(cm)
-        return cms
+        self._sim_models = _tsim.SimulatorModels(self._native, m, self.frame_ids, self.dt)
+        self._sim_models.arm(self.x, self.x[:m.nq], self._plant, self._friction, self._actuators, self._sensors, self._foot_sensors, self._estimator)
 
     def _build_native(self):
-        m = self.model
-        nu = m.nv - 6
-        space = _manifolds.MultibodyPhaseSpace(m)
-        self._ctx = ctx = core.LoweringContext()
-        cms = self._contact_models()
-        act = np.eye(m.nv, nu, -6)
-        prox = pin.ProximalSettings(1e-9, 1e-10, 1)
-        self._stage_tables = {}
-        for mask in ((True, True), (True, False), (False, True)):
-            ode = _dyn.MultibodyConstraintFwdDynamics(space, act, [c for c, on in zip(cms, mask) if on], prox)
-            cost = core.CostStack(space, nu)
-            cost.addCost(core.QuadraticControlCost(space, np.zeros(nu), np.eye(nu)))
-            stage = core.StageModel(cost, _dyn.IntegratorSemiImplEuler(ode, self.dt))
-            self._stage_tables[mask] = core.lower_stage(ctx, stage.cost, stage.dynamics, stage.constraints)
-        tcost = core.CostStack(space, nu)
-        tcost.addCost(core.QuadraticStateCost(space, nu, space.neutral(), np.eye(space.ndx)))
-        term = core.lower_stage(ctx, tcost, None, core._ConstraintStack())
-        if self._native is None:
-            lib = self._lib if self._lib is not None else K.load_hip_library()
-            d = K.MpcDims()
-            d.horizon, d.batch, d.space = 1, 1, K.SPACE_MULTIBODY
-            d.nx, d.ndx, d.nu, d.nc_max = space.nx, space.ndx, nu, 1
-            d.max_stage_ints = 8 + 8 * 24
-            d.max_stage_doubles = max(t[1].size for t in self._stage_tables.values()) + term[1].size + 1024
-            d.device = 0
-            self._native = K.NativeSolver(lib, d)
-            self._native.set_options(_sim_options())
-        self._native.set_model(*ctx.model_tables())
-        self._native.set_stage(1, *term)
+        """the handle (opened once) with the model, the terminal stage and the contact-mask stages at the anchors ``_contact_pose`` as they stand"""
+        frames = self.model.frames
+        contacts = [(name, frames[fid].parentJoint, frames[fid].placement, pose)
+                    for name, fid, pose in zip(self.contact_frames, self.frame_ids, self._contact_pose)]
+        self._native, self._stage_tables = _tsim.build_simulator(self._lib, self.model, contacts, 1, self.dt, 0, sim=self._native)
         self._mask_uploaded = None
 
     def _upload_mask(self):
         mask = tuple(bool(c) for c in self.in_contact)
         if mask == (False, False):
             raise RuntimeError("headless BulletRobot: both feet off the ground (flight phases are not simulated)")
-        if mask != self._mask_uploaded:
-            self._native.set_stage(0, *self._stage_tables[mask])
-            self._mask_uploaded = mask
+        self._mask_uploaded = _tsim.upload_stage0(self._native, self._stage_tables, mask, self._mask_uploaded)
 
     # -- simulation -------------------------------------------------------------------------------------------------------------
     def execute(self, torques):
@@ -273,9 +219,7 @@ class BulletRobot:
     def measureState(self):
         """-> (q, v) of the COMPLETE model (bullet_robot.py:172-196): locked joints at their initial positions, zero velocity."""
         m = self.model
-        x = self._sensed()
-        if self._estimator is not None and self._native is not None:  # (setEstimator: the estimate)
-            x = self._native.read_estimator()["x"][0]
+        x = self.x if self._sim_models is None else np.reshape(self._sim_models.x_est(self.x), -1)   # (the estimate, the measurement or the true state)
         q, v = self.q_complete.copy(), self.v_complete.copy()
         q[:7] = x[:7]
         v[:6] = x[m.nq:m.nq + 6]
@@ -285,18 +229,15 @@ class BulletRobot:
             v[src] = x[m.nq + dst]
         return q, v
 
-    def _sensed(self):
-        """what the sensors deliver: the measurement of the sensor model (setSensors), the true state without one"""
-        return self.x if (self._sensors is None or self._native is None) else self._native.read_sensors()["x"][0]
-
     def resetState(self, q0Start):
         m = self.model
         self.x[:m.nq] = np.asarray(q0Start, dtype=float)[:m.nq]
         self.x[m.nq:] = 0.0
-        if self._sensors is not None and self._native is not None:  # (an imposed state: the sensor model is armed again, on it)
-            self.setSensors(self._sensors)
-        elif self._estimator is not None and self._native is not None:  # (... and so is the estimator, after the sensors)
-            self.setEstimator(self._estimator)
+        if self._sim_models is not None:
+            if self._sensors is not None:  # (an imposed state: the sensor model is armed again, on it, and the estimator after the sensors)
+                self._sim_models.set_sensors(self._sensors, self.x)
+            elif self._estimator is not None:
+                self._sim_models.set_estimator(self._estimator, self.x)
 
     def apply_force(self, force, position):
         """PyBullet's applyExternalForce(robot, -1, force, position, WORLD_FRAME): a world-frame force on the base link at a world point, acting
@@ -357,23 +298,18 @@ class BulletRobot:
         or a dict by field name (``mu`` / ``mu_spin``: both soles; missing fields as in ``friction_model.defaults`` of this robot: coefficients
         +inf, slider masses from its mass and posture); None: off.  Arms the model with every sole at rest; before ``initializeJoints`` it is kept
         for then."""
+        self._refuse_friction_without_rule(rows)
+        self._friction = rows
+        if self._sim_models is not None:
+            self._sim_models.set_friction(rows, self.x[:self.model.nq])
+
+    def _refuse_friction_without_rule(self, rows):
         if rows is not None and not self.device_contacts:
             raise ValueError("setFriction: the friction model needs device_contacts=True (it slides the soles the device contact rule holds)")
-        self._friction = rows
-        if self._native is None:
-            return
-        if rows is None:
-            if hasattr(self._native.lib, "mpc_sim_friction"):
-                self._native.friction(None)
-            return
-        base = _friction_model.defaults(self.model, self.x[:self.model.nq], self.frame_ids, self.dt)
-        self._native.friction(_friction_model.validate(_friction_model.rows(rows, 1, base)))
 
     def frictionState(self):
         """the state rows of the friction model by ``friction_model.unpack`` (``v``, ``sliding``, ``slip_dist`` ...); None without one"""
-        if self._friction is None or self._native is None:
-            return None
-        return self._native.read_friction()
+        return None if self._sim_models is None else self._sim_models.friction_state()
 
     def addStairs(self, path, position, orientation):
         raise NotImplementedError("headless BulletRobot: flat ground only")  # (a URDF staircase; createStairs / setTerrain lay boxes under the contact rule)
@@ -398,74 +334,40 @@ class BulletRobot:
         dict by field name (missing fields: the identity value); ``limit``: the effort limits of the controlled joints (default: the model's);
         None: off.  Arms and resets the model; before ``initializeJoints`` it is kept for then."""
         self._actuators = None if params is None else (params, limit, friction_shape)
-        if self._native is None:
-            return
-        if params is None:
-            if hasattr(self._native.lib, "mpc_sim_actuators"):
-                self._native.actuators(None)
-            return
-        if limit is None:
-            limit = np.asarray(self.model.effortLimit, dtype=float)[6:]
-        self._native.actuators(params, limit=limit, friction_shape=friction_shape)
+        if self._sim_models is not None:
+            self._sim_models.set_actuators(params, limit, friction_shape)
 
     def setPlant(self, rows, link_scale=None):
         """The plant's own link inertias (``plant_model``; HIP library only): ``rows`` one row of 16, (1, 16), or a dict by field name (missing fields:
         the identity value); ``link_scale``: None or (1, nj) / (nj,), every link's own mass factor; None: off.  Body indices are table joint indices
         of the REDUCED model (``model.names[j + 1]``).  Checked here before any library call; before ``initializeJoints`` it is kept for then."""
-        self._plant = None if rows is None else (rows, link_scale)
-        if self._native is None:
-            return
-        if rows is None:
-            if hasattr(self._native.lib, "mpc_sim_plant"):
-                self._native.plant(None)
-            return
-        rows, link_scale = self._checked_plant()
-        self._native.plant(rows, link_scale=link_scale)
-
-    def _checked_plant(self):
-        from . import plant_model as _plant_model
-        rows, link_scale = self._plant
-        nj = self.model.njoints - 1
         if link_scale is not None:
             link_scale = np.asarray(link_scale, dtype=float).reshape(1, -1)
-        return _plant_model.validate(_plant_model.rows(rows, 1), nj, link_scale)
+        self._plant = None if rows is None else (rows, link_scale)
+        if self._sim_models is not None:
+            self._sim_models.set_plant(rows, link_scale)
 
     def plantModel(self):
         """the ``minipin.Model`` the simulator integrates: ``model`` with the inertias of ``setPlant`` (``model`` itself without one)"""
         if self._plant is None:
             return self.model
-        from . import plant_model as _plant_model
-        return _plant_model.models(self.model, *self._checked_plant())[0]
+        return _plant_model.models(self.model, *_tsim.checked_plant(*self._plant, 1, self.model.njoints - 1))[0]
 
     def setSensors(self, params):
         """The sensor model between the dynamics and ``measureState()`` (``sensor_model``; HIP library only): ``params`` one row of 16, (1, 16), or a
         dict by field name (missing fields 0: the identity); None: off.  Arms and resets the model at the current true state; before
         ``initializeJoints`` it is kept for then."""
         self._sensors = params
-        if self._native is None:
-            return
-        if params is None:
-            if hasattr(self._native.lib, "mpc_sim_sensors"):
-                self._native.sensors(None)
-            if self._estimator is not None:  # (the estimator reads the true state from here on: armed again, on it)
-                self.setEstimator(self._estimator)
-            return
-        self._native.sensors(params, self.x)
-        if self._estimator is not None:  # (the estimator arms after the sensors, on their first measurement)
-            self.setEstimator(self._estimator)
+        if self._sim_models is not None:
+            self._sim_models.set_sensors(params, self.x)
 
     def setEstimator(self, params):
         """The base-state estimator between the sensors and ``measureState()`` (``state_estimator``; HIP library only, needs
         ``device_contacts=True``): ``params`` one row of 16, (1, 16), or a dict by field name (``w_p``, ``w_v``; missing fields 0: the identity); None:
         off.  Arms and resets the estimator at the current measurement; before ``initializeJoints`` it is kept for then."""
         self._estimator = params
-        if self._native is None:
-            return
-        if params is None:
-            if hasattr(self._native.lib, "mpc_sim_estimator"):
-                self._native.estimator(None)
-            return
-        self._native.estimator(params, self._sensed())
+        if self._sim_models is not None:
+            self._sim_models.set_estimator(params, self.x)
 
     def setFootSensors(self, params, detected_contacts=()):
         """The foot force sensors and the contact detector after every step (``foot_sensors``; HIP library only, needs ``device_contacts=True``):
@@ -473,20 +375,14 @@ class BulletRobot:
         () or ("estimator",): the estimator works from the detected pair.  Arms the detector on the rule's ``in_contact`` pair; before
         ``initializeJoints`` it is kept for then."""
         self._foot_sensors = None if params is None else (params, tuple(detected_contacts))
-        if self._native is None:
-            return
-        if params is None:
-            if hasattr(self._native.lib, "mpc_sim_foot_sensors"):
-                self._native.foot_sensors(None)
-            return
-        self._native.foot_sensors(params)
-        self._native.foot_sensors_feed(tuple(detected_contacts))
+        if self._sim_models is not None:
+            self._sim_models.set_foot_sensors(params, tuple(detected_contacts))
 
     def detectedContacts(self):
         """[left, right] the contacts the detector of ``setFootSensors`` reports; ``in_contact`` without one"""
-        if self._foot_sensors is None or self._native is None:
+        if self._sim_models is None or self._sim_models.rows["foot_sensors"] is None:
             return list(self.in_contact)
-        return [bool(v) for v in self._native.read_foot_sensors()["det"][0]]
+        return [bool(v) for v in self._sim_models.detected[0]]
 
     def createStairs(self, pose_stairs, height_step):
         """bullet_robot.py:275-340 of the reference: three steps of half extents 0.2 x 0.5 x height_step / 2, each 0.3 m further and height_step higher,
@@ -496,4 +392,4 @@ class BulletRobot:
     def close(self):
         if self._native is not None:
             self._native.close()
-            self._native = None
+            self._native = self._sim_models = None

@@ -15,7 +15,8 @@ The kinodynamic control pipeline of kinodynamic_talos.py:361-497, every stage on
 The three native pieces are the library's own (include/mpc_abi.h, include/mpc_qp_abi.h); between them travel the small per-robot
 vectors (states, K_0, torques), not problem data.  The simulator is the stand-in of ``mpc_simulate_torque``: the whole-body contact
 dynamics of the CONTACT STATE OF KNOT 0 of the schedule (what ``problem.stages[0]`` says, :419) — rigid contacts at the measured-at-start
-foot placements, no physics engine.  ``library``: the HIP library by default; tests pass the oracle to get the reference run.
+foot placements, no physics engine.  ``library``: the HIP library by default; tests pass the oracle to get the reference run.  The handle, its
+contact-mask stages and the rules by which the models below are armed are ``torque_simulator``'s, shared with the headless BulletRobot.
 
 ``contact_rule`` (all three pipelines): None, the simulator of the schedule above; or a dict over ``contact_rule.DEFAULTS`` ({} for the defaults,
 the ground at the lower initial foothold): the simulator's stage 0 is double support and the unilateral rule of the headless BulletRobot decides
@@ -90,30 +91,19 @@ sole whose force leaves its cone slips.  The MPC stages and the low-level QPs ke
 slip velocities and counters; ``set_friction`` changes or removes the model later."""
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 from . import _capi as K
-from . import actuator_model as _actuator_model
 from . import contact_rule as _contact_rule
 from . import foot_sensors as _foot_sensors
-from . import plant_model as _plant_model
-from . import friction_model as _friction_model
 from . import qp_utils
-from . import sensor_model as _sensor_model
-from . import state_estimator as _state_estimator
-from .aligator import _core as core
-from .aligator import dynamics as _dyn
+from . import torque_simulator as _tsim
 from .aligator import manifolds as _manifolds
 from .ensemble import EnsembleMPC
 from .problems import common
 from .robot import minipin as pin
-
-
-def _sim_options():
-    """option block of a simulator handle (never solves: only the library's own consistency checks look at it)"""
-    o = K.default_options(1e-5, 1e-8)
-    o.force_initial_condition, o.rollout_linear = 1, 1
-    return o
 
 
 # -- the push experiment of the scripts (commented out there): device.apply_force(f_disturbance, [0, 0, 0]) on ticks 160 - 170 -------------------------
@@ -149,42 +139,12 @@ def _push_array(push, batch):
 
 
 def build_torque_simulator(lib, robot, batch, sim_dt, device):
-    """The simulator stand-in of both pipelines: one handle, horizon 1, whole-body contact dynamics of the three contact patterns (rigid contacts at
-    the robot's initial foot placements).  -> (NativeSolver, {(left, right): lowered stage 0})."""
-    m = robot.model
-    nu = m.nv - 6
-    space = _manifolds.MultibodyPhaseSpace(m)
-    ctx = core.LoweringContext()
-    cms = []
-    for name, fid, jid, oMf in zip(common.FOOT_FRAMES, robot.foot_frame_ids, robot.foot_joint_ids, robot.foot_placements):
-        cm = pin.RigidConstraintModel(pin.ContactType.CONTACT_6D, m, jid, m.frames[fid].placement, 0, oMf, pin.LOCAL)
-        cm.corrector.Kp[:] = (0, 0, 10, 0, 0, 0)      # fulldynamic_talos.py:93-94
-        cm.corrector.Kd[:] = (50, 50, 50, 50, 50, 50)
-        cm.name = name
-        cms.append(cm)
-    act, prox = np.eye(m.nv, nu, -6), pin.ProximalSettings(1e-9, 1e-10, 1)
-    tables = {}
-    for mask in ((True, True), (True, False), (False, True)):
-        ode = _dyn.MultibodyConstraintFwdDynamics(space, act, [c for c, on in zip(cms, mask) if on], prox)
-        cost = core.CostStack(space, nu)
-        cost.addCost(core.QuadraticControlCost(space, np.zeros(nu), np.eye(nu)))
-        st = core.StageModel(cost, _dyn.IntegratorSemiImplEuler(ode, sim_dt))
-        tables[mask] = core.lower_stage(ctx, st.cost, st.dynamics, st.constraints)
-    tcost = core.CostStack(space, nu)
-    tcost.addCost(core.QuadraticStateCost(space, nu, space.neutral(), np.eye(space.ndx)))
-    term = core.lower_stage(ctx, tcost, None, core._ConstraintStack())
-    d = K.MpcDims()
-    d.horizon, d.batch, d.space = 1, batch, K.SPACE_MULTIBODY
-    d.nx, d.ndx, d.nu, d.nc_max = space.nx, space.ndx, nu, 1
-    d.max_stage_ints = 8 + 8 * 24
-    d.max_stage_doubles = max(t[1].size for t in tables.values()) + term[1].size + 1024
-    d.device = device
-    sim = K.NativeSolver(lib, d)
-    sim.set_options(_sim_options())
-    sim.set_model(*ctx.model_tables())
-    sim.set_stage(1, *term)
-    sim.ctx = ctx   # (whoever needs a frame of this handle's model tables adds it here: EnsembleMPC.enable_walk(model_handle=...))
-    return sim, tables
+    """The simulator stand-in of the three pipelines: one handle, horizon 1, whole-body contact dynamics of the three contact patterns (rigid contacts
+    at the robot's initial foot placements; ``torque_simulator.build_simulator``).  -> (NativeSolver, {(left, right): lowered stage 0})."""
+    frames = robot.model.frames
+    contacts = [(name, jid, frames[fid].placement, oMf)
+                for name, fid, jid, oMf in zip(common.FOOT_FRAMES, robot.foot_frame_ids, robot.foot_joint_ids, robot.foot_placements)]
+    return _tsim.build_simulator(lib, robot.model, contacts, batch, sim_dt, device)
 
 
 def _checked_terrain(name, terrain, contact_rule, batch):
@@ -198,13 +158,7 @@ def _checked_terrain(name, terrain, contact_rule, batch):
 
 def _checked_plant(plant, batch, problem_def):
     """``plant`` of a pipeline: None, or (rows (B, 16), link_scale (B, nj) or None) checked before any library call (``plant_model.validate``)"""
-    if plant is None:
-        return None
-    link_scale = None
-    if isinstance(plant, dict):
-        plant = dict(plant)
-        link_scale = plant.pop("link_scale", None)
-    return _plant_model.validate(_plant_model.rows(plant, batch), problem_def.robot.model.njoints - 1, link_scale)
+    return None if plant is None else _tsim.checked_plant(plant, None, batch, problem_def.robot.model.njoints - 1)
 
 
 def _checked_friction(name, friction, contact_rule):
@@ -223,16 +177,6 @@ def _checked_walk(name, walk, batch):
     walk = dict(walk)
     walk["commands"] = refgen.check_commands(walk["commands"], batch, "%s: walk commands" % name)
     return walk
-
-
-def _enable_contact_rule(sim, tables, robot, cfg, terrain=None):
-    """``contact_rule`` of a pipeline: stage 0 of the simulator is the double-support stage once, and the rule is on from the initial footholds
-    (the ground plane at the lower one unless ``cfg`` names ``ground_z``), over ``terrain`` if there is one."""
-    sim.set_stage(0, *tables[(True, True)])
-    gz = min(float(np.asarray(M.translation)[2]) for M in robot.foot_placements)
-    sim.contacts(_contact_rule.config(cfg, ground_z=gz))
-    if terrain is not None:
-        sim.terrain(terrain)
 
 
 def stairs_under_walk(robot, x_forward, z_height, y_gap=0.18, n_steps=3, half_extents=(0.2, 0.5)):
@@ -259,58 +203,25 @@ def stairs_under_walk(robot, x_forward, z_height, y_gap=0.18, n_steps=3, half_ex
     return boxes, holds
 
 
-class _Actuators:
-    """``actuators``, ``sensors`` and ``estimator`` of the three pipelines (module docstring): the models are armed on the simulator handle; the host
-    glue reads the applied torque back after a step and the estimate (the measurement without an estimator) before one."""
-    _actuators_on = False
-    _sensors_on = False
-    _estimator_rows = None
-    _foot_rows = None
-    _detected_contacts = ()
-    _plant_rows = None   # (rows (B, 16), link_scale (B, nj) or None) of the plant model in force
+class _Pipeline:
+    """What the three pipelines share: the argument checks of a constructor, the simulator handle with its contact rule and its models
+    (``torque_simulator.SimulatorModels``; module docstring), and the frame of a tick around the low-level loop."""
+    contact_source = None     # (a pipeline without a low-level QP has none)
 
-    def set_plant(self, rows, link_scale=None):
-        """Arm the per-robot plant model on ``self.sim``: ``rows`` in the forms of ``NativeSolver.plant``, a dict may also carry ``link_scale``;
-        checked before any library call.  None turns the model off."""
-        if rows is None:
-            if self._plant_rows is not None:
-                self.sim.plant(None)
-            self._plant_rows = None
-            return
-        if isinstance(rows, dict):
-            rows = dict(rows)
-            link_scale = rows.pop("link_scale", link_scale)
-        checked = _plant_model.validate(_plant_model.rows(rows, self.batch), self.model.njoints - 1, link_scale)
-        self.sim.plant(checked[0], link_scale=checked[1])
-        self._plant_rows = checked
+    def _init_contact_source(self, name, source, contact_rule):
+        """(the hook of the pipelines with a low-level QP, ``_QpContactSource``)"""
 
-    _friction_rows = None   # (B, 8) rows of the friction model in force
-
-    def set_friction(self, rows):
-        """Arm the per-robot ground friction on ``self.sim`` with every sole at rest: ``rows`` in the forms of ``NativeSolver.friction``, a dict's
-        missing fields from ``friction_model.defaults`` of the nominal robot; needs ``contact_rule``; checked before any library call.  None turns
-        the model off."""
-        if rows is None:
-            if self._friction_rows is not None:
-                self.sim.friction(None)
-            self._friction_rows = None
-            return
-        _checked_friction(type(self).__name__, rows, self.contact_rule)
-        rb = self.pd.robot
-        base = _friction_model.defaults(self.model, rb.x0[:self.model.nq], rb.foot_frame_ids, self.sim_dt)   # (a simulator step is one low-level period)
-        checked = _friction_model.validate(_friction_model.rows(rows, self.batch, base))
-        self.sim.friction(checked)
-        self._friction_rows = checked
-
-    def friction_state(self):
-        """the state rows of the friction model by ``friction_model.unpack`` (``v``, ``sliding``, ``slip_dist`` ...); None without ``friction``"""
-        return None if self._friction_rows is None else self.sim.read_friction()
-
-    def plant_models(self):
-        """one ``minipin.Model`` per robot: what the simulator integrates (``plant_model.models``; the nominal model B times without ``plant``)"""
-        if self._plant_rows is None:
-            return [self.model] * self.batch
-        return _plant_model.models(self.model, *self._plant_rows)
+    def _check_arguments(self, problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts, contact_source=None):
+        """the arguments every pipeline takes, checked before the library is loaded -> (walk, detected_contacts)"""
+        name = type(self).__name__
+        self.pd, self.batch = problem_def, int(batch)
+        self._init_contact_source(name, contact_source, contact_rule)
+        detected_contacts = self._check_detected(name, foot_sensors, detected_contacts, contact_rule, self.contact_source)
+        self.terrain = _checked_terrain(name, terrain, contact_rule, self.batch)
+        walk = _checked_walk(name, walk, self.batch)
+        _checked_friction(name, friction, contact_rule)
+        self.contact_rule = None if contact_rule is None else dict(contact_rule)
+        return walk, detected_contacts
 
     def _check_detected(self, name, foot_sensors, detected_contacts, contact_rule, contact_source=None):
         """``foot_sensors`` / ``detected_contacts`` of a pipeline, checked before any library call -> the consumers as a tuple"""
@@ -326,90 +237,145 @@ class _Actuators:
                              "place of the plant's rows there)" % name)
         return tuple(n for n in _foot_sensors.CONSUMERS if n in names)
 
+    def _load(self, library, substeps, sim_dt):
+        self.lib = library if library is not None else K.load_hip_library()
+        m = self.model = self.pd.robot.model
+        self.nq, self.nv = m.nq, m.nv
+        self.substeps, self.sim_dt = int(substeps), float(sim_dt)
+
+    def _build_simulator(self, plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=None):
+        """The simulator stand-in (``build_torque_simulator``) with its contact rule and terrain, stage 0 on ``stage0`` if one is given, and the
+        models armed at ``self.x``; ``x_prev`` starts from what the controllers read then."""
+        rb = self.pd.robot
+        self.sim, self._sim_tables = build_torque_simulator(self.lib, rb, self.batch, self.sim_dt, self.mpc.dims.device)
+        self._sim_mask = None
+        if self.contact_rule is not None:   # stage 0 is the double-support stage once; the rule is on from the initial footholds (the ground
+            self.sim.set_stage(0, *self._sim_tables[(True, True)])   # plane at the lower one unless the config names ``ground_z``)
+            gz = min(float(np.asarray(M.translation)[2]) for M in rb.foot_placements)
+            self.sim.contacts(_contact_rule.config(self.contact_rule, ground_z=gz))
+            if self.terrain is not None:
+                self.sim.terrain(self.terrain)
+        if stage0 is not None:
+            self._set_sim_contacts(stage0)
+        self.sim_models = _tsim.SimulatorModels(self.sim, self.model, rb.foot_frame_ids, self.sim_dt)
+        self.sim_models.arm(self.x, rb.x0[:self.nq], plant, friction, None if actuators is None else (actuators,), sensors,
+                            None if foot_sensors is None else (foot_sensors, detected_contacts), estimator)
+        self.x_prev = self.x_est.copy()      # the measurement of the period before (the solve's initial condition)
+        self.torques = np.zeros((self.batch, self.nv - 6))
+        self._plan_stale = True
+
+    def _set_sim_contacts(self, mask):
+        if self.contact_rule is None:   # (else the rule decides every robot's contacts on the device)
+            self._sim_mask = _tsim.upload_stage0(self.sim, self._sim_tables, mask, self._sim_mask)
+
+    # -- the models of the plant (module docstring): ``None`` turns a model off ------------------------------------------------------------------------
+    def set_plant(self, rows, link_scale=None):
+        """Arm the per-robot plant model on ``self.sim``: ``rows`` in the forms of ``NativeSolver.plant``, a dict may also carry ``link_scale``."""
+        self.sim_models.set_plant(rows, link_scale)
+
+    def set_friction(self, rows):
+        """Arm the per-robot ground friction on ``self.sim`` with every sole at rest: ``rows`` in the forms of ``NativeSolver.friction``, a dict's
+        missing fields from ``friction_model.defaults`` of the nominal robot; needs ``contact_rule``."""
+        _checked_friction(type(self).__name__, rows, self.contact_rule)
+        self.sim_models.set_friction(rows, self.pd.robot.x0[:self.nq])   # (a simulator step is one low-level period)
+
+    def set_actuators(self, params, limit=None, friction_shape=None):
+        """Arm (and reset) the per-robot actuator model on ``self.sim``: ``params`` in the forms of ``NativeSolver.actuators``, a dict may also carry
+        ``limit`` and ``friction_shape``; ``limit`` defaults to the model's effort limits."""
+        self.sim_models.set_actuators(params, limit, friction_shape)
+
+    def set_sensors(self, params):
+        """Arm (and reset) the per-robot sensor model on ``self.sim`` at the current true states ``self.x``: ``params`` in the forms of
+        ``NativeSolver.sensors``.  An estimator in force arms again, after the sensors."""
+        self.sim_models.set_sensors(params, self.x)
+
+    def set_estimator(self, params):
+        """Arm (and reset) the per-robot base-state estimator on ``self.sim`` at the current measured states ``self.x_meas``: ``params`` in the
+        forms of ``NativeSolver.estimator``; needs ``contact_rule``."""
+        self.sim_models.set_estimator(params, self.x)
+
     def set_foot_sensors(self, params, detected_contacts=None):
         """Arm (and reset) the per-robot foot force sensors and contact detector on ``self.sim``: ``params`` in the forms of
         ``NativeSolver.foot_sensors``; needs ``contact_rule``.  ``detected_contacts``: who works from the detected pair (None: as before).  ``params``
         None turns the model off, and the consumers go back to the plant's pair."""
-        if params is None:
-            if self._foot_rows is not None:
-                self.sim.foot_sensors(None)
-            self._foot_rows, self._detected_contacts = None, ()
-            return
-        if detected_contacts is not None:
-            names = self._check_detected(type(self).__name__, params, detected_contacts, self.contact_rule, getattr(self, "contact_source", None))
-        else:
-            names = self._detected_contacts
-        rows = _foot_sensors.rows(params, self.batch)
-        self.sim.foot_sensors(rows)
-        self.sim.foot_sensors_feed(names)
-        self._foot_rows, self._detected_contacts = rows, names
-
-    @property
-    def detected(self):
-        """(B, 2) the pair every robot's detector reports; without ``foot_sensors`` the ``in_contact`` pair of the contact rule"""
-        if self._foot_rows is not None:
-            return self.sim.read_foot_sensors()["det"].copy()
-        return self.sim.read_contacts()["in_contact"].copy()
-
-    def set_sensors(self, params):
-        """Arm (and reset) the per-robot sensor model on ``self.sim`` at the current true states ``self.x``: ``params`` in the forms of
-        ``NativeSolver.sensors``.  None turns the model off."""
-        if params is None:
-            if self._sensors_on:
-                self.sim.sensors(None)
-            self._sensors_on = False
-        else:
-            self.sim.sensors(_sensor_model.rows(params, self.batch), self.x)
-            self._sensors_on = True
-        if self._estimator_rows is not None:  # (the estimator arms again, after the sensors, on what they deliver now)
-            self.set_estimator(self._estimator_rows)
-
-    def set_estimator(self, params):
-        """Arm (and reset) the per-robot base-state estimator on ``self.sim`` at the current measured states ``self.x_meas``: ``params`` in the
-        forms of ``NativeSolver.estimator``; needs ``contact_rule``.  None turns the estimator off."""
-        if params is None:
-            if self._estimator_rows is not None:
-                self.sim.estimator(None)
-            self._estimator_rows = None
-            return
-        rows = _state_estimator.rows(params, self.batch)
-        self.sim.estimator(rows, self.x_meas)
-        self._estimator_rows = rows
-
-    @property
-    def x_est(self):
-        """the state the controllers read: the estimate of the base-state estimator, ``x_meas`` without one"""
-        return self.sim.read_estimator()["x"] if self._estimator_rows is not None else self.x_meas
+        if params is not None and detected_contacts is not None:
+            detected_contacts = self._check_detected(type(self).__name__, params, detected_contacts, self.contact_rule, self.contact_source)
+        self.sim_models.set_foot_sensors(params, detected_contacts)
 
     @property
     def x_meas(self):
         """what the sensors deliver: the measurement of the sensor model, ``x`` itself without one"""
-        return self.sim.read_sensors()["x"] if self._sensors_on else self.x
+        return self.sim_models.x_meas(self.x)
 
-    def set_actuators(self, params, limit=None, friction_shape=None):
-        """Arm (and reset) the per-robot actuator model on ``self.sim``: ``params`` in the forms of ``NativeSolver.actuators``, a dict may also carry
-        ``limit`` and ``friction_shape``; ``limit`` defaults to the model's effort limits.  None turns the model off."""
-        if params is None:
-            if self._actuators_on:
-                self.sim.actuators(None)
-            self._actuators_on = False
-            return
-        if isinstance(params, dict):
-            params = dict(params)
-            limit = params.pop("limit", limit)
-            friction_shape = params.pop("friction_shape", friction_shape)
-        if limit is None:
-            limit = np.asarray(self.model.effortLimit, dtype=float)[6:]
-        self.sim.actuators(_actuator_model.rows(params, self.batch), limit=limit, friction_shape=friction_shape)
-        self._actuators_on = True
+    @property
+    def x_est(self):
+        """the state the controllers read: the estimate of the base-state estimator, ``x_meas`` without one"""
+        return self.sim_models.x_est(self.x)
 
-    def _applied_torques(self):
-        """host glue, after a simulator step: with the model on ``torques`` is what the step integrated, as on the device loop"""
-        if self._actuators_on:
-            self.torques = self.sim.read_actuators()["applied"].copy()
+    @property
+    def detected(self):
+        """(B, 2) the pair every robot's detector reports; without ``foot_sensors`` the ``in_contact`` pair of the contact rule"""
+        return self.sim_models.detected
+
+    def plant_models(self):
+        """one ``minipin.Model`` per robot: what the simulator integrates (``plant_model.models``; the nominal model B times without ``plant``)"""
+        return self.sim_models.plant_models()
+
+    def friction_state(self):
+        """the state rows of the friction model by ``friction_model.unpack`` (``v``, ``sliding``, ``slip_dist`` ...); None without ``friction``"""
+        return self.sim_models.friction_state()
+
+    # -- the loop ---------------------------------------------------------------------------------------------------------------------
+    def _walk_kwargs(self):
+        return self._walk_args
+
+    def cold_solve(self, max_iters=100):
+        st = self.mpc.cold_solve(max_iters=max_iters)
+        if self._walk_args is not None:
+            self.mpc.enable_walk(**self._walk_kwargs())
+        self._fetch()
+        return st
+
+    def _fetch(self):
+        self._plan_stale = False
+        r = self.mpc.native.get_results(gains=False)
+        self.xs0, self.us0 = r["xs"][:, 0].copy(), r["us"][:, 0].copy()
+        self.K0 = self.mpc.native.get_gain(0)[0]
+
+    def contact_state(self):
+        """[left, right] the low-level loop of this MPC period works with: ``problem.stages[0]`` AFTER this period's
+        ``replaceStageCircular(stages_full[t])`` (kinodynamic_talos.py:393, 419-420) — the stage that was appended at tick t + 1 - N (the
+        initial double support before that), one rotation later than knot 0 of the solution the feedback terms come from."""
+        N, t = self.mpc.problem.num_steps, self.mpc.tick
+        return self.pd.contact_phases[max(0, t + 1 - N) % self.pd.t_mpc]
+
+    @contextlib.contextmanager
+    def _pushed(self, push):
+        """``push`` (checked, or None) armed on the simulator for the low-level steps inside the block only"""
+        if push is not None:
+            self.sim.set_push(push)
+        try:
+            yield
+        finally:
+            if push is not None:
+                self.sim.set_push(None)
+
+    def _solve_from_x_prev(self, x_last):
+        """the tail of a tick: the walk references planned from the state that becomes the initial condition (walking_loop.py,
+        fulldynamic_talos.py:440-462), the solve from ``x_prev``, and ``x_last`` the ``x_prev`` of the next tick"""
+        e = self.mpc
+        if e._walk is not None:
+            e._walk["x_measured"] = self.x_prev[0].copy()
+            if "x_measured_all" in e._walk:
+                e._walk["x_measured_all"] = self.x_prev.copy()
+        e.native.set_x0(self.x_prev)
+        st = e.step()
+        self.x_prev = x_last
+        self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
+        return st
 
 
-class _QpContactSource:
+class _QpContactSource(_Pipeline):
     """``contact_source`` of the two pipelines with a low-level QP (module docstring): the checks, the host-glue form of the selection (the numpy mirror
     ``contact_rule.qp_contact_states`` on the rows read before every step) and ``qp_contacts``."""
 
@@ -431,7 +397,7 @@ class _QpContactSource:
         if self.contact_source == "schedule":
             self._qp_used = _contact_rule.qp_contact_states("schedule", cs, np.ones((self.batch, 2)))
             return self._qp_used
-        p = self.detected if "qp" in self._detected_contacts else self.sim.read_contacts()["in_contact"]   # (the detector's rows, read back)
+        p = self.detected if "qp" in self.sim_models.consumers else self.sim.read_contacts()["in_contact"]   # (the detector's rows, read back)
         self._qp_used = _contact_rule.qp_contact_states(self.contact_source, cs, p)
         self._qp_counts = _contact_rule.qp_contact_counts(self._qp_counts, cs, p)
         return self._qp_used
@@ -459,7 +425,7 @@ class _QpContactSource:
         return dict(used=used, counts=counts)
 
 
-class KinodynamicPipeline(_QpContactSource, _Actuators):
+class KinodynamicPipeline(_QpContactSource):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
                  terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, foot_sensors=None,
                  detected_contacts=(), plant=None, friction=None, **ens_kw):
@@ -469,19 +435,11 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the rows of the foot force sensors,
         ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model, ``friction``: None or the rows of
         the ground friction (module docstring)."""
-        self.pd, self.batch = problem_def, int(batch)
-        self._init_contact_source("KinodynamicPipeline", contact_source, contact_rule)
-        detected_contacts = self._check_detected("KinodynamicPipeline", foot_sensors, detected_contacts, contact_rule, contact_source)
-        self.terrain = _checked_terrain("KinodynamicPipeline", terrain, contact_rule, self.batch)
-        walk = _checked_walk("KinodynamicPipeline", walk, self.batch)
-        _checked_friction("KinodynamicPipeline", friction, contact_rule)
+        walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
+                                                        contact_source)
         plant = _checked_plant(plant, self.batch, problem_def)
-        self.contact_rule = None if contact_rule is None else dict(contact_rule)
-        self.lib = library if library is not None else K.load_hip_library()
-        rb = problem_def.robot
-        m = self.model = rb.model
-        self.nq, self.nv = m.nq, m.nv
-        self.substeps, self.sim_dt = int(substeps), float(sim_dt)
+        self._load(library, substeps, sim_dt)
+        rb, m = problem_def.robot, self.model
         self.mpc = EnsembleMPC(problem_def, batch=batch, library=self.lib, x0=x0, **ens_kw)
         self._walk_args = walk
         # the low-level QP of the script: weights [1, 10000] on acceleration / force increments (kinodynamic_talos.py:350-351)
@@ -489,61 +447,13 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
                                          list(rb.foot_frame_ids), 6, library=self.lib, batch=self.batch)
         self.qp.enable_device_assembly()
         self.umax = np.asarray(m.effortLimit, dtype=float)[6:]
-        self._build_simulator()
-        if plant is not None:
-            self.set_plant(*plant)
-        if friction is not None:
-            self.set_friction(friction)
-        if actuators is not None:
-            self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
-        if sensors is not None:
-            self.set_sensors(sensors)
-        if foot_sensors is not None:   # (before the estimator: its arming event already reads the pair it will be fed)
-            self.set_foot_sensors(foot_sensors, detected_contacts)
-        if estimator is not None:
-            self.set_estimator(estimator)
-        self.x_prev = self.x_est.copy()                  # the measurement of the tick before (the solve's initial condition)
-        self.torques = np.zeros((self.batch, m.nv - 6))
+        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator)
         self.forces = np.zeros((self.batch, 12))
-        self._plan_stale = True
-
-    # -- simulator stand-in: one handle, horizon 1, whole-body contact dynamics of the three contact patterns ----------------------
-    def _build_simulator(self):
-        self.sim, self._sim_tables = build_torque_simulator(self.lib, self.pd.robot, self.batch, self.sim_dt, self.mpc.dims.device)
-        self._sim_mask = None
-        if self.contact_rule is not None:
-            _enable_contact_rule(self.sim, self._sim_tables, self.pd.robot, self.contact_rule, self.terrain)
-
-    def _set_sim_contacts(self, mask):
-        if self.contact_rule is not None:   # (the rule decides every robot's contacts on the device)
-            return
-        mask = (bool(mask[0]), bool(mask[1]))
-        if mask != self._sim_mask:
-            self.sim.set_stage(0, *self._sim_tables[mask])
-            self._sim_mask = mask
-
-    # -- the loop ---------------------------------------------------------------------------------------------------------------------
-    def cold_solve(self, max_iters=100):
-        st = self.mpc.cold_solve(max_iters=max_iters)
-        if self._walk_args is not None:
-            self.mpc.enable_walk(**self._walk_args)
-        self._fetch()
-        return st
 
     def _fetch(self):
-        self._plan_stale = False
-        r = self.mpc.native.get_results(gains=False)
-        self.xs0, self.us0 = r["xs"][:, 0].copy(), r["us"][:, 0].copy()
-        self.K0 = self.mpc.native.get_gain(0)[0]
+        super()._fetch()
         self.xdot0 = self.mpc.native.get_stage_data(0)[0]
-
-    def contact_state(self):
-        """[left, right] the low-level loop of this MPC period works with: ``problem.stages[0]`` AFTER this period's
-        ``replaceStageCircular(stages_full[t])`` (kinodynamic_talos.py:393, 419-420) — the stage that was appended at tick t + 1 - N (the
-        initial double support before that), one rotation later than knot 0 of the solution the feedback terms come from."""
-        N, t = self.mpc.problem.num_steps, self.mpc.tick
-        return self.pd.contact_phases[max(0, t + 1 - N) % self.pd.t_mpc]
 
     def low_level_step(self, cs):
         """One 1 kHz step of kinodynamic_talos.py:411-462 for every robot, the glue between the library calls on the host.  ``cs``: (2,) for every
@@ -559,8 +469,7 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         a_new, f_new, tau = self.qp.solve_batch_device(x, a0, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
         tau = np.clip(tau, -self.umax, self.umax)
         self.x = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt)
-        self.torques, self.forces = tau, f_new
-        self._applied_torques()
+        self.torques, self.forces = self.sim_models.applied_torques(tau), f_new
         return tau
 
     def low_level_loop(self, cs):
@@ -579,9 +488,7 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
         push = _push_array(push, self.batch)
         cs = self.contact_state()
         self._set_sim_contacts(cs)
-        if push is not None:
-            self.sim.set_push(push)
-        try:
+        with self._pushed(push):
             if host_glue:
                 if self._plan_stale:
                     self._fetch()
@@ -593,19 +500,7 @@ class KinodynamicPipeline(_QpContactSource, _Actuators):
                         self.forces = _contact_rule.qp_zero_unused(self.forces, used)
             else:
                 x_last = self.low_level_loop(cs)
-        finally:
-            if push is not None:
-                self.sim.set_push(None)
-        e = self.mpc
-        if e._walk is not None:     # the references are planned from the state that becomes the initial condition (walking_loop.py)
-            e._walk["x_measured"] = self.x_prev[0].copy()
-            if "x_measured_all" in e._walk:
-                e._walk["x_measured_all"] = self.x_prev.copy()
-        e.native.set_x0(self.x_prev)
-        st = e.step()
-        self.x_prev = x_last
-        self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
-        return st
+        return self._solve_from_x_prev(x_last)
 
 
 # -- the centroidal pipeline ------------------------------------------------------------------------------------------------------------
@@ -632,7 +527,7 @@ def posture_gains(nv):
     return G, 2 * np.sqrt(G)
 
 
-class CentroidalPipeline(_QpContactSource, _Actuators):
+class CentroidalPipeline(_QpContactSource):
     """The centroidal control pipeline of centroidal_talos.py:353-468 for an ensemble of robots, every stage on the solver library:
 
         MPC tick (centroidal OCP, x = [com ; h_lin ; h_ang], one ProxDDP iteration)
@@ -674,19 +569,12 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
         rows of the foot force sensors, ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model,
         ``friction``: None or the rows of the ground friction (module docstring)."""
         from .ensemble import ensemble_initial_states
-        self.pd, self.batch = problem_def, int(batch)
-        self._init_contact_source("CentroidalPipeline", contact_source, contact_rule)
-        detected_contacts = self._check_detected("CentroidalPipeline", foot_sensors, detected_contacts, contact_rule, contact_source)
-        self.terrain = _checked_terrain("CentroidalPipeline", terrain, contact_rule, self.batch)
-        walk = _checked_walk("CentroidalPipeline", walk, self.batch)
-        _checked_friction("CentroidalPipeline", friction, contact_rule)
+        walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
+                                                        contact_source)
         plant = _checked_plant(plant, self.batch, problem_def)
-        self.contact_rule = None if contact_rule is None else dict(contact_rule)
-        self.lib = library if library is not None else K.load_hip_library()
-        rb = problem_def.robot
-        m = self.model = rb.model
-        self.nq, self.nv = m.nq, m.nv
-        self.substeps, self.sim_dt, self.ref_dt = int(substeps), float(sim_dt), float(problem_def.dt)
+        self._load(library, substeps, sim_dt)
+        rb, m = problem_def.robot, self.model
+        self.ref_dt = float(problem_def.dt)
         if x0 is not None:
             self.x = np.array(np.broadcast_to(np.asarray(x0, dtype=float), (self.batch, m.nq + m.nv)))
         elif perturb:
@@ -695,7 +583,6 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
             self.x = np.tile(rb.x0, (self.batch, 1))
         self.x_posture = np.array(rb.x0, dtype=float)     # x0_multibody: the posture reference of compute_ID_references
         self.c_prev = centroidal_state(m, self.x)          # the next solve's initial condition
-        self.x_prev = self.x.copy()                        # the stale measurement the task errors are taken at
         self.mpc = EnsembleMPC(problem_def, batch=batch, library=self.lib, x0=self.c_prev, **ens_kw)
         self._walk_args = walk
         Kq = posture_gains(m.nv)
@@ -705,54 +592,20 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
                                          list(rb.foot_frame_ids), m.getFrameId("base_link"), m.getFrameId("torso_2_link"), 6, library=self.lib,
                                          batch=self.batch)
         self.qp.enable_device_assembly()
-        self.sim, self._sim_tables = build_torque_simulator(self.lib, rb, self.batch, self.sim_dt, self.mpc.dims.device)
-        self._sim_mask = None
-        if self.contact_rule is not None:
-            _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule, self.terrain)
-        self._set_sim_contacts((True, True))   # (the schedule starts in double support)
-        if plant is not None:
-            self.set_plant(*plant)
-        if friction is not None:
-            self.set_friction(friction)
-        if actuators is not None:
-            self.set_actuators(actuators)
-        if sensors is not None:
-            self.set_sensors(sensors)
-        if foot_sensors is not None:   # (before the estimator: its arming event already reads the pair it will be fed)
-            self.set_foot_sensors(foot_sensors, detected_contacts)
-        if estimator is not None:
-            self.set_estimator(estimator)
-        if sensors is not None or estimator is not None:
-            self.x_prev = self.x_est.copy()
-        self.torques = np.zeros((self.batch, m.nv - 6))
+        # (the schedule starts in double support; ``x_prev`` is the stale measurement the task errors are taken at)
+        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=(True, True))
         self.forces = np.zeros((self.batch, 12))
         self.ik = None                 # the task errors of the last period
-        self._plan_stale = True
         self._xik_on_device = False    # the QP handle keeps x_prev of its last device loop
 
-    def _set_sim_contacts(self, mask):
-        if self.contact_rule is not None:   # (the rule decides every robot's contacts on the device)
-            return
-        mask = (bool(mask[0]), bool(mask[1]))
-        if mask != self._sim_mask:
-            self.sim.set_stage(0, *self._sim_tables[mask])
-            self._sim_mask = mask
-
-    def cold_solve(self, max_iters=100):
-        st = self.mpc.cold_solve(max_iters=max_iters)
-        if self._walk_args is not None:
-            kw = dict(self._walk_args)
-            if kw.get("per_instance") and kw.get("generator") == "device":
-                kw.setdefault("model_handle", self.sim)   # the forward kinematics of the soles run on the simulator handle's model tables
-            self.mpc.enable_walk(**kw)
-        self._fetch()
-        return st
+    def _walk_kwargs(self):
+        kw = dict(self._walk_args)
+        if kw.get("per_instance") and kw.get("generator") == "device":
+            kw.setdefault("model_handle", self.sim)   # the forward kinematics of the soles run on the simulator handle's model tables
+        return kw
 
     def _fetch(self):
-        self._plan_stale = False
-        r = self.mpc.native.get_results(gains=False)
-        self.xs0, self.us0 = r["xs"][:, 0].copy(), r["us"][:, 0].copy()
-        self.K0 = self.mpc.native.get_gain(0)[0]
+        super()._fetch()
         self.dH = self.mpc.native.get_stage_data(0)[0][:, 3:9].copy()
 
     def contact_state(self):
@@ -786,8 +639,7 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
         forces = self.us0 - np.einsum("bij,bj->bi", self.K0, self.xs0 - new_x)   # us[0] - K_0 difference(new_x, xs[0])
         _, f_new, tau = self.qp.solve_batch_device_ik(x, ik, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
         self.x = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt)
-        self.torques, self.forces = tau, f_new
-        self._applied_torques()
+        self.torques, self.forces = self.sim_models.applied_torques(tau), f_new
         return new_x
 
     def low_level_loop(self, cs, refs):
@@ -818,9 +670,7 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
         e.plan_tick()
         refs = None if (on_device and not host_glue) else self.foot_refs()
         self._set_sim_contacts(cs)
-        if push is not None:
-            self.sim.set_push(push)
-        try:
+        with self._pushed(push):
             if host_glue:
                 if self._plan_stale:
                     self._fetch()
@@ -835,9 +685,6 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
                 self._xik_on_device = False
             else:
                 self.low_level_loop(cs, refs)
-        finally:
-            if push is not None:
-                self.sim.set_push(None)
         e.native.set_x0(self.c_prev)
         st = e.solve_tick()
         self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
@@ -845,7 +692,7 @@ class CentroidalPipeline(_QpContactSource, _Actuators):
 
 
 # -- the full-dynamics pipeline ---------------------------------------------------------------------------------------------------------
-class FullDynamicPipeline(_Actuators):
+class FullDynamicPipeline(_Pipeline):
     """The full-dynamics control pipeline of fulldynamic_talos.py:437-550 for an ensemble of robots, every stage on the solver library:
 
         MPC tick (full-dynamics OCP, one ProxDDP iteration)                                                    fulldynamic_talos.py:536-541
@@ -870,71 +717,18 @@ class FullDynamicPipeline(_Actuators):
         actuator model, ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state
         estimator, ``foot_sensors``: None or the rows of the foot force sensors, ``detected_contacts``: () or ("estimator",), ``plant``: None or the rows of the plant
         model, ``friction``: None or the rows of the ground friction (module docstring of pipeline.py)."""
-        detected_contacts = self._check_detected("FullDynamicPipeline", foot_sensors, detected_contacts, contact_rule)
-        self.terrain = _checked_terrain("FullDynamicPipeline", terrain, contact_rule, int(batch))
-        walk = _checked_walk("FullDynamicPipeline", walk, int(batch))
-        _checked_friction("FullDynamicPipeline", friction, contact_rule)
+        walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts)
         if ens_kw.get("closed_loop") is not None:
             raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
                              "EnsembleMPC(closed_loop=...) would simulate a second time)")
         ens_kw.pop("closed_loop", None)
-        plant = _checked_plant(plant, int(batch), problem_def)
-        self.pd, self.batch = problem_def, int(batch)
-        self.contact_rule = None if contact_rule is None else dict(contact_rule)
-        self.lib = library if library is not None else K.load_hip_library()
-        rb = problem_def.robot
-        m = self.model = rb.model
-        self.nq, self.nv = m.nq, m.nv
-        self.substeps, self.sim_dt = int(substeps), float(sim_dt)
+        plant = _checked_plant(plant, self.batch, problem_def)
+        self._load(library, substeps, sim_dt)
         self.mpc = EnsembleMPC(problem_def, batch=batch, library=self.lib, x0=x0, **ens_kw)
         self._walk_args = walk
-        self.sim, self._sim_tables = build_torque_simulator(self.lib, rb, self.batch, self.sim_dt, self.mpc.dims.device)
-        self._sim_mask = None
-        if self.contact_rule is not None:
-            _enable_contact_rule(self.sim, self._sim_tables, rb, self.contact_rule, self.terrain)
-        if plant is not None:
-            self.set_plant(*plant)
-        if friction is not None:
-            self.set_friction(friction)
-        if actuators is not None:
-            self.set_actuators(actuators)
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
-        if sensors is not None:
-            self.set_sensors(sensors)
-        if foot_sensors is not None:   # (before the estimator: its arming event already reads the pair it will be fed)
-            self.set_foot_sensors(foot_sensors, detected_contacts)
-        if estimator is not None:
-            self.set_estimator(estimator)
-        self.x_prev = self.x_est.copy()                  # the measurement of the period before (the solve's initial condition)
-        self.torques = np.zeros((self.batch, m.nv - 6))
+        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator)
         self.wrenches = np.zeros((self.batch, 2, 6))     # contact wrenches of the last simulator step (LOCAL frame of the sole)
-        self._plan_stale = True
-
-    def _set_sim_contacts(self, mask):
-        if self.contact_rule is not None:   # (the rule decides every robot's contacts on the device)
-            return
-        mask = (bool(mask[0]), bool(mask[1]))
-        if mask != self._sim_mask:
-            self.sim.set_stage(0, *self._sim_tables[mask])
-            self._sim_mask = mask
-
-    def cold_solve(self, max_iters=100):
-        st = self.mpc.cold_solve(max_iters=max_iters)
-        if self._walk_args is not None:
-            self.mpc.enable_walk(**self._walk_args)
-        self._fetch()
-        return st
-
-    def _fetch(self):
-        self._plan_stale = False
-        r = self.mpc.native.get_results(gains=False)
-        self.xs0, self.us0 = r["xs"][:, 0].copy(), r["us"][:, 0].copy()
-        self.K0 = self.mpc.native.get_gain(0)[0]
-
-    def contact_state(self):
-        """[left, right] the low-level loop of this MPC period works with: the rule of ``KinodynamicPipeline.contact_state``."""
-        N, t = self.mpc.problem.num_steps, self.mpc.tick
-        return self.pd.contact_phases[max(0, t + 1 - N) % self.pd.t_mpc]
 
     def low_level_step(self, cs):
         """One 1 kHz step of fulldynamic_talos.py:514-523 for every robot, the feedback law on the host (``cs``: the simulator's contact set is
@@ -946,8 +740,7 @@ class FullDynamicPipeline(_Actuators):
         d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], self.xs0[:, :nq]), self.xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
         tau = self.us0 - np.einsum("bij,bj->bi", self.K0, d)
         self.x, wr = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt, wrenches=True)
-        self.torques, self.wrenches = tau, wr
-        self._applied_torques()
+        self.torques, self.wrenches = self.sim_models.applied_torques(tau), wr
         return tau
 
     def low_level_loop(self, cs):
@@ -964,9 +757,7 @@ class FullDynamicPipeline(_Actuators):
         push = _push_array(push, self.batch)
         cs = self.contact_state()
         self._set_sim_contacts(cs)
-        if push is not None:
-            self.sim.set_push(push)
-        try:
+        with self._pushed(push):
             if host_glue:
                 if self._plan_stale:
                     self._fetch()
@@ -975,16 +766,4 @@ class FullDynamicPipeline(_Actuators):
                     self.low_level_step(cs)
             else:
                 x_last = self.low_level_loop(cs)
-        finally:
-            if push is not None:
-                self.sim.set_push(None)
-        e = self.mpc
-        if e._walk is not None:     # the references are planned from the state that becomes the initial condition (fulldynamic_talos.py:440-462)
-            e._walk["x_measured"] = self.x_prev[0].copy()
-            if "x_measured_all" in e._walk:
-                e._walk["x_measured_all"] = self.x_prev.copy()
-        e.native.set_x0(self.x_prev)
-        st = e.step()
-        self.x_prev = x_last
-        self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
-        return st
+        return self._solve_from_x_prev(x_last)
