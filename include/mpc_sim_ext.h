@@ -23,7 +23,8 @@ extern "C" {
  *   width 3: f_ext[B][3], a world-frame force at the base origin (mpc_simulate_push's convention: the point moves with the base);
  *   width 6: f_ext[B][6] = (world-frame force, fixed world-frame point it acts at), as PyBullet's applyExternalForce(..., WORLD_FRAME): the moment
  *            (p - p_base) x f about the base origin is taken at the base position of every sub-step.  At p = p_base it is the width-3 push.
- * The push acts on the base link only.  mpc_simulate and mpc_simulate_push (the feedback-law form) do not see it.  The upload is synchronous on
+ * This push acts on the base link and is held until the host arms another; a per-robot schedule of pushes on any link, timed on the device, is
+ * include/mpc_sim_disturbances.h (while one is on, a non-NULL push is refused here).  mpc_simulate and mpc_simulate_push (the feedback-law form) do not see it.  The upload is synchronous on
  * the handle's stream. */
 int mpc_sim_set_push(mpc_solver* sim, const double* f_ext, int32_t width);
 

@@ -17,6 +17,7 @@ from . import sensor_model as _sensor_model
 from . import state_estimator as _state_estimator
 from . import foot_sensors as _foot_sensors
 from . import plant_model as _plant_model
+from . import disturbance_model as _disturbance_model
 from . import friction_model as _friction_model
 from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
@@ -214,6 +215,16 @@ _SIM_FRICTION_SIGNATURES = {
     "mpc_sim_friction_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_disturbances.h: exported by the HIP library alone, bound when present (``NativeSolver.disturbances`` / ``read_disturbances`` /
+# ``reset_disturbances``)
+_SIM_DISTURBANCES_SIGNATURES = {
+    "mpc_sim_disturbances": (C.c_int, [C.c_void_p, _DP, C.c_int32]),
+    "mpc_sim_disturbances_read": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
+    "mpc_sim_disturbances_reset": (C.c_int, [C.c_void_p]),
+    "mpc_sim_disturbances_width": (C.c_int32, [C.c_void_p]),
+    "mpc_sim_disturbances_events": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_sim_terrain.h: exported by the HIP library alone, bound when present (``NativeSolver.terrain`` / ``read_terrain`` / ``terrain_height``)
 class MpcSimTerrainConfig(C.Structure):
     _fields_ = [("n_boxes", C.c_int32), ("per_robot", C.c_int32)]
@@ -266,6 +277,7 @@ _HIP_ONLY = (
     ("mpc_sim_foot_sensors.h", _SIM_FOOT_SENSORS_SIGNATURES, "the foot force sensors of torque-driven simulator steps are HIP only", RuntimeError),
     ("mpc_sim_plant.h", _SIM_PLANT_SIGNATURES, "the plant model of torque-driven simulator steps is HIP only", RuntimeError),
     ("mpc_sim_friction.h", _SIM_FRICTION_SIGNATURES, "the ground friction of torque-driven simulator steps is HIP only", RuntimeError),
+    ("mpc_sim_disturbances.h", _SIM_DISTURBANCES_SIGNATURES, "the push schedules of torque-driven simulator steps are HIP only", RuntimeError),
     ("mpc_sim_terrain.h", _SIM_TERRAIN_SIGNATURES, "the terrain of the contact rule needs the HIP library", NotImplementedError),
     ("mpc_walk_poses.h", _WALK_POSES_SIGNATURES, "the device generator of the contact-pose references is HIP only", RuntimeError),
     ("mpc_walk_commands.h", _WALK_COMMANDS_SIGNATURES, "a walk command per robot on the device generators needs the HIP library", NotImplementedError),
@@ -689,6 +701,37 @@ class NativeSolver:
         fn = self._hip("mpc_sim_foot_sensors_feed")
         mask = int(consumers) if isinstance(consumers, (int, np.integer)) else _foot_sensors.feed_mask(consumers)
         self._check(fn(self._h, mask), "mpc_sim_foot_sensors_feed")
+
+    # -- include/mpc_sim_disturbances.h (HIP library only): per-robot push schedules on any link, timed on the device --------------------------------
+    def disturbances(self, events):
+        """Give every robot of this simulator handle its own schedule of pushes (mpc_sim_disturbances; ``disturbance_model`` is the definition):
+        ``events`` in the forms of ``disturbance_model.rows`` ((B, n, 16) tables, one table for every robot, or one list of events per robot);
+        turns the model on and resets its clock and state rows.  Contact triggers need the contact rule (``contacts``).  None turns it off."""
+        fn = self._hip("mpc_sim_disturbances")
+        if events is None:
+            self._check(fn(self._h, None, 0), "mpc_sim_disturbances")
+            return
+        ev = _f64(_disturbance_model.rows(events, self.dims.batch))
+        self._check(fn(self._h, _dp(ev), ev.shape[1]), "mpc_sim_disturbances")
+
+    def read_disturbances(self, raw=False):
+        """The schedule as it stands (mpc_sim_disturbances_read) -> dict: ``events`` (B, n, 16) the tables in force, the state rows by
+        ``disturbance_model.unpack`` (``step``, ``acting``, ``occurrences``, ``fire_step``, ``impulse``, ``pushed_steps``, ``shadowed_steps``,
+        ``peak_force``, ``applied``, ``link``, ``seen``) and ``applied_now`` (B, 7): world force, world point and link (-1: none) as the buffers the
+        dynamics read hold them; ``raw``: the (B, WIDTH) rows themselves."""
+        fn, out = self._hip("mpc_sim_disturbances_read"), self._state_rows("mpc_sim_disturbances_width")
+        ev = np.zeros((self.dims.batch, max(self._width("mpc_sim_disturbances_events"), 1), _disturbance_model.EVENT))
+        now = np.zeros((self.dims.batch, 7))
+        self._check(fn(self._h, _dp(ev), _dp(out), _dp(now)), "mpc_sim_disturbances_read")
+        if raw:
+            return out
+        r = _disturbance_model.unpack(out)
+        r["events"], r["applied_now"] = ev, now
+        return r
+
+    def reset_disturbances(self):
+        """Clock, counters and accumulators of the schedule back to the state after arming; the tables stay (mpc_sim_disturbances_reset)."""
+        self._check(self._hip("mpc_sim_disturbances_reset")(self._h), "mpc_sim_disturbances_reset")
 
     # -- include/mpc_sim_friction.h (HIP library only): per-robot ground friction under the soles of the torque-driven simulator steps -------------
     def friction(self, params, base=None):

@@ -35,6 +35,10 @@ table from the rows in force.
 mpc_sim_friction, include/mpc_sim_friction.h): a sole whose tangential force leaves the cone ``mu f_z`` slips, and turns when its yaw moment leaves
 ``mu_spin f_z``.  ``setFrictionCoefficients(link_id, lateral, spinning)``, the reference's knob, sets ``mu`` and ``mu_spin`` of one sole.  Without
 either every sole holds whatever force it takes, as before.
+``disturbances=`` / ``setDisturbances(events)`` (HIP library only) give the robot a schedule of pushes on any link, timed on the device by the
+simulator's step clock or by the touchdowns and lift-offs of its soles (``disturbance_model``; mpc_sim_disturbances,
+include/mpc_sim_disturbances.h; contact triggers need ``device_contacts=True``).  ``disturbanceState()`` returns the clock, the counters and what
+acted.  While a schedule is armed ``apply_force`` is refused: its events are the pushes.
 
 Differences from PyBullet worth knowing: ``measureState`` returns the base velocity in the LOCAL frame of the base (Pinocchio's
 convention, which is what the scripts assume when they copy it into the state, talos_utils.py:337-348); PyBullet reports it in the
@@ -55,7 +59,7 @@ class BulletRobot:
 
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
                  inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
-                 device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None, plant=None, friction=None):
+                 device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None, plant=None, friction=None, disturbances=None):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -74,6 +78,7 @@ class BulletRobot:
         self._foot_sensors = None if foot_sensors is None else (foot_sensors, ())  # (params, detected_contacts) of setFootSensors, armed at initializeJoints
         self._plant = None if plant is None else (plant, None)  # (rows, link_scale) of setPlant, armed at initializeJoints
         self._friction = friction  # rows of setFriction, armed at initializeJoints
+        self._disturbances = disturbances  # events of setDisturbances, armed at initializeJoints
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
         self._native = None       # the simulator handle, and ``_sim_models``, the models armed on it (``torque_simulator.SimulatorModels``)
@@ -122,7 +127,8 @@ class BulletRobot:
             if self.terrain is not None:
                 self._native.terrain(self.terrain)
         self._sim_models = _tsim.SimulatorModels(self._native, m, self.frame_ids, self.dt)
-        self._sim_models.arm(self.x, self.x[:m.nq], self._plant, self._friction, self._actuators, self._sensors, self._foot_sensors, self._estimator)
+        self._sim_models.arm(self.x, self.x[:m.nq], self._plant, self._friction, self._actuators, self._sensors, self._foot_sensors, self._estimator,
+                             None if self._disturbances is None else (self._disturbances, self.device_contacts))
 
     def _build_native(self):
         """the handle (opened once) with the model, the terminal stage and the contact-mask stages at the anchors ``_contact_pose`` as they stand"""
@@ -246,6 +252,9 @@ class BulletRobot:
         p = np.asarray(position, dtype=float).reshape(-1)
         if f.size != 3 or p.size != 3:
             raise ValueError("apply_force: a 3-vector force and a 3-vector world position expected")
+        if self._disturbances is not None:
+            raise ValueError("apply_force: a push schedule is armed on this robot (setDisturbances): its events are the pushes; setDisturbances(None) "
+                             "turns it off")
         self._pending_force = (f, p)
 
     # -- GUI calls of the scripts: recorded, nothing to draw ------------------------------------------------------------------------
@@ -302,6 +311,19 @@ class BulletRobot:
         self._friction = rows
         if self._sim_models is not None:
             self._sim_models.set_friction(rows, self.x[:self.model.nq])
+
+    def setDisturbances(self, events):
+        """The push schedule of the robot (``disturbance_model``; HIP library only): ``events`` an (n, 16) table, (1, n, 16), or a list holding one
+        list of events; contact triggers need ``device_contacts=True``.  Arms the schedule and resets its clock; None turns it off."""
+        if events is not None and self._pending_force is not None:
+            raise ValueError("setDisturbances: a force of apply_force is pending for the next execute; execute it first")
+        if self._sim_models is not None:
+            self._sim_models.set_disturbances(events, self.device_contacts)
+        self._disturbances = events
+
+    def disturbanceState(self):
+        """the state rows of the push schedule by ``disturbance_model.unpack`` (``step``, ``acting``, ``impulse`` ...); None without one"""
+        return None if self._sim_models is None else self._sim_models.disturbance_state()
 
     def _refuse_friction_without_rule(self, rows):
         if rows is not None and not self.device_contacts:

@@ -212,7 +212,10 @@ DEV void jlog6_blocks(const M3& Ji, const M3& Q, double sgn, double* out) {
 // FJ, FV, FU > 0: the model's body / velocity / control counts as compile-time constants (a free-flyer model: nq = nv + 1, n = 2 nv; FCD: the
 // carve-out with the blocks of the contact-constrained dynamics) — the loop bounds, strides and LDS offsets of the carve-out fold into the instructions, as in the
 // fixed-dimension instantiations of the Riccati sweep (riccati_mfma.h).  The launcher picks such an instantiation only for that model.
-template <int TRIAL, int FJ = 0, int FV = 0, int FU = 0, bool FCD = true>
+// LINKED (TRIAL == 2 only): the simulator form of a handle with the disturbance schedule on (include/mpc_sim_disturbances.h): the width-6 push acts
+// on the dofs below robot b's own link.  An instantiation of its own, launched only while a schedule is armed, so that k_eval_multibody<2>, which
+// every other simulator step runs, keeps the parent's instructions, registers and scratch (profiles/sim_disturbances.txt).
+template <int TRIAL, int FJ = 0, int FV = 0, int FU = 0, bool FCD = true, bool LINKED = false>
 __global__ void __launch_bounds__(EVAL_THREADS, EVAL_MIN_WAVES) k_eval_multibody(SolverArgs a, Layout KL, double* records, MbArgs mb, int cand0) {
   constexpr bool FX = FJ > 0;
   constexpr MbLds SC_ = FX ? make_mb_lds(FJ, FV, FV + 1, FU, 2 * FV + FU, FCD) : MbLds{};
@@ -837,7 +840,14 @@ sim_u_set:
           if (TRIAL == 2 && mb.f_ext && mb.f_ext_width != 6 && l < 3) s += J[0 * nv + l] * mb.f_ext[3 * b] + J[1 * nv + l] * mb.f_ext[3 * b + 1] + J[2 * nv + l] * mb.f_ext[3 * b + 2];
           // width 6: f at a fixed world point p, the wrench [f ; p x f] about the world origin on the base columns (the columns are world-frame
           // twists at the origin: J_lin . f + J_ang . (p x f) = (R e_l) . f on the translations, (R e_l) . ((p - p_base) x f) on the rotations)
-          if (TRIAL == 2 && mb.f_ext && mb.f_ext_width == 6 && l < 6) {
+          // LINKED: the optional per-robot body, int32 link[B] behind the [B][6] rows (-1: nothing acts on robot b, which skips the term: a branch
+          // the workgroup takes together).  l < 6 becomes BELOW(l, link): for the base the same dofs and the same arithmetic
+          bool pushed = l < 6;
+          if constexpr (LINKED) {
+            const int body = ((const int32_t*)(mb.f_ext + 6 * (size_t)L.B))[b];
+            pushed = body >= 0 && BELOW(l, body < 0 ? 0 : body);
+          }
+          if (TRIAL == 2 && mb.f_ext && mb.f_ext_width == 6 && pushed) {
             const double* fe = mb.f_ext + 6 * (size_t)b;
             const V3 mo = cross(v3(fe[3], fe[4], fe[5]), v3(fe[0], fe[1], fe[2]));
             s += (J[0 * nv + l] * fe[0] + J[1 * nv + l] * fe[1] + J[2 * nv + l] * fe[2]) + (J[3 * nv + l] * mo.x + J[4 * nv + l] * mo.y + J[5 * nv + l] * mo.z);

@@ -10,7 +10,7 @@
 void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
                            bool trial, int cand0, int ncand, int sim_substeps, double sim_dt, bool with_derivs, const double* f_ext, bool contact_dyn,
                            const double* sim_u, double* sim_wrench, int f_ext_width, const double* sim_contacts, const double* sim_model,
-                           size_t sim_model_stride, const double* sim_friction) {
+                           size_t sim_model_stride, const double* sim_friction, bool f_ext_linked) {
   const Layout& L = a.L;
   MbArgs mb;
   mb.lds = make_mb_lds(L.nj, L.n / 2, L.nx - L.n / 2, L.m, L.nz, contact_dyn);
@@ -34,6 +34,7 @@ void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout
     hipError_t e2 = hipFuncSetAttribute((const void*)k_eval_multibody<1>, hipFuncAttributeMaxDynamicSharedMemorySize, mb.lds.total_bytes);
     if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)k_eval_multibody<2>, hipFuncAttributeMaxDynamicSharedMemorySize, mb.lds.total_bytes);
     if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)k_eval_multibody<3>, hipFuncAttributeMaxDynamicSharedMemorySize, mb.lds.total_bytes);
+    if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)k_eval_multibody<2, 0, 0, 0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mb.lds.total_bytes);
     if (e1 != hipSuccess || e2 != hipSuccess) throw std::runtime_error(std::string("hipFuncSetAttribute(LDS) failed: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     attr_bytes.store(mb.lds.total_bytes + 1);  // + 1: the zero-initialised slots mean "not set"
   }
@@ -72,7 +73,8 @@ void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout
 #undef X1
     return;
   }
-  if (sim_substeps > 0) hipLaunchKernelGGL(k_eval_multibody<2>, dim3(1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, 0);
+  if (sim_substeps > 0 && f_ext_linked) hipLaunchKernelGGL((k_eval_multibody<2, 0, 0, 0, true, true>), dim3(1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, 0);
+  else if (sim_substeps > 0) hipLaunchKernelGGL(k_eval_multibody<2>, dim3(1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, 0);
   else if (trial && with_derivs) hipLaunchKernelGGL(k_eval_multibody<3>, dim3(L.N + 1 + (a.spec_knot ? 1 : 0), L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, L, records, mb, 0);  // records = the knot records (+ the speculative knot)
   else if (!trial) hipLaunchKernelGGL(k_eval_multibody<0>, dim3(a.only_knot >= 0 ? 1 : L.N + 1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, L, records, mb, 0);
   else hipLaunchKernelGGL(k_eval_multibody<1>, dim3(L.N + 1, L.B, mb.ncand_loop > 0 ? 1 : ncand), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, cand0);

@@ -124,7 +124,11 @@ struct MbArgs {
   int sim_substeps;       // TRIAL == 2 (closed-loop simulation stand-in): integration steps ...
   double sim_dt;          // ... of this length
   const double* f_ext;    // TRIAL == 2: the push on the base per instance, or nullptr: f_ext_width 3: [B][3] world-frame force at the base origin
-                          // (mpc_simulate_push) ; 6: [B][6] = (world-frame force, fixed world point it acts at) (include/mpc_sim_ext.h)
+                          // (mpc_simulate_push) ; 6: [B][6] = (world-frame force, fixed world point it acts at) (include/mpc_sim_ext.h).
+                          // With f_ext_linked of launch_eval_multibody (the disturbance schedule, include/mpc_sim_disturbances.h; width 6): the
+                          // per-robot body rides behind the rows, int32 link[B] at f_ext + 6 B (-1: nothing acts on that robot), and the LINKED
+                          // instantiation of the simulator form applies the wrench on the dofs below that link.  Not a member of its own: MbArgs
+                          // keeps its layout and cand0 its offset, so no other instantiation changes
   const double* sim_friction;  // TRIAL == 2: the state rows of the friction model [B][MPC_SIM_FRICTION_WIDTH] (include/mpc_sim_friction.h), or
                                // nullptr: every held sole is held to rest.  It has the eight bytes f_ext_width and its padding had here: no
                                // other member moved and the kernel argument after the struct (cand0) kept its offset, so every instantiation
@@ -145,5 +149,5 @@ void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout
                            bool trial, int cand0 = 0, int ncand = 1, int sim_substeps = 0, double sim_dt = 0.0, bool with_derivs = false,
                            const double* f_ext = nullptr, bool contact_dyn = true, const double* sim_u = nullptr, double* sim_wrench = nullptr,
                            int f_ext_width = 3, const double* sim_contacts = nullptr, const double* sim_model = nullptr, size_t sim_model_stride = 0,
-                           const double* sim_friction = nullptr);
+                           const double* sim_friction = nullptr, bool f_ext_linked = false);
 const void* eval_multibody_kernel(int trial);  // entry point of k_eval_multibody<trial> (occupancy tooling)

@@ -39,6 +39,7 @@
 #include "sim_foot_sensors.h"
 #include "sim_plant.h"
 #include "sim_friction.h"
+#include "sim_disturbances.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
 #include "../../include/mpc_walk_poses.h"
@@ -118,9 +119,15 @@ struct SimPlant {
   // rows [B][17]
   double* d_fr = nullptr;
   std::vector<double> h_fr;  // params as they are in force
+  // include/mpc_sim_disturbances.h: the per-robot push schedule (nullptr: off), one allocation: events [B][dis_ne][16] | state rows [B][32] | what
+  // acts in the step [B][6] | its link, int32 [B] (the dynamics read the last two in place of d_push)
+  double* d_dis = nullptr;
+  std::vector<double> h_dis;  // events as they are in force
+  int dis_ne = 0;
+  bool dis_contact = false;   // an event of the table has a contact trigger: the table goes with the contact rule
   // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
   void free_owned() {
-    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est, &d_fs, &d_plant, &d_fr}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est, &d_fs, &d_plant, &d_fr, &d_dis}) if (*p) { (void)hipFree(*p); *p = nullptr; }
   }
 };
 
@@ -1089,6 +1096,9 @@ int mpc_set_model(mpc_solver* s, const int32_t* itab, int32_t n_i, const double*
     if (s->plant.d_plant && nj != s->L.nj)  // (before anything changes: the rows in force name joints of the model they were armed on)
       throw std::runtime_error("set_model: the plant model is on (mpc_sim_plant) and its rows were armed on a model of " + std::to_string(s->L.nj) +
                                " joints; this one has " + std::to_string(nj) + ": turn the plant model off first");
+    if (s->plant.d_dis && nj != s->L.nj)  // (the same for the links of the disturbance schedule, include/mpc_sim_disturbances.h)
+      throw std::runtime_error("set_model: the disturbance schedule is on (mpc_sim_disturbances) and its links were checked against a model of " +
+                               std::to_string(s->L.nj) + " joints; this one has " + std::to_string(nj) + ": turn the schedule off first");
     if (s->dims.space == MPC_SPACE_MULTIBODY) {  // (every check of the tables before anything changes: a refused model leaves the one in force, and the
                                                  // per-robot tables an armed plant model built from it, whole)
       if (itab[2] * 2 != s->L.n || itab[1] + itab[2] != s->L.nx) throw std::runtime_error("model dimensions do not match the state space");

@@ -1,6 +1,6 @@
 // sim_host.h — host side of the torque-driven simulator (the plant): mpc_simulate_torque and the entry points of include/mpc_sim_ext.h (push, record),
-// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h, mpc_sim_estimator.h, mpc_sim_foot_sensors.h, mpc_sim_plant.h and mpc_sim_friction.h.  Its state is mpc_solver::plant (SimPlant); its kernels
-// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h, sim_estimator.h, sim_foot_sensors.h, sim_plant.h and sim_friction.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
+// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h, mpc_sim_estimator.h, mpc_sim_foot_sensors.h, mpc_sim_plant.h, mpc_sim_friction.h and mpc_sim_disturbances.h.  Its state is mpc_solver::plant (SimPlant); its kernels
+// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h, sim_estimator.h, sim_foot_sensors.h, sim_plant.h, sim_friction.h and sim_disturbances.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
 // loops of the three pipelines in pipeline_loops.h — goes through sim_steps_check, sim_steps_begin and sim_step_enqueue: an extension of the simulator
 // is added there, once.  Included at the end of mpc_hip.hip (mpc_solver, MPC_TRY, copy_sync, slot_of).
 #pragma once
@@ -55,6 +55,47 @@ static double* sim_plant_tables(const mpc_solver* s) { return s->plant.d_plant +
 static const double* sim_plant_md(const mpc_solver* s) { return s->plant.d_plant ? sim_plant_tables(s) : s->d_model_d; }
 static size_t sim_plant_stride(const mpc_solver* s) { return s->plant.d_plant ? s->plant.plant_nd : 0; }
 
+// the disturbance schedule (include/mpc_sim_disturbances.h), one allocation: events | state rows | what acts in the step [B][6] | its link int32 [B]
+static double* sim_disturbances_rows(const mpc_solver* s) { return s->plant.d_dis + (size_t)s->L.B * s->plant.dis_ne * MPC_SIM_DISTURBANCES_EVENT; }
+static double* sim_disturbances_out(const mpc_solver* s) { return sim_disturbances_rows(s) + (size_t)s->L.B * MPC_SIM_DISTURBANCES_WIDTH; }
+static size_t sim_disturbances_doubles(const Layout& L, int ne) {
+  return (size_t)L.B * ((size_t)ne * MPC_SIM_DISTURBANCES_EVENT + MPC_SIM_DISTURBANCES_WIDTH + 6) + ((size_t)L.B + 1) / 2;
+}
+// the schedule's event of the step of length dt_step about to be enqueued on stream st (sim_disturbances.h), when the model is on: it reads the state
+// the step starts from and the rows the contact rule left after the step before
+static void sim_disturbances_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
+  const SimPlant& p = s->plant;
+  if (!p.d_dis) return;
+  const Layout& L = s->L;
+  SimDisturbancesArgs a;
+  a.mi = s->d_model_i; a.md = s->d_model_d; a.nv = L.n / 2; a.nq = L.nx - L.n / 2;
+  a.x = s->d_x0; a.con = p.d_con; a.events = p.d_dis; a.n_events = p.dis_ne;
+  a.rows = sim_disturbances_rows(s); a.out = sim_disturbances_out(s); a.link = (int32_t*)(a.out + (size_t)L.B * 6); a.dt = dt_step;
+  hipLaunchKernelGGL(k_sim_disturbances, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, a);
+  HIP_OK(hipGetLastError());
+}
+// the state rows, what acts and its link after arming or a reset: clock 0, nothing counted, nothing fired, no pair seen, nothing acting
+static void sim_disturbances_reset(mpc_solver* s) {
+  const Layout& L = s->L;
+  const size_t head = (size_t)L.B * s->plant.dis_ne * MPC_SIM_DISTURBANCES_EVENT, count = sim_disturbances_doubles(L, s->plant.dis_ne) - head;
+  std::vector<double> h(count, 0.0);
+  for (int b = 0; b < L.B; ++b) {
+    double* r = h.data() + (size_t)b * MPC_SIM_DISTURBANCES_WIDTH;
+    r[SIM_DIS_O_ACTING] = r[SIM_DIS_O_LINK] = r[SIM_DIS_O_SEEN] = r[SIM_DIS_O_SEEN + 1] = -1.0;
+    for (int e = 0; e < MPC_SIM_DISTURBANCES_MAX_EVENTS; ++e) r[SIM_DIS_O_FIRE + e] = -1.0;
+  }
+  int32_t* link = (int32_t*)(h.data() + (size_t)L.B * (MPC_SIM_DISTURBANCES_WIDTH + 6));
+  for (int b = 0; b < L.B; ++b) link[b] = -1;
+  HIP_OK(hipStreamSynchronize(s->stream));
+  copy_sync(s, sim_disturbances_rows(s), h.data(), count * sizeof(double), hipMemcpyHostToDevice);
+}
+static void sim_disturbances_drop(mpc_solver* s) {
+  sim_realloc(s, s->plant.d_dis, 0);
+  s->plant.h_dis.clear();
+  s->plant.dis_ne = 0;
+  s->plant.dis_contact = false;
+}
+
 // the record of the step just enqueued on stream st (sim_record.h), when recording is on
 static void sim_record_enqueue(mpc_solver* s, hipStream_t st) {
   SimPlant& p = s->plant;
@@ -62,7 +103,7 @@ static void sim_record_enqueue(mpc_solver* s, hipStream_t st) {
   const Layout& L = s->L;
   SimRecordArgs r;
   r.mi = s->d_model_i; r.md = sim_plant_md(s); r.md_stride = sim_plant_stride(s); r.nv = L.n / 2; r.nq = L.nx - L.n / 2;
-  r.x = s->d_x0; r.tau = p.d_simu; r.wr = p.d_simwr; r.push = p.push_width ? p.d_push : nullptr; r.push_width = p.push_width;
+  r.x = s->d_x0; r.tau = p.d_simu; r.wr = p.d_simwr; r.push = p.d_dis ? sim_disturbances_out(s) : (p.push_width ? p.d_push : nullptr); r.push_width = p.d_dis ? 6 : p.push_width;  // (the schedule: what acted)
   r.out = p.d_rec + (size_t)p.rec_count * L.B * sim_record_width(L.nx, L.m);
   hipLaunchKernelGGL(k_sim_record, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, r);
   HIP_OK(hipGetLastError());
@@ -292,7 +333,9 @@ static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
     HIP_OK(hipMemcpyAsync(s->plant.d_met + (size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1), s->d_x0, (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
 }
 // One step of the plant on stream st: `substeps` integration steps of length dt under the torque the caller put into plant.d_simu.  The order is the
-// contract of the extensions.  The actuator model first: it turns the command into the applied torque in place, over the whole step (substeps * dt),
+// contract of the extensions.  The disturbance schedule (include/mpc_sim_disturbances.h) before everything: from the state the step starts from and the
+// rows the contact rule left after the step before it writes the force, point and link that act in this step's dynamics, in place of the armed push.
+// The actuator model next: it turns the command into the applied torque in place, over the whole step (substeps * dt),
 // and everything after it sees the applied torque.  Then the dynamics, with the armed push and the contacts the rule's rows held when the step BEFORE
 // ended (the rows the low-level QPs of pipeline_loops.h read for this step); wrenches are written when the caller, the record, the metrics or the rule
 // want them.  Then the record and the metrics of the step: the new state, the applied torque, its wrenches, the rows it was integrated with.  The
@@ -302,15 +345,18 @@ static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
 // the contact detector: the detection event of this step's wrenches (which the dynamics then always write), so that an estimator fed by detection reads
 // the pair this step's event left, and the low-level QPs of the next step the same pair.  The friction model (include/mpc_sim_friction.h) directly
 // after the contact rule: from this step's wrenches and the flags the rule just wrote it sets the slip velocity each held sole has in the NEXT
-// step's dynamics, and advances the anchors of the soles that slid in this one.  In one line: actuator model -> dynamics -> record -> metrics
+// step's dynamics, and advances the anchors of the soles that slid in this one.  In one line: disturbances -> actuator model -> dynamics -> record -> metrics
 // -> contact rule -> friction -> sensors -> foot sensors -> estimator.  The plant model (include/mpc_sim_plant.h) launches nothing here: the dynamics, the record and
 // the metrics read robot b's own model table, built when the model was armed.
 static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& args, int substeps, double dt, bool want_wrenches) {
   const SimPlant& p = s->plant;
+  sim_disturbances_enqueue(s, st, substeps * dt);
   sim_actuators_enqueue(s, st, substeps * dt);
-  launch_eval_multibody(st, args, s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, p.push_width ? p.d_push : nullptr, true,
-                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con || p.d_fs || p.d_fr) ? p.d_simwr : nullptr, p.push_width ? p.push_width : 3, p.d_con,
-                        p.d_plant ? sim_plant_tables(s) : nullptr, sim_plant_stride(s), p.d_fr ? sim_friction_rows(s) : nullptr);
+  const double* push = p.d_dis ? sim_disturbances_out(s) : (p.push_width ? p.d_push : nullptr);  // (the two exclude each other: mpc_sim_set_push)
+  launch_eval_multibody(st, args, s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, push, true,
+                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con || p.d_fs || p.d_fr) ? p.d_simwr : nullptr,
+                        p.d_dis ? 6 : (p.push_width ? p.push_width : 3), p.d_con,
+                        p.d_plant ? sim_plant_tables(s) : nullptr, sim_plant_stride(s), p.d_fr ? sim_friction_rows(s) : nullptr, p.d_dis != nullptr);
   HIP_OK(hipGetLastError());
   sim_record_enqueue(s, st);
   sim_metrics_enqueue(s, st, substeps * dt);
@@ -328,6 +374,9 @@ int mpc_sim_set_push(mpc_solver* s, const double* f_ext, int32_t width) {
   MPC_TRY(s, {
     sim_check(s, "sim_set_push");
     if (!f_ext) { s->plant.push_width = 0; return 0; }
+    if (s->plant.d_dis)
+      throw std::runtime_error("sim_set_push: the disturbance schedule is on (mpc_sim_disturbances): its events are the pushes of this handle; turn it off "
+                               "with mpc_sim_disturbances(sim, NULL, 0) before arming a push");
     if (width != 3 && width != 6) throw std::runtime_error("sim_set_push: width must be 3 (force at the base origin) or 6 (force, world point)");
     const Layout& L = s->L;
     if (!s->plant.d_push) s->plant.d_push = s->alloc<double>((size_t)L.B * 6);
@@ -422,6 +471,7 @@ int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
       sim_friction_drop(s);
       sim_estimator_drop(s);
       sim_foot_sensors_drop(s);
+      if (s->plant.dis_contact) sim_disturbances_drop(s);  // (a table with a contact trigger reads the rows)
     }
     if (cfg) {
       s->plant.con_cfg = *cfg;
@@ -1002,6 +1052,97 @@ int mpc_sim_friction_set(mpc_solver* s, const double* state) {
 }
 
 int32_t mpc_sim_friction_width(mpc_solver* s) { return sim_width(s, "sim_friction_width", [&] { return MPC_SIM_FRICTION_WIDTH; }); }
+
+// ---- include/mpc_sim_disturbances.h: per-robot push schedules on any link ----------------------------------------------------------------------
+int mpc_sim_disturbances(mpc_solver* s, const double* events, int32_t n_events) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_disturbances");
+    const Layout& L = s->L;
+    if (!events) {
+      sim_disturbances_drop(s);
+      return 0;
+    }
+    // (every check before anything changes: a bad event leaves the previous configuration in force)
+    if (n_events < 1 || n_events > MPC_SIM_DISTURBANCES_MAX_EVENTS)
+      throw std::runtime_error("sim_disturbances: n_events must be 1 .. " + std::to_string(MPC_SIM_DISTURBANCES_MAX_EVENTS));
+    if (!s->have_model || s->h_model_i.empty()) throw std::runtime_error("sim_disturbances: no model is set on this handle (mpc_set_model first)");
+    if (L.nj > CG_MAX_NJ) throw std::runtime_error("sim_disturbances: more moving joints than the simulator's kernels hold (" + std::to_string(CG_MAX_NJ) + ")");
+    static const char* const field[MPC_SIM_DISTURBANCES_EVENT] = {"trigger", "start", "delay", "steps", "period", "shape", "link", "force_frame", "point_frame",
+                                                                  "force[0]", "force[1]", "force[2]", "point[0]", "point[1]", "point[2]", "reserved"};
+    bool contact = false;
+    for (int b = 0; b < L.B; ++b)
+      for (int e = 0; e < n_events; ++e) {
+        const double* v = events + ((size_t)b * n_events + e) * MPC_SIM_DISTURBANCES_EVENT;
+        const std::string ev = "sim_disturbances: robot " + std::to_string(b) + ", event " + std::to_string(e) + ": ";
+        for (int i = 0; i < MPC_SIM_DISTURBANCES_EVENT; ++i)
+          if (!std::isfinite(v[i])) throw std::runtime_error(ev + field[i] + " is not finite");
+        for (int i : {0, 1, 2, 3, 4, 5, 6, 7, 8})
+          if (v[i] != std::floor(v[i])) throw std::runtime_error(ev + field[i] + " must be an integer value");
+        if (v[0] < 0.0 || v[0] > 5.0) throw std::runtime_error(ev + "trigger must be 0 .. 5");
+        if (v[15] != 0.0) throw std::runtime_error(ev + "reserved must be 0");
+        if (v[0] == 0.0) continue;  // (an empty slot: the other fields are not read)
+        if (v[0] == 1.0 && v[1] < 0.0) throw std::runtime_error(ev + "start must be >= 0 (a step of the clock)");
+        if (v[0] >= 2.0 && v[1] < 1.0) throw std::runtime_error(ev + "start must be >= 1 (an occurrence of the transition)");
+        if (v[2] < 0.0) throw std::runtime_error(ev + "delay must be >= 0");
+        if (v[3] < 1.0) throw std::runtime_error(ev + "steps must be >= 1");
+        if (v[4] < 0.0 || (v[0] == 1.0 && v[4] > 0.0 && v[4] < v[3])) throw std::runtime_error(ev + "period must be 0 (once) or, on an absolute trigger, >= steps");
+        for (int i : {5, 7, 8})
+          if (v[i] != 0.0 && v[i] != 1.0) throw std::runtime_error(ev + field[i] + " must be 0 or 1");
+        if (v[6] < 0.0 || v[6] > L.nj - 1) throw std::runtime_error(ev + "link must be in [0, " + std::to_string(L.nj - 1) + "] (table joint indices)");
+        if (v[0] >= 2.0) contact = true;
+      }
+    if (contact && !s->plant.d_con)
+      throw std::runtime_error("sim_disturbances: a contact trigger (2 to 5) needs the contact rule, which is off on this handle (turn it on with mpc_sim_contacts first)");
+    if (s->plant.push_width)
+      throw std::runtime_error("sim_disturbances: a push is armed on this handle (mpc_sim_set_push): disarm it with mpc_sim_set_push(sim, NULL, 0) before arming a schedule");
+    const size_t head = (size_t)L.B * n_events * MPC_SIM_DISTURBANCES_EVENT;
+    sim_ensure(s);
+    {  // (the new buffer before the old one goes: an allocation that fails leaves the table in force as it was)
+      void* fresh = nullptr;
+      HIP_OK(hipMalloc(&fresh, sim_disturbances_doubles(L, n_events) * sizeof(double)));
+      HIP_OK(hipStreamSynchronize(s->stream));
+      if (s->plant.d_dis) (void)hipFree(s->plant.d_dis);
+      s->plant.d_dis = (double*)fresh;
+    }
+    s->plant.h_dis.assign(events, events + head);
+    s->plant.dis_ne = n_events;
+    s->plant.dis_contact = contact;
+    copy_sync(s, s->plant.d_dis, events, head * sizeof(double), hipMemcpyHostToDevice);
+    sim_disturbances_reset(s);
+  })
+}
+
+int mpc_sim_disturbances_read(mpc_solver* s, double* events, double* state, double* applied) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_disturbances_read");
+    if (!s->plant.d_dis) throw std::runtime_error("sim_disturbances_read: the disturbance schedule is off on this handle (turn it on with mpc_sim_disturbances)");
+    const Layout& L = s->L;
+    if (events) std::copy(s->plant.h_dis.begin(), s->plant.h_dis.end(), events);
+    HIP_OK(hipStreamSynchronize(s->stream));
+    if (state) copy_sync(s, state, sim_disturbances_rows(s), (size_t)L.B * MPC_SIM_DISTURBANCES_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
+    if (applied) {
+      std::vector<double> h((size_t)L.B * 6 + ((size_t)L.B + 1) / 2);
+      copy_sync(s, h.data(), sim_disturbances_out(s), h.size() * sizeof(double), hipMemcpyDeviceToHost);
+      const int32_t* link = (const int32_t*)(h.data() + (size_t)L.B * 6);
+      for (int b = 0; b < L.B; ++b) {
+        std::copy(h.begin() + (size_t)b * 6, h.begin() + (size_t)b * 6 + 6, applied + (size_t)b * 7);
+        applied[(size_t)b * 7 + 6] = (double)link[b];
+      }
+    }
+  })
+}
+
+int mpc_sim_disturbances_reset(mpc_solver* s) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_disturbances_reset");
+    if (!s->plant.d_dis) throw std::runtime_error("sim_disturbances_reset: the disturbance schedule is off on this handle (turn it on with mpc_sim_disturbances)");
+    sim_disturbances_reset(s);
+  })
+}
+
+int32_t mpc_sim_disturbances_width(mpc_solver* s) { return sim_width(s, "sim_disturbances_width", [&] { return MPC_SIM_DISTURBANCES_WIDTH; }); }
+
+int32_t mpc_sim_disturbances_events(mpc_solver* s) { return sim_width(s, "sim_disturbances_events", [&] { return s->plant.dis_ne; }); }
 
 // ---- include/mpc_abi.h: one step under the caller's torques -------------------------------------------------------------------------------------
 int mpc_simulate_torque(mpc_solver* s, const double* x, const double* tau, int32_t substeps, double dt, double* wrenches) {

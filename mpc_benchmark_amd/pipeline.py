@@ -88,7 +88,15 @@ parameter rows of the per-robot ground friction (``friction_model``: ``mu`` and 
 row of 8 for every robot, or a dict by field name whose missing fields are the identity coefficients and ``friction_model.defaults`` of the robot),
 armed on the simulator handle when the pipeline is built (mpc_sim_friction, include/mpc_sim_friction.h; HIP library only).  Only the plant changes: a
 sole whose force leaves its cone slips.  The MPC stages and the low-level QPs keep their own cones (``mu = 0.8``).  ``friction_state()`` returns the
-slip velocities and counters; ``set_friction`` changes or removes the model later."""
+slip velocities and counters; ``set_friction`` changes or removes the model later.
+
+``disturbances`` (all three pipelines): None, the only push is the one ``tick(push=...)`` arms for a whole period; or every robot's own schedule of
+pushes (``disturbance_model``: up to 8 events per robot, each an absolute step of the simulator's clock or the n-th touchdown or lift-off of a sole
+plus a delay, a duration, a rectangular or half-sine shape, and a force and point on any link in world or link axes; (B, n, 16) tables, one table for
+every robot, or one list of events per robot), armed on the simulator handle when the pipeline is built (mpc_sim_disturbances,
+include/mpc_sim_disturbances.h; HIP library only).  The device times the events step by step inside the low-level loop; contact triggers need
+``contact_rule``.  ``disturbance_state()`` returns the clock, the counters and what acted; ``set_disturbances`` changes or removes the table later.
+While a table is armed ``tick(push=...)`` raises."""
 from __future__ import annotations
 
 import contextlib
@@ -97,6 +105,7 @@ import numpy as np
 
 from . import _capi as K
 from . import contact_rule as _contact_rule
+from . import disturbance_model as _disturbance_model
 from . import foot_sensors as _foot_sensors
 from . import qp_utils
 from . import torque_simulator as _tsim
@@ -167,6 +176,17 @@ def _checked_friction(name, friction, contact_rule):
         raise ValueError("%s: friction needs contact_rule (the model slides the soles the unilateral contact rule holds; contact_rule={} turns it on)" % name)
 
 
+def _checked_disturbances(name, events, contact_rule, batch, problem_def):
+    """``disturbances`` of a pipeline: None, or the tables (B, n, 16) checked before any library call (``disturbance_model.validate``); contact
+    triggers are refused without ``contact_rule``"""
+    if events is None:
+        return None
+    try:
+        return _disturbance_model.validate(_disturbance_model.rows(events, batch), problem_def.robot.model.njoints - 1, contact_rule is not None)
+    except ValueError as e:
+        raise ValueError("%s: %s" % (name, e)) from None
+
+
 def _checked_walk(name, walk, batch):
     """``walk`` of a pipeline: the ``commands`` table in it is checked before any library call (shape, finite values, ``per_instance=True``)"""
     if walk is None or walk.get("commands") is None:
@@ -211,7 +231,8 @@ class _Pipeline:
     def _init_contact_source(self, name, source, contact_rule):
         """(the hook of the pipelines with a low-level QP, ``_QpContactSource``)"""
 
-    def _check_arguments(self, problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts, contact_source=None):
+    def _check_arguments(self, problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts, contact_source=None,
+                         disturbances=None):
         """the arguments every pipeline takes, checked before the library is loaded -> (walk, detected_contacts)"""
         name = type(self).__name__
         self.pd, self.batch = problem_def, int(batch)
@@ -220,6 +241,7 @@ class _Pipeline:
         self.terrain = _checked_terrain(name, terrain, contact_rule, self.batch)
         walk = _checked_walk(name, walk, self.batch)
         _checked_friction(name, friction, contact_rule)
+        self._disturbances = _checked_disturbances(name, disturbances, contact_rule, self.batch, problem_def)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         return walk, detected_contacts
 
@@ -259,7 +281,8 @@ class _Pipeline:
             self._set_sim_contacts(stage0)
         self.sim_models = _tsim.SimulatorModels(self.sim, self.model, rb.foot_frame_ids, self.sim_dt)
         self.sim_models.arm(self.x, rb.x0[:self.nq], plant, friction, None if actuators is None else (actuators,), sensors,
-                            None if foot_sensors is None else (foot_sensors, detected_contacts), estimator)
+                            None if foot_sensors is None else (foot_sensors, detected_contacts), estimator,
+                            None if self._disturbances is None else (self._disturbances, self.contact_rule is not None))
         self.x_prev = self.x_est.copy()      # the measurement of the period before (the solve's initial condition)
         self.torques = np.zeros((self.batch, self.nv - 6))
         self._plan_stale = True
@@ -272,6 +295,25 @@ class _Pipeline:
     def set_plant(self, rows, link_scale=None):
         """Arm the per-robot plant model on ``self.sim``: ``rows`` in the forms of ``NativeSolver.plant``, a dict may also carry ``link_scale``."""
         self.sim_models.set_plant(rows, link_scale)
+
+    def set_disturbances(self, events):
+        """Arm the per-robot push schedule on ``self.sim`` and reset its clock: ``events`` in the forms of ``NativeSolver.disturbances``; contact
+        triggers need ``contact_rule``.  None: off.  While a table is armed ``tick(push=...)`` is refused."""
+        checked = _checked_disturbances(type(self).__name__, events, self.contact_rule, self.batch, self.pd)
+        self.sim_models.set_disturbances(checked, self.contact_rule is not None)
+        self._disturbances = checked   # (after the library took it: a refused table leaves the pipeline as it was)
+
+    def disturbance_state(self):
+        """the state rows of the push schedule by ``disturbance_model.unpack`` (``step``, ``acting``, ``impulse`` ...); None without ``disturbances``"""
+        return self.sim_models.disturbance_state()
+
+    def _checked_push(self, push):
+        """``tick(push=...)`` checked before any library call: the array, and that no push schedule is armed (its events are the pushes)"""
+        push = _push_array(push, self.batch)
+        if push is not None and getattr(self, "_disturbances", None) is not None:
+            raise ValueError("%s: tick(push=...) conflicts with the push schedule armed on this pipeline (disturbances=...): the schedule's events are "
+                             "the pushes; set_disturbances(None) turns it off" % type(self).__name__)
+        return push
 
     def set_friction(self, rows):
         """Arm the per-robot ground friction on ``self.sim`` with every sole at rest: ``rows`` in the forms of ``NativeSolver.friction``, a dict's
@@ -428,7 +470,7 @@ class _QpContactSource(_Pipeline):
 class KinodynamicPipeline(_QpContactSource):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
                  terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, foot_sensors=None,
-                 detected_contacts=(), plant=None, friction=None, **ens_kw):
+                 detected_contacts=(), plant=None, friction=None, disturbances=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
         ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model, ``sensors``: None or the rows of the
@@ -436,7 +478,7 @@ class KinodynamicPipeline(_QpContactSource):
         ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model, ``friction``: None or the rows of
         the ground friction (module docstring)."""
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
-                                                        contact_source)
+                                                        contact_source, disturbances=disturbances)
         plant = _checked_plant(plant, self.batch, problem_def)
         self._load(library, substeps, sim_dt)
         rb, m = problem_def.robot, self.model
@@ -485,7 +527,7 @@ class KinodynamicPipeline(_QpContactSource):
         periods one at a time with the small vectors travelling through the host (``low_level_step``: the readable form, what the library call is tested against).
         ``push``: (B, 3) world force at the base origin or (B, 6) (force, world point), armed on the simulator for the low-level steps of this period
         only (mpc_sim_set_push, HIP library; ``push_schedule``)."""
-        push = _push_array(push, self.batch)
+        push = self._checked_push(push)
         cs = self.contact_state()
         self._set_sim_contacts(cs)
         with self._pushed(push):
@@ -560,7 +602,7 @@ class CentroidalPipeline(_QpContactSource):
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
                  sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, sensors=None,
-                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, **ens_kw):
+                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
@@ -570,7 +612,7 @@ class CentroidalPipeline(_QpContactSource):
         ``friction``: None or the rows of the ground friction (module docstring)."""
         from .ensemble import ensemble_initial_states
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
-                                                        contact_source)
+                                                        contact_source, disturbances=disturbances)
         plant = _checked_plant(plant, self.batch, problem_def)
         self._load(library, substeps, sim_dt)
         rb, m = problem_def.robot, self.model
@@ -657,7 +699,7 @@ class CentroidalPipeline(_QpContactSource):
         the low-level periods one at a time with the small vectors travelling through the host (``low_level_step``: the readable form, what the
         library call is tested against).  ``push``: (B, 3) world force at the base origin or (B, 6) (force, world point), armed on the simulator for
         the low-level steps of this period only (mpc_sim_set_push, HIP library; ``push_schedule``)."""
-        push = _push_array(push, self.batch)
+        push = self._checked_push(push)
         e = self.mpc
         cs = self.contact_state()
         w = e._walk
@@ -710,14 +752,15 @@ class FullDynamicPipeline(_Pipeline):
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
-                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, **ens_kw):
+                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
         actuator model, ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state
         estimator, ``foot_sensors``: None or the rows of the foot force sensors, ``detected_contacts``: () or ("estimator",), ``plant``: None or the rows of the plant
         model, ``friction``: None or the rows of the ground friction (module docstring of pipeline.py)."""
-        walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts)
+        walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
+                                                        disturbances=disturbances)
         if ens_kw.get("closed_loop") is not None:
             raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
                              "EnsembleMPC(closed_loop=...) would simulate a second time)")
@@ -754,7 +797,7 @@ class FullDynamicPipeline(_Pipeline):
         travelling through the host (``low_level_step``: the readable form, what the library call is tested against).  ``push``: (B, 3) world force
         at the base origin or (B, 6) (force, world point), armed on the simulator for the low-level steps of this period only (mpc_sim_set_push,
         HIP library; ``push_schedule``)."""
-        push = _push_array(push, self.batch)
+        push = self._checked_push(push)
         cs = self.contact_state()
         self._set_sim_contacts(cs)
         with self._pushed(push):

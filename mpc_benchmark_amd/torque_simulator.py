@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _capi as K
 from . import actuator_model as _actuator_model
+from . import disturbance_model as _disturbance_model
 from . import foot_sensors as _foot_sensors
 from . import friction_model as _friction_model
 from . import plant_model as _plant_model
@@ -92,7 +93,7 @@ class SimulatorModels:
     The caller hands in what is its own: ``x``, the true states (B, nx) (or (nx,) for B = 1) as they stand, wherever a model arms at them or falls
     back to them, and ``q``, the configuration the defaults of the friction model are taken at (nothing here refers back to the caller).
     ``rows[name]`` is what model ``name`` was armed with, None while it is off; turning a model off touches the library only if it was on.  Refusals that name their caller (a model that needs the contact rule) are the caller's, before it calls here."""
-    NAMES = ("plant", "friction", "actuators", "sensors", "foot_sensors", "estimator")
+    NAMES = ("disturbances", "plant", "friction", "actuators", "sensors", "foot_sensors", "estimator")
 
     def __init__(self, sim, model, sole_frames, sim_dt):
         self.sim, self.model, self.batch = sim, model, sim.dims.batch
@@ -100,8 +101,11 @@ class SimulatorModels:
         self.rows = dict.fromkeys(self.NAMES)
         self.consumers = ()      # who works from the detected contacts (``foot_sensors.CONSUMERS``)
 
-    def arm(self, x, q, plant=None, friction=None, actuators=None, sensors=None, foot_sensors=None, estimator=None):
-        """Arm the models that are given, in the one order.  ``plant``, ``actuators`` and ``foot_sensors``: the argument tuples of their ``set_*``."""
+    def arm(self, x, q, plant=None, friction=None, actuators=None, sensors=None, foot_sensors=None, estimator=None, disturbances=None):
+        """Arm the models that are given, in the one order.  ``plant``, ``actuators`` and ``foot_sensors``: the argument tuples of their ``set_*``;
+        ``disturbances``: (events, contact_rule) of ``set_disturbances``."""
+        if disturbances is not None:
+            self.set_disturbances(*disturbances)
         if plant is not None:
             self.set_plant(*plant)
         if friction is not None:
@@ -119,6 +123,19 @@ class SimulatorModels:
         if self.rows[name] is not None:
             getattr(self.sim, name)(None)
         self.rows[name] = None
+
+    def set_disturbances(self, events, contact_rule=True):
+        """``events`` in the forms of ``NativeSolver.disturbances``; ``contact_rule``: is the contact rule on (contact triggers are refused without
+        it).  Checked before any library call; arms the schedule and resets its clock.  None: off."""
+        if events is None:
+            return self._turn_off("disturbances")
+        checked = _disturbance_model.validate(_disturbance_model.rows(events, self.batch), self.model.njoints - 1, contact_rule)
+        self.sim.disturbances(checked)
+        self.rows["disturbances"] = checked
+
+    def disturbance_state(self):
+        """the state rows of the push schedule by ``disturbance_model.unpack`` (``step``, ``acting``, ``impulse`` ...); None while it is off"""
+        return None if self.rows["disturbances"] is None else self.sim.read_disturbances()
 
     def set_plant(self, rows, link_scale=None):
         """``rows`` in the forms of ``NativeSolver.plant``, a dict may also carry ``link_scale``; checked before any library call.  None: off."""
