@@ -7,26 +7,17 @@
 #define CHOL16_RIGHT_LOOKING  // (mfma_blocks.h: the 16 x 16 inverse with independent updates — pays in this kernel's one-wavefront chain only)
 #include "eval_multibody.h"
 
-void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
-                           bool trial, int cand0, int ncand, int sim_substeps, double sim_dt, bool with_derivs, const double* f_ext, bool contact_dyn,
-                           const double* sim_u, double* sim_wrench, int f_ext_width, const double* sim_contacts, const double* sim_model,
-                           size_t sim_model_stride, const double* sim_friction, bool f_ext_linked) {
-  const Layout& L = a.L;
-  MbArgs mb;
+// The MbArgs of one launch with no simulator member set, and the LDS carve-out it needs granted to the generic instantiations
+static MbArgs mb_args(const Layout& L, double* scratch, size_t scratch_stride, bool contact_dyn, int dev) {
+  MbArgs mb = {};  // (every simulator member 0 or nullptr, no candidate loop)
   mb.lds = make_mb_lds(L.nj, L.n / 2, L.nx - L.n / 2, L.m, L.nz, contact_dyn);
   mb.scratch = scratch;
   mb.scratch_stride = scratch_stride;
-  mb.sim_substeps = sim_substeps; mb.sim_dt = sim_dt; mb.f_ext = f_ext; mb.f_ext_width = f_ext_width; mb.sim_u = sim_u; mb.sim_wrench = sim_wrench;
-  mb.sim_contacts = sim_contacts;
-  mb.sim_model = sim_model; mb.sim_model_stride = sim_model_stride;
-  mb.sim_friction = sim_friction;
-  mb.ncand_loop = (trial && !with_derivs && ncand > 1) ? ncand : 0;
+  mb.f_ext_width = 3;
   if (mb.lds.total_bytes > 160 * 1024) throw std::runtime_error("multibody model too large for the LDS budget of the stage kernel");
   // hipFuncSetAttribute is a per-device setting: remember what was requested on every device (a process may hold handles on several
   // devices, driven from different threads)
   static std::atomic<int> attr_bytes_dev[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
   std::atomic<int>& attr_bytes = attr_bytes_dev[dev & 63];
   if (attr_bytes.load() < mb.lds.total_bytes + 1) {  // (the largest request so far stays: the two carve-outs of a process differ)
     // the kernel also owns a few bytes of static LDS, so request exactly what the carve-out needs
@@ -38,12 +29,36 @@ void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout
     if (e1 != hipSuccess || e2 != hipSuccess) throw std::runtime_error(std::string("hipFuncSetAttribute(LDS) failed: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     attr_bytes.store(mb.lds.total_bytes + 1);  // + 1: the zero-initialised slots mean "not set"
   }
+  return mb;
+}
+
+void launch_sim_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
+                          const MbSimStep& step) {
+  const Layout& L = a.L;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  MbArgs mb = mb_args(L, scratch, scratch_stride, /*contact_dyn=*/true, dev);
+  mb.sim_substeps = step.substeps; mb.sim_dt = step.dt; mb.f_ext = step.push; mb.f_ext_width = step.width; mb.sim_u = step.torques; mb.sim_wrench = step.wrenches;
+  mb.sim_contacts = step.contact_rows;
+  mb.sim_model = step.model_tables; mb.sim_model_stride = step.model_stride;
+  mb.sim_friction = step.friction_rows;
+  if (step.linked) hipLaunchKernelGGL((k_eval_multibody<2, 0, 0, 0, true, true>), dim3(1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, 0);
+  else hipLaunchKernelGGL(k_eval_multibody<2>, dim3(1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, 0);
+}
+
+void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
+                           bool trial, int cand0, int ncand, bool with_derivs, bool contact_dyn) {
+  const Layout& L = a.L;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  MbArgs mb = mb_args(L, scratch, scratch_stride, contact_dyn, dev);
+  mb.ncand_loop = (trial && !with_derivs && ncand > 1) ? ncand : 0;
   // fixed-dimension instantiations (eval_multibody.h):  X(id, bodies, velocity dofs, controls, contact-constrained dynamics)
   //   1, 2: the complete Talos (33 bodies, 38 dofs), full-dynamics OCP (32 joint torques) and kinodynamic OCP (12 wrench components + 32 joint
   //   accelerations, no contact-dynamics blocks) ; 3, 4: the Talos with the upper body locked as the scripts lock it (23 bodies, 28 dofs)
 #define MB_FIXED_MODELS(X) X(1, 33, 38, 32, true) X(2, 33, 38, 44, false) X(3, 23, 28, 22, true) X(4, 23, 28, 34, false)
   int fixed = 0;
-  if (!getenv("MPC_HIP_GENERIC_DIMS") && sim_substeps <= 0) {
+  if (!getenv("MPC_HIP_GENERIC_DIMS")) {
 #define X(ID, FJ, FV, FU, FCD) if (L.nj == FJ && L.n == 2 * FV && L.nx == 2 * FV + 1 && L.m == FU && L.nz == 2 * FV + FU && contact_dyn == FCD) fixed = ID;
     MB_FIXED_MODELS(X)
 #undef X
@@ -73,9 +88,7 @@ void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout
 #undef X1
     return;
   }
-  if (sim_substeps > 0 && f_ext_linked) hipLaunchKernelGGL((k_eval_multibody<2, 0, 0, 0, true, true>), dim3(1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, 0);
-  else if (sim_substeps > 0) hipLaunchKernelGGL(k_eval_multibody<2>, dim3(1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, 0);
-  else if (trial && with_derivs) hipLaunchKernelGGL(k_eval_multibody<3>, dim3(L.N + 1 + (a.spec_knot ? 1 : 0), L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, L, records, mb, 0);  // records = the knot records (+ the speculative knot)
+  if (trial && with_derivs) hipLaunchKernelGGL(k_eval_multibody<3>, dim3(L.N + 1 + (a.spec_knot ? 1 : 0), L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, L, records, mb, 0);  // records = the knot records (+ the speculative knot)
   else if (!trial) hipLaunchKernelGGL(k_eval_multibody<0>, dim3(a.only_knot >= 0 ? 1 : L.N + 1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, L, records, mb, 0);
   else hipLaunchKernelGGL(k_eval_multibody<1>, dim3(L.N + 1, L.B, mb.ncand_loop > 0 ? 1 : ncand), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, cand0);
 }

@@ -125,7 +125,7 @@ struct MbArgs {
   double sim_dt;          // ... of this length
   const double* f_ext;    // TRIAL == 2: the push on the base per instance, or nullptr: f_ext_width 3: [B][3] world-frame force at the base origin
                           // (mpc_simulate_push) ; 6: [B][6] = (world-frame force, fixed world point it acts at) (include/mpc_sim_ext.h).
-                          // With f_ext_linked of launch_eval_multibody (the disturbance schedule, include/mpc_sim_disturbances.h; width 6): the
+                          // With MbSimStep::linked (the disturbance schedule, include/mpc_sim_disturbances.h; width 6): the
                           // per-robot body rides behind the rows, int32 link[B] at f_ext + 6 B (-1: nothing acts on that robot), and the LINKED
                           // instantiation of the simulator form applies the wrench on the dofs below that link.  Not a member of its own: MbArgs
                           // keeps its layout and cand0 its offset, so no other instantiation changes
@@ -144,10 +144,25 @@ struct MbArgs {
 static_assert(sizeof(MbLds) % 8 == 4 && sizeof(MbArgs) == sizeof(MbLds) + 4 + 11 * 8, "MbArgs: f_ext_width fills the padding after lds");
 
 
-// defined in eval_multibody.hip
+// One call of the simulator form of the stage kernel (TRIAL == 2): what the MbArgs members of the same names take (above)
+struct MbSimStep {
+  int substeps = 0;                      // integration steps ...
+  double dt = 0.0;                       // ... of this length
+  const double* push = nullptr;          // f_ext, of `width` doubles per robot
+  int width = 3;
+  bool linked = false;                   // int32 link[B] rides behind the push rows: the LINKED instantiation
+  const double* torques = nullptr;       // sim_u
+  double* wrenches = nullptr;            // sim_wrench
+  const double* contact_rows = nullptr;  // sim_contacts
+  const double* model_tables = nullptr;  // sim_model ...
+  size_t model_stride = 0;               // ... and sim_model_stride
+  const double* friction_rows = nullptr; // sim_friction
+};
+
+// defined in eval_multibody.hip: the solver's forms of the stage kernel (the knot records, the trial candidates cand0 .. cand0 + ncand - 1, the
+// trial with derivatives), and the simulator form
 void launch_eval_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
-                           bool trial, int cand0 = 0, int ncand = 1, int sim_substeps = 0, double sim_dt = 0.0, bool with_derivs = false,
-                           const double* f_ext = nullptr, bool contact_dyn = true, const double* sim_u = nullptr, double* sim_wrench = nullptr,
-                           int f_ext_width = 3, const double* sim_contacts = nullptr, const double* sim_model = nullptr, size_t sim_model_stride = 0,
-                           const double* sim_friction = nullptr, bool f_ext_linked = false);
+                           bool trial, int cand0, int ncand, bool with_derivs, bool contact_dyn);
+void launch_sim_multibody(hipStream_t stream, const SolverArgs& a, const Layout& LT, double* records, double* scratch, size_t scratch_stride,
+                          const MbSimStep& step);
 const void* eval_multibody_kernel(int trial);  // entry point of k_eval_multibody<trial> (occupancy tooling)

@@ -73,8 +73,21 @@ static void lds_attr_max(const void* fn, int bytes) {
 // (28 dofs), full dynamics   4: the same, kinodynamic.  The stage kernel has its own list (eval_multibody.hip).
 #define MPC_FIXED_MODELS(X) X(1, 76, 32, 1, 1, 80, 32) X(2, 76, 44, 3, 0, 80, 48) X(3, 56, 22, 3, 1, 64, 32) X(4, 56, 34, 3, 1, 64, 48)
 
+// One model of the plant: its device allocation (nullptr: the model is off) and the host mirror of what the caller gave, as it is in force
+struct SimModel {
+  const char* const off;    // what an entry point answers while the model is off
+  const bool needs_rule;    // the model reads the rows of the contact rule: armed only while the rule is on, dropped when the rule goes
+  double* d = nullptr;
+  std::vector<double> h;
+  SimModel(const char* off_, bool needs_rule_) : off(off_), needs_rule(needs_rule_) {}
+  bool on() const { return d != nullptr; }
+  void drop() { if (d) { (void)hipFree(d); d = nullptr; } h.clear(); }
+};
+
 // The plant: state of the torque-driven simulator steps (mpc_simulate_torque and the device loops of the three pipelines; host code: sim_host.h)
 struct SimPlant {
+  SimPlant() = default;
+  SimPlant(const SimPlant&) = delete;  // (models points into this object)
   double* d_simu = nullptr;  // [B][nu] torques, [B][12] wrenches of mpc_simulate_torque
   double* d_simwr = nullptr;
   double* d_xlast = nullptr;  // [B][nx] the states before the last period of mpc_feedback_low_level_steps
@@ -89,45 +102,36 @@ struct SimPlant {
   // include/mpc_sim_contacts.h: the rows of the contact rule (nullptr: rule off, stage 0 decides the contacts), [B][W]
   double* d_con = nullptr;
   mpc_sim_contacts_config con_cfg = {};
-  // include/mpc_sim_terrain.h: the boxes under the contact rule (nullptr: the plane; also with zero boxes), [n] or [B][n] boxes; h_ter as they were given
-  double* d_ter = nullptr;
+  // The models the steps run through, each with one device allocation (layout: the model's sim_*_layout in sim_host.h) and, beside the owner, what
+  // only that model keeps.  include/mpc_sim_terrain.h: the boxes under the contact rule (off: the plane; also with zero boxes); h as they were given
+  SimModel ter{nullptr, true};  // (no entry point refuses a handle without boxes)
   mpc_sim_terrain_config ter_cfg = {};
-  std::vector<double> h_ter;
-  // include/mpc_sim_actuators.h: the actuator model (nullptr: off), one allocation: params [B][8] | limit [nu] | friction shape [nu] | state rows [B][18 nu + 2]
-  double* d_act = nullptr;
-  std::vector<double> h_act;  // params | limit | shape as they are in force
-  // include/mpc_sim_sensors.h: the sensor model (nullptr: off), one allocation: params [B][16] | the measurement the controllers read [B][nx] | staging of
-  // the states to arm on [B][nx] | state rows [B][17 nx + 2 nu + 2]
-  double* d_sen = nullptr;
-  std::vector<double> h_sen;  // params as they are in force
-  // include/mpc_sim_estimator.h: the base-state estimator (nullptr: off), one allocation: params [B][16] | the estimate the controllers read [B][nx] |
-  // staging of the states to arm on [B][nx] | state rows [B][nx + 17]
-  double* d_est = nullptr;
-  std::vector<double> h_est;  // params as they are in force
-  // include/mpc_sim_foot_sensors.h: the foot force sensors and the contact detector (nullptr: off), one allocation: params [B][16] | state rows [B][232];
-  // fs_feed: who works from the detected pair (the MPC_SIM_FOOT_SENSORS_FEED_* bits)
-  double* d_fs = nullptr;
-  std::vector<double> h_fs;  // params as they are in force
+  // include/mpc_sim_actuators.h ; h: params | limit | shape
+  SimModel act{"the actuator model is off on this handle (turn it on with mpc_sim_actuators)", false};
+  // include/mpc_sim_sensors.h (off: the controllers read the true state) ; h: params
+  SimModel sen{"the sensor model is off on this handle (turn it on with mpc_sim_sensors)", false};
+  // include/mpc_sim_estimator.h: the base-state estimator ; h: params
+  SimModel est{"the estimator is off on this handle (turn it on with mpc_sim_estimator)", true};
+  // include/mpc_sim_foot_sensors.h: the foot force sensors and the contact detector ; h: params ; fs_feed: who works from the detected pair (the
+  // MPC_SIM_FOOT_SENSORS_FEED_* bits)
+  SimModel fs{"the foot sensors are off on this handle (turn them on with mpc_sim_foot_sensors)", true};
   int fs_feed = 0;
-  // include/mpc_sim_plant.h: the per-robot plant inertias (nullptr: off, every robot is integrated with the handle's one table), one allocation:
-  // params [B][16] | link_scale [B][nj] | tables [B][plant_nd]
-  double* d_plant = nullptr;
-  std::vector<double> h_plant;  // params | link_scale (ones when none was given) as they are in force
-  size_t plant_nd = 0;          // doubles of one robot's table: the handle's model_nd when the tables were built
-  size_t plant_off = 0;         // doubles before the tables: B (16 + nj) with the joint count the rows were armed on
-  // include/mpc_sim_friction.h: the per-robot ground friction (nullptr: off, every held sole is held to rest), one allocation: params [B][8] | state
-  // rows [B][17]
-  double* d_fr = nullptr;
-  std::vector<double> h_fr;  // params as they are in force
-  // include/mpc_sim_disturbances.h: the per-robot push schedule (nullptr: off), one allocation: events [B][dis_ne][16] | state rows [B][32] | what
-  // acts in the step [B][6] | its link, int32 [B] (the dynamics read the last two in place of d_push)
-  double* d_dis = nullptr;
-  std::vector<double> h_dis;  // events as they are in force
+  // include/mpc_sim_plant.h: the per-robot plant inertias (off: every robot is integrated with the handle's one table) ; h: params | link_scale (ones
+  // when none was given)
+  SimModel pm{"the plant model is off on this handle (turn it on with mpc_sim_plant)", false};
+  size_t plant_nd = 0;   // doubles of one robot's table: the handle's model_nd when the tables were built
+  size_t plant_off = 0;  // doubles before the tables, with the joint count the rows were armed on
+  // include/mpc_sim_friction.h: the per-robot ground friction (off: every held sole is held to rest) ; h: params
+  SimModel fr{"the friction model is off on this handle (turn it on with mpc_sim_friction)", true};
+  // include/mpc_sim_disturbances.h: the per-robot push schedule (the dynamics read what it writes in place of d_push) ; h: events
+  SimModel dis{"the disturbance schedule is off on this handle (turn it on with mpc_sim_disturbances)", false};
   int dis_ne = 0;
-  bool dis_contact = false;   // an event of the table has a contact trigger: the table goes with the contact rule
+  bool dis_contact = false;  // an event of the table has a contact trigger: the table goes with the contact rule
+  SimModel* const models[8] = {&act, &sen, &pm, &ter, &fr, &est, &fs, &dis};
   // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
   void free_owned() {
-    for (double** p : {&d_rec, &d_met, &d_con, &d_ter, &d_act, &d_sen, &d_est, &d_fs, &d_plant, &d_fr, &d_dis}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (double** p : {&d_rec, &d_met, &d_con}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (SimModel* m : models) m->drop();
   }
 };
 
@@ -755,7 +759,7 @@ static void launch_eval(mpc_solver* s, bool trial, int cand0 = 0, int ncand = 1,
     if (!trial) hipLaunchKernelGGL(k_eval_vector<0>, dim3(a.only_knot >= 0 ? 1 : L.N + 1, L.B, 1), dim3(64), 0, s->stream, a, s->L, s->d_knots, 0);
     else hipLaunchKernelGGL(k_eval_vector<1>, dim3(L.N + 1, L.B, ncand), dim3(64), 0, s->stream, a, s->LT, s->d_tknots, cand0);
   } else {
-    launch_eval_multibody(s->stream, a, s->LT, (trial && !with_derivs) ? s->d_tknots : s->d_knots, s->d_mbwork, s->mb_work_stride, trial, cand0, ncand, 0, 0.0, with_derivs, nullptr, s->contact_dyn);
+    launch_eval_multibody(s->stream, a, s->LT, (trial && !with_derivs) ? s->d_tknots : s->d_knots, s->d_mbwork, s->mb_work_stride, trial, cand0, ncand, with_derivs, s->contact_dyn);
   }
   HIP_OK(hipGetLastError());
 }
@@ -1093,10 +1097,10 @@ int mpc_set_model(mpc_solver* s, const int32_t* itab, int32_t n_i, const double*
     if (n_i < MPC_MODEL_HEADER_WORDS + MPC_MODEL_JOINT_WORDS * nj + nf + ncn ||
         n_d < MPC_MODEL_HEADER_DOUBLES + MPC_MODEL_JOINT_DOUBLES * nj + MPC_MODEL_FRAME_DOUBLES * nf + MPC_MODEL_CONTACT_DOUBLES * ncn)
       throw std::runtime_error("model table size mismatch");
-    if (s->plant.d_plant && nj != s->L.nj)  // (before anything changes: the rows in force name joints of the model they were armed on)
+    if (s->plant.pm.on() && nj != s->L.nj)  // (before anything changes: the rows in force name joints of the model they were armed on)
       throw std::runtime_error("set_model: the plant model is on (mpc_sim_plant) and its rows were armed on a model of " + std::to_string(s->L.nj) +
                                " joints; this one has " + std::to_string(nj) + ": turn the plant model off first");
-    if (s->plant.d_dis && nj != s->L.nj)  // (the same for the links of the disturbance schedule, include/mpc_sim_disturbances.h)
+    if (s->plant.dis.on() && nj != s->L.nj)  // (the same for the links of the disturbance schedule, include/mpc_sim_disturbances.h)
       throw std::runtime_error("set_model: the disturbance schedule is on (mpc_sim_disturbances) and its links were checked against a model of " +
                                std::to_string(s->L.nj) + " joints; this one has " + std::to_string(nj) + ": turn the schedule off first");
     if (s->dims.space == MPC_SPACE_MULTIBODY) {  // (every check of the tables before anything changes: a refused model leaves the one in force, and the
@@ -1471,7 +1475,9 @@ static void simulate_impl(mpc_solver* s, int32_t substeps, double dt, const doub
     copy_sync(s, s->d_fext, f_ext, (size_t)s->L.B * 3 * sizeof(double), hipMemcpyHostToDevice);
     d_f = s->d_fext;
   }
-  launch_eval_multibody(s->stream, s->args(), s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, d_f);
+  MbSimStep step;
+  step.substeps = substeps; step.dt = dt; step.push = d_f;
+  launch_sim_multibody(s->stream, s->args(), s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, step);
   HIP_OK(hipGetLastError());
   s->perfect_feedback = false;
 }

@@ -1,8 +1,8 @@
-// sim_host.h — host side of the torque-driven simulator (the plant): mpc_simulate_torque and the entry points of include/mpc_sim_ext.h (push, record),
-// mpc_sim_metrics.h, mpc_sim_contacts.h, mpc_sim_terrain.h, mpc_sim_actuators.h, mpc_sim_sensors.h, mpc_sim_estimator.h, mpc_sim_foot_sensors.h, mpc_sim_plant.h, mpc_sim_friction.h and mpc_sim_disturbances.h.  Its state is mpc_solver::plant (SimPlant); its kernels
-// are in sim_record.h, sim_metrics.h, sim_contacts.h, sim_terrain.h, sim_actuators.h, sim_sensors.h, sim_estimator.h, sim_foot_sensors.h, sim_plant.h, sim_friction.h and sim_disturbances.h.  Every caller that steps the plant — mpc_simulate_torque here, the device
-// loops of the three pipelines in pipeline_loops.h — goes through sim_steps_check, sim_steps_begin and sim_step_enqueue: an extension of the simulator
-// is added there, once.  Included at the end of mpc_hip.hip (mpc_solver, MPC_TRY, copy_sync, slot_of).
+// sim_host.h — host side of the torque-driven simulator (the plant): mpc_simulate_torque and the entry points of include/mpc_sim_*.h.  Its state is
+// mpc_solver::plant (SimPlant: one SimModel owner per model); its kernels are in the sim_*.h of the same names.  Every caller that steps the plant —
+// mpc_simulate_torque here, the device loops of the three pipelines in pipeline_loops.h — goes through sim_steps_check, sim_steps_begin and
+// sim_step_enqueue: an extension of the simulator is added there, once, with one layout function and its row checks from the helpers below.
+// Included at the end of mpc_hip.hip (mpc_solver, MPC_TRY, copy_sync, slot_of).
 #pragma once
 
 // Which handles an entry point takes.  Every simulator handle is a whole-body handle; SIM_NU: with nu = nv - 6 (the handle of mpc_simulate_torque) ;
@@ -37,6 +37,16 @@ static void sim_realloc(mpc_solver* s, double*& buf, size_t count) {
   if (buf) { HIP_OK(hipFree(buf)); buf = nullptr; }
   if (count) { void* p = nullptr; HIP_OK(hipMalloc(&p, count * sizeof(double))); buf = (double*)p; }
 }
+// a model goes off: its allocation, its mirror and what the plant keeps beside the owner
+static void sim_drop(mpc_solver* s, SimModel& m) {
+  SimPlant& p = s->plant;
+  sim_realloc(s, m.d, 0);
+  m.h.clear();
+  if (&m == &p.ter) p.ter_cfg = {};
+  if (&m == &p.fs) p.fs_feed = 0;
+  if (&m == &p.pm) p.plant_nd = p.plant_off = 0;
+  if (&m == &p.dis) { p.dis_ne = 0; p.dis_contact = false; }
+}
 // the *_width entry points: the width on a simulator handle, -1 otherwise
 template <class F> static int32_t sim_width(mpc_solver* s, const char* who, F&& width) {
   if (!s) return -1;
@@ -49,51 +59,197 @@ template <class F> static int32_t sim_width(mpc_solver* s, const char* who, F&& 
   }
 }
 
+// ---- refusals: every wording is built here, once ---------------------------------------------------------------------------------------------------
+static void sim_on_check(const SimModel& m, const char* who) {
+  if (!m.on()) throw std::runtime_error(std::string(who) + ": " + m.off);
+}
+// the contact rule is on: for what reads its rows (`first`: an arming call, which names the order of the two)
+static void sim_rule_check(const mpc_solver* s, const char* who, bool first = true) {
+  if (!s->plant.d_con)
+    throw std::runtime_error(std::string(who) + ": the contact rule is off on this handle (turn it on with mpc_sim_contacts" + (first ? " first)" : ")"));
+}
+// The caller's rows [B][W], one after the other: every entry of a row finite, then the model's own rules of that row, rest(row, r, b), where `row` opens
+// the message ("who: row b") and r is the row.  The helpers below are what those rules are written with
+template <class F> static void sim_check_rows(const char* who, const double* rows, int B, size_t W, F&& rest) {
+  for (int b = 0; b < B; ++b) {
+    const double* r = rows + (size_t)b * W;
+    const std::string row = std::string(who) + ": row " + std::to_string(b);
+    for (size_t e = 0; e < W; ++e)
+      if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+    rest(row, r, b);
+  }
+}
+static bool sim_is_index(double v, double n) { return v == std::floor(v) && v >= 0.0 && v < n; }
+// v is one of the integers 0 .. n - 1; `bound` is the upper end as the message prints it ("7]", "2^32)")
+static void sim_int_check(const std::string& row, const char* what, double v, double n, const std::string& bound) {
+  if (!sim_is_index(v, n)) throw std::runtime_error(row + ": " + what + " must be an integer value in [0, " + bound);
+}
+static void sim_flags_check(const std::string& row, const char* what, const double* r, int n) {
+  for (int e = 0; e < n; ++e)
+    if (r[e] != 0.0 && r[e] != 1.0) throw std::runtime_error(row + ": " + what + " must be 0 or 1");
+}
+static void sim_nonneg_check(const std::string& row, const char* what, const double* r, int n) {
+  for (int e = 0; e < n; ++e)
+    if (r[e] < 0.0) throw std::runtime_error(row + ": " + what + " must be >= 0");
+}
+static void sim_nonneg_check(const std::string& row, const char* what, const double* r, std::initializer_list<int> entries) {
+  for (int e : entries) sim_nonneg_check(row, what, r + e, 1);
+}
+static void sim_reserved_check(const std::string& row, const double* r, int lo, int hi) {
+  for (int e = lo; e < hi; ++e)
+    if (r[e] != 0.0) throw std::runtime_error(row + ": the reserved entries must be 0");
+}
+// the last entry of a state row counts the events so far; `held`: why a model that always holds something starts at 1
+static void sim_count_check(const std::string& row, double count, int min, const char* held = nullptr) {
+  if (count < min) throw std::runtime_error(row + ": count must be >= " + std::to_string(min) + (held ? std::string(" (") + held + ")" : std::string()));
+}
+// the last two entries of a state row with a ring of `ring` slots: head, count
+static void sim_ring_check(const std::string& row, const double* r, size_t W, int ring, int min_count, const char* held = nullptr) {
+  sim_int_check(row, "head", r[W - 2], ring, std::to_string(ring) + ")");
+  sim_count_check(row, r[W - 1], min_count, held);
+}
+// the states [B][nx] a model is armed on; `why`: what the model does with them
+static void sim_x0_check(const mpc_solver* s, const char* who, const double* x0, const char* why) {
+  if (!x0) throw std::runtime_error(std::string(who) + ": x0 must not be null (" + why + ")");
+  for (size_t e = 0; e < (size_t)s->L.B * s->L.nx; ++e)
+    if (!std::isfinite(x0[e])) throw std::runtime_error(std::string(who) + ": x0 holds a non-finite entry");
+}
+
+// ---- layouts ------------------------------------------------------------------------------------------------------------------------------------------
+// Where the parts of a model's one allocation start, in doubles from SimModel::d.  The params (the schedule: the events) come first, at 0; a model fills
+// the parts it has, its layout function says which
+struct SimLayout {
+  size_t np = 0;                  // doubles of the params: what follows them starts here
+  size_t tables = 0, tables_b = 0;  // what all the rows share, or the caller's second array
+  size_t out = 0;                 // what the model hands on (the consumers read it in place)
+  size_t stage = 0;               // staging of the states to arm on
+  size_t rows = 0, width = 0;     // the state rows [B][width]
+  size_t tail = 0;                // what follows `out`
+  size_t total = 0;
+};
+// params [B][P] | state rows [B][W]: the foot sensors and the contact detector (P 16, W 232), the friction model (P 8, W 17)
+static SimLayout sim_rows_layout(const Layout& L, size_t P, size_t W) {
+  SimLayout l;
+  l.np = l.rows = (size_t)L.B * P;
+  l.width = W;
+  l.total = l.rows + (size_t)L.B * W;
+  return l;
+}
+static SimLayout sim_foot_sensors_layout(const Layout& L) { return sim_rows_layout(L, MPC_SIM_FOOT_SENSORS_PARAMS, MPC_SIM_FOOT_SENSORS_WIDTH); }
+static SimLayout sim_friction_layout(const Layout& L) { return sim_rows_layout(L, MPC_SIM_FRICTION_PARAMS, MPC_SIM_FRICTION_WIDTH); }
+// the actuator model: params [B][8] | tables: limit [nu] | tables_b: friction shape [nu] | state rows [B][18 nu + 2].  The mirror holds all before the rows
+static SimLayout sim_actuators_layout(const Layout& L) {
+  SimLayout l;
+  l.np = l.tables = (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS;
+  l.tables_b = l.tables + L.m;
+  l.rows = l.tables_b + L.m;
+  l.width = (size_t)(MPC_SIM_ACTUATORS_RING + 2) * L.m + 2;
+  l.total = l.rows + (size_t)L.B * l.width;
+  return l;
+}
+// the two models between the plant and the controllers: params [B][P] | out: what the controllers read [B][nx] | stage [B][nx] | state rows [B][W]
+static SimLayout sim_filter_layout(const Layout& L, size_t P, size_t W) {
+  SimLayout l;
+  l.np = l.out = (size_t)L.B * P;
+  l.stage = l.out + (size_t)L.B * L.nx;
+  l.rows = l.stage + (size_t)L.B * L.nx;
+  l.width = W;
+  l.total = l.rows + (size_t)L.B * W;
+  return l;
+}
+// the sensor model: P 16, out: the measurement, W 17 nx + 2 nu + 2 ; the base-state estimator: P 16, out: the estimate, W nx + 17
+static SimLayout sim_sensors_layout(const Layout& L) {
+  return sim_filter_layout(L, MPC_SIM_SENSORS_PARAMS, (size_t)(MPC_SIM_SENSORS_RING + 1) * L.nx + 2 * (size_t)L.m + 2);
+}
+static SimLayout sim_estimator_layout(const Layout& L) { return sim_filter_layout(L, MPC_SIM_ESTIMATOR_PARAMS, (size_t)L.nx + MPC_SIM_ESTIMATOR_TAIL); }
+// the plant model: params [B][16] | tables: link_scale [B][nj] | out: the model tables [B][nd], built on the device.  The mirror holds all before `out`;
+// SimPlant::plant_off keeps `out` and plant_nd keeps nd for the steps
+static SimLayout sim_plant_layout(const Layout& L, size_t nd) {
+  SimLayout l;
+  l.np = l.tables = (size_t)L.B * MPC_SIM_PLANT_PARAMS;
+  l.out = l.tables + (size_t)L.B * L.nj;
+  l.total = l.out + (size_t)L.B * nd;
+  return l;
+}
+// the disturbance schedule: events [B][ne][16] | state rows [B][32] | out: what acts in the step [B][6] | tail: its link, int32 [B]
+static SimLayout sim_disturbances_layout(const Layout& L, int ne) {
+  SimLayout l;
+  l.np = l.rows = (size_t)L.B * ne * MPC_SIM_DISTURBANCES_EVENT;
+  l.width = MPC_SIM_DISTURBANCES_WIDTH;
+  l.out = l.rows + (size_t)L.B * l.width;
+  l.tail = l.out + (size_t)L.B * 6;
+  l.total = l.tail + ((size_t)L.B + 1) / 2;
+  return l;
+}
+
+// ---- what *_read and *_set share --------------------------------------------------------------------------------------------------------------------
+// *_read: the params from the mirror, then, the stream drained, the state rows and what the model hands on from the device
+static void sim_model_read(mpc_solver* s, const char* who, const SimModel& m, const SimLayout& l, double* params, double* state, double* out = nullptr) {
+  sim_check(s, who);
+  sim_on_check(m, who);
+  if (params) std::copy(m.h.begin(), m.h.begin() + l.np, params);
+  HIP_OK(hipStreamSynchronize(s->stream));
+  if (state) copy_sync(s, state, m.d + l.rows, (size_t)s->L.B * l.width * sizeof(double), hipMemcpyDeviceToHost);
+  if (out) copy_sync(s, out, m.d + l.out, (size_t)s->L.B * s->L.nx * sizeof(double), hipMemcpyDeviceToHost);
+}
+// *_set: the state rows are replaced by the caller's.  The checks (state, the handle, the model on, then row by row: finite, `rest`), the stream
+// drained, the upload.  slice >= 0 (the sensor model, the estimator): entries slice .. slice + nx - 1 of every row are what the controllers read, and
+// go to `out`
+template <class F> static void sim_rows_set(mpc_solver* s, const char* who, SimModel& m, const SimLayout& l, const double* state, long slice, F&& rest) {
+  const Layout& L = s->L;
+  if (!state) throw std::runtime_error(std::string(who) + ": state must not be null");
+  sim_check(s, who);
+  sim_on_check(m, who);
+  sim_check_rows(who, state, L.B, l.width, rest);
+  std::vector<double> out;
+  if (slice >= 0)
+    for (int b = 0; b < L.B; ++b) out.insert(out.end(), state + b * l.width + slice, state + b * l.width + slice + L.nx);
+  HIP_OK(hipStreamSynchronize(s->stream));
+  copy_sync(s, m.d + l.rows, state, (size_t)L.B * l.width * sizeof(double), hipMemcpyHostToDevice);
+  if (slice >= 0) copy_sync(s, m.d + l.out, out.data(), out.size() * sizeof(double), hipMemcpyHostToDevice);
+}
+
+// ---- the stages of a step ---------------------------------------------------------------------------------------------------------------------------
 // the model tables the plant is integrated and recorded with (include/mpc_sim_plant.h): robot b's own table at sim_plant_md + b * sim_plant_stride
 // while the plant model is on, the handle's one table (stride 0) otherwise.  Everything else keeps s->d_model_d, the controllers' belief
-static double* sim_plant_tables(const mpc_solver* s) { return s->plant.d_plant + s->plant.plant_off; }
-static const double* sim_plant_md(const mpc_solver* s) { return s->plant.d_plant ? sim_plant_tables(s) : s->d_model_d; }
-static size_t sim_plant_stride(const mpc_solver* s) { return s->plant.d_plant ? s->plant.plant_nd : 0; }
+static double* sim_plant_tables(const mpc_solver* s) { return s->plant.pm.d + s->plant.plant_off; }
+static const double* sim_plant_md(const mpc_solver* s) { return s->plant.pm.on() ? sim_plant_tables(s) : s->d_model_d; }
+static size_t sim_plant_stride(const mpc_solver* s) { return s->plant.pm.on() ? s->plant.plant_nd : 0; }
 
-// the disturbance schedule (include/mpc_sim_disturbances.h), one allocation: events | state rows | what acts in the step [B][6] | its link int32 [B]
-static double* sim_disturbances_rows(const mpc_solver* s) { return s->plant.d_dis + (size_t)s->L.B * s->plant.dis_ne * MPC_SIM_DISTURBANCES_EVENT; }
-static double* sim_disturbances_out(const mpc_solver* s) { return sim_disturbances_rows(s) + (size_t)s->L.B * MPC_SIM_DISTURBANCES_WIDTH; }
-static size_t sim_disturbances_doubles(const Layout& L, int ne) {
-  return (size_t)L.B * ((size_t)ne * MPC_SIM_DISTURBANCES_EVENT + MPC_SIM_DISTURBANCES_WIDTH + 6) + ((size_t)L.B + 1) / 2;
+static SimLayout sim_disturbances_layout(const mpc_solver* s) { return sim_disturbances_layout(s->L, s->plant.dis_ne); }
+// the push of a step and its width: what the schedule wrote when it is on, the armed push otherwise (the two exclude each other: mpc_sim_set_push)
+static const double* sim_push(const mpc_solver* s) {
+  const SimPlant& p = s->plant;
+  return p.dis.on() ? p.dis.d + sim_disturbances_layout(s).out : (p.push_width ? p.d_push : nullptr);
 }
 // the schedule's event of the step of length dt_step about to be enqueued on stream st (sim_disturbances.h), when the model is on: it reads the state
 // the step starts from and the rows the contact rule left after the step before
 static void sim_disturbances_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
   const SimPlant& p = s->plant;
-  if (!p.d_dis) return;
+  if (!p.dis.on()) return;
   const Layout& L = s->L;
+  const SimLayout l = sim_disturbances_layout(s);
   SimDisturbancesArgs a;
   a.mi = s->d_model_i; a.md = s->d_model_d; a.nv = L.n / 2; a.nq = L.nx - L.n / 2;
-  a.x = s->d_x0; a.con = p.d_con; a.events = p.d_dis; a.n_events = p.dis_ne;
-  a.rows = sim_disturbances_rows(s); a.out = sim_disturbances_out(s); a.link = (int32_t*)(a.out + (size_t)L.B * 6); a.dt = dt_step;
+  a.x = s->d_x0; a.con = p.d_con; a.events = p.dis.d; a.n_events = p.dis_ne;
+  a.rows = p.dis.d + l.rows; a.out = p.dis.d + l.out; a.link = (int32_t*)(p.dis.d + l.tail); a.dt = dt_step;
   hipLaunchKernelGGL(k_sim_disturbances, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
 }
 // the state rows, what acts and its link after arming or a reset: clock 0, nothing counted, nothing fired, no pair seen, nothing acting
 static void sim_disturbances_reset(mpc_solver* s) {
   const Layout& L = s->L;
-  const size_t head = (size_t)L.B * s->plant.dis_ne * MPC_SIM_DISTURBANCES_EVENT, count = sim_disturbances_doubles(L, s->plant.dis_ne) - head;
-  std::vector<double> h(count, 0.0);
+  const SimLayout l = sim_disturbances_layout(s);
+  std::vector<double> h(l.total - l.rows, 0.0);
   for (int b = 0; b < L.B; ++b) {
-    double* r = h.data() + (size_t)b * MPC_SIM_DISTURBANCES_WIDTH;
+    double* r = h.data() + (size_t)b * l.width;
     r[SIM_DIS_O_ACTING] = r[SIM_DIS_O_LINK] = r[SIM_DIS_O_SEEN] = r[SIM_DIS_O_SEEN + 1] = -1.0;
     for (int e = 0; e < MPC_SIM_DISTURBANCES_MAX_EVENTS; ++e) r[SIM_DIS_O_FIRE + e] = -1.0;
   }
-  int32_t* link = (int32_t*)(h.data() + (size_t)L.B * (MPC_SIM_DISTURBANCES_WIDTH + 6));
+  int32_t* link = (int32_t*)(h.data() + (l.tail - l.rows));
   for (int b = 0; b < L.B; ++b) link[b] = -1;
   HIP_OK(hipStreamSynchronize(s->stream));
-  copy_sync(s, sim_disturbances_rows(s), h.data(), count * sizeof(double), hipMemcpyHostToDevice);
-}
-static void sim_disturbances_drop(mpc_solver* s) {
-  sim_realloc(s, s->plant.d_dis, 0);
-  s->plant.h_dis.clear();
-  s->plant.dis_ne = 0;
-  s->plant.dis_contact = false;
+  copy_sync(s, s->plant.dis.d + l.rows, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
 }
 
 // the record of the step just enqueued on stream st (sim_record.h), when recording is on
@@ -103,7 +259,7 @@ static void sim_record_enqueue(mpc_solver* s, hipStream_t st) {
   const Layout& L = s->L;
   SimRecordArgs r;
   r.mi = s->d_model_i; r.md = sim_plant_md(s); r.md_stride = sim_plant_stride(s); r.nv = L.n / 2; r.nq = L.nx - L.n / 2;
-  r.x = s->d_x0; r.tau = p.d_simu; r.wr = p.d_simwr; r.push = p.d_dis ? sim_disturbances_out(s) : (p.push_width ? p.d_push : nullptr); r.push_width = p.d_dis ? 6 : p.push_width;  // (the schedule: what acted)
+  r.x = s->d_x0; r.tau = p.d_simu; r.wr = p.d_simwr; r.push = sim_push(s); r.push_width = p.dis.on() ? 6 : p.push_width;  // (the schedule: what acted)
   r.out = p.d_rec + (size_t)p.rec_count * L.B * sim_record_width(L.nx, L.m);
   hipLaunchKernelGGL(k_sim_record, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, r);
   HIP_OK(hipGetLastError());
@@ -113,12 +269,13 @@ static void sim_record_enqueue(mpc_solver* s, hipStream_t st) {
 static SimTerrain sim_terrain_args(const mpc_solver* s) {
   const SimPlant& p = s->plant;
   SimTerrain t;
-  t.boxes = p.d_con ? p.d_ter : nullptr;
+  t.boxes = p.d_con ? p.ter.d : nullptr;
   t.n = p.ter_cfg.n_boxes;
   t.stride = p.ter_cfg.per_robot ? p.ter_cfg.n_boxes * MPC_SIM_TERRAIN_BOX_WIDTH : 0;
   return t;
 }
-// the metrics of the step of length dt just enqueued on stream st (sim_metrics.h), when they are on
+// the metrics of the step of length dt just enqueued on stream st (sim_metrics.h), when they are on.  One allocation: rows [B][W] | frozen flags [B] |
+// the state the next step starts from [B][nx]
 static void sim_metrics_enqueue(mpc_solver* s, hipStream_t st, double dt) {
   const SimPlant& p = s->plant;
   if (!p.d_met) return;
@@ -176,68 +333,59 @@ static void sim_contacts_reset(mpc_solver* s) {
   copy_sync(s, s->plant.d_con, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
 }
 
-static size_t sim_actuators_width(const Layout& L) { return (size_t)(MPC_SIM_ACTUATORS_RING + 2) * L.m + 2; }
-static double* sim_actuators_rows(const mpc_solver* s) { return s->plant.d_act + (size_t)s->L.B * MPC_SIM_ACTUATORS_PARAMS + 2 * (size_t)s->L.m; }
 // the actuator model of the step of length dt_step about to be enqueued on stream st (sim_actuators.h), when it is on
 static void sim_actuators_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
   const SimPlant& p = s->plant;
-  if (!p.d_act) return;
+  if (!p.act.on()) return;
   const Layout& L = s->L;
+  const SimLayout l = sim_actuators_layout(L);
   SimActuatorsArgs a;
   a.nv = L.n / 2; a.nq = L.nx - L.n / 2; a.nu = L.m;
   a.x = s->d_x0; a.tau = p.d_simu;
-  a.params = p.d_act; a.limit = p.d_act + (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS; a.shape = a.limit + L.m;
-  a.rows = sim_actuators_rows(s); a.dt = dt_step;
+  a.params = p.act.d; a.limit = p.act.d + l.tables; a.shape = p.act.d + l.tables_b;
+  a.rows = p.act.d + l.rows; a.dt = dt_step;
   hipLaunchKernelGGL(k_sim_actuators, dim3((unsigned)L.B), dim3(SIM_ACT_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
 }
 
-static size_t sim_sensors_width(const Layout& L) { return (size_t)(MPC_SIM_SENSORS_RING + 1) * L.nx + 2 * (size_t)L.m + 2; }
-static double* sim_sensors_meas(const mpc_solver* s) { return s->plant.d_sen + (size_t)s->L.B * MPC_SIM_SENSORS_PARAMS; }
-static double* sim_sensors_stage(const mpc_solver* s) { return sim_sensors_meas(s) + (size_t)s->L.B * s->L.nx; }
-static double* sim_sensors_rows(const mpc_solver* s) { return sim_sensors_stage(s) + (size_t)s->L.B * s->L.nx; }
 // what the sensors deliver, [B][nx]: the measurement of the sensor model when it is on, the true state otherwise
-static const double* sim_sensed(const mpc_solver* s) { return s->plant.d_sen ? sim_sensors_meas(s) : s->d_x0; }
-static double* sim_estimator_est(const mpc_solver* s) { return s->plant.d_est + (size_t)s->L.B * MPC_SIM_ESTIMATOR_PARAMS; }
-static double* sim_estimator_stage(const mpc_solver* s) { return sim_estimator_est(s) + (size_t)s->L.B * s->L.nx; }
-static double* sim_estimator_rows(const mpc_solver* s) { return sim_estimator_stage(s) + (size_t)s->L.B * s->L.nx; }
-static size_t sim_estimator_width(const Layout& L) { return (size_t)L.nx + MPC_SIM_ESTIMATOR_TAIL; }
+static const double* sim_sensed(const mpc_solver* s) { return s->plant.sen.on() ? s->plant.sen.d + sim_sensors_layout(s->L).out : s->d_x0; }
 // the state the controllers read, [B][nx]: the estimate of the base-state estimator when it is on, what the sensors deliver otherwise
-static const double* sim_measured(const mpc_solver* s) { return s->plant.d_est ? sim_estimator_est(s) : sim_sensed(s); }
+static const double* sim_measured(const mpc_solver* s) { return s->plant.est.on() ? s->plant.est.d + sim_estimator_layout(s->L).out : sim_sensed(s); }
 // the measurement event of the true states x, produced by a step of length dt_step, on stream st (sim_sensors.h), when the model is on
 static void sim_sensors_enqueue(mpc_solver* s, hipStream_t st, const double* x, double dt_step) {
   const SimPlant& p = s->plant;
-  if (!p.d_sen) return;
+  if (!p.sen.on()) return;
   const Layout& L = s->L;
+  const SimLayout l = sim_sensors_layout(L);
   SimSensorsArgs a;
   a.nv = L.n / 2; a.nq = L.nx - L.n / 2; a.nu = L.m;
-  a.x = x; a.params = p.d_sen; a.xm = sim_sensors_meas(s); a.rows = sim_sensors_rows(s); a.dt = dt_step;
+  a.x = x; a.params = p.sen.d; a.xm = p.sen.d + l.out; a.rows = p.sen.d + l.rows; a.dt = dt_step;
   hipLaunchKernelGGL(k_sim_sensors, dim3((unsigned)L.B), dim3(SIM_SEN_THREADS), sim_sensors_lds_bytes(a.nv), st, a);
   HIP_OK(hipGetLastError());
 }
 
-static double* sim_foot_sensors_rows(const mpc_solver* s) { return s->plant.d_fs + (size_t)s->L.B * MPC_SIM_FOOT_SENSORS_PARAMS; }
 // the rows a consumer of contact flags indexes by 0 and 1, and their width: the state rows of the contact detector when it feeds that consumer
 // (mpc_sim_foot_sensors_feed: one MPC_SIM_FOOT_SENSORS_FEED_* bit), the rows of the contact rule otherwise
 struct SimContactRows { const double* rows; int width; };
 static SimContactRows sim_contact_rows(const mpc_solver* s, int consumer) {
   const SimPlant& p = s->plant;
-  if (p.d_fs && (p.fs_feed & consumer)) return {sim_foot_sensors_rows(s), MPC_SIM_FOOT_SENSORS_WIDTH};
+  if (p.fs.on() && (p.fs_feed & consumer)) return {p.fs.d + sim_foot_sensors_layout(s->L).rows, MPC_SIM_FOOT_SENSORS_WIDTH};
   return {p.d_con, MPC_SIM_CONTACTS_WIDTH};
 }
 // the detection event of the wrenches of the step of length dt_step just enqueued on stream st (sim_foot_sensors.h), when the model is on
 static void sim_foot_sensors_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
   const SimPlant& p = s->plant;
-  if (!p.d_fs) return;
+  if (!p.fs.on()) return;
   SimFootSensorsArgs a;
-  a.wr = p.d_simwr; a.con = p.d_con; a.params = p.d_fs; a.rows = sim_foot_sensors_rows(s); a.dt = dt_step;
+  a.wr = p.d_simwr; a.con = p.d_con; a.params = p.fs.d; a.rows = p.fs.d + sim_foot_sensors_layout(s->L).rows; a.dt = dt_step;
   hipLaunchKernelGGL(k_sim_foot_sensors, dim3((unsigned)s->L.B), dim3(SIM_FS_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
 }
 // the state rows after arming: det = the in_contact pair of the contact rule's rows (`con` the rows on the host, NULL: read from the device),
 // everything else 0.  Host work, not part of the steady loop
 static void sim_foot_sensors_arm(mpc_solver* s, const double* con) {
-  if (!s->plant.d_fs) return;
+  if (!s->plant.fs.on()) return;
   const Layout& L = s->L;
   std::vector<double> c;
   if (!con) {
@@ -250,62 +398,49 @@ static void sim_foot_sensors_arm(mpc_solver* s, const double* con) {
   for (int b = 0; b < L.B; ++b)
     for (int i = 0; i < 2; ++i) h[(size_t)b * MPC_SIM_FOOT_SENSORS_WIDTH + i] = con[(size_t)b * MPC_SIM_CONTACTS_WIDTH + i] != 0.0 ? 1.0 : 0.0;
   HIP_OK(hipStreamSynchronize(s->stream));
-  copy_sync(s, sim_foot_sensors_rows(s), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-}
-static void sim_foot_sensors_drop(mpc_solver* s) {
-  sim_realloc(s, s->plant.d_fs, 0);
-  s->plant.h_fs.clear();
-  s->plant.fs_feed = 0;
+  copy_sync(s, s->plant.fs.d + sim_foot_sensors_layout(L).rows, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
 }
 
 // the estimation event of the measured states xm and the true states xt on stream st (sim_estimator.h), when the estimator is on: it reads the rows
 // of the contact rule, or of the contact detector when that feeds it (sim_contact_rows), as they stand on the stream
 static void sim_estimator_enqueue(mpc_solver* s, hipStream_t st, const double* xm, const double* xt) {
   const SimPlant& p = s->plant;
-  if (!p.d_est) return;
+  if (!p.est.on()) return;
   const Layout& L = s->L;
+  const SimLayout l = sim_estimator_layout(L);
   SimEstimatorArgs a;
   a.mi = s->d_model_i; a.md = s->d_model_d; a.nv = L.n / 2; a.nq = L.nx - L.n / 2;
   const SimContactRows cr = sim_contact_rows(s, MPC_SIM_FOOT_SENSORS_FEED_ESTIMATOR);
-  a.xm = xm; a.xt = xt; a.con = cr.rows; a.con_width = cr.width; a.params = p.d_est; a.xe = sim_estimator_est(s); a.rows = sim_estimator_rows(s);
+  a.xm = xm; a.xt = xt; a.con = cr.rows; a.con_width = cr.width; a.params = p.est.d; a.xe = p.est.d + l.out; a.rows = p.est.d + l.rows;
   hipLaunchKernelGGL(k_sim_estimator, dim3((unsigned)L.B), dim3(CG_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
 }
 // the friction model of the step of length dt_step just enqueued on stream st, after the contact rule (sim_friction.h), when the model is on
-static double* sim_friction_rows(const mpc_solver* s) { return s->plant.d_fr + (size_t)s->L.B * MPC_SIM_FRICTION_PARAMS; }
 static void sim_friction_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
   const SimPlant& p = s->plant;
-  if (!p.d_fr) return;
+  if (!p.fr.on()) return;
   SimFrictionArgs a;
-  a.B = s->L.B; a.wr = p.d_simwr; a.con = p.d_con; a.params = p.d_fr; a.rows = sim_friction_rows(s); a.dt = dt_step;
+  a.B = s->L.B; a.wr = p.d_simwr; a.con = p.d_con; a.params = p.fr.d; a.rows = p.fr.d + sim_friction_layout(s->L).rows; a.dt = dt_step;
   hipLaunchKernelGGL(k_sim_friction, dim3((unsigned)((2 * s->L.B + SIM_FR_THREADS - 1) / SIM_FR_THREADS)), dim3(SIM_FR_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
 }
-static void sim_friction_drop(mpc_solver* s) {
-  sim_realloc(s, s->plant.d_fr, 0);
-  s->plant.h_fr.clear();
-}
-static void sim_estimator_drop(mpc_solver* s) {
-  sim_realloc(s, s->plant.d_est, 0);
-  s->plant.h_est.clear();
-}
 
-// the plant model's tables, built from the rows in force (h_plant) and the handle's nominal table: when the model is armed, and when mpc_set_model
+// the plant model's tables, built from the rows in force (the mirror) and the handle's nominal table: when the model is armed, and when mpc_set_model
 // replaced the nominal table of an armed handle (the joint count is then unchanged; the table may have grown by a frame).  Synchronous: the tables
 // may be read from any stream at once (the loops of the QP pipelines step the plant on the QP handle's).  Host work, not part of the steady loop
 static void sim_plant_build(mpc_solver* s) {
   SimPlant& p = s->plant;
-  if (!p.d_plant) return;
+  if (!p.pm.on()) return;
   const Layout& L = s->L;
-  const size_t head = p.plant_off;
+  const SimLayout l = sim_plant_layout(L, s->model_nd);
   if (p.plant_nd != s->model_nd) {
-    sim_realloc(s, p.d_plant, head + (size_t)L.B * s->model_nd);
+    sim_realloc(s, p.pm.d, l.total);
     p.plant_nd = s->model_nd;
   }
-  copy_sync(s, p.d_plant, p.h_plant.data(), head * sizeof(double), hipMemcpyHostToDevice);
+  copy_sync(s, p.pm.d, p.pm.h.data(), l.out * sizeof(double), hipMemcpyHostToDevice);
   SimPlantArgs a;
   a.md = s->d_model_d; a.nd = (int)p.plant_nd; a.nj = L.nj;
-  a.params = p.d_plant; a.link_scale = p.d_plant + (size_t)L.B * MPC_SIM_PLANT_PARAMS; a.tables = sim_plant_tables(s);
+  a.params = p.pm.d; a.link_scale = p.pm.d + l.tables; a.tables = p.pm.d + l.out;
   hipLaunchKernelGGL(k_sim_plant_models, dim3((unsigned)L.B), dim3(SIM_PLANT_THREADS), 0, s->stream, a);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(s->stream));
@@ -332,31 +467,40 @@ static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
   if (s->plant.d_met)
     HIP_OK(hipMemcpyAsync(s->plant.d_met + (size_t)L.B * (MPC_SIM_METRICS_WIDTH + 1), s->d_x0, (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
 }
+// the dynamics write the wrenches of the step when the caller or anything after the dynamics reads them
+static bool sim_wrenches_wanted(const SimPlant& p, bool by_caller) {
+  return by_caller || p.rec_cap > 0 || p.d_met || p.d_con || p.fs.on() || p.fr.on();
+}
 // One step of the plant on stream st: `substeps` integration steps of length dt under the torque the caller put into plant.d_simu.  The order is the
-// contract of the extensions.  The disturbance schedule (include/mpc_sim_disturbances.h) before everything: from the state the step starts from and the
-// rows the contact rule left after the step before it writes the force, point and link that act in this step's dynamics, in place of the armed push.
-// The actuator model next: it turns the command into the applied torque in place, over the whole step (substeps * dt),
-// and everything after it sees the applied torque.  Then the dynamics, with the armed push and the contacts the rule's rows held when the step BEFORE
-// ended (the rows the low-level QPs of pipeline_loops.h read for this step); wrenches are written when the caller, the record, the metrics or the rule
-// want them.  Then the record and the metrics of the step: the new state, the applied torque, its wrenches, the rows it was integrated with.  The
-// contact rule: it rewrites the rows for the NEXT step from the new state and this step's wrenches.  The sensor model last: the measurement event of
-// the new state, over the whole step.  The base-state estimator after it: the estimation event of that measurement (the true state without a
-// sensor model) and of the rows the contact rule just wrote; nothing of this step reads either, the controllers of the next step do (sim_measured).  Between the two, the foot force sensors and
-// the contact detector: the detection event of this step's wrenches (which the dynamics then always write), so that an estimator fed by detection reads
-// the pair this step's event left, and the low-level QPs of the next step the same pair.  The friction model (include/mpc_sim_friction.h) directly
-// after the contact rule: from this step's wrenches and the flags the rule just wrote it sets the slip velocity each held sole has in the NEXT
-// step's dynamics, and advances the anchors of the soles that slid in this one.  In one line: disturbances -> actuator model -> dynamics -> record -> metrics
-// -> contact rule -> friction -> sensors -> foot sensors -> estimator.  The plant model (include/mpc_sim_plant.h) launches nothing here: the dynamics, the record and
-// the metrics read robot b's own model table, built when the model was armed.
+// contract of the extensions; a stage whose model is off launches nothing.  Each event covers the whole step (substeps * dt).
+//    1 disturbances  reads the state the step starts from and the contact rows of the step BEFORE ; writes the force, point and link that act in
+//                    this step's dynamics, in place of the armed push
+//    2 actuators     reads the commanded torque and the state ; writes the applied torque in place: everything after it sees the applied torque
+//    3 dynamics      reads the applied torque, the push, the contact rows of the step BEFORE (the rows the low-level QPs of pipeline_loops.h read
+//                    for this step), the slip velocities friction set after the step before, robot b's own model table (the plant model, built
+//                    when it was armed: it launches nothing here) ; writes the new state and, when wanted (sim_wrenches_wanted), the wrenches
+//    4 record        reads the new state, the applied torque, the wrenches, the push, the plant's model tables ; writes its slot of the ring
+//    5 metrics       reads the same and the contact rows the step was integrated with ; writes the metric rows
+//    6 contact rule  reads the new state and this step's wrenches ; rewrites the contact rows, for the NEXT step
+//    7 friction      reads this step's wrenches and the flags the rule just wrote ; writes the slip velocity each held sole has in the NEXT step's
+//                    dynamics and advances the anchors of the soles that slid in this one
+//    8 sensors       reads the new state ; writes the measurement
+//    9 foot sensors  reads this step's wrenches ; writes the detected pair: an estimator fed by detection reads the pair this step's event left,
+//                    and the low-level QPs of the next step the same pair
+//   10 estimator     reads that measurement (the true state without a sensor model) and the contact rows the rule, or the detector, just wrote ;
+//                    writes the estimate.  Nothing of this step reads 8 to 10: the controllers of the next step do (sim_measured)
 static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& args, int substeps, double dt, bool want_wrenches) {
   const SimPlant& p = s->plant;
   sim_disturbances_enqueue(s, st, substeps * dt);
   sim_actuators_enqueue(s, st, substeps * dt);
-  const double* push = p.d_dis ? sim_disturbances_out(s) : (p.push_width ? p.d_push : nullptr);  // (the two exclude each other: mpc_sim_set_push)
-  launch_eval_multibody(st, args, s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, true, 0, 1, substeps, dt, false, push, true,
-                        p.d_simu, (want_wrenches || p.rec_cap > 0 || p.d_met || p.d_con || p.d_fs || p.d_fr) ? p.d_simwr : nullptr,
-                        p.d_dis ? 6 : (p.push_width ? p.push_width : 3), p.d_con,
-                        p.d_plant ? sim_plant_tables(s) : nullptr, sim_plant_stride(s), p.d_fr ? sim_friction_rows(s) : nullptr, p.d_dis != nullptr);
+  MbSimStep step;
+  step.substeps = substeps; step.dt = dt;
+  step.push = sim_push(s); step.width = p.dis.on() ? 6 : (p.push_width ? p.push_width : 3); step.linked = p.dis.on();
+  step.torques = p.d_simu; step.wrenches = sim_wrenches_wanted(p, want_wrenches) ? p.d_simwr : nullptr;
+  step.contact_rows = p.d_con;
+  step.model_tables = p.pm.on() ? sim_plant_tables(s) : nullptr; step.model_stride = sim_plant_stride(s);
+  step.friction_rows = p.fr.on() ? p.fr.d + sim_friction_layout(s->L).rows : nullptr;
+  launch_sim_multibody(st, args, s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, step);
   HIP_OK(hipGetLastError());
   sim_record_enqueue(s, st);
   sim_metrics_enqueue(s, st, substeps * dt);
@@ -367,6 +511,23 @@ static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& ar
   sim_estimator_enqueue(s, st, sim_sensed(s), s->d_x0);
 }
 
+// Arming the sensor model or the estimator (params NULL: off), after the model's own checks of the params: the checks of x0, then of the contact
+// rule if the model reads its rows — every check before anything changes, so that a bad call leaves the previous configuration in force.  Then the
+// rows all 0 and the arming event (count 1) on x0, which `event` enqueues on the staged states; synchronous
+template <class E> static void sim_filter_arm(mpc_solver* s, const char* who, SimModel& m, const SimLayout& l, const double* params, const double* x0,
+                                              const char* x0_why, E&& event) {
+  if (!params) { sim_drop(s, m); return; }
+  sim_x0_check(s, who, x0, x0_why);
+  if (m.needs_rule) sim_rule_check(s, who);
+  sim_realloc(s, m.d, l.total);
+  m.h.assign(params, params + l.np);
+  HIP_OK(hipMemsetAsync(m.d, 0, l.total * sizeof(double), s->stream));
+  copy_sync(s, m.d, params, l.np * sizeof(double), hipMemcpyHostToDevice);
+  copy_sync(s, m.d + l.stage, x0, (size_t)s->L.B * s->L.nx * sizeof(double), hipMemcpyHostToDevice);
+  event(m.d + l.stage);
+  HIP_OK(hipStreamSynchronize(s->stream));
+}
+
 extern "C" {
 
 // ---- include/mpc_sim_ext.h: push and record -----------------------------------------------------------------------------------------------
@@ -374,7 +535,7 @@ int mpc_sim_set_push(mpc_solver* s, const double* f_ext, int32_t width) {
   MPC_TRY(s, {
     sim_check(s, "sim_set_push");
     if (!f_ext) { s->plant.push_width = 0; return 0; }
-    if (s->plant.d_dis)
+    if (s->plant.dis.on())
       throw std::runtime_error("sim_set_push: the disturbance schedule is on (mpc_sim_disturbances): its events are the pushes of this handle; turn it off "
                                "with mpc_sim_disturbances(sim, NULL, 0) before arming a push");
     if (width != 3 && width != 6) throw std::runtime_error("sim_set_push: width must be 3 (force at the base origin) or 6 (force, world point)");
@@ -448,16 +609,10 @@ int mpc_sim_metrics_read(mpc_solver* s, double* out, int32_t reset) {
 int32_t mpc_sim_metrics_width(mpc_solver* s) { return sim_width(s, "sim_metrics_width", [&] { return MPC_SIM_METRICS_WIDTH; }); }
 
 // ---- include/mpc_sim_contacts.h, include/mpc_sim_terrain.h: the contact rule and the terrain under it -----------------------------------------
-static void sim_terrain_drop(mpc_solver* s) {
-  sim_realloc(s, s->plant.d_ter, 0);
-  s->plant.ter_cfg = {};
-  s->plant.h_ter.clear();
-}
-
 int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
   MPC_TRY(s, {
     sim_check(s, "sim_contacts");
-    const Layout& L = s->L;
+    SimPlant& p = s->plant;
     if (cfg) {
       sim_model_check(s, "sim_contacts");
       if (!std::isfinite(cfg->ground_z) || !std::isfinite(cfg->ground_tol) || !std::isfinite(cfg->release_force))
@@ -465,17 +620,13 @@ int mpc_sim_contacts(mpc_solver* s, const mpc_sim_contacts_config* cfg) {
       if (cfg->ground_tol < 0.0 || cfg->release_force < 0.0) throw std::runtime_error("sim_contacts: ground_tol and release_force must be >= 0");
       if (cfg->release_steps < 1) throw std::runtime_error("sim_contacts: release_steps must be >= 1");
     }
-    sim_realloc(s, s->plant.d_con, cfg ? (size_t)L.B * MPC_SIM_CONTACTS_WIDTH : 0);
-    if (!cfg) {  // (the terrain, the friction model, the estimator and the contact detector go with the rows; a reset keeps them)
-      sim_terrain_drop(s);
-      sim_friction_drop(s);
-      sim_estimator_drop(s);
-      sim_foot_sensors_drop(s);
-      if (s->plant.dis_contact) sim_disturbances_drop(s);  // (a table with a contact trigger reads the rows)
-    }
+    sim_realloc(s, p.d_con, cfg ? (size_t)s->L.B * MPC_SIM_CONTACTS_WIDTH : 0);
+    if (!cfg)  // (what reads the rows goes with them, a schedule when one of its triggers is a contact; a reset keeps them all)
+      for (SimModel* m : p.models)
+        if (m->needs_rule || (m == &p.dis && p.dis_contact)) sim_drop(s, *m);
     if (cfg) {
-      s->plant.con_cfg = *cfg;
-      s->plant.con_cfg.reserved = 0;
+      p.con_cfg = *cfg;
+      p.con_cfg.reserved = 0;
       sim_ensure(s);
       sim_contacts_reset(s);
       sim_foot_sensors_arm(s, nullptr);  // (the contact detector starts again from the rows just reset)
@@ -487,18 +638,12 @@ int mpc_sim_contacts_set(mpc_solver* s, const double* rows) {
   MPC_TRY(s, {
     if (!rows) throw std::runtime_error("sim_contacts_set: rows must not be null");
     sim_check(s, "sim_contacts_set");
-    if (!s->plant.d_con) throw std::runtime_error("sim_contacts_set: the contact rule is off on this handle (turn it on with mpc_sim_contacts)");
+    sim_rule_check(s, "sim_contacts_set", false);
     const Layout& L = s->L;
-    for (int b = 0; b < L.B; ++b) {
-      const double* r = rows + (size_t)b * MPC_SIM_CONTACTS_WIDTH;
-      const std::string row = "sim_contacts_set: row " + std::to_string(b);
-      for (int e = 0; e < MPC_SIM_CONTACTS_WIDTH; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-      for (int e = 0; e < 4; ++e)
-        if (r[e] != 0.0 && r[e] != 1.0) throw std::runtime_error(row + ": in_contact and lifted must be 0 or 1");
+    sim_check_rows("sim_contacts_set", rows, L.B, MPC_SIM_CONTACTS_WIDTH, [&](const std::string& row, const double* r, int) {
+      sim_flags_check(row, "in_contact and lifted", r, 4);
       if (r[0] == 0.0 && r[1] == 0.0) throw std::runtime_error(row + " has no sole in contact (flight phases are not simulated)");
-      for (int e : {4, 5, 32, 33, 34, 35, 40})
-        if (r[e] < 0.0) throw std::runtime_error(row + ": pulling, the counts and steps must be >= 0");
+      sim_nonneg_check(row, "pulling, the counts and steps", r, {4, 5, 32, 33, 34, 35, 40});
       for (int i = 0; i < 2; ++i) {
         const double* R = r + 8 + 12 * i;
         double dev = 0.0;
@@ -510,7 +655,7 @@ int mpc_sim_contacts_set(mpc_solver* s, const double* rows) {
         const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
         if (dev > 1e-9 || det < 0.0) throw std::runtime_error(row + ": the anchor of sole " + std::to_string(i) + " is not a rotation");
       }
-    }
+    });
     HIP_OK(hipStreamSynchronize(s->stream));
     copy_sync(s, s->plant.d_con, rows, (size_t)L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyHostToDevice);
     sim_foot_sensors_arm(s, rows);  // (... and from rows imposed)
@@ -521,7 +666,7 @@ int mpc_sim_contacts_read(mpc_solver* s, double* rows) {
   MPC_TRY(s, {
     if (!rows) throw std::runtime_error("sim_contacts_read: rows must not be null");
     sim_check(s, "sim_contacts_read");
-    if (!s->plant.d_con) throw std::runtime_error("sim_contacts_read: the contact rule is off on this handle (turn it on with mpc_sim_contacts)");
+    sim_rule_check(s, "sim_contacts_read", false);
     HIP_OK(hipStreamSynchronize(s->stream));
     copy_sync(s, rows, s->plant.d_con, (size_t)s->L.B * MPC_SIM_CONTACTS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
   })
@@ -530,15 +675,15 @@ int mpc_sim_contacts_read(mpc_solver* s, double* rows) {
 int mpc_sim_terrain(mpc_solver* s, const mpc_sim_terrain_config* cfg, const double* boxes) {
   MPC_TRY(s, {
     sim_check(s, "sim_terrain");
-    if (!s->plant.d_con) throw std::runtime_error("sim_terrain: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
-    const Layout& L = s->L;
+    sim_rule_check(s, "sim_terrain");
+    SimPlant& p = s->plant;
     size_t count = 0;
     if (cfg) {
       if (cfg->n_boxes < 0 || cfg->n_boxes > MPC_SIM_TERRAIN_MAX_BOXES)
         throw std::runtime_error("sim_terrain: n_boxes must be 0 .. " + std::to_string(MPC_SIM_TERRAIN_MAX_BOXES));
       if (cfg->per_robot != 0 && cfg->per_robot != 1) throw std::runtime_error("sim_terrain: per_robot must be 0 or 1");
       if (cfg->n_boxes > 0 && !boxes) throw std::runtime_error("sim_terrain: boxes must not be null with n_boxes > 0");
-      count = (size_t)(cfg->per_robot ? L.B : 1) * cfg->n_boxes;
+      count = (size_t)(cfg->per_robot ? s->L.B : 1) * cfg->n_boxes;
       for (size_t k = 0; k < count; ++k) {
         const double* bx = boxes + k * MPC_SIM_TERRAIN_BOX_WIDTH;
         for (int e = 0; e < MPC_SIM_TERRAIN_BOX_WIDTH; ++e)
@@ -546,15 +691,15 @@ int mpc_sim_terrain(mpc_solver* s, const mpc_sim_terrain_config* cfg, const doub
         if (bx[0] > bx[1] || bx[2] > bx[3]) throw std::runtime_error("sim_terrain: box " + std::to_string(k) + " has x_lo > x_hi or y_lo > y_hi");
       }
     }
-    sim_terrain_drop(s);
+    sim_drop(s, p.ter);
     if (cfg) {
-      s->plant.ter_cfg = *cfg;
-      s->plant.h_ter.assign(boxes, boxes + count * MPC_SIM_TERRAIN_BOX_WIDTH);
+      p.ter_cfg = *cfg;
+      p.ter.h.assign(boxes, boxes + count * MPC_SIM_TERRAIN_BOX_WIDTH);
       if (count > 0) {  // (zero boxes: the plane, by the old path)
-        std::vector<double> h(s->plant.h_ter);
+        std::vector<double> h(p.ter.h);
         for (size_t k = 0; k < count; ++k) h[k * MPC_SIM_TERRAIN_BOX_WIDTH + 4] += 0.0;  // (a top of -0 counts as +0, as in the numpy definition)
-        sim_realloc(s, s->plant.d_ter, h.size());
-        copy_sync(s, s->plant.d_ter, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+        sim_realloc(s, p.ter.d, h.size());
+        copy_sync(s, p.ter.d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
       }
     }
   })
@@ -564,16 +709,16 @@ int mpc_sim_terrain_read(mpc_solver* s, mpc_sim_terrain_config* cfg, double* box
   MPC_TRY(s, {
     if (!cfg) throw std::runtime_error("sim_terrain_read: cfg must not be null");
     sim_check(s, "sim_terrain_read");
-    if (!s->plant.d_con) throw std::runtime_error("sim_terrain_read: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    sim_rule_check(s, "sim_terrain_read");
     *cfg = s->plant.ter_cfg;
-    if (boxes) std::copy(s->plant.h_ter.begin(), s->plant.h_ter.end(), boxes);
+    if (boxes) std::copy(s->plant.ter.h.begin(), s->plant.ter.h.end(), boxes);
   })
 }
 
 int mpc_sim_terrain_height(mpc_solver* s, const double* xy, int32_t n, double* h) {
   MPC_TRY(s, {
     sim_check(s, "sim_terrain_height");
-    if (!s->plant.d_con) throw std::runtime_error("sim_terrain_height: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+    sim_rule_check(s, "sim_terrain_height");
     if (n < 0) throw std::runtime_error("sim_terrain_height: n must be >= 0");
     if (n > 0 && (!xy || !h)) throw std::runtime_error("sim_terrain_height: xy and h must not be null");
     const Layout& L = s->L;
@@ -607,306 +752,154 @@ int mpc_sim_actuators(mpc_solver* s, const double* params, const double* limit, 
   MPC_TRY(s, {
     sim_check(s, "sim_actuators");
     const Layout& L = s->L;
-    const size_t nu = L.m, np = (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS;
-    std::vector<double> h;
-    if (params) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
-      h.assign(np + 2 * nu, 0.0);
-      bool any_sat = false;
-      for (int b = 0; b < L.B; ++b) {
-        const double* r = params + (size_t)b * MPC_SIM_ACTUATORS_PARAMS;
-        const std::string row = "sim_actuators: row " + std::to_string(b);
-        for (int e = 0; e < MPC_SIM_ACTUATORS_PARAMS; ++e)
-          if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-        if (r[0] != std::floor(r[0]) || r[0] < 0.0 || r[0] > MPC_SIM_ACTUATORS_RING - 1)
-          throw std::runtime_error(row + ": delay must be an integer value in [0, " + std::to_string(MPC_SIM_ACTUATORS_RING - 1) + "]");
-        if (!(r[1] > 0.0)) throw std::runtime_error(row + ": scale must be > 0");
-        for (int e = 2; e < 7; ++e)
-          if (r[e] < 0.0) throw std::runtime_error(row + ": time_constant, damping, coulomb, v_eps and sat must be >= 0");
-        if (r[4] > 0.0 && !(r[5] > 0.0)) throw std::runtime_error(row + ": coulomb > 0 needs v_eps > 0");
-        if (r[6] > 0.0) any_sat = true;
-        std::copy(r, r + MPC_SIM_ACTUATORS_PARAMS, h.begin() + (size_t)b * MPC_SIM_ACTUATORS_PARAMS);
-        h[(size_t)b * MPC_SIM_ACTUATORS_PARAMS + 7] = 0.0;
-      }
-      if (any_sat && !limit) throw std::runtime_error("sim_actuators: a row with sat > 0 needs the effort limits (limit must not be null)");
-      for (size_t j = 0; j < nu; ++j) {
-        const double l = limit ? limit[j] : 0.0, f = friction_shape ? friction_shape[j] : 1.0;
-        if (!std::isfinite(l) || l < 0.0 || !std::isfinite(f) || f < 0.0)
-          throw std::runtime_error("sim_actuators: limit and friction_shape must be finite and >= 0");
-        h[np + j] = l;
-        h[np + nu + j] = f;
-      }
+    const SimLayout l = sim_actuators_layout(L);
+    SimModel& m = s->plant.act;
+    if (!params) { sim_drop(s, m); return 0; }
+    // (every check before anything changes: a bad row leaves the previous configuration in force)
+    std::vector<double> h(params, params + l.np);
+    h.resize(l.total, 0.0);  // (params | limit | shape, then the state rows after a reset: all 0)
+    bool any_sat = false;
+    sim_check_rows("sim_actuators", params, L.B, MPC_SIM_ACTUATORS_PARAMS, [&](const std::string& row, const double* r, int b) {
+      sim_int_check(row, "delay", r[0], MPC_SIM_ACTUATORS_RING, std::to_string(MPC_SIM_ACTUATORS_RING - 1) + "]");
+      if (!(r[1] > 0.0)) throw std::runtime_error(row + ": scale must be > 0");
+      sim_nonneg_check(row, "time_constant, damping, coulomb, v_eps and sat", r + 2, 5);
+      if (r[4] > 0.0 && !(r[5] > 0.0)) throw std::runtime_error(row + ": coulomb > 0 needs v_eps > 0");
+      if (r[6] > 0.0) any_sat = true;
+      h[(size_t)b * MPC_SIM_ACTUATORS_PARAMS + 7] = 0.0;  // (the reserved entry)
+    });
+    if (any_sat && !limit) throw std::runtime_error("sim_actuators: a row with sat > 0 needs the effort limits (limit must not be null)");
+    for (int j = 0; j < L.m; ++j) {
+      const double lim = limit ? limit[j] : 0.0, f = friction_shape ? friction_shape[j] : 1.0;
+      if (!std::isfinite(lim) || lim < 0.0 || !std::isfinite(f) || f < 0.0)
+        throw std::runtime_error("sim_actuators: limit and friction_shape must be finite and >= 0");
+      h[l.tables + j] = lim;
+      h[l.tables_b + j] = f;
     }
-    const size_t rows = (size_t)L.B * sim_actuators_width(L);
-    sim_realloc(s, s->plant.d_act, params ? h.size() + rows : 0);
-    s->plant.h_act = h;
-    if (params) {
-      h.resize(h.size() + rows, 0.0);  // (the state rows after a reset: all 0)
-      copy_sync(s, s->plant.d_act, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-    }
+    sim_realloc(s, m.d, l.total);
+    m.h.assign(h.begin(), h.begin() + l.rows);
+    copy_sync(s, m.d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
   })
 }
 
 int mpc_sim_actuators_read(mpc_solver* s, double* params, double* state) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_actuators_read");
-    if (!s->plant.d_act) throw std::runtime_error("sim_actuators_read: the actuator model is off on this handle (turn it on with mpc_sim_actuators)");
-    const Layout& L = s->L;
-    if (params) std::copy(s->plant.h_act.begin(), s->plant.h_act.begin() + (size_t)L.B * MPC_SIM_ACTUATORS_PARAMS, params);
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (state) copy_sync(s, state, sim_actuators_rows(s), (size_t)L.B * sim_actuators_width(L) * sizeof(double), hipMemcpyDeviceToHost);
-  })
+  MPC_TRY(s, { sim_model_read(s, "sim_actuators_read", s->plant.act, sim_actuators_layout(s->L), params, state); })
 }
 
 int mpc_sim_actuators_set(mpc_solver* s, const double* state) {
   MPC_TRY(s, {
-    if (!state) throw std::runtime_error("sim_actuators_set: state must not be null");
-    sim_check(s, "sim_actuators_set");
-    if (!s->plant.d_act) throw std::runtime_error("sim_actuators_set: the actuator model is off on this handle (turn it on with mpc_sim_actuators)");
-    const Layout& L = s->L;
-    const size_t W = sim_actuators_width(L);
-    for (int b = 0; b < L.B; ++b) {
-      const double* r = state + (size_t)b * W;
-      const std::string row = "sim_actuators_set: row " + std::to_string(b);
-      for (size_t e = 0; e < W; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-      const double head = r[W - 2], count = r[W - 1];
-      if (head != std::floor(head) || head < 0.0 || head >= MPC_SIM_ACTUATORS_RING)
-        throw std::runtime_error(row + ": head must be an integer value in [0, " + std::to_string(MPC_SIM_ACTUATORS_RING) + ")");
-      if (count < 0.0) throw std::runtime_error(row + ": count must be >= 0");
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    copy_sync(s, sim_actuators_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
+    const SimLayout l = sim_actuators_layout(s->L);
+    sim_rows_set(s, "sim_actuators_set", s->plant.act, l, state, -1,
+                 [&](const std::string& row, const double* r, int) { sim_ring_check(row, r, l.width, MPC_SIM_ACTUATORS_RING, 0); });
   })
 }
 
-int32_t mpc_sim_actuators_width(mpc_solver* s) { return sim_width(s, "sim_actuators_width", [&] { return sim_actuators_width(s->L); }); }
+int32_t mpc_sim_actuators_width(mpc_solver* s) { return sim_width(s, "sim_actuators_width", [&] { return sim_actuators_layout(s->L).width; }); }
 
-// ---- include/mpc_sim_sensors.h: the per-robot sensor model between the simulator steps and the controllers -----------------------------------
+// ---- include/mpc_sim_sensors.h, include/mpc_sim_estimator.h: the two per-robot models between the simulator steps and the controllers ----------
 int mpc_sim_sensors(mpc_solver* s, const double* params, const double* x0) {
   MPC_TRY(s, {
     sim_check(s, "sim_sensors");
-    const Layout& L = s->L;
-    const size_t np = (size_t)L.B * MPC_SIM_SENSORS_PARAMS, nxs = (size_t)L.B * L.nx;
-    if (params) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
-      for (int b = 0; b < L.B; ++b) {
-        const double* r = params + (size_t)b * MPC_SIM_SENSORS_PARAMS;
-        const std::string row = "sim_sensors: row " + std::to_string(b);
-        for (int e = 0; e < MPC_SIM_SENSORS_PARAMS; ++e)
-          if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-        if (r[0] != std::floor(r[0]) || r[0] < 0.0 || r[0] > MPC_SIM_SENSORS_RING - 1)
-          throw std::runtime_error(row + ": delay must be an integer value in [0, " + std::to_string(MPC_SIM_SENSORS_RING - 1) + "]");
-        for (int e : {1, 2, 3, 4, 5, 6, 7, 8, 10})
-          if (r[e] < 0.0) throw std::runtime_error(row + ": the noise levels (sigma_*), quantum, q_bias and v_time_constant must be >= 0");
-        if (r[9] != 0.0 && r[9] != 1.0) throw std::runtime_error(row + ": v_from_q must be 0 or 1");
-        if (r[11] != std::floor(r[11]) || r[11] < 0.0 || r[11] >= 4294967296.0) throw std::runtime_error(row + ": seed must be an integer value in [0, 2^32)");
-        for (int e = 12; e < MPC_SIM_SENSORS_PARAMS; ++e)
-          if (r[e] != 0.0) throw std::runtime_error(row + ": the reserved entries must be 0");
-      }
-      if (!x0) throw std::runtime_error("sim_sensors: x0 must not be null (the first measurement is taken of it)");
-      for (size_t e = 0; e < nxs; ++e)
-        if (!std::isfinite(x0[e])) throw std::runtime_error("sim_sensors: x0 holds a non-finite entry");
-    }
-    sim_realloc(s, s->plant.d_sen, params ? np + 2 * nxs + (size_t)L.B * sim_sensors_width(L) : 0);
-    s->plant.h_sen.clear();
-    if (params) {
-      s->plant.h_sen.assign(params, params + np);
-      // the rows after a reset: all 0, then the arming event (count 1) on x0
-      HIP_OK(hipMemsetAsync(s->plant.d_sen, 0, (np + 2 * nxs + (size_t)L.B * sim_sensors_width(L)) * sizeof(double), s->stream));
-      copy_sync(s, s->plant.d_sen, params, np * sizeof(double), hipMemcpyHostToDevice);
-      copy_sync(s, sim_sensors_stage(s), x0, nxs * sizeof(double), hipMemcpyHostToDevice);
-      sim_sensors_enqueue(s, s->stream, sim_sensors_stage(s), 0.0);
-      HIP_OK(hipStreamSynchronize(s->stream));
-    }
+    if (params)
+      sim_check_rows("sim_sensors", params, s->L.B, MPC_SIM_SENSORS_PARAMS, [&](const std::string& row, const double* r, int) {
+        sim_int_check(row, "delay", r[0], MPC_SIM_SENSORS_RING, std::to_string(MPC_SIM_SENSORS_RING - 1) + "]");
+        sim_nonneg_check(row, "the noise levels (sigma_*), quantum, q_bias and v_time_constant", r, {1, 2, 3, 4, 5, 6, 7, 8, 10});
+        sim_flags_check(row, "v_from_q", r + 9, 1);
+        sim_int_check(row, "seed", r[11], 4294967296.0, "2^32)");
+        sim_reserved_check(row, r, 12, MPC_SIM_SENSORS_PARAMS);
+      });
+    sim_filter_arm(s, "sim_sensors", s->plant.sen, sim_sensors_layout(s->L), params, x0, "the first measurement is taken of it",
+                   [&](const double* stage) { sim_sensors_enqueue(s, s->stream, stage, 0.0); });
   })
 }
 
 int mpc_sim_sensors_read(mpc_solver* s, double* params, double* state, double* x_meas) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_sensors_read");
-    if (!s->plant.d_sen) throw std::runtime_error("sim_sensors_read: the sensor model is off on this handle (turn it on with mpc_sim_sensors)");
-    const Layout& L = s->L;
-    if (params) std::copy(s->plant.h_sen.begin(), s->plant.h_sen.end(), params);
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (state) copy_sync(s, state, sim_sensors_rows(s), (size_t)L.B * sim_sensors_width(L) * sizeof(double), hipMemcpyDeviceToHost);
-    if (x_meas) copy_sync(s, x_meas, sim_sensors_meas(s), (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToHost);
-  })
+  MPC_TRY(s, { sim_model_read(s, "sim_sensors_read", s->plant.sen, sim_sensors_layout(s->L), params, state, x_meas); })
 }
 
 int mpc_sim_sensors_set(mpc_solver* s, const double* state) {
   MPC_TRY(s, {
-    if (!state) throw std::runtime_error("sim_sensors_set: state must not be null");
-    sim_check(s, "sim_sensors_set");
-    if (!s->plant.d_sen) throw std::runtime_error("sim_sensors_set: the sensor model is off on this handle (turn it on with mpc_sim_sensors)");
-    const Layout& L = s->L;
-    const size_t W = sim_sensors_width(L), o_meas = (size_t)MPC_SIM_SENSORS_RING * L.nx;
-    std::vector<double> xm((size_t)L.B * L.nx);
-    for (int b = 0; b < L.B; ++b) {
-      const double* r = state + (size_t)b * W;
-      const std::string row = "sim_sensors_set: row " + std::to_string(b);
-      for (size_t e = 0; e < W; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-      const double head = r[W - 2], count = r[W - 1];
-      if (head != std::floor(head) || head < 0.0 || head >= MPC_SIM_SENSORS_RING)
-        throw std::runtime_error(row + ": head must be an integer value in [0, " + std::to_string(MPC_SIM_SENSORS_RING) + ")");
-      if (count < 1.0) throw std::runtime_error(row + ": count must be >= 1 (a measurement is always held)");
-      std::copy(r + o_meas, r + o_meas + L.nx, xm.begin() + (size_t)b * L.nx);
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    copy_sync(s, sim_sensors_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
-    copy_sync(s, sim_sensors_meas(s), xm.data(), xm.size() * sizeof(double), hipMemcpyHostToDevice);  // (the controllers read the rows' measurement)
+    const SimLayout l = sim_sensors_layout(s->L);  // (the controllers read the rows' measurement: the slice behind the ring)
+    sim_rows_set(s, "sim_sensors_set", s->plant.sen, l, state, (long)MPC_SIM_SENSORS_RING * s->L.nx, [&](const std::string& row, const double* r, int) {
+      sim_ring_check(row, r, l.width, MPC_SIM_SENSORS_RING, 1, "a measurement is always held");
+    });
   })
 }
 
-int32_t mpc_sim_sensors_width(mpc_solver* s) { return sim_width(s, "sim_sensors_width", [&] { return sim_sensors_width(s->L); }); }
+int32_t mpc_sim_sensors_width(mpc_solver* s) { return sim_width(s, "sim_sensors_width", [&] { return sim_sensors_layout(s->L).width; }); }
 
-// ---- include/mpc_sim_estimator.h: the per-robot base-state estimator between the sensor model and the controllers ----------------------------
 int mpc_sim_estimator(mpc_solver* s, const double* params, const double* x0) {
   MPC_TRY(s, {
     sim_check(s, "sim_estimator");
-    const Layout& L = s->L;
-    const size_t np = (size_t)L.B * MPC_SIM_ESTIMATOR_PARAMS, nxs = (size_t)L.B * L.nx;
-    if (params) {  // (every check before anything changes: a bad call leaves the previous configuration in force)
+    if (params) {
       sim_model_check(s, "sim_estimator");
-      if (L.nx > SIM_EST_MAX_NX) throw std::runtime_error("sim_estimator: a longer state than the estimator's kernel holds (" + std::to_string(SIM_EST_MAX_NX) + ")");
-      for (int b = 0; b < L.B; ++b) {
-        const double* r = params + (size_t)b * MPC_SIM_ESTIMATOR_PARAMS;
-        const std::string row = "sim_estimator: row " + std::to_string(b);
-        for (int e = 0; e < MPC_SIM_ESTIMATOR_PARAMS; ++e)
-          if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+      if (s->L.nx > SIM_EST_MAX_NX) throw std::runtime_error("sim_estimator: a longer state than the estimator's kernel holds (" + std::to_string(SIM_EST_MAX_NX) + ")");
+      sim_check_rows("sim_estimator", params, s->L.B, MPC_SIM_ESTIMATOR_PARAMS, [&](const std::string& row, const double* r, int) {
         for (int e = 0; e < 2; ++e)
           if (r[e] < 0.0 || r[e] > 1.0) throw std::runtime_error(row + ": the weights w_p and w_v must be in [0, 1]");
-        for (int e = 2; e < MPC_SIM_ESTIMATOR_PARAMS; ++e)
-          if (r[e] != 0.0) throw std::runtime_error(row + ": the reserved entries must be 0");
-      }
-      if (!x0) throw std::runtime_error("sim_estimator: x0 must not be null (the arming event is run on it)");
-      for (size_t e = 0; e < nxs; ++e)
-        if (!std::isfinite(x0[e])) throw std::runtime_error("sim_estimator: x0 holds a non-finite entry");
-      if (!s->plant.d_con) throw std::runtime_error("sim_estimator: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
+        sim_reserved_check(row, r, 2, MPC_SIM_ESTIMATOR_PARAMS);
+      });
     }
-    const size_t total = np + 2 * nxs + (size_t)L.B * sim_estimator_width(L);
-    sim_realloc(s, s->plant.d_est, params ? total : 0);
-    s->plant.h_est.clear();
-    if (params) {
-      s->plant.h_est.assign(params, params + np);
-      // the rows after a reset: all 0, then the arming event (count 1) on x0
-      HIP_OK(hipMemsetAsync(s->plant.d_est, 0, total * sizeof(double), s->stream));
-      copy_sync(s, s->plant.d_est, params, np * sizeof(double), hipMemcpyHostToDevice);
-      copy_sync(s, sim_estimator_stage(s), x0, nxs * sizeof(double), hipMemcpyHostToDevice);
-      sim_estimator_enqueue(s, s->stream, sim_estimator_stage(s), sim_estimator_stage(s));
-      HIP_OK(hipStreamSynchronize(s->stream));
-    }
+    sim_filter_arm(s, "sim_estimator", s->plant.est, sim_estimator_layout(s->L), params, x0, "the arming event is run on it",
+                   [&](const double* stage) { sim_estimator_enqueue(s, s->stream, stage, stage); });
   })
 }
 
 int mpc_sim_estimator_read(mpc_solver* s, double* params, double* state, double* x_est) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_estimator_read");
-    if (!s->plant.d_est) throw std::runtime_error("sim_estimator_read: the estimator is off on this handle (turn it on with mpc_sim_estimator)");
-    const Layout& L = s->L;
-    if (params) std::copy(s->plant.h_est.begin(), s->plant.h_est.end(), params);
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (state) copy_sync(s, state, sim_estimator_rows(s), (size_t)L.B * sim_estimator_width(L) * sizeof(double), hipMemcpyDeviceToHost);
-    if (x_est) copy_sync(s, x_est, sim_estimator_est(s), (size_t)L.B * L.nx * sizeof(double), hipMemcpyDeviceToHost);
-  })
+  MPC_TRY(s, { sim_model_read(s, "sim_estimator_read", s->plant.est, sim_estimator_layout(s->L), params, state, x_est); })
 }
 
 int mpc_sim_estimator_set(mpc_solver* s, const double* state) {
   MPC_TRY(s, {
-    if (!state) throw std::runtime_error("sim_estimator_set: state must not be null");
-    sim_check(s, "sim_estimator_set");
-    if (!s->plant.d_est) throw std::runtime_error("sim_estimator_set: the estimator is off on this handle (turn it on with mpc_sim_estimator)");
-    const Layout& L = s->L;
-    const size_t W = sim_estimator_width(L);
-    std::vector<double> xe((size_t)L.B * L.nx);
-    for (int b = 0; b < L.B; ++b) {
-      const double* r = state + (size_t)b * W;
-      const std::string row = "sim_estimator_set: row " + std::to_string(b);
-      for (size_t e = 0; e < W; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-      for (int i = 0; i < 2; ++i)
-        if (r[L.nx + i] != 0.0 && r[L.nx + i] != 1.0) throw std::runtime_error(row + ": held must be 0 or 1");
-      if (r[W - 1] < 1.0) throw std::runtime_error(row + ": count must be >= 1 (an estimate is always held)");
-      std::copy(r, r + L.nx, xe.begin() + (size_t)b * L.nx);
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    copy_sync(s, sim_estimator_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
-    copy_sync(s, sim_estimator_est(s), xe.data(), xe.size() * sizeof(double), hipMemcpyHostToDevice);  // (the controllers read the rows' estimate)
+    const SimLayout l = sim_estimator_layout(s->L);  // (the controllers read the rows' estimate: the slice at 0)
+    sim_rows_set(s, "sim_estimator_set", s->plant.est, l, state, 0, [&](const std::string& row, const double* r, int) {
+      sim_flags_check(row, "held", r + s->L.nx, 2);
+      sim_count_check(row, r[l.width - 1], 1, "an estimate is always held");
+    });
   })
 }
 
-int32_t mpc_sim_estimator_width(mpc_solver* s) { return sim_width(s, "sim_estimator_width", [&] { return sim_estimator_width(s->L); }); }
+int32_t mpc_sim_estimator_width(mpc_solver* s) { return sim_width(s, "sim_estimator_width", [&] { return sim_estimator_layout(s->L).width; }); }
 
 // ---- include/mpc_sim_foot_sensors.h: the per-robot foot force sensors and the contact detector ----------------------------------------------------
 int mpc_sim_foot_sensors(mpc_solver* s, const double* params) {
   MPC_TRY(s, {
     sim_check(s, "sim_foot_sensors");
-    const Layout& L = s->L;
-    const size_t np = (size_t)L.B * MPC_SIM_FOOT_SENSORS_PARAMS;
-    if (!params) {
-      sim_foot_sensors_drop(s);
-      return 0;
-    }
-    for (int b = 0; b < L.B; ++b) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
-      const double* r = params + (size_t)b * MPC_SIM_FOOT_SENSORS_PARAMS;
-      const std::string row = "sim_foot_sensors: row " + std::to_string(b);
-      for (int e = 0; e < MPC_SIM_FOOT_SENSORS_PARAMS; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-      if (r[0] != std::floor(r[0]) || r[0] < 0.0 || r[0] > MPC_SIM_FOOT_SENSORS_RING - 1)
-        throw std::runtime_error(row + ": delay must be an integer value in [0, " + std::to_string(MPC_SIM_FOOT_SENSORS_RING - 1) + "]");
-      for (int e = 1; e < 6; ++e)
-        if (r[e] < 0.0) throw std::runtime_error(row + ": sigma_f, sigma_m, bias_f, bias_m and time_constant must be >= 0");
+    const SimLayout l = sim_foot_sensors_layout(s->L);
+    SimModel& m = s->plant.fs;
+    if (!params) { sim_drop(s, m); return 0; }
+    // (every check before anything changes: a bad row leaves the previous configuration in force)
+    sim_check_rows("sim_foot_sensors", params, s->L.B, MPC_SIM_FOOT_SENSORS_PARAMS, [&](const std::string& row, const double* r, int) {
+      sim_int_check(row, "delay", r[0], MPC_SIM_FOOT_SENSORS_RING, std::to_string(MPC_SIM_FOOT_SENSORS_RING - 1) + "]");
+      sim_nonneg_check(row, "sigma_f, sigma_m, bias_f, bias_m and time_constant", r + 1, 5);
       if (r[7] > r[6]) throw std::runtime_error(row + ": f_off must be <= f_on");
       for (int e = 8; e < 10; ++e)
         if (r[e] != std::floor(r[e]) || r[e] < 1.0) throw std::runtime_error(row + ": on_steps and off_steps must be integer values >= 1");
-      if (r[10] != std::floor(r[10]) || r[10] < 0.0 || r[10] >= 4294967296.0) throw std::runtime_error(row + ": seed must be an integer value in [0, 2^32)");
-      for (int e = 11; e < MPC_SIM_FOOT_SENSORS_PARAMS; ++e)
-        if (r[e] != 0.0) throw std::runtime_error(row + ": the reserved entries must be 0");
-    }
-    if (!s->plant.d_con) throw std::runtime_error("sim_foot_sensors: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
-    sim_realloc(s, s->plant.d_fs, np + (size_t)L.B * MPC_SIM_FOOT_SENSORS_WIDTH);
-    s->plant.h_fs.assign(params, params + np);
+      sim_int_check(row, "seed", r[10], 4294967296.0, "2^32)");
+      sim_reserved_check(row, r, 11, MPC_SIM_FOOT_SENSORS_PARAMS);
+    });
+    if (m.needs_rule) sim_rule_check(s, "sim_foot_sensors");
+    sim_realloc(s, m.d, l.total);
+    m.h.assign(params, params + l.np);
     sim_ensure(s);
-    copy_sync(s, s->plant.d_fs, params, np * sizeof(double), hipMemcpyHostToDevice);
+    copy_sync(s, m.d, params, l.np * sizeof(double), hipMemcpyHostToDevice);
     sim_foot_sensors_arm(s, nullptr);
   })
 }
 
 int mpc_sim_foot_sensors_read(mpc_solver* s, double* params, double* state) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_foot_sensors_read");
-    if (!s->plant.d_fs) throw std::runtime_error("sim_foot_sensors_read: the foot sensors are off on this handle (turn them on with mpc_sim_foot_sensors)");
-    if (params) std::copy(s->plant.h_fs.begin(), s->plant.h_fs.end(), params);
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (state) copy_sync(s, state, sim_foot_sensors_rows(s), (size_t)s->L.B * MPC_SIM_FOOT_SENSORS_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
-  })
+  MPC_TRY(s, { sim_model_read(s, "sim_foot_sensors_read", s->plant.fs, sim_foot_sensors_layout(s->L), params, state); })
 }
 
 int mpc_sim_foot_sensors_set(mpc_solver* s, const double* state) {
   MPC_TRY(s, {
-    if (!state) throw std::runtime_error("sim_foot_sensors_set: state must not be null");
-    sim_check(s, "sim_foot_sensors_set");
-    if (!s->plant.d_fs) throw std::runtime_error("sim_foot_sensors_set: the foot sensors are off on this handle (turn them on with mpc_sim_foot_sensors)");
-    const Layout& L = s->L;
-    const size_t W = MPC_SIM_FOOT_SENSORS_WIDTH;
-    for (int b = 0; b < L.B; ++b) {
-      const double* r = state + (size_t)b * W;
-      const std::string row = "sim_foot_sensors_set: row " + std::to_string(b);
-      for (size_t e = 0; e < W; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
-      for (int i = 0; i < 2; ++i)
-        if (r[i] != 0.0 && r[i] != 1.0) throw std::runtime_error(row + ": det must be 0 or 1");
+    const SimLayout l = sim_foot_sensors_layout(s->L);
+    sim_rows_set(s, "sim_foot_sensors_set", s->plant.fs, l, state, -1, [&](const std::string& row, const double* r, int) {
+      sim_flags_check(row, "det", r, 2);
       if (r[0] == 0.0 && r[1] == 0.0) throw std::runtime_error(row + " has no sole detected (the detector never reports an empty set)");
-      for (int e = SIM_FS_O_ABOVE; e < SIM_FS_O_WF; ++e)
-        if (r[e] < 0.0) throw std::runtime_error(row + ": the counters above and below must be >= 0");
-      for (int e = SIM_FS_O_COUNTS; e < SIM_FS_O_RING; ++e)
-        if (r[e] < 0.0) throw std::runtime_error(row + ": the confusion counts must be >= 0");
-      const double head = r[W - 2], count = r[W - 1];
-      if (head != std::floor(head) || head < 0.0 || head >= MPC_SIM_FOOT_SENSORS_RING)
-        throw std::runtime_error(row + ": head must be an integer value in [0, " + std::to_string(MPC_SIM_FOOT_SENSORS_RING) + ")");
-      if (count < 0.0) throw std::runtime_error(row + ": count must be >= 0");
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    copy_sync(s, sim_foot_sensors_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
+      sim_nonneg_check(row, "the counters above and below", r + SIM_FS_O_ABOVE, SIM_FS_O_WF - SIM_FS_O_ABOVE);
+      sim_nonneg_check(row, "the confusion counts", r + SIM_FS_O_COUNTS, SIM_FS_O_RING - SIM_FS_O_COUNTS);
+      sim_ring_check(row, r, l.width, MPC_SIM_FOOT_SENSORS_RING, 0);
+    });
   })
 }
 
@@ -915,7 +908,7 @@ int32_t mpc_sim_foot_sensors_width(mpc_solver* s) { return sim_width(s, "sim_foo
 int mpc_sim_foot_sensors_feed(mpc_solver* s, int32_t consumers) {
   MPC_TRY(s, {
     sim_check(s, "sim_foot_sensors_feed");
-    if (!s->plant.d_fs) throw std::runtime_error("sim_foot_sensors_feed: the foot sensors are off on this handle (turn them on with mpc_sim_foot_sensors)");
+    sim_on_check(s->plant.fs, "sim_foot_sensors_feed");
     if (consumers & ~(MPC_SIM_FOOT_SENSORS_FEED_ESTIMATOR | MPC_SIM_FOOT_SENSORS_FEED_QP))
       throw std::runtime_error("sim_foot_sensors_feed: unknown consumer bit in " + std::to_string(consumers) + " (1: the estimator, 2: the low-level QPs)");
     HIP_OK(hipStreamSynchronize(s->stream));
@@ -928,41 +921,32 @@ int mpc_sim_plant(mpc_solver* s, const double* params, const double* link_scale)
   MPC_TRY(s, {
     sim_check(s, "sim_plant");
     const Layout& L = s->L;
-    if (!params) {
-      sim_realloc(s, s->plant.d_plant, 0);
-      s->plant.h_plant.clear();
-      s->plant.plant_nd = s->plant.plant_off = 0;
-      return 0;
-    }
+    SimPlant& p = s->plant;
+    if (!params) { sim_drop(s, p.pm); return 0; }
     // (every check before anything changes: a bad row leaves the previous configuration in force)
     if (!s->have_model || !s->d_model_d || s->h_model_i.empty()) throw std::runtime_error("sim_plant: no model is set on this handle (mpc_set_model first)");
     const int nj = L.nj;
-    const size_t np = (size_t)L.B * MPC_SIM_PLANT_PARAMS;
-    std::vector<double> h(np + (size_t)L.B * nj, 1.0);
-    for (int b = 0; b < L.B; ++b) {
-      const double* r = params + (size_t)b * MPC_SIM_PLANT_PARAMS;
-      const std::string row = "sim_plant: row " + std::to_string(b);
-      for (int e = 0; e < MPC_SIM_PLANT_PARAMS; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+    const SimLayout l = sim_plant_layout(L, s->model_nd);
+    std::vector<double> h(params, params + l.np);
+    h.resize(l.out, 1.0);  // (link_scale: ones when none is given)
+    sim_check_rows("sim_plant", params, L.B, MPC_SIM_PLANT_PARAMS, [&](const std::string& row, const double* r, int) {
       if (!(r[0] > 0.0) || !(r[1] > 0.0)) throw std::runtime_error(row + ": mass_scale and inertia_scale must be > 0");
-      if (r[7] < 0.0) throw std::runtime_error(row + ": payload_mass must be >= 0");
+      sim_nonneg_check(row, "payload_mass", r + 7, 1);
       for (int e : {2, 6})
-        if (r[e] != std::floor(r[e]) || r[e] < 0.0 || r[e] > nj - 1)
+        if (!sim_is_index(r[e], nj))
           throw std::runtime_error(row + ": shift_body and payload_body must be integer values in [0, " + std::to_string(nj - 1) + "] (table joint indices)");
-      for (int e = 11; e < MPC_SIM_PLANT_PARAMS; ++e)
-        if (r[e] != 0.0) throw std::runtime_error(row + ": the reserved entries must be 0");
-      std::copy(r, r + MPC_SIM_PLANT_PARAMS, h.begin() + (size_t)b * MPC_SIM_PLANT_PARAMS);
-    }
+      sim_reserved_check(row, r, 11, MPC_SIM_PLANT_PARAMS);
+    });
     if (link_scale)
       for (size_t e = 0; e < (size_t)L.B * nj; ++e) {
         if (!std::isfinite(link_scale[e]) || !(link_scale[e] > 0.0))
           throw std::runtime_error("sim_plant: link_scale must be finite and > 0 (robot " + std::to_string(e / nj) + ", joint " + std::to_string(e % nj) + ")");
-        h[np + e] = link_scale[e];
+        h[l.tables + e] = link_scale[e];
       }
-    sim_realloc(s, s->plant.d_plant, h.size() + (size_t)L.B * s->model_nd);
-    s->plant.plant_nd = s->model_nd;
-    s->plant.plant_off = h.size();
-    s->plant.h_plant = h;
+    sim_realloc(s, p.pm.d, l.total);
+    p.plant_nd = s->model_nd;
+    p.plant_off = l.out;
+    p.pm.h = h;
     sim_plant_build(s);
   })
 }
@@ -970,13 +954,13 @@ int mpc_sim_plant(mpc_solver* s, const double* params, const double* link_scale)
 int mpc_sim_plant_read(mpc_solver* s, double* params, double* link_scale, double* tables) {
   MPC_TRY(s, {
     sim_check(s, "sim_plant_read");
-    if (!s->plant.d_plant) throw std::runtime_error("sim_plant_read: the plant model is off on this handle (turn it on with mpc_sim_plant)");
-    const Layout& L = s->L;
-    const size_t np = (size_t)L.B * MPC_SIM_PLANT_PARAMS;
-    if (params) std::copy(s->plant.h_plant.begin(), s->plant.h_plant.begin() + np, params);
-    if (link_scale) std::copy(s->plant.h_plant.begin() + np, s->plant.h_plant.end(), link_scale);
+    const SimPlant& p = s->plant;
+    sim_on_check(p.pm, "sim_plant_read");
+    const SimLayout l = sim_plant_layout(s->L, p.plant_nd);
+    if (params) std::copy(p.pm.h.begin(), p.pm.h.begin() + l.np, params);
+    if (link_scale) std::copy(p.pm.h.begin() + l.tables, p.pm.h.end(), link_scale);
     HIP_OK(hipStreamSynchronize(s->stream));
-    if (tables) copy_sync(s, tables, sim_plant_tables(s), (size_t)L.B * s->plant.plant_nd * sizeof(double), hipMemcpyDeviceToHost);
+    if (tables) copy_sync(s, tables, p.pm.d + l.out, (l.total - l.out) * sizeof(double), hipMemcpyDeviceToHost);
   })
 }
 
@@ -992,12 +976,10 @@ int mpc_sim_friction(mpc_solver* s, const double* params) {
   MPC_TRY(s, {
     sim_check(s, "sim_friction");
     const Layout& L = s->L;
-    const size_t np = (size_t)L.B * MPC_SIM_FRICTION_PARAMS;
-    if (!params) {
-      sim_friction_drop(s);
-      return 0;
-    }
-    for (int b = 0; b < L.B; ++b) {  // (every check before anything changes: a bad row leaves the previous configuration in force)
+    const SimLayout l = sim_friction_layout(L);
+    SimModel& m = s->plant.fr;
+    if (!params) { sim_drop(s, m); return 0; }
+    for (int b = 0; b < L.B; ++b) {  // (every check before anything changes: a bad row leaves the previous configuration in force; mu may be +inf)
       const double* r = params + (size_t)b * MPC_SIM_FRICTION_PARAMS;
       const std::string row = "sim_friction: row " + std::to_string(b);
       for (int e = 0; e < 4; ++e)
@@ -1005,49 +987,31 @@ int mpc_sim_friction(mpc_solver* s, const double* params) {
       for (int e = 4; e < MPC_SIM_FRICTION_PARAMS; ++e)
         if (!std::isfinite(r[e]) || !(r[e] > 0.0)) throw std::runtime_error(row + ": m_slip, I_slip, v_max and w_max must be finite and > 0, entry " + std::to_string(e));
     }
-    if (!s->plant.d_con) throw std::runtime_error("sim_friction: the contact rule is off on this handle (turn it on with mpc_sim_contacts first)");
-    sim_realloc(s, s->plant.d_fr, np + (size_t)L.B * MPC_SIM_FRICTION_WIDTH);
-    s->plant.h_fr.assign(params, params + np);
+    if (m.needs_rule) sim_rule_check(s, "sim_friction");
+    sim_realloc(s, m.d, l.total);
+    m.h.assign(params, params + l.np);
     sim_ensure(s);
-    std::vector<double> h(s->plant.h_fr);
-    h.resize(np + (size_t)L.B * MPC_SIM_FRICTION_WIDTH, 0.0);  // (the state rows after a reset: all 0)
-    copy_sync(s, s->plant.d_fr, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+    std::vector<double> h(m.h);
+    h.resize(l.total, 0.0);  // (the state rows after a reset: all 0)
+    copy_sync(s, m.d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
   })
 }
 
 int mpc_sim_friction_read(mpc_solver* s, double* params, double* state) {
-  MPC_TRY(s, {
-    sim_check(s, "sim_friction_read");
-    if (!s->plant.d_fr) throw std::runtime_error("sim_friction_read: the friction model is off on this handle (turn it on with mpc_sim_friction)");
-    if (params) std::copy(s->plant.h_fr.begin(), s->plant.h_fr.end(), params);
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (state) copy_sync(s, state, sim_friction_rows(s), (size_t)s->L.B * MPC_SIM_FRICTION_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
-  })
+  MPC_TRY(s, { sim_model_read(s, "sim_friction_read", s->plant.fr, sim_friction_layout(s->L), params, state); })
 }
 
 int mpc_sim_friction_set(mpc_solver* s, const double* state) {
   MPC_TRY(s, {
-    if (!state) throw std::runtime_error("sim_friction_set: state must not be null");
-    sim_check(s, "sim_friction_set");
-    if (!s->plant.d_fr) throw std::runtime_error("sim_friction_set: the friction model is off on this handle (turn it on with mpc_sim_friction)");
-    const Layout& L = s->L;
-    const size_t W = MPC_SIM_FRICTION_WIDTH;
-    for (int b = 0; b < L.B; ++b) {
-      const double* r = state + (size_t)b * W;
-      const std::string row = "sim_friction_set: row " + std::to_string(b);
-      for (size_t e = 0; e < W; ++e)
-        if (!std::isfinite(r[e])) throw std::runtime_error(row + " holds a non-finite entry (" + std::to_string(e) + ")");
+    const SimLayout l = sim_friction_layout(s->L);
+    sim_rows_set(s, "sim_friction_set", s->plant.fr, l, state, -1, [&](const std::string& row, const double* r, int) {
       for (int i = 0; i < 2; ++i) {
-        const double fl = r[SIM_FR_O_SLIDING + i];
-        if (fl != 0.0 && fl != 1.0) throw std::runtime_error(row + ": sliding must be 0 or 1");
-        if (fl == 0.0 && (r[3 * i] != 0.0 || r[3 * i + 1] != 0.0 || r[3 * i + 2] != 0.0))
+        sim_flags_check(row, "sliding", r + SIM_FR_O_SLIDING + i, 1);
+        if (r[SIM_FR_O_SLIDING + i] == 0.0 && (r[3 * i] != 0.0 || r[3 * i + 1] != 0.0 || r[3 * i + 2] != 0.0))
           throw std::runtime_error(row + ": sole " + std::to_string(i) + " holds a velocity but its sliding flag is 0");
       }
-      for (size_t e = SIM_FR_O_STEPS; e < W; ++e)
-        if (r[e] < 0.0) throw std::runtime_error(row + ": slip_steps, slip_dist, slip_yaw, peak_excess and steps must be >= 0");
-    }
-    HIP_OK(hipStreamSynchronize(s->stream));
-    copy_sync(s, sim_friction_rows(s), state, (size_t)L.B * W * sizeof(double), hipMemcpyHostToDevice);
+      sim_nonneg_check(row, "slip_steps, slip_dist, slip_yaw, peak_excess and steps", r + SIM_FR_O_STEPS, (int)l.width - SIM_FR_O_STEPS);
+    });
   })
 }
 
@@ -1058,10 +1022,8 @@ int mpc_sim_disturbances(mpc_solver* s, const double* events, int32_t n_events) 
   MPC_TRY(s, {
     sim_check(s, "sim_disturbances");
     const Layout& L = s->L;
-    if (!events) {
-      sim_disturbances_drop(s);
-      return 0;
-    }
+    SimPlant& p = s->plant;
+    if (!events) { sim_drop(s, p.dis); return 0; }
     // (every check before anything changes: a bad event leaves the previous configuration in force)
     if (n_events < 1 || n_events > MPC_SIM_DISTURBANCES_MAX_EVENTS)
       throw std::runtime_error("sim_disturbances: n_events must be 1 .. " + std::to_string(MPC_SIM_DISTURBANCES_MAX_EVENTS));
@@ -1091,39 +1053,36 @@ int mpc_sim_disturbances(mpc_solver* s, const double* events, int32_t n_events) 
         if (v[6] < 0.0 || v[6] > L.nj - 1) throw std::runtime_error(ev + "link must be in [0, " + std::to_string(L.nj - 1) + "] (table joint indices)");
         if (v[0] >= 2.0) contact = true;
       }
-    if (contact && !s->plant.d_con)
+    if (contact && !p.d_con)
       throw std::runtime_error("sim_disturbances: a contact trigger (2 to 5) needs the contact rule, which is off on this handle (turn it on with mpc_sim_contacts first)");
-    if (s->plant.push_width)
+    if (p.push_width)
       throw std::runtime_error("sim_disturbances: a push is armed on this handle (mpc_sim_set_push): disarm it with mpc_sim_set_push(sim, NULL, 0) before arming a schedule");
-    const size_t head = (size_t)L.B * n_events * MPC_SIM_DISTURBANCES_EVENT;
+    const SimLayout l = sim_disturbances_layout(L, n_events);
     sim_ensure(s);
     {  // (the new buffer before the old one goes: an allocation that fails leaves the table in force as it was)
       void* fresh = nullptr;
-      HIP_OK(hipMalloc(&fresh, sim_disturbances_doubles(L, n_events) * sizeof(double)));
+      HIP_OK(hipMalloc(&fresh, l.total * sizeof(double)));
       HIP_OK(hipStreamSynchronize(s->stream));
-      if (s->plant.d_dis) (void)hipFree(s->plant.d_dis);
-      s->plant.d_dis = (double*)fresh;
+      if (p.dis.d) (void)hipFree(p.dis.d);
+      p.dis.d = (double*)fresh;
     }
-    s->plant.h_dis.assign(events, events + head);
-    s->plant.dis_ne = n_events;
-    s->plant.dis_contact = contact;
-    copy_sync(s, s->plant.d_dis, events, head * sizeof(double), hipMemcpyHostToDevice);
+    p.dis.h.assign(events, events + l.np);
+    p.dis_ne = n_events;
+    p.dis_contact = contact;
+    copy_sync(s, p.dis.d, events, l.np * sizeof(double), hipMemcpyHostToDevice);
     sim_disturbances_reset(s);
   })
 }
 
 int mpc_sim_disturbances_read(mpc_solver* s, double* events, double* state, double* applied) {
   MPC_TRY(s, {
-    sim_check(s, "sim_disturbances_read");
-    if (!s->plant.d_dis) throw std::runtime_error("sim_disturbances_read: the disturbance schedule is off on this handle (turn it on with mpc_sim_disturbances)");
     const Layout& L = s->L;
-    if (events) std::copy(s->plant.h_dis.begin(), s->plant.h_dis.end(), events);
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (state) copy_sync(s, state, sim_disturbances_rows(s), (size_t)L.B * MPC_SIM_DISTURBANCES_WIDTH * sizeof(double), hipMemcpyDeviceToHost);
+    const SimLayout l = sim_disturbances_layout(s);
+    sim_model_read(s, "sim_disturbances_read", s->plant.dis, l, events, state);
     if (applied) {
-      std::vector<double> h((size_t)L.B * 6 + ((size_t)L.B + 1) / 2);
-      copy_sync(s, h.data(), sim_disturbances_out(s), h.size() * sizeof(double), hipMemcpyDeviceToHost);
-      const int32_t* link = (const int32_t*)(h.data() + (size_t)L.B * 6);
+      std::vector<double> h(l.total - l.out);
+      copy_sync(s, h.data(), s->plant.dis.d + l.out, h.size() * sizeof(double), hipMemcpyDeviceToHost);
+      const int32_t* link = (const int32_t*)(h.data() + (l.tail - l.out));
       for (int b = 0; b < L.B; ++b) {
         std::copy(h.begin() + (size_t)b * 6, h.begin() + (size_t)b * 6 + 6, applied + (size_t)b * 7);
         applied[(size_t)b * 7 + 6] = (double)link[b];
@@ -1135,7 +1094,7 @@ int mpc_sim_disturbances_read(mpc_solver* s, double* events, double* state, doub
 int mpc_sim_disturbances_reset(mpc_solver* s) {
   MPC_TRY(s, {
     sim_check(s, "sim_disturbances_reset");
-    if (!s->plant.d_dis) throw std::runtime_error("sim_disturbances_reset: the disturbance schedule is off on this handle (turn it on with mpc_sim_disturbances)");
+    sim_on_check(s->plant.dis, "sim_disturbances_reset");
     sim_disturbances_reset(s);
   })
 }
