@@ -37,6 +37,16 @@
 #define LK_PT 13     // matrix elements per thread parked in registers (np <= 80: 6400 / 512)
 #define LK_TILES 5   // output tiles per wavefront: nb (nb + nbm) <= 35 on 8 wavefronts
 
+// Row-mapped operand moves of the fixed-dimension instantiations (n, m compile-time constants): a wavefront owns the rows wv, wv + 8, ...
+// of a matrix and a lane a fixed PAIR of adjacent columns, so an element's address is one per-lane base (computed once per knot) plus a
+// compile-time constant per row — no division, no column select and no bounds predicate per element, as the flat index tid + u * 512
+// of the generic form needs.  A pair is one 16-byte global load: n, m and every leading dimension in HBM (n, nz, mpad) are even, every
+// offset inside a record and both record strides are rounded to even counts by take() (layout.h), the buffers come from hipMalloc.
+// Pad columns are written by the spare lanes of the same pass, pad rows by the wavefronts that own them: registers that loaded nothing
+// hold 0.0.  Narrow matrices (Mu, Znu: mp / 2 pairs in a row) put 64 / (mp / 2) rows into one wavefront instruction.
+DEV double2 leg_ld2(const double* p) { return *(const double2*)p; }
+DEV void leg_st2(double* p, double2 v) { *(double2*)p = v; }  // 16-byte aligned destinations only (even leading dimension)
+
 struct LkLds {
   int np, mp, nzp, lda, ldp, ldm, nb, nbm;  // lda: leading dimension of the [A B] buffer (odd: rows AND columns are read with a lane stride)
   int AB, PR, TM, ZN, vec, total_bytes;
@@ -95,10 +105,45 @@ DEV void leg_knot_body(const SolverArgs& a, const LkLds& Srt, const int b, const
 
   // ---- the operands of a knot, as the registers of the prefetch hold them ----
   double pab[NAB], pkm[NK], ptv[LK_PT], pmu[NMU], pzn[NZN], psm = 0.0, pact = 0.0;  // psm: k / T6 / mx element of this thread
+  // fixed dimensions: the same operands by rows (see leg_ld2 above).  XRW / XRK: rows of an np-row / mp-row matrix per wavefront ;
+  // XML lanes hold a row of Mu / Znu, XMR rows go into one instruction, XQM / XQZ instructions per wavefront cover mp / 16 rows
+  static_assert(!FX || (FN % 2 == 0 && FM % 2 == 0), "row-mapped moves: column pairs must not straddle the A | B boundary and must be 16-byte aligned");
+  constexpr int XNP = FX ? SC_.np : 16, XMP = FX ? SC_.mp : 16, XRW = XNP / (LK_THREADS / 64), XRK = XMP / (LK_THREADS / 64);
+  constexpr int XML = XMP / 2, XMR = 64 / XML, XQM = (XMP + 8 * XMR - 1) / (8 * XMR), XQZ = (16 + 8 * XMR - 1) / (8 * XMR);
+  static_assert(!FX || (XNP + XMP <= 128 && XML <= 64 && XMP % XMR == 0 && 16 % XMR == 0), "row-mapped moves: a row of [A B] is at most 64 column pairs, whole groups of Mu / Znu rows");
+  double2 rab[XRW], rkm[XRK], rpt[XRW], rmu[XQM], rzn[XQZ];
   auto request_ab = [&](int k) {  // [A B], K, the small vectors, the active-row flags
     const double* kn = knot_ptr(a, b, k);
     const double* g = gain_ptr(a, b, k);
     const int m = (int)kn[L.oMISC + MISC_M], c = (int)kn[L.oMISC + MISC_NC];
+    if constexpr (FX) {
+      // [A B]: lane -> LDS columns zp, zp + 1 ; the u columns start at np in LDS and at n in the record
+      const int zp = 2 * lane;
+      const bool isa = zp < FN;
+      const double* src = kn + L.oAB + wv * (FN + FM) + (isa ? zp : zp - (XNP - FN));
+      const bool ld = isa || (zp >= XNP && zp - XNP < m);
+#pragma unroll
+      for (int r = 0; r < XRW; ++r) rab[r] = double2{0.0, 0.0};
+      if (ld) {
+#pragma unroll
+        for (int r = 0; r < XRW; ++r) if (8 * r + 7 < FN || wv + 8 * r < FN) rab[r] = leg_ld2(src + 8 * r * (FN + FM));
+      }
+      // K: mp x np, rows below the knot's m, columns below n
+      const double* ksrc = g + L.oK + wv * FN + zp;
+#pragma unroll
+      for (int r = 0; r < XRK; ++r) rkm[r] = double2{0.0, 0.0};
+      if (isa) {
+#pragma unroll
+        for (int r = 0; r < XRK; ++r) if (wv + 8 * r < m) rkm[r] = leg_ld2(ksrc + 8 * r * FN);
+      }
+      // wavefront 0: k ; 1: T6 ; 2, 3: mx
+      psm = 0.0;
+      if (wv == 0) { if (lane < m) psm = g[L.ok + lane]; }
+      else if (wv == 1) { if (lane < 36) psm = g[L.oT6 + lane]; }
+      else if (wv < 4) { if (tid - 128 < FN) psm = g[L.omx + tid - 128]; }
+      pact = (tid < c) ? kn[L.oACT + tid] : 0.0;  // c <= LK_THREADS (checked by the host)
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < NAB; ++u) {
       const int idx = tid + u * nthr, i = qdiv(idx, S.mg_nzp), zp = (idx - qdiv(idx, S.mg_nzp) * nzp);
@@ -116,6 +161,16 @@ DEV void leg_knot_body(const SolverArgs& a, const LkLds& Srt, const int b, const
   };
   auto request_pt = [&](int k) {  // Pt, Mu, Znu
     const double* g = gain_ptr(a, b, k);
+    if constexpr (FX) {
+      const double* src = g + L.oMx + wv * FN + 2 * lane;
+#pragma unroll
+      for (int r = 0; r < XRW; ++r) rpt[r] = double2{0.0, 0.0};
+      if (2 * lane < FN) {
+#pragma unroll
+        for (int r = 0; r < XRW; ++r) if (8 * r + 7 < FN || wv + 8 * r < FN) rpt[r] = leg_ld2(src + 8 * r * FN);
+      }
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < LK_PT; ++u) {
       const int idx = tid + u * nthr, i = qdiv(idx, S.mg_np), j = (idx - qdiv(idx, S.mg_np) * np);
@@ -124,25 +179,56 @@ DEV void leg_knot_body(const SolverArgs& a, const LkLds& Srt, const int b, const
   };
   auto request_mu = [&](int k) {
     const double* g = gain_ptr(a, b, k);
+    if constexpr (FX) {
+      // Mu (mp x mp) and the first 16 rows of Znu, both with leading dimension mp in the record: XMR rows per instruction
+      const int sub = lane / XML, off = (wv * XMR + sub) * XMP + 2 * (lane - sub * XML);
+      const bool on = lane < XMR * XML;
+#pragma unroll
+      for (int q = 0; q < XQM; ++q) { rmu[q] = double2{0.0, 0.0}; if ((wv + 8 * q) * XMR < XMP && on) rmu[q] = leg_ld2(g + L.oMu + off + 8 * q * XMR * XMP); }
+#pragma unroll
+      for (int q = 0; q < XQZ; ++q) { rzn[q] = double2{0.0, 0.0}; if ((wv + 8 * q) * XMR < 16 && on) rzn[q] = leg_ld2(g + L.oZnu + off + 8 * q * XMR * XMP); }
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < NMU; ++u) { const int idx = tid + u * nthr; pmu[u] = (idx < mp * mp) ? g[L.oMu + idx] : 0.0; }
 #pragma unroll
     for (int u = 0; u < NZN; ++u) { const int idx = tid + u * nthr; pzn[u] = (idx < 16 * mp) ? g[L.oZnu + idx] : 0.0; }
   };
 
+  // knot k lies in a parametric leg: below the start of the last leg.  Fixed dimensions: that start once per workgroup (leg_of_knot walks
+  // the legs with a 64-bit division each, three times per knot)
+  const int klast = FX ? leg_start(a, a.nlegs - 1) : 0;
+  auto parametric = [&](int k) { if constexpr (FX) return k < klast; else return leg_of_knot(a, k) + 1 < a.nlegs; };
   request_ab(kbeg);
   request_pt(kbeg);
-  if (leg_of_knot(a, kbeg) + 1 < a.nlegs) request_mu(kbeg);
+  if (parametric(kbeg)) request_mu(kbeg);
   for (int k = kbeg; k < kend; ++k) {
     const double* kn = knot_ptr(a, b, k);
     double* g = gain_ptr(a, b, k);
     const int m = (int)kn[L.oMISC + MISC_M];
-    const bool par = leg_of_knot(a, k) + 1 < a.nlegs;
-    const bool more = k + 1 < kend, par_next = more && leg_of_knot(a, k + 1) + 1 < a.nlegs;
+    const bool par = parametric(k);
+    const bool more = k + 1 < kend, par_next = more && parametric(k + 1);
     LEG_BARRIER();  // the previous knot of the chunk is done with every buffer
     LEG_LAUNDER();
     if (a.prof) tk0_ = clock64();
     // ---- stage 1: [A B] and K into LDS (zero padded; u-columns of [A B] start at np) ; A_cl = A + B K in place ; y0 = B k + mx ----
+    if constexpr (FX) {
+      const int zp = 2 * lane;
+      if (zp < XNP + XMP) {  // lda is odd: two 8-byte stores ; a pair whose second column is at or beyond the knot's m keeps only its first
+        const bool hi = zp < XNP || zp + 1 - XNP < m;
+        double* d = AB + wv * lda + zp;
+#pragma unroll
+        for (int r = 0; r < XRW; ++r) { d[8 * r * lda] = rab[r].x; d[8 * r * lda + 1] = hi ? rab[r].y : 0.0; }
+      }
+      if (zp < XNP) {
+        double* d = KM + wv * XNP + zp;
+#pragma unroll
+        for (int r = 0; r < XRK; ++r) leg_st2(d + 8 * r * XNP, rkm[r]);
+      }
+      if (wv == 0) { if (lane < XMP) kf[lane] = psm; }
+      else if (wv == 1) { if (lane < 36) t6[lane] = psm; }
+      else if (wv < 4) { if (tid - 128 < XNP) mxs[tid - 128] = psm; }
+    } else {
 #pragma unroll
     for (int u = 0; u < NAB; ++u) { const int idx = tid + u * nthr; if (idx < np * nzp) AB[(qdiv(idx, S.mg_nzp)) * lda + (idx - qdiv(idx, S.mg_nzp) * nzp)] = pab[u]; }
 #pragma unroll
@@ -150,6 +236,7 @@ DEV void leg_knot_body(const SolverArgs& a, const LkLds& Srt, const int b, const
     if (tid < mp) kf[tid] = psm;
     else if (tid >= 64 && tid < 100) t6[tid - 64] = psm;
     else if (tid >= 128 && tid < 128 + np) mxs[tid - 128] = psm;
+    }
     int ca = 0;
     if (par) {
       const unsigned long long act = __ballot(pact != 0.0);
@@ -177,8 +264,16 @@ DEV void leg_knot_body(const SolverArgs& a, const LkLds& Srt, const int b, const
     LEG_BARRIER();  // K is dead: Pt takes its place
     LEG_LAUNDER();
     // ---- stage 2: Pt into LDS ; [M | Bl] = (I - mu_d Pt) [A_cl | B] (products to registers, then in place) ; z0 = y0 - mu_d Pt y0 ----
+    if constexpr (FX) {
+      if (2 * lane < XNP) {
+        double* d = PT + wv * ldp + 2 * lane;
+#pragma unroll
+        for (int r = 0; r < XRW; ++r) { d[8 * r * ldp] = rpt[r].x; d[8 * r * ldp + 1] = rpt[r].y; }
+      }
+    } else {
 #pragma unroll
     for (int u = 0; u < LK_PT; ++u) { const int idx = tid + u * nthr; if (idx < np * np) PT[(qdiv(idx, S.mg_np)) * ldp + (idx - qdiv(idx, S.mg_np) * np)] = ptv[u]; }
+    }
     LEG_BARRIER();
     LEG_LAUNDER();
     if (more) request_pt(k + 1);
@@ -244,10 +339,22 @@ DEV void leg_knot_body(const SolverArgs& a, const LkLds& Srt, const int b, const
     LEG_LAUNDER();
     if (par) {
       // ---- stage 4: Mu (into PR behind the place of U1: Pt is dead), Znu ; U1 = Mu Bc^T (-> Ku = -U1, kept for stage 5) ; V1 = Znu Bc^T (-> Knup = -V1) ----
+      if constexpr (FX) {
+        const int sub = lane / XML, off = (wv * XMR + sub) * ldm + 2 * (lane - sub * XML);
+        const bool on = lane < XMR * XML;
+#pragma unroll
+        for (int q = 0; q < XQM; ++q) if ((wv + 8 * q) * XMR < XMP && on) { double* d = MU + off + 8 * q * XMR * ldm; d[0] = rmu[q].x; d[1] = rmu[q].y; }
+#pragma unroll
+        for (int q = 0; q < XQZ; ++q) if ((wv + 8 * q) * XMR < 16 && on) {
+          const bool live = (wv + 8 * q) * XMR + sub < ca && ca <= 16;
+          double* d = ZN + off + 8 * q * XMR * ldm; d[0] = live ? rzn[q].x : 0.0; d[1] = live ? rzn[q].y : 0.0;
+        }
+      } else {
 #pragma unroll
       for (int u = 0; u < NMU; ++u) { const int idx = tid + u * nthr; if (idx < mp * mp) MU[(qdiv(idx, S.mg_mp)) * ldm + (idx - qdiv(idx, S.mg_mp) * mp)] = pmu[u]; }
 #pragma unroll
       for (int u = 0; u < NZN; ++u) { const int idx = tid + u * nthr; if (idx < 16 * mp) ZN[(qdiv(idx, S.mg_mp)) * ldm + (idx - qdiv(idx, S.mg_mp) * mp)] = (qdiv(idx, S.mg_mp) < ca && ca <= 16) ? pzn[u] : 0.0; }
+      }
       LEG_BARRIER();
       LEG_LAUNDER();
       if (par_next) request_mu(k + 1);
@@ -287,11 +394,20 @@ DEV void leg_knot_body(const SolverArgs& a, const LkLds& Srt, const int b, const
         const int t = wv + sidx * nw;
         if (t < nbm * nb) {
           const int ri = t / nb, cj = t % nb, col = cj * 16 + (lane & 15);
+          if (FX && ri * 16 + 15 < m && cj + 1 < nb) {  // a tile inside Ku (wave-uniform): no bounds tests
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int row = ri * 16 + (lane >> 4) + 4 * q;
+              U1[row * np + col] = ures[sidx][q];
+              g[L.oKu + row * n + col] = -ures[sidx][q];
+            }
+          } else {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int row = ri * 16 + (lane >> 4) + 4 * q;
             U1[row * np + col] = ures[sidx][q];  // beside Mu (other wavefronts may still read it), not over it
             if (row < m && col < n) g[L.oKu + row * n + col] = -ures[sidx][q];
+          }
           }
         }
       }
@@ -305,6 +421,20 @@ DEV void leg_knot_body(const SolverArgs& a, const LkLds& Srt, const int b, const
       for (int t = wv; t < nb * nb; t += nw) {
         const int ri = t / nb, cj = t % nb, col = cj * 16 + (lane & 15);
         double ptt[4];
+        if (FX && ri > 0 && cj > 0 && ri + 1 < nb && cj + 1 < nb) {  // a tile off block row / column 0 and off the last ones (wave-uniform): T T^T is the identity there, T Pt T^T is Pt
+#pragma unroll
+          for (int q = 0; q < 4; ++q) ptt[q] = g[L.oMx + (ri * 16 + (lane >> 4) + 4 * q) * n + col];
+          d4_t acc = d4_t{0, 0, 0, 0};
+          mma_tile<false>(acc, AB + (ri * 16) * lda + np, lda, 1, U1 + cj * 16, np, 1, mp, lane);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int row = ri * 16 + (lane >> 4) + 4 * q;
+            const double tt = row == col ? 1.0 : 0.0;
+            const double tp = ptt[q];
+            g[L.oGam + row * n + col] = -acc[q] - mud * (tt - mud * tp);
+          }
+          continue;
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int row = ri * 16 + (lane >> 4) + 4 * q;
@@ -393,8 +523,23 @@ DEV void leg_condense_body(const SolverArgs& a, const LcLds& Srt, const int j, c
   }
   const int nst = nb * (nb + 1) / 2;
   double pa[LK_PT], pb[LK_PT], pphi;
+  // fixed dimensions: Phi and Gamma by rows (see leg_ld2 above), XRW rows per wavefront
+  static_assert(!FX || FN % 2 == 0, "row-mapped moves: 16-byte column pairs");
+  constexpr int XNP = FX ? SC_.np : 16, XRW = XNP / (LK_THREADS / 64);
+  double2 ra[XRW], rb[XRW];
   auto prefetch = [&](int kk) {
     const double* gk = gain_ptr(a, b, kk);
+    if constexpr (FX) {
+      const double* src = gk + wv * FN + 2 * lane;
+#pragma unroll
+      for (int r = 0; r < XRW; ++r) { ra[r] = double2{0.0, 0.0}; rb[r] = double2{0.0, 0.0}; }
+      if (2 * lane < FN) {
+#pragma unroll
+        for (int r = 0; r < XRW; ++r) if (8 * r + 7 < FN || wv + 8 * r < FN) { ra[r] = leg_ld2(src + L.oPhi + 8 * r * FN); rb[r] = leg_ld2(src + L.oGam + 8 * r * FN); }
+      }
+      pphi = gk[L.ophi + (tid < n ? tid : 0)];
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < LK_PT; ++u) {
       const int idx = tid + u * nthr, i = qdiv(idx, S.mg_np), c0 = (idx - qdiv(idx, S.mg_np) * np);
@@ -410,10 +555,18 @@ DEV void leg_condense_body(const SolverArgs& a, const LcLds& Srt, const int j, c
 #define LC_PROF(slot) do { if (a.prof && j == 0 && b == 2 && tid == 0) { const long long t1_ = clock64(); a.prof[128 + 32 + (slot)] += (double)(t1_ - tc0_); tc0_ = t1_; } } while (0)
   for (int k = ke; k >= ks; --k) {
     LEG_LAUNDER();
+    if constexpr (FX) {
+      if (2 * lane < XNP) {  // ldp is even: one 16-byte store per pair
+        const int off = wv * ldp + 2 * lane;
+#pragma unroll
+        for (int r = 0; r < XRW; ++r) { leg_st2(BA + off + 8 * r * ldp, ra[r]); leg_st2(BB + off + 8 * r * ldp, rb[r]); }
+      }
+    } else {
 #pragma unroll
     for (int u = 0; u < LK_PT; ++u) {
       const int idx = tid + u * nthr;
       if (idx < np * np) { BA[(qdiv(idx, S.mg_np)) * ldp + (idx - qdiv(idx, S.mg_np) * np)] = pa[u]; BB[(qdiv(idx, S.mg_np)) * ldp + (idx - qdiv(idx, S.mg_np) * np)] = pb[u]; }
+    }
     }
     if (tid < np) phi[tid] = (tid < n) ? pphi : 0.0;
     LEG_BARRIER();
@@ -470,7 +623,7 @@ DEV void leg_condense_body(const SolverArgs& a, const LcLds& Srt, const int j, c
         const int ri = t / nb, cj = t % nb, col = cj * 16 + (lane & 15);
         tile_store(LM + (ri * 16) * ldp + cj * 16, ldp, lres[sidx], lane);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { const int row = ri * 16 + (lane >> 4) + 4 * q; if (row < n && col < n) gk[L.oLm + row * n + col] = lres[sidx][q]; }
+        for (int q = 0; q < 4; ++q) { const int row = ri * 16 + (lane >> 4) + 4 * q; if (row < n && col < n) gk[L.oLm + row * n + col] = lres[sidx][q]; }  // (an interior form without the bounds tests was measured: slower, tools/experiments/README.md)
       }
     }
     LEG_BARRIER();

@@ -247,6 +247,7 @@ struct mpc_solver {
   // MPC_LEG_TAIL_KNOTS unset (-1): automatic, see leg_tail_knots ; 0: always the separate launches ; t > 0: t knots (at most the last leg)
   // whatever the grid.  MPC_LEG_TAIL_CUS: the compute-unit count the automatic rule sees (tests of the fallback).
   int env_tail_knots = -1, cu_count = 0;
+  int env_knot_chunk = 0;  // MPC_LEG_KNOT_CHUNK: knots per workgroup of k_leg_knot (unset or 0: one), read when the handle is created like the knobs above
   int tail_last = 0, tail_sweeps_last = 0;          // developer probes (debug_get "leg_tail"): tail knots and sweeps of the last pass,
   long long tail_fused = 0, tail_separate = 0;      // launches of k_leg_condense_tail / k_leg_condense so far,
   long long leg_passes_multi = 0, leg_passes_single = 0;  // passes with legs that swept several times (no cut guess yet) / once
@@ -258,10 +259,12 @@ struct mpc_solver {
     // add a round to the condensation), and k_leg_knot must need more than one round (N x B workgroups: with one round, batch 1 with 32
     // legs, taking knots away from it gains nothing and the tail only lengthens the condensation: p50 1.114 -> 1.136 ms measured).
     if ((long long)J * L.B > cu_count || (long long)L.N * L.B <= cu_count) return 0;
-    // A knot of the tail (stages 1 - 3 of the per-knot pass) takes about 1.2 times a knot of the condensation beside it, so the tail is
-    // 21 / 25 of a parametric leg: 64 x 4 legs, N = 100, sum of the two launches 1.221 ms with none, 1.142 / 1.126 / 1.125 / 1.140 / 1.171
-    // with 16 / 20 / 21 / 22 / 25 knots.
-    const int t = 21 * (L.N / J) / 25;
+    // A knot of the tail (stages 1 - 3 of the per-knot pass) takes about 1.26 times a knot of the condensation beside it (18.9 against 15.0 us
+    // since both move their operands by rows ; 21.3 against 17.6 before, when the rule was 21 / 25), so the tail is 4 / 5 of a parametric
+    // leg: 64 x 4 legs, N = 100, sum of the two launches 1.119 ms with none, 1.041 / 1.043 / 1.048 / 1.026 / 1.035 / 1.054 / 1.085 with
+    // 16 / 18 / 19 / 20 / 21 / 22 / 25 knots (profiles/leg_moves_measurements.txt).  (There k_leg_knot keeps 80 knots x 64
+    // instances = 20 full rounds of 256 compute units: one knot more is a 21st round, up to three fewer are the same 20.)
+    const int t = 4 * (L.N / J) / 5;
     return t < last ? t : last;
   }
   // back-substitution kernels.  k_leg_apply (legs.h): knots per workgroup.  MPC_LEG_APPLY_CHUNK unset (-1): automatic, see leg_apply_chunk ;
@@ -412,6 +415,7 @@ static void create_impl(mpc_solver* s, const mpc_dims& d) {
     e = getenv("MPC_TREE_SWEEPS"); s->env_tree_sweeps = e ? atoi(e) : 0;
     e = getenv("MPC_HIP_TRACE"); s->env_trace = e ? atoi(e) : -1;
     e = getenv("MPC_LEG_TAIL_KNOTS"); s->env_tail_knots = e ? (atoi(e) > 0 ? atoi(e) : 0) : -1;
+    e = getenv("MPC_LEG_KNOT_CHUNK"); s->env_knot_chunk = (e && atoi(e) > 0) ? atoi(e) : 0;
     e = getenv("MPC_LEG_APPLY_CHUNK"); s->env_apply_chunk = (e && atoi(e) > 0) ? atoi(e) : -1;
     e = getenv("MPC_DUALS_PLAIN"); s->env_duals_plain = e && atoi(e) > 0; }
   HIP_OK(hipSetDevice(d.device));
@@ -827,9 +831,11 @@ static void launch_pass(mpc_solver* s) {
     // affine terms, then the forward sweeps of the legs side by side
     s->timed(12, "k_closed_loop", [&] {
       // knots per workgroup: 1 (measured: with the operands of the next knot prefetched, chunks of 4 .. 25 knots take the same time per
-      // knot — the kernel is bound by its own instruction stream, not by the loads; MPC_LEG_KNOT_CHUNK for experiments)
-      static const int chunk_env = getenv("MPC_LEG_KNOT_CHUNK") ? atoi(getenv("MPC_LEG_KNOT_CHUNK")) : 0;
-      const int chunk = chunk_env > 0 ? chunk_env : 1;
+      // knot, so the loads do not bound the kernel.  Its instruction stream does only in part: the row-mapped operand moves of the
+      // fixed-dimension instantiations took 40 % of the vector instructions and half of the predication out of it (static count) and
+      // 5 % off the launch, 0.785 -> 0.745 ms over all 100 knots — profiles/leg_moves_measurements.txt.  MPC_LEG_KNOT_CHUNK, read when
+      // the handle is created, for experiments)
+      const int chunk = s->env_knot_chunk > 0 ? s->env_knot_chunk : 1;
       const int kmax = L.N - tail;  // the knots from kmax on: k_leg_condense_tail below (kmax >= leg_start(J - 1) >= 1)
       const dim3 grid((kmax + chunk - 1) / chunk, L.B);
       if (false) {}
