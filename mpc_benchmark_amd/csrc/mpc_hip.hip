@@ -26,6 +26,7 @@
 #include "closed_loop.h"
 #include "legs.h"
 #include "legs_tree.h"
+#include "pass_kernels.h"
 #include "pipeline_glue.h"
 #include "pipeline_ikid_glue.h"
 #include "pipeline_contacts.h"
@@ -65,13 +66,6 @@ static void lds_attr_max(const void* fn, int bytes) {
     h = bytes;
   }
 }
-
-// Problems whose dimensions get compile-time instantiations of the sweep and the leg kernels (riccati_mfma.h "FN, FM"):
-//   X(id, n, m, gfull, st_lds, NP, MP)   — (n, m): state / control dimension ; gfull, st_lds: the sweep's LDS plan for them (make_ric_lds) ;
-//   NP, MP: padded state / control dimension (the template arguments of the tree and of k_leg_knot)
-// 1: complete Talos (38 dofs), full dynamics   2: complete Talos, kinodynamic   3: Talos with the upper body locked as the scripts lock it
-// (28 dofs), full dynamics   4: the same, kinodynamic.  The stage kernel has its own list (eval_multibody.hip).
-#define MPC_FIXED_MODELS(X) X(1, 76, 32, 1, 1, 80, 32) X(2, 76, 44, 3, 0, 80, 48) X(3, 56, 22, 3, 1, 64, 32) X(4, 56, 34, 3, 1, 64, 48)
 
 // One model of the plant: its device allocation (nullptr: the model is off) and the host mirror of what the caller gave, as it is in force
 struct SimModel {
@@ -232,9 +226,10 @@ struct mpc_solver {
   hipEvent_t stage_ev[STAGE_RING] = {};
   int stage_next = 0;
   RicLds ric{};
-  int ric_fixed = 0;  // id of the fixed-dimension instantiations of the sweep and the leg kernels that serve this handle (MPC_FIXED_MODELS below), 0: the generic kernels
+  int ric_fixed = 0;  // id of the fixed-dimension instantiations of the sweep and the leg kernels that serve this handle (MPC_FIXED_MODELS, pass_kernels.h), 0: the generic kernels
   ClLds cl{};
   bool use_mfma_riccati = false;
+  PassKernels pk{};  // the instantiations that serve this handle, chosen at the end of create_impl from what stands above and below (pass_kernels.h)
   // parallel-in-time legs (legs.h)
   LkLds lk{};
   LcLds lc{};
@@ -248,6 +243,7 @@ struct mpc_solver {
   // whatever the grid.  MPC_LEG_TAIL_CUS: the compute-unit count the automatic rule sees (tests of the fallback).
   int env_tail_knots = -1, cu_count = 0;
   int env_knot_chunk = 0;  // MPC_LEG_KNOT_CHUNK: knots per workgroup of k_leg_knot (unset or 0: one), read when the handle is created like the knobs above
+  int leg_knot_chunk() const { return env_knot_chunk > 0 ? env_knot_chunk : 1; }
   int tail_last = 0, tail_sweeps_last = 0;          // developer probes (debug_get "leg_tail"): tail knots and sweeps of the last pass,
   long long tail_fused = 0, tail_separate = 0;      // launches of k_leg_condense_tail / k_leg_condense so far,
   long long leg_passes_multi = 0, leg_passes_single = 0;  // passes with legs that swept several times (no cut guess yet) / once
@@ -509,62 +505,20 @@ static void create_impl(mpc_solver* s, const mpc_dims& d) {
   if (s->cl.total_bytes <= 160 * 1024)
     lds_attr_max((const void*)k_closed_loop, s->cl.total_bytes);
   s->use_mfma_riccati = s->ric.total_bytes <= 160 * 1024 && (s->ric.st_lds || s->ric.mp * s->ric.np <= L.n * L.nz) && !getenv("MPC_HIP_GENERIC_RICCATI");
-  if (s->use_mfma_riccati)
-  {
-    lds_attr_max((const void*)k_riccati_mfma<RIC_THREADS, 96>, s->ric.total_bytes);
-    lds_attr_max((const void*)k_riccati_mfma<RIC_THREADS, 80>, s->ric.total_bytes);
-    lds_attr_max((const void*)k_riccati_mfma<RIC_THREADS, 96, true>, s->ric.total_bytes);
-    lds_attr_max((const void*)k_riccati_mfma<RIC_THREADS, 80, true>, s->ric.total_bytes);
-    lds_attr_max((const void*)k_riccati_mfma<RIC_SMALL_THREADS, 16>, s->ric.total_bytes);
-  }
   // parallel-in-time legs: every kernel of legs.h keeps three n x n operands (or [A B] + Pt) in LDS
   s->lk = make_lk_lds(L.n, L.m); s->lc = make_lc_lds(L.n); s->lx = make_lx_lds(L.n, L.m);
   s->legs_ok = s->use_mfma_riccati && s->ric.np <= 80 && s->ric.mp <= 48 && L.c <= 256 && s->ric.gfull >= 1 && s->lk.total_bytes <= 160 * 1024 &&
                s->lc.total_bytes <= 160 * 1024 && s->lx.total_bytes <= 160 * 1024 && !getenv("MPC_HIP_NO_LEGS");
-  if (s->legs_ok) {
-    lds_attr_max((const void*)k_riccati_mfma<RIC_THREADS, 80, true, true>, s->ric.total_bytes);
-    // fixed-dimension instantiations (MPC_FIXED_MODELS): only when the handle's LDS plan IS the one they were compiled for
-    s->ric_fixed = 0;
-    if (!getenv("MPC_HIP_GENERIC_DIMS") && s->ric.sq) {
+  // fixed-dimension instantiations (MPC_FIXED_MODELS): only when the handle's LDS plan IS the one they were compiled for
+  s->ric_fixed = 0;
+  if (s->legs_ok && !getenv("MPC_HIP_GENERIC_DIMS") && s->ric.sq) {
 #define X(ID, FN, FM, GF, ST, NPV, MPV) if (!s->ric_fixed && L.n == FN && L.m == FM && L.nz == FN + FM && ric_same_layout(s->ric, ric_fixed_layout(FN, FM, true, GF, ST))) s->ric_fixed = ID;
-      MPC_FIXED_MODELS(X)
-#undef X
-    }
-    const int leg_tail_lds = s->lc.total_bytes > s->lk.total_bytes ? s->lc.total_bytes : s->lk.total_bytes;  // a workgroup runs either body
-#define X(ID, FN, FM, GF, ST, NPV, MPV) if (s->ric_fixed == ID) { \
-      lds_attr_max((const void*)k_riccati_mfma<RIC_THREADS, 80, true, true, FN, FM, GF, ST>, s->ric.total_bytes); \
-      lds_attr_max((const void*)k_leg_knot<MPV, FN, FM>, s->lk.total_bytes); \
-      lds_attr_max((const void*)k_leg_condense<FN>, s->lc.total_bytes); \
-      lds_attr_max((const void*)k_leg_condense_tail<MPV, FN, FM>, leg_tail_lds); \
-      lds_attr_max((const void*)k_leg_compose<NPV, FN, FM>, s->lx.total_bytes); \
-      lds_attr_max((const void*)k_leg_tree_down<NPV, FN, FM>, s->lx.total_bytes); }
     MPC_FIXED_MODELS(X)
 #undef X
-    lds_attr_max((const void*)k_riccati_mfma<RIC_THREADS, 80, false, true>, s->ric.total_bytes);
-    lds_attr_max((const void*)k_riccati_mfma<RIC_SMALL_THREADS, 16, false, true>, s->ric.total_bytes);
-    lds_attr_max((const void*)k_leg_knot<16>, s->lk.total_bytes);
-    lds_attr_max((const void*)k_leg_knot<32>, s->lk.total_bytes);
-    lds_attr_max((const void*)k_leg_knot<48>, s->lk.total_bytes);
-    lds_attr_max((const void*)k_leg_condense<0>, s->lc.total_bytes);
-    lds_attr_max((const void*)k_leg_condense_tail<16>, leg_tail_lds);
-    lds_attr_max((const void*)k_leg_condense_tail<32>, leg_tail_lds);
-    lds_attr_max((const void*)k_leg_condense_tail<48>, leg_tail_lds);
-    lds_attr_max((const void*)k_leg_consensus<16>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_consensus<32>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_consensus<48>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_consensus<64>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_consensus<80>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_compose<16>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_compose<32>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_compose<48>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_compose<64>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_compose<80>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_tree_down<16>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_tree_down<32>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_tree_down<48>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_tree_down<64>, s->lx.total_bytes);
-    lds_attr_max((const void*)k_leg_tree_down<80>, s->lx.total_bytes);
   }
+  // the instantiations a pass of this handle launches, with legs and without, and the LDS carve-out each of them asks for
+  s->pk = select_pass_kernels(*s);
+  s->pk.for_each_carve_out([](const void* fn, int lds) { lds_attr_max(fn, lds); });
   ensure_leg_capacity(s, s->eff_legs());
   HIP_OK(hipStreamSynchronize(s->stream));
 }
@@ -768,9 +722,57 @@ static void launch_eval(mpc_solver* s, bool trial, int cand0 = 0, int ncand = 1,
   HIP_OK(hipGetLastError());
 }
 
+// One backward sweep of a pass through the handle's kernels (pass_kernels.h): the Riccati sweep and, with J > 1 legs, what joins them at the
+// cuts — per-knot closed-loop transitions and parametric terms, condensation of every leg (the last `tail` knots of the horizon beside it
+// when tail > 0), then the tree over the cuts or the chain of k_leg_consensus
+static void launch_backward(mpc_solver* s, const SolverArgs& a, int J, bool tree, int tail) {
+  const Layout& L = s->L;
+  const PassKernels& pk = s->pk;
+  s->timed(3, "k_riccati_backward", [&] {
+    // parallel-in-time: workgroup (instance, leg), the last leg first
+    if (J > 1) hipLaunchKernelGGL(pk.sweep_legs.fn, dim3(L.B * J), dim3(pk.sweep_legs.threads), pk.sweep_legs.lds, s->stream, a, s->ric);
+    else if (pk.sweep_serial.fn) hipLaunchKernelGGL(pk.sweep_serial.fn, dim3(L.B), dim3(pk.sweep_serial.threads), pk.sweep_serial.lds, s->stream, a, s->ric);
+    else hipLaunchKernelGGL(k_riccati_backward, dim3(L.B), dim3(pk.sweep_serial.threads), pk.sweep_serial.lds, s->stream, a);
+  });
+  if (J <= 1) return;
+  s->timed(12, "k_closed_loop", [&] {
+    // knots per workgroup: 1 (measured: with the operands of the next knot prefetched, chunks of 4 .. 25 knots take the same time per
+    // knot, so the loads do not bound the kernel.  Its instruction stream does only in part: the row-mapped operand moves of the
+    // fixed-dimension instantiations took 40 % of the vector instructions and half of the predication out of it (static count) and
+    // 5 % off the launch, 0.785 -> 0.745 ms over all 100 knots — profiles/leg_moves_measurements.txt.  MPC_LEG_KNOT_CHUNK, read when
+    // the handle is created, for experiments)
+    const int chunk = s->leg_knot_chunk();
+    hipLaunchKernelGGL(pk.leg_knot.fn, leg_knot_grid(L.N, L.B, tail, chunk), dim3(pk.leg_knot.threads), pk.leg_knot.lds, s->stream, a, s->lk, chunk, L.N - tail);
+  });
+  // (one profile slot and one name for both forms of the condensation: the per-kernel tables and the traffic table keep their rows)
+  s->timed(13, "k_leg_condense", [&] {
+    if (tail > 0) {
+      s->tail_fused++;
+      hipLaunchKernelGGL(pk.leg_condense_tail.fn, leg_condense_grid(J, L.B, tail), dim3(pk.leg_condense_tail.threads), pk.leg_condense_tail.lds, s->stream, a, s->lc, s->lk, tail);
+    } else {
+      s->tail_separate++;
+      hipLaunchKernelGGL(pk.leg_condense.fn, leg_condense_grid(J, L.B, 0), dim3(pk.leg_condense.threads), pk.leg_condense.lds, s->stream, a, s->lc);
+    }
+  });
+  if (tree) {
+    const TreeDesc& T = s->tree;
+    s->timed(14, "k_leg_consensus", [&] {
+      for (int lev = 0; lev < T.nlev; ++lev)
+        hipLaunchKernelGGL(pk.leg_compose.fn, leg_compose_grid(T, lev, L.B), dim3(pk.leg_compose.threads), pk.leg_compose.lds, s->stream, a, s->lx, T, lev);
+    });
+    s->timed(16, "k_leg_tree_down", [&] {
+      for (int lev = T.nlev - 1; lev >= 0; --lev)
+        hipLaunchKernelGGL(pk.leg_tree_down.fn, leg_tree_down_grid(T, lev, L.B), dim3(pk.leg_tree_down.threads), pk.leg_tree_down.lds, s->stream, a, s->lx, T, lev);
+    });
+  } else {
+    s->timed(14, "k_leg_consensus", [&] { hipLaunchKernelGGL(pk.leg_consensus.fn, dim3(L.B), dim3(pk.leg_consensus.threads), pk.leg_consensus.lds, s->stream, a, s->lx); });
+  }
+}
+
 // one pass of the inner loop for every instance that is not done
 static void launch_pass(mpc_solver* s) {
   const Layout& L = s->L;
+  const PassKernels& pk = s->pk;
   if (s->pass_in_run > 0 && s->tick_reuse && s->opt.max_iters <= 4) {
     // a further iteration of the same tick: instances whose full step was accepted find their records already written, for the same knots
     s->reuse_this_pass = true; s->reuse_same_now = true;
@@ -804,110 +806,10 @@ static void launch_pass(mpc_solver* s) {
   s->tail_last = tail; s->tail_sweeps_last = sweeps;
   if (J > 1) { if (sweeps > 1) s->leg_passes_multi++; else s->leg_passes_single++; }
   for (int sweep = 0; sweep < sweeps; ++sweep) {
-  s->leg_guess_now = (J > 1 && !plain && (s->leg_guess_valid || sweep > 0)) ? 1 : 0;
-  a = s->args();
-  a.abdz = nullptr;
-  s->timed(3, "k_riccati_backward", [&] {
-    if (J > 1) {
-      // parallel-in-time: workgroup (instance, leg), the last leg first
-      if (s->ric.np == 16 && s->ric.mp == 16 && L.c <= RIC_SMALL_THREADS)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_riccati_mfma<RIC_SMALL_THREADS, 16, false, true>), dim3(L.B * J), dim3(RIC_SMALL_THREADS), s->ric.total_bytes, s->stream, a, s->ric);
-#define X(ID, FN, FM, GF, ST, NPV, MPV) else if (s->ric_fixed == ID) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_riccati_mfma<RIC_THREADS, 80, true, true, FN, FM, GF, ST>), dim3(L.B * J), dim3(RIC_THREADS), s->ric.total_bytes, s->stream, a, s->ric);
-      MPC_FIXED_MODELS(X)
-#undef X
-      else if (s->ric.sq) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_riccati_mfma<RIC_THREADS, 80, true, true>), dim3(L.B * J), dim3(RIC_THREADS), s->ric.total_bytes, s->stream, a, s->ric);
-      else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_riccati_mfma<RIC_THREADS, 80, false, true>), dim3(L.B * J), dim3(RIC_THREADS), s->ric.total_bytes, s->stream, a, s->ric);
-    }
-    else if (s->use_mfma_riccati && s->ric.np == 16 && s->ric.mp == 16 && L.c <= RIC_SMALL_THREADS)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_riccati_mfma<RIC_SMALL_THREADS, 16>), dim3(L.B), dim3(RIC_SMALL_THREADS), s->ric.total_bytes, s->stream, a, s->ric);  // small problems: one wavefront
-    else if (s->use_mfma_riccati && s->ric.sq && s->ric.np <= 80) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_riccati_mfma<RIC_THREADS, 80, true>), dim3(L.B), dim3(RIC_THREADS), s->ric.total_bytes, s->stream, a, s->ric);
-    else if (s->use_mfma_riccati && s->ric.sq) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_riccati_mfma<RIC_THREADS, 96, true>), dim3(L.B), dim3(RIC_THREADS), s->ric.total_bytes, s->stream, a, s->ric);
-    else if (s->use_mfma_riccati && s->ric.np <= 80) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_riccati_mfma<RIC_THREADS, 80>), dim3(L.B), dim3(RIC_THREADS), s->ric.total_bytes, s->stream, a, s->ric);  // fewer tiles per wavefront: lower register pressure
-    else if (s->use_mfma_riccati) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_riccati_mfma<RIC_THREADS, 96>), dim3(L.B), dim3(RIC_THREADS), s->ric.total_bytes, s->stream, a, s->ric);
-    else hipLaunchKernelGGL(k_riccati_backward, dim3(L.B), dim3(256), s->riccati_lds(), s->stream, a);
-  });
-  if (J > 1) {
-    // legs: per-knot closed-loop transitions and parametric terms, condensation of every leg, consensus over the cuts, final
-    // affine terms, then the forward sweeps of the legs side by side
-    s->timed(12, "k_closed_loop", [&] {
-      // knots per workgroup: 1 (measured: with the operands of the next knot prefetched, chunks of 4 .. 25 knots take the same time per
-      // knot, so the loads do not bound the kernel.  Its instruction stream does only in part: the row-mapped operand moves of the
-      // fixed-dimension instantiations took 40 % of the vector instructions and half of the predication out of it (static count) and
-      // 5 % off the launch, 0.785 -> 0.745 ms over all 100 knots — profiles/leg_moves_measurements.txt.  MPC_LEG_KNOT_CHUNK, read when
-      // the handle is created, for experiments)
-      const int chunk = s->env_knot_chunk > 0 ? s->env_knot_chunk : 1;
-      const int kmax = L.N - tail;  // the knots from kmax on: k_leg_condense_tail below (kmax >= leg_start(J - 1) >= 1)
-      const dim3 grid((kmax + chunk - 1) / chunk, L.B);
-      if (false) {}
-#define X(ID, FN, FM, GF, ST, NPV, MPV) else if (s->ric_fixed == ID) hipLaunchKernelGGL((k_leg_knot<MPV, FN, FM>), grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk, kmax);
-      MPC_FIXED_MODELS(X)
-#undef X
-      else if (s->lk.mp <= 16) hipLaunchKernelGGL(k_leg_knot<16>, grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk, kmax);
-      else if (s->lk.mp <= 32) hipLaunchKernelGGL(k_leg_knot<32>, grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk, kmax);
-      else hipLaunchKernelGGL(k_leg_knot<48>, grid, dim3(LK_THREADS), s->lk.total_bytes, s->stream, a, s->lk, chunk, kmax);
-    });
-    // (one profile slot and one name for both forms of the condensation: the per-kernel tables and the traffic table keep their rows)
-    if (tail > 0) s->timed(13, "k_leg_condense", [&] {
-      const int lds = s->lc.total_bytes > s->lk.total_bytes ? s->lc.total_bytes : s->lk.total_bytes;
-      const dim3 grid(J, L.B);
-      s->tail_fused++;
-      if (false) {}
-#define X(ID, FN, FM, GF, ST, NPV, MPV) else if (s->ric_fixed == ID) hipLaunchKernelGGL((k_leg_condense_tail<MPV, FN, FM>), grid, dim3(LK_THREADS), lds, s->stream, a, s->lc, s->lk, tail);
-      MPC_FIXED_MODELS(X)
-#undef X
-      else if (s->lk.mp <= 16) hipLaunchKernelGGL(k_leg_condense_tail<16>, grid, dim3(LK_THREADS), lds, s->stream, a, s->lc, s->lk, tail);
-      else if (s->lk.mp <= 32) hipLaunchKernelGGL(k_leg_condense_tail<32>, grid, dim3(LK_THREADS), lds, s->stream, a, s->lc, s->lk, tail);
-      else hipLaunchKernelGGL(k_leg_condense_tail<48>, grid, dim3(LK_THREADS), lds, s->stream, a, s->lc, s->lk, tail);
-    });
-    else s->timed(13, "k_leg_condense", [&] {
-      s->tail_separate++;
-      if (false) {}
-#define X(ID, FN, FM, GF, ST, NPV, MPV) else if (s->ric_fixed == ID) hipLaunchKernelGGL(k_leg_condense<FN>, dim3(J - 1, L.B), dim3(LK_THREADS), s->lc.total_bytes, s->stream, a, s->lc);
-      MPC_FIXED_MODELS(X)
-#undef X
-      else hipLaunchKernelGGL(k_leg_condense<0>, dim3(J - 1, L.B), dim3(LK_THREADS), s->lc.total_bytes, s->stream, a, s->lc);
-    });
-    if (tree) s->timed(14, "k_leg_consensus", [&] {
-      const TreeDesc& T = s->tree;
-#define MPC_TREE_LAUNCH(NPV) do { \
-        for (int lev = 0; lev < T.nlev; ++lev) hipLaunchKernelGGL(k_leg_compose<NPV>, dim3(T.lev_cnt[lev] + 1, L.B, 2), dim3(LCMP_THREADS), s->lx.total_bytes, s->stream, a, s->lx, T, lev); } while (0)
-      if (false) {
-#define X(ID, FN, FM, GF, ST, NPV, MPV) } else if (s->ric_fixed == ID) { for (int lev = 0; lev < T.nlev; ++lev) hipLaunchKernelGGL((k_leg_compose<NPV, FN, FM>), dim3(T.lev_cnt[lev] + 1, L.B, 2), dim3(LCMP_THREADS), s->lx.total_bytes, s->stream, a, s->lx, T, lev);
-      MPC_FIXED_MODELS(X)
-#undef X
-      } else switch (s->lx.np) {
-        case 16: MPC_TREE_LAUNCH(16); break;
-        case 32: MPC_TREE_LAUNCH(32); break;
-        case 48: MPC_TREE_LAUNCH(48); break;
-        case 64: MPC_TREE_LAUNCH(64); break;
-        default: MPC_TREE_LAUNCH(80); break;
-      }
-#undef MPC_TREE_LAUNCH
-    });
-    if (tree) s->timed(16, "k_leg_tree_down", [&] {
-      const TreeDesc& T = s->tree;
-      if (false) {
-#define X(ID, FN, FM, GF, ST, NPV, MPV) } else if (s->ric_fixed == ID) { for (int lev = T.nlev - 1; lev >= 0; --lev) hipLaunchKernelGGL((k_leg_tree_down<NPV, FN, FM>), dim3(T.lev_cnt[lev] + (lev == T.nlev - 1 ? 1 : 0), L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx, T, lev);
-      MPC_FIXED_MODELS(X)
-#undef X
-      } else switch (s->lx.np) {
-        case 16: for (int lev = T.nlev - 1; lev >= 0; --lev) hipLaunchKernelGGL(k_leg_tree_down<16>, dim3(T.lev_cnt[lev] + (lev == T.nlev - 1 ? 1 : 0), L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx, T, lev); break;
-        case 32: for (int lev = T.nlev - 1; lev >= 0; --lev) hipLaunchKernelGGL(k_leg_tree_down<32>, dim3(T.lev_cnt[lev] + (lev == T.nlev - 1 ? 1 : 0), L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx, T, lev); break;
-        case 48: for (int lev = T.nlev - 1; lev >= 0; --lev) hipLaunchKernelGGL(k_leg_tree_down<48>, dim3(T.lev_cnt[lev] + (lev == T.nlev - 1 ? 1 : 0), L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx, T, lev); break;
-        case 64: for (int lev = T.nlev - 1; lev >= 0; --lev) hipLaunchKernelGGL(k_leg_tree_down<64>, dim3(T.lev_cnt[lev] + (lev == T.nlev - 1 ? 1 : 0), L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx, T, lev); break;
-        default: for (int lev = T.nlev - 1; lev >= 0; --lev) hipLaunchKernelGGL(k_leg_tree_down<80>, dim3(T.lev_cnt[lev] + (lev == T.nlev - 1 ? 1 : 0), L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx, T, lev); break;
-      }
-    });
-    else s->timed(14, "k_leg_consensus", [&] {
-      switch (s->lx.np) {
-        case 16: hipLaunchKernelGGL(k_leg_consensus<16>, dim3(L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx); break;
-        case 32: hipLaunchKernelGGL(k_leg_consensus<32>, dim3(L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx); break;
-        case 48: hipLaunchKernelGGL(k_leg_consensus<48>, dim3(L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx); break;
-        case 64: hipLaunchKernelGGL(k_leg_consensus<64>, dim3(L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx); break;
-        default: hipLaunchKernelGGL(k_leg_consensus<80>, dim3(L.B), dim3(LK_THREADS), s->lx.total_bytes, s->stream, a, s->lx); break;
-      }
-    });
-  }
+    s->leg_guess_now = (J > 1 && !plain && (s->leg_guess_valid || sweep > 0)) ? 1 : 0;
+    a = s->args();
+    a.abdz = nullptr;
+    launch_backward(s, a, J, tree, tail);
   }
   if (J > 1) {
     s->leg_guess_valid = true;
@@ -915,32 +817,24 @@ static void launch_pass(mpc_solver* s) {
       const int C = s->leg_apply_chunk(J);
       s->apply_chunk_last = C;
       if (C > 1) s->apply_chunked++; else s->apply_single++;
-      hipLaunchKernelGGL(k_leg_apply, dim3(leg_apply_chunks(L.N, J, C), L.B), dim3(256), leg_apply_lds(L.n, C), s->stream, a, C);
+      hipLaunchKernelGGL(k_leg_apply, leg_apply_grid(L.N, J, C, L.B), dim3(256), leg_apply_lds(L.n, C), s->stream, a, C);
     });
-    s->timed(4, "k_forward", [&] {
-      if (L.m <= 32) hipLaunchKernelGGL((k_forward_phi<4, 10>), dim3(L.B * J), dim3(512), 2 * L.n * sizeof(double), s->stream, a);
-      else hipLaunchKernelGGL((k_forward_phi<6, 10>), dim3(L.B * J), dim3(512), 2 * L.n * sizeof(double), s->stream, a);
-    });
+    s->timed(4, "k_forward", [&] { hipLaunchKernelGGL(pk.forward_phi.fn, forward_phi_grid(L.B, J), dim3(pk.forward_phi.threads), pk.forward_phi.lds, s->stream, a); });
   } else {
-  const bool fw_phi = s->cl.total_bytes <= 160 * 1024 && L.n <= 80 && L.m <= 32 && (s->opt.forward_mode == 0 ? L.B * L.N <= 2048 : s->opt.forward_mode == 2);
-  if (fw_phi) {
-    s->timed(12, "k_closed_loop", [&] { hipLaunchKernelGGL(k_closed_loop, dim3(L.N, L.B), dim3(CL_THREADS), s->cl.total_bytes, s->stream, a, s->cl); });
-    s->timed(4, "k_forward", [&] { hipLaunchKernelGGL((k_forward_phi<4, 10>), dim3(L.B), dim3(512), 2 * L.n * sizeof(double), s->stream, a); });
-  } else {
-    s->timed(4, "k_forward", [&] {
-      const size_t fw_lds = (L.nz + 2 * L.n) * sizeof(double);
-      const bool fits = L.nz <= 128 && L.n + L.m <= L.nz;
-      if (fits && L.n <= 80 && L.m <= 48) a.abdz = s->d_abdz;  // the register-prefetch sweeps leave [A B] [dx; du] of every knot for k_duals
-      if (fits && L.n <= 80 && L.m <= 32) hipLaunchKernelGGL((k_forward_prefetch<4, 10>), dim3(L.B), dim3(512), fw_lds, s->stream, a);
-      else if (fits && L.n <= 80 && L.m <= 48) hipLaunchKernelGGL((k_forward_prefetch<6, 10>), dim3(L.B), dim3(512), fw_lds, s->stream, a);
-      else hipLaunchKernelGGL(k_forward, dim3(L.B), dim3(1024), fw_lds, s->stream, a);
-    });
-  }
+    const bool fw_phi = s->cl.total_bytes <= 160 * 1024 && L.n <= 80 && L.m <= 32 && (s->opt.forward_mode == 0 ? L.B * L.N <= 2048 : s->opt.forward_mode == 2);
+    if (fw_phi) {
+      s->timed(12, "k_closed_loop", [&] { hipLaunchKernelGGL(k_closed_loop, dim3(L.N, L.B), dim3(CL_THREADS), s->cl.total_bytes, s->stream, a, s->cl); });
+      s->timed(4, "k_forward", [&] { hipLaunchKernelGGL(pk.forward_phi.fn, forward_phi_grid(L.B, 1), dim3(pk.forward_phi.threads), pk.forward_phi.lds, s->stream, a); });
+    } else {
+      s->timed(4, "k_forward", [&] {
+        if (pk.forward_serial_leaves_abdz) a.abdz = s->d_abdz;  // the register-prefetch sweeps leave [A B] [dx; du] of every knot for k_duals
+        hipLaunchKernelGGL(pk.forward_serial.fn, dim3(L.B), dim3(pk.forward_serial.threads), pk.forward_serial.lds, s->stream, a);
+      });
+    }
   }
   s->timed(5, "k_duals", [&] {
-    // (LDS: the step, three vectors of n, the partial sums, then three per-row scalars of the constraint block — four in the staged form)
-    if (s->env_duals_plain) { s->duals_plain++; hipLaunchKernelGGL(k_duals<true>, dim3(L.N + 1, L.B), dim3(256), (L.nz + 3 * L.n + 16 + 3 * L.c) * sizeof(double), s->stream, a); }
-    else { s->duals_staged++; hipLaunchKernelGGL(k_duals<false>, dim3(L.N + 1, L.B), dim3(256), (L.nz + 3 * L.n + 16 + 4 * L.c) * sizeof(double), s->stream, a); }
+    if (s->env_duals_plain) s->duals_plain++; else s->duals_staged++;
+    hipLaunchKernelGGL(pk.duals.fn, dim3(L.N + 1, L.B), dim3(pk.duals.threads), pk.duals.lds, s->stream, a);
   });
   // linesearch: evaluate the full step first; the backtracking candidates alpha = 2^-i, i >= 1, are only
   // evaluated for instances whose full step failed the Armijo test (their workgroups exit immediately otherwise)
@@ -1386,53 +1280,26 @@ int mpc_kernel_info(mpc_solver* s, int32_t idx, char* name, int32_t name_cap, in
       e.push_back({"k_eval_multibody<3> (alpha = 1 candidate with derivatives)", eval_multibody_kernel(3), EVAL_THREADS, ml.total_bytes, (long long)(L.N + 1) * L.B});
       e.push_back({"k_eval_multibody<1> (backtracking candidates, values only)", eval_multibody_kernel(1), EVAL_THREADS, ml.total_bytes, (long long)(L.N + 1) * L.B});
     }
-    const bool small = s->ric.np == 16 && s->ric.mp == 16 && L.c <= RIC_SMALL_THREADS;
+    // the kernels of the table (pass_kernels.h), by the decisions launch_pass takes and on the grids it launches
+    const PassKernels& pk = s->pk;
+    auto add = [&](const auto& k, dim3 grid) { e.push_back({k.name, (const void*)k.fn, k.threads, k.lds, grid_workgroups(grid)}); };
     if (J > 1) {
-      if (small) e.push_back({"k_riccati_mfma<256,16,false,true> (sweep, legs)", (const void*)k_riccati_mfma<RIC_SMALL_THREADS, 16, false, true>, RIC_SMALL_THREADS, s->ric.total_bytes, (long long)L.B * J});
-#define X(ID, FN, FM, GF, ST, NPV, MPV) else if (s->ric_fixed == ID) e.push_back({"k_riccati_mfma<512,80,true,true," #FN "," #FM "," #GF "," #ST "> (sweep, legs, fixed dimensions)", (const void*)k_riccati_mfma<RIC_THREADS, 80, true, true, FN, FM, GF, ST>, RIC_THREADS, s->ric.total_bytes, (long long)L.B * J});
-      MPC_FIXED_MODELS(X)
-#undef X
-      else if (s->ric.sq) e.push_back({"k_riccati_mfma<512,80,true,true> (sweep, legs)", (const void*)k_riccati_mfma<RIC_THREADS, 80, true, true>, RIC_THREADS, s->ric.total_bytes, (long long)L.B * J});
-      else e.push_back({"k_riccati_mfma<512,80,false,true> (sweep, legs)", (const void*)k_riccati_mfma<RIC_THREADS, 80, false, true>, RIC_THREADS, s->ric.total_bytes, (long long)L.B * J});
-      // (the instantiations the launch sites pick: the fixed-dimension ones when the handle's layout is one of MPC_FIXED_MODELS)
-      const void* lk = s->lk.mp <= 16 ? (const void*)k_leg_knot<16> : (s->lk.mp <= 32 ? (const void*)k_leg_knot<32> : (const void*)k_leg_knot<48>);
-      const void* lcd = (const void*)k_leg_condense<0>;
-      const void* lct = s->lk.mp <= 16 ? (const void*)k_leg_condense_tail<16> : (s->lk.mp <= 32 ? (const void*)k_leg_condense_tail<32> : (const void*)k_leg_condense_tail<48>);
-      const char* lct_name = "k_leg_condense_tail (condensation + the last leg's knots)";
-      const char *lk_name = "k_leg_knot", *lcd_name = "k_leg_condense", *lcmp_name = "k_leg_compose (first level of the tree over the cuts)", *ltd_name = "k_leg_tree_down (last level)";
-      const void *lcmp_fixed = nullptr, *ltd_fixed = nullptr;
-#define X(ID, FN, FM, GF, ST, NPV, MPV) if (s->ric_fixed == ID) { lk = (const void*)k_leg_knot<MPV, FN, FM>; lcd = (const void*)k_leg_condense<FN>; lct = (const void*)k_leg_condense_tail<MPV, FN, FM>; lct_name = "k_leg_condense_tail<" #MPV "," #FN "," #FM "> (fixed dimensions)"; lcmp_fixed = (const void*)k_leg_compose<NPV, FN, FM>; ltd_fixed = (const void*)k_leg_tree_down<NPV, FN, FM>; \
-        lk_name = "k_leg_knot<" #MPV "," #FN "," #FM "> (fixed dimensions)"; lcd_name = "k_leg_condense<" #FN "> (fixed dimensions)"; \
-        lcmp_name = "k_leg_compose<" #NPV "," #FN "," #FM "> (first level of the tree over the cuts, fixed dimensions)"; ltd_name = "k_leg_tree_down<" #NPV "," #FN "," #FM "> (last level, fixed dimensions)"; }
-      MPC_FIXED_MODELS(X)
-#undef X
       const int tail = s->leg_tail_knots(J);
-      e.push_back({lk_name, lk, LK_THREADS, s->lk.total_bytes, (long long)(L.N - tail) * L.B});
-      if (tail > 0) e.push_back({lct_name, lct, LK_THREADS, s->lc.total_bytes > s->lk.total_bytes ? s->lc.total_bytes : s->lk.total_bytes, (long long)J * L.B});
-      else e.push_back({lcd_name, lcd, LK_THREADS, s->lc.total_bytes, (long long)(J - 1) * L.B});
+      add(pk.sweep_legs, dim3(L.B * J));
+      add(pk.leg_knot, leg_knot_grid(L.N, L.B, tail, s->leg_knot_chunk()));
+      if (tail > 0) add(pk.leg_condense_tail, leg_condense_grid(J, L.B, tail));
+      else add(pk.leg_condense, leg_condense_grid(J, L.B, 0));
       if (s->use_tree()) {
         const TreeDesc T = make_tree_desc(J);
-        const void* lc = s->lx.np == 16 ? (const void*)k_leg_compose<16> : s->lx.np == 32 ? (const void*)k_leg_compose<32> : s->lx.np == 48 ? (const void*)k_leg_compose<48>
-                       : s->lx.np == 64 ? (const void*)k_leg_compose<64> : (const void*)k_leg_compose<80>;
-        const void* ld = s->lx.np == 16 ? (const void*)k_leg_tree_down<16> : s->lx.np == 32 ? (const void*)k_leg_tree_down<32> : s->lx.np == 48 ? (const void*)k_leg_tree_down<48>
-                       : s->lx.np == 64 ? (const void*)k_leg_tree_down<64> : (const void*)k_leg_tree_down<80>;
-        e.push_back({lcmp_name, lcmp_fixed ? lcmp_fixed : lc, LCMP_THREADS, s->lx.total_bytes, (long long)(T.lev_cnt[0] + 1) * L.B * 2});
-        e.push_back({ltd_name, ltd_fixed ? ltd_fixed : ld, LK_THREADS, s->lx.total_bytes, (long long)T.lev_cnt[0] * L.B});
-      } else {
-      const void* lx = s->lx.np == 16 ? (const void*)k_leg_consensus<16> : s->lx.np == 32 ? (const void*)k_leg_consensus<32> : s->lx.np == 48 ? (const void*)k_leg_consensus<48>
-                     : s->lx.np == 64 ? (const void*)k_leg_consensus<64> : (const void*)k_leg_consensus<80>;
-      e.push_back({"k_leg_consensus", lx, LK_THREADS, s->lx.total_bytes, (long long)L.B});
-      }
+        add(pk.leg_compose, leg_compose_grid(T, 0, L.B));
+        add(pk.leg_tree_down, leg_tree_down_grid(T, T.nlev - 1, L.B));
+      } else add(pk.leg_consensus, dim3(L.B));
       { const int C = s->leg_apply_chunk(J);
-        e.push_back({"k_leg_apply", (const void*)k_leg_apply, 256, (int)leg_apply_lds(L.n, C), (long long)leg_apply_chunks(L.N, J, C) * L.B}); }
-      e.push_back({"k_forward_phi (forward sweeps of the legs)", L.m <= 32 ? (const void*)k_forward_phi<4, 10> : (const void*)k_forward_phi<6, 10>, 512, (int)(2 * L.n * sizeof(double)), (long long)L.B * J});
-    } else if (s->use_mfma_riccati) {
-      const void* fn = small ? (const void*)k_riccati_mfma<RIC_SMALL_THREADS, 16> : (s->ric.sq && s->ric.np <= 80) ? (const void*)k_riccati_mfma<RIC_THREADS, 80, true>
-                     : s->ric.sq ? (const void*)k_riccati_mfma<RIC_THREADS, 96, true> : s->ric.np <= 80 ? (const void*)k_riccati_mfma<RIC_THREADS, 80> : (const void*)k_riccati_mfma<RIC_THREADS, 96>;
-      e.push_back({"k_riccati_mfma (serial sweep)", fn, small ? RIC_SMALL_THREADS : RIC_THREADS, s->ric.total_bytes, (long long)L.B});
-    } else e.push_back({"k_riccati_backward (serial sweep, no matrix cores)", (const void*)k_riccati_backward, 256, (int)s->riccati_lds(), (long long)L.B});
-    if (s->env_duals_plain) e.push_back({"k_duals<true> (MPC_DUALS_PLAIN)", (const void*)k_duals<true>, 256, (int)((L.nz + 3 * L.n + 16 + 3 * L.c) * sizeof(double)), (long long)(L.N + 1) * L.B});
-    else e.push_back({"k_duals", (const void*)k_duals<false>, 256, (int)((L.nz + 3 * L.n + 16 + 4 * L.c) * sizeof(double)), (long long)(L.N + 1) * L.B});
+        e.push_back({"k_leg_apply", (const void*)k_leg_apply, 256, (int)leg_apply_lds(L.n, C), grid_workgroups(leg_apply_grid(L.N, J, C, L.B))}); }
+      add(pk.forward_phi, forward_phi_grid(L.B, J));
+    } else if (pk.sweep_serial.fn) add(pk.sweep_serial, dim3(L.B));
+    else e.push_back({pk.sweep_serial.name, (const void*)k_riccati_backward, pk.sweep_serial.threads, pk.sweep_serial.lds, (long long)L.B});
+    add(pk.duals, dim3(L.N + 1, L.B));
     e.push_back({"k_lagrangian", (const void*)k_lagrangian, 64, 0, (long long)(L.N + 1) * L.B});
     if (idx < 0 || idx >= (int)e.size()) return (int)e.size();
     const Ent& k = e[idx];

@@ -142,7 +142,7 @@ def test_partial_tails(hip_lib, monkeypatch, t):
 def test_fallback_when_the_grid_exceeds_the_chip(hip_lib, monkeypatch):
     """Automatic choice (MPC_LEG_TAIL_KNOTS unset): nlegs x B = 9 workgroups in the fused grid, N x B = 27 in k_leg_knot.  With 8 compute
     units (MPC_LEG_TAIL_CUS) the fused grid exceeds one round of the chip and the separate launches stay ; with 9 it fits and the tail is
-    21 / 25 of a parametric leg (2 of 3 knots) ; on the real device (27 workgroups: k_leg_knot is one round already) the separate launches
+    4 / 5 of a parametric leg (2 of 3 knots) ; on the real device (27 workgroups: k_leg_knot is one round already) the separate launches
     stay again.  Same bits every time."""
     args = ("fulldynamic", 9, 3, 3, False)
     small = _handle(monkeypatch, hip_lib, *args, None, cus=8)
