@@ -356,8 +356,11 @@ int mpc_revive_instance(mpc_solver* s, int32_t dst, int32_t src);
  * Parallel-in-time sweep (riccati_legs > 1), knots of a leg other than the last: "Mu" "Znu" "Lm" and, HIP, "Phi" "phi" "Gam" "Ku" "Knup" /
  * oracle, "Mx" "Mth" "Kth" "Knuth" "Kexact" (same quantities: Phi = Mx everywhere, Gam = Mth, Ku = Kth, Knup = Knuth at the last knot of a leg) ;
  * with k = index of the leg instead of a knot: "Sg" "sg" (HIP; the oracle keeps them per knot) "Zx" "zc" "calP" "calp" "theta" ;
- * HIP only: "ls_knot" (knot k of the last pass: the merit of every linesearch candidate alpha_i = 2^-i at this knot, then the knot's cost
- * and penalty at the current point), "fixed_dims" (one value: which fixed-dimension instantiations of the hot kernels serve this handle,
+ * linesearch of the last pass: "ls" (phi0, dphi0, alpha, backtracking steps, then the merit of every candidate alpha_i = 2^-i summed over
+ * the knots), "ls_knot" (knot k: the merit of every candidate at this knot, then the knot's cost and penalty at the current point), "dmerit"
+ * (knot k: the knot's part of dphi0).  The HIP library evaluates either candidate 0 alone or all of them; the oracle evaluates 0 .. steps
+ * and reports the others as NaN ;
+ * HIP only: "fixed_dims" (one value: which fixed-dimension instantiations of the hot kernels serve this handle,
  * 0 = the generic ones ). */
 int mpc_debug_get(mpc_solver* s, const char* name, int32_t b, int32_t k, double* out, int32_t cap);
 /* Evaluate (value + derivatives) at the current iterate without stepping; fills the LQ knots. */

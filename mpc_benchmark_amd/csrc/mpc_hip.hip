@@ -1750,6 +1750,7 @@ int mpc_debug_get(mpc_solver* s, const char* name, int32_t b, int32_t k, double*
       for (int i = 0; i < L.n_alpha; ++i) v.push_back(tp[(size_t)i * (L.N + 1) + k]);
       v.push_back(kn[L.oMISC + MISC_COST]); v.push_back(kn[L.oMISC + MISC_PEN]);
     }
+    else if (nm == "dmerit") mat(kn.data() + L.oMISC + MISC_DMERIT, 1, 1, 1);  // the knot's part of the merit slope dphi0 (k_duals of the last pass)
     else if (nm == "leg_tail") v = {(double)s->tail_last, (double)s->tail_fused, (double)s->tail_separate, (double)s->tail_sweeps_last, (double)s->eff_legs(), (double)s->cu_count,
                                    (double)s->leg_passes_multi, (double)s->leg_passes_single};  // k_leg_condense_tail: tail knots and sweeps of the last pass, fused / separate condensation launches so far, legs, compute units, passes with several sweeps / with one
     else if (nm == "backsubst") v = {(double)s->apply_chunk_last, (double)s->apply_chunked, (double)s->apply_single, (double)s->duals_staged, (double)s->duals_plain,

@@ -631,6 +631,22 @@ int mpc_debug_get(mpc_solver* h, const char* name, int32_t b, int32_t k, double*
     else if (nm == "du") { if (k >= s.N()) throw std::runtime_error("no du at the terminal knot"); v = &in.dus[k]; }
     else if (nm == "dvs") v = &in.dvs[k];
     else if (nm == "dlams") v = &in.dlams[k];
+    // linesearch of the last pass, in the layout of the HIP library (include/mpc_abi.h): candidates the oracle never evaluated are NaN
+    else if (nm == "ls") {
+      tmp = {in.ls_phi0, in.ls_dphi0, in.stats.alpha, (double)in.stats.ls_steps};
+      for (const auto& cand : in.ls_cand) { double t = 0; for (double e : cand) t += e; tmp.push_back(t); }
+      v = &tmp;
+    }
+    else if (nm == "ls_knot") {
+      if (in.ls_cost.empty()) throw std::runtime_error("debug_get: no pass has run");
+      for (const auto& cand : in.ls_cand) tmp.push_back(cand[k]);
+      tmp.push_back(in.ls_cost[k]); tmp.push_back(in.ls_pen[k]);
+      v = &tmp;
+    }
+    else if (nm == "dmerit") {
+      if (in.ls_dmerit.empty()) throw std::runtime_error("debug_get: no pass has run");
+      tmp.assign(1, in.ls_dmerit[k]); v = &tmp;
+    }
     else throw std::runtime_error("debug_get: unknown quantity " + nm);
     const int cnt = (int)v->size();
     if (cnt > cap) throw std::runtime_error("debug_get: output buffer too small");

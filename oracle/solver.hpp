@@ -119,6 +119,11 @@ struct Instance {
   std::vector<struct TreeNode> tree;
   std::vector<std::vector<double>> tree_guess;
   bool tree_guess_valid = false;
+  // linesearch of the last pass (debug dumps "ls", "ls_knot", "dmerit"): merit and slope at the start of the pass, the choice, the merit of
+  // every candidate alpha_i = 2^-i per knot (NaN: never evaluated), cost, penalty and slope part of every knot at the start of the pass
+  double ls_phi0 = 0, ls_dphi0 = 0;
+  std::vector<std::vector<double>> ls_cand;
+  std::vector<double> ls_cost, ls_pen, ls_dmerit;
 };
 
 struct Solver {
@@ -207,12 +212,14 @@ struct Solver {
   // P2 + merit: first-order multiplier estimates and primal-dual AL merit at (knots, vs, lams)
   //   M = sum l + sum_k mu/2 |v+|^2 + mu/2 |v+ - v|^2 + sum_k mud/2 |l+|^2 + mud/2 |l+ - l|^2
   double merit(const Instance& in, const std::vector<Knot>& knots, const std::vector<std::vector<double>>& vs,
-               const std::vector<std::vector<double>>& lams, double* cost_out = nullptr, double* prim_out = nullptr) const {
+               const std::vector<std::vector<double>>& lams, double* cost_out = nullptr, double* prim_out = nullptr,
+               double* knot_cost = nullptr, double* knot_pen = nullptr) const {  // knot_cost, knot_pen: N + 1 each, the knot's own terms
     const int N = dims.horizon;
     const double mu = in.mu, mud = mu_dyn(in);
     double cost = 0, pen = 0, prim = 0;
     for (int k = 0; k <= N; ++k) {
       const Knot& kn = knots[k];
+      double kpen = 0;  // the knot's own penalty, summed on its own (pen - pen before the knot would cancel against the other knots)
       cost += kn.cost;
       for (int i = 0; i < kn.c; ++i) {
         bool act;
@@ -220,15 +227,19 @@ struct Solver {
         const double pn = proj_normal(kn.ctype[i], z, kn.lo[i], kn.hi[i], act);
         const double vp = pn / mu;
         pen += 0.5 * mu * vp * vp + 0.5 * mu * (vp - vs[k][i]) * (vp - vs[k][i]);
+        kpen += 0.5 * mu * vp * vp + 0.5 * mu * (vp - vs[k][i]) * (vp - vs[k][i]);
         prim = std::max(prim, std::fabs(pn - mu * in.vs_e[k][i]));
       }
       if (k < N) {
         for (int i = 0; i < kn.n; ++i) {
           const double lp = in.lams_e[k + 1][i] + kn.f[i] / mud;
           pen += 0.5 * mud * lp * lp + 0.5 * mud * (lp - lams[k + 1][i]) * (lp - lams[k + 1][i]);
+          kpen += 0.5 * mud * lp * lp + 0.5 * mud * (lp - lams[k + 1][i]) * (lp - lams[k + 1][i]);
           prim = std::max(prim, std::fabs(kn.f[i]));
         }
       }
+      if (knot_cost) knot_cost[k] = kn.cost;
+      if (knot_pen) knot_pen[k] = kpen;
     }
     if (cost_out) *cost_out = cost;
     if (prim_out) *prim_out = prim;
@@ -863,7 +874,7 @@ struct Solver {
   }
 
   // directional derivative of the merit along the step
-  double dmerit(const Instance& in) const {
+  double dmerit(const Instance& in, double* knot_part = nullptr) const {  // knot_part: N + 1, the knot's own terms
     const int N = dims.horizon, n = dims.ndx;
     const double mu = in.mu, mud = mu_dyn(in);
     const bool ff = dims.space == MPC_SPACE_MULTIBODY && model.has_freeflyer();
@@ -871,10 +882,11 @@ struct Solver {
     for (int k = 0; k <= N; ++k) {
       const Knot& kn = in.knots[k];
       const int nz = kn.n + kn.m;
+      double kd = 0;  // the knot's own terms, summed on their own
       std::vector<double> dz(nz);
       for (int a = 0; a < kn.n; ++a) dz[a] = in.dxs[k][a];
       for (int a = 0; a < kn.m; ++a) dz[kn.n + a] = in.dus[k][a];
-      for (int a = 0; a < nz; ++a) d += kn.grad[a] * dz[a];
+      for (int a = 0; a < nz; ++a) { d += kn.grad[a] * dz[a]; kd += kn.grad[a] * dz[a]; }
       for (int i = 0; i < kn.c; ++i) {
         bool act;
         const double pn = proj_normal(kn.ctype[i], kn.cval[i] + mu * in.vs_e[k][i], kn.lo[i], kn.hi[i], act);
@@ -882,6 +894,7 @@ struct Solver {
         double jd = 0;
         for (int a = 0; a < nz; ++a) jd += kn.CD[i * nz + a] * dz[a];
         d += (vp + (act ? (vp - v) : 0.0)) * jd - mu * (vp - v) * in.dvs[k][i];
+        kd += (vp + (act ? (vp - v) : 0.0)) * jd - mu * (vp - v) * in.dvs[k][i];
       }
       if (k < N) {
         for (int i = 0; i < n; ++i) {
@@ -891,8 +904,10 @@ struct Solver {
           if (ff && i < 6) { for (int a = 0; a < 6; ++a) jd += kn.E6[i * 6 + a] * in.dxs[k + 1][a]; }
           else jd -= in.dxs[k + 1][i];
           d += (2 * lp - l) * jd - mud * (lp - l) * in.dlams[k + 1][i];
+          kd += (2 * lp - l) * jd - mud * (lp - l) * in.dlams[k + 1][i];
         }
       }
+      if (knot_part) knot_part[k] = kd;
     }
     return d;
   }
@@ -933,7 +948,12 @@ struct Solver {
   int iterate(Instance& in) {
     evaluate(in, in.xs, in.us, in.knots, true);
     double cost, prim, dual, crit;
-    const double phi0 = merit(in, in.knots, in.vs, in.lams, &cost, &prim);
+    const int N1 = dims.horizon + 1, n_alpha = opt.ls_max_steps > 1 ? opt.ls_max_steps : 1;
+    const double nan = std::nan("");
+    in.ls_cand.assign(n_alpha, std::vector<double>(N1, nan));
+    in.ls_cost.assign(N1, nan); in.ls_pen.assign(N1, nan); in.ls_dmerit.assign(N1, nan);
+    const double phi0 = merit(in, in.knots, in.vs, in.lams, &cost, &prim, in.ls_cost.data(), in.ls_pen.data());
+    in.ls_phi0 = phi0; in.ls_dphi0 = nan;
     lagrangian_residuals(in, dual, crit);
     in.stats.traj_cost = cost; in.stats.merit = phi0; in.stats.prim_infeas = prim; in.stats.dual_infeas = dual; in.stats.mu = in.mu;
     if (std::getenv("MPC_ORACLE_DEBUG")) fprintf(stderr, "it %d: cost %.10e merit %.10e prim %.3e dual %.3e crit %.3e (inner_tol %.3e) mu %.1e\n", in.stats.num_iters, cost, phi0, prim, dual, crit, in.inner_tol, in.mu);
@@ -966,7 +986,8 @@ struct Solver {
       backward(in);
       forward(in);
     }
-    const double dphi0 = dmerit(in);
+    const double dphi0 = dmerit(in, in.ls_dmerit.data());
+    in.ls_dphi0 = dphi0;
     // no descent left in the inner problem (round-off floor of the 1/mu-conditioned system): counts as solved, no step
     // (MPC_STALL_TOL of csrc/solver_kernels.h)
     if (std::fabs(dphi0) <= 1e-13 * (1.0 + std::fabs(phi0))) return 2;
@@ -975,7 +996,11 @@ struct Solver {
     for (;; ++step) {
       make_trial(in, alpha);
       evaluate(in, in.txs, in.tus, in.tknots, false);
-      phi = merit(in, in.tknots, in.tvs, in.tlams);
+      {
+        std::vector<double> kc(N1), kp(N1);
+        phi = merit(in, in.tknots, in.tvs, in.tlams, nullptr, nullptr, kc.data(), kp.data());
+        if (step < n_alpha) for (int k = 0; k < N1; ++k) in.ls_cand[step][k] = kc[k] + kp[k];
+      }
       if (std::getenv("MPC_ORACLE_DEBUG")) fprintf(stderr, "  ls: alpha %.4g phi %.10e phi0 %.10e dphi0 %.4e\n", alpha, phi, phi0, dphi0);
       if (phi <= phi0 + opt.ls_armijo_c1 * alpha * dphi0) break;
       if (step + 1 >= opt.ls_max_steps || 0.5 * alpha < opt.ls_alpha_min) break;
