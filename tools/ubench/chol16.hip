@@ -2,6 +2,8 @@
 // chol16_wave_mfma (accumulator layout, four panels, two MFMAs each: round 5) — the serial piece of the Riccati sweep's stage KKT system and
 // of the stage kernel's contact solve: clocks per call, alone on its SIMD and with the other wavefronts busy on MFMA; and the two against
 // each other (L, L^-1) and against the identity (L L^-1).
+// This tool is for TIMING.  Its comparison line is for the eye, on one well-conditioned block; correctness of these routines (exact planted cases, the
+// header's same-bits claims, backward errors up to condition 1e12, the refusal flag) is held by tests/test_gpu_mfma_blocks.py through tests/kernels/.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cmath>
