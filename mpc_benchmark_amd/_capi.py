@@ -19,6 +19,7 @@ from . import foot_sensors as _foot_sensors
 from . import plant_model as _plant_model
 from . import disturbance_model as _disturbance_model
 from . import friction_model as _friction_model
+from . import plan_latency as _plan_latency
 from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
 
@@ -241,6 +242,14 @@ _FEEDBACK_PIPELINE_SIGNATURES = {
     "mpc_feedback_low_level_steps": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int32, C.c_double, _DP, _DP, _DP, _DP]),
 }
 
+# include/mpc_plan_latency.h: exported by the HIP library alone, bound when present (``NativeSolver.plan_latency`` / ``read_plan_latency`` /
+# ``publish_plan``)
+_PLAN_LATENCY_SIGNATURES = {
+    "mpc_plan_latency": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_plan_latency_publish": (C.c_int, [C.c_void_p]),
+    "mpc_plan_latency_read": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
+}
+
 # include/mpc_walk_poses.h: exported by the HIP library alone, bound when present (``NativeSolver.walk_poses_*``)
 class MpcWalkPosesConfig(C.Structure):
     _fields_ = [("T_ss", C.c_int32), ("T_ds", C.c_int32), ("frame_lf", C.c_int32), ("frame_rf", C.c_int32), ("pose_offs", C.c_int32 * 6),
@@ -269,6 +278,7 @@ _WALK_COMMANDS_SIGNATURES = {
 _HIP_ONLY = (
     ("mpc_sim_ext.h", _SIM_EXT_SIGNATURES, "the push and the record of torque-driven simulator steps are HIP only", RuntimeError),
     ("mpc_feedback_pipeline.h", _FEEDBACK_PIPELINE_SIGNATURES, "the full-dynamics device loop is HIP only", RuntimeError),
+    ("mpc_plan_latency.h", _PLAN_LATENCY_SIGNATURES, "the hand-over latency of the plan in the device loops is HIP only", RuntimeError),
     ("mpc_sim_metrics.h", _SIM_METRICS_SIGNATURES, "the locomotion metrics of torque-driven simulator steps are HIP only", RuntimeError),
     ("mpc_sim_contacts.h", _SIM_CONTACTS_SIGNATURES, "the contact rule of torque-driven simulator steps is HIP only", RuntimeError),
     ("mpc_sim_actuators.h", _SIM_ACTUATORS_SIGNATURES, "the actuator model of torque-driven simulator steps is HIP only", RuntimeError),
@@ -805,6 +815,34 @@ class NativeSolver:
         self._check(fn(self._h, sim._h, _dp(xa), int(steps), float(dt), _dp(x_prev), _dp(x_out), _dp(tau), _dp(wr)),
                     "mpc_feedback_low_level_steps")
         return x_prev, x_out, tau, wr
+
+    # -- include/mpc_plan_latency.h (HIP library only): the per-robot hand-over latency of the plan in the three device loops ---------------------
+    def plan_latency(self, params):
+        """Arm (and reset) the per-robot hand-over latency of this plan handle (mpc_plan_latency; ``plan_latency`` is the definition): after every
+        ``publish_plan`` robot b of a device loop keeps running knot 1 of the plan before for its first L_b low-level steps.  ``params``: in the
+        forms of ``plan_latency.rows`` (an int, (B,) steps, (B, 4) rows of steps / jitter / seed / 0, or a dict).  None turns the model off and frees
+        what it allocated."""
+        fn = self._hip("mpc_plan_latency")
+        p = _plan_latency.rows(params, self.dims.batch)
+        self._check(fn(self._h, _dp(p)), "mpc_plan_latency")
+
+    def publish_plan(self):
+        """A publication (mpc_plan_latency_publish): called while the outgoing plan is still in the handle's buffers, before the run that replaces
+        it.  Every robot's held record is taken from knot 1, its latency drawn and its countdown set."""
+        self._check(self._hip("mpc_plan_latency_publish")(self._h), "mpc_plan_latency_publish")
+
+    def read_plan_latency(self, raw=False):
+        """The latency model as it stands (mpc_plan_latency_read) -> dict: ``params`` (B, 4) the rows in force, the state rows by
+        ``plan_latency.unpack`` (``remaining``, ``drawn``, ``plans``, ``late_steps``, ``steps_total``, ``max_drawn``, ``held_valid``: (B,) ints) and
+        ``held``: the held records by ``plan_latency.unpack_held`` (``xs`` (B, nx), ``us`` (B, nu), ``K`` (B, nu, ndx), ``xdot`` (B, 6)).  ``raw``:
+        ``state`` (B, 8) and ``held`` (B, W) as they are stored."""
+        fn, d = self._hip("mpc_plan_latency_read"), self.dims
+        params, state = np.zeros((d.batch, _plan_latency.PARAMS)), np.zeros((d.batch, _plan_latency.STATE))
+        held = np.zeros((d.batch, _plan_latency.held_width(d.nx, d.ndx, d.nu)))
+        self._check(fn(self._h, _dp(params), _dp(state), _dp(held)), "mpc_plan_latency_read")
+        if raw:
+            return dict(params=params, state=state, held=held)
+        return dict(_plan_latency.unpack(state), params=params, held=_plan_latency.unpack_held(held, d.nx, d.ndx, d.nu))
 
     def get_x0(self):
         x0 = np.zeros((self.dims.batch, self.dims.nx))

@@ -43,6 +43,7 @@
 #include "sim_disturbances.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
+#include "../../include/mpc_plan_latency.h"
 #include "../../include/mpc_walk_poses.h"
 #include "qp_device_api.h"
 
@@ -196,6 +197,9 @@ struct mpc_solver {
   int since_change = 1 << 20;      // mpc_cycle calls since the appended stage last changed its contact pattern (corrector_window)
   bool refine_now = false;         // ... and this run refines the warm start of the appended knot after k_begin_run
   SimPlant plant;  // the torque-driven simulator steps on this handle (sim_host.h)
+  // include/mpc_plan_latency.h (pipeline_loops.h): params [B][4] | state [B][8] | held [B][W] in one buffer from hipMalloc, nullptr while the model is off
+  double* d_plan_lat = nullptr;
+  bool has_run = false;  // a run left a plan in the buffers (mpc_plan_latency_publish refuses a handle without one)
   // per-slot invalidation (mpc_update_stage_params*): slots whose parameters changed since the last pass was enqueued ; dirty_all:
   // an update on a horizon too long for the mask of SolverArgs
   std::vector<uint8_t> slot_dirty;
@@ -972,6 +976,7 @@ void mpc_destroy(mpc_solver* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   for (double* p : {s->d_work, s->d_legbuf, s->d_treebuf}) if (p) (void)hipFree(p);
   s->plant.free_owned();
+  if (s->d_plan_lat) (void)hipFree(s->d_plan_lat);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1451,6 +1456,12 @@ int mpc_set_state(mpc_solver* s, const double* buf, int64_t len) {
     // every stage went through upload_stage above, which hands the instances the SHARED tables again: with the reference generator in the library the next
     // mpc_walk_update must rewrite the references of every knot, not only of the appended one
     s->walk_force_all = s->walk_on;
+    // include/mpc_plan_latency.h: a restored checkpoint is followed at once (remaining = 0, no held record ; the counters stay)
+    if (s->d_plan_lat) {
+      double* st = s->d_plan_lat + (size_t)L.B * MPC_PLAN_LATENCY_PARAMS;
+      for (int col : {0, 6})
+        HIP_OK(hipMemset2DAsync(st + col, MPC_PLAN_LATENCY_STATE * sizeof(double), 0, sizeof(double), (size_t)L.B, s->stream));
+    }
   })
 }
 
@@ -1473,6 +1484,7 @@ int mpc_run(mpc_solver* s, const double* xs, const double* us, mpc_stats* stats)
     // guesses stay — refreshing them there would cost one sweep per tree level on every tick of the drop-in path.
     if (s->opt.max_iters > 1) s->leg_guess_valid = false;
     s->spec_skip_pass = false;
+    s->has_run = true;
     const Layout& L = s->L;
     HIP_OK(hipMemcpyAsync(s->d_xs, xs, (size_t)L.B * (L.N + 1) * L.nx * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_OK(hipMemcpyAsync(s->d_us, us, (size_t)L.B * L.N * L.m * sizeof(double), hipMemcpyHostToDevice, s->stream));
@@ -1487,6 +1499,7 @@ int mpc_run_shifted(mpc_solver* s, mpc_stats* stats) {
     begin_refine(s);
     begin_reuse_pass(s);
     launch_shift(s);
+    s->has_run = true;
     run_impl(s, stats);
   })
 }
@@ -1505,6 +1518,7 @@ int mpc_run_shifted_async(mpc_solver* s) {
     begin_refine(s);
     begin_reuse_pass(s);
     launch_shift(s);
+    s->has_run = true;
     hipLaunchKernelGGL(k_begin_run, dim3(L.B), dim3(64), 0, s->stream, s->args());
     launch_refine(s);
     // with max_iters = 1 one pass takes the step; a few iterations per tick (max_iters <= 4) are enqueued together — a younger tick

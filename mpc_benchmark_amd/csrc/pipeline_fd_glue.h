@@ -13,13 +13,20 @@ struct FdPipeArgs {
 };
 
 // d = difference(x_measured, xs[0]) ; tau = us[0] - K_0 d, unclamped (the script executes it as it is)
-__global__ void __launch_bounds__(64) k_pipe_state_feedback(FdPipeArgs p) {
+// HELD (include/mpc_plan_latency.h; launched while a latency is armed on the plan, `h` is read by it alone): a robot whose hand-over latency has
+// not run out takes xs, us and K from its held record (knot 1 of the plan before) instead; then one lane advances its clock.
+template <bool HELD> __global__ void __launch_bounds__(64) k_pipe_state_feedback(FdPipeArgs p, PlanLatencyArgs h) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nx = p.nx, nq = p.nq, nv = p.nv, n = p.n, m = p.m;
   const double* x = p.x + (size_t)b * nx;
   const double* x0 = p.xs + (size_t)b * (p.N + 1) * nx;
   const double* us0 = p.us + (size_t)b * p.N * m;
   const double* K0 = p.gains + (size_t)b * (p.N + 1) * p.gain_stride + p.oK;
+  bool held = false;
+  if (HELD) {
+    held = plan_latency_in_force(h, b);
+    if (held) { x0 = h.held + (size_t)b * h.W; us0 = x0 + nx; K0 = us0 + m; }
+  }
   __shared__ double dd[PIPE_MAX_N];
   if (lane == 0) {  // the base: log of the relative SE(3) placement, as k_pipe_feedback
     const M3 Rx = quat_to_rot(x + 3), R0 = quat_to_rot(x0 + 3);
@@ -35,4 +42,5 @@ __global__ void __launch_bounds__(64) k_pipe_state_feedback(FdPipeArgs p) {
     for (int j = 0; j < n; ++j) su += K0[(size_t)i * n + j] * dd[j];
     p.sim_u[(size_t)b * m + i] = us0[i] - su;
   }
+  if (HELD) plan_latency_count(h, b, held, lane);
 }

@@ -3,6 +3,7 @@
 // torque — clamped — into the simulator step.  One workgroup of one wavefront per robot; the vectors are a few hundred bytes.
 #pragma once
 #include "solver_args.h"
+#include "plan_latency.h"
 
 struct PipeArgs {
   // the plan (kinodynamic MPC handle): solution of knot 0, its Riccati gain, xdot of its stage data
@@ -22,7 +23,9 @@ struct PipeArgs {
 #define PIPE_MAX_N 160  // tangent dimension 2 nv of the plan
 
 // d = difference(x_measured, xs[0]) ; forces = us[0][:6 nk] - K_0[:6 nk] d ; a0 = [xdot(knot 0) base acceleration ; us[0][6 nk:] - K_0[6 nk:] d]
-__global__ void __launch_bounds__(64) k_pipe_feedback(PipeArgs p) {
+// HELD (include/mpc_plan_latency.h; launched while a latency is armed on the plan, `h` is read by it alone): a robot whose hand-over latency has
+// not run out takes xs, us, K and the base acceleration from its held record (knot 1 of the plan before) instead; then one lane advances its clock.
+template <bool HELD> __global__ void __launch_bounds__(64) k_pipe_feedback(PipeArgs p, PlanLatencyArgs h) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nx = p.nx, nq = p.nq, nv = p.nv, n = p.n, m = p.m, nf = 6 * p.nk;
   const double* x = p.x + (size_t)b * nx;
@@ -30,6 +33,11 @@ __global__ void __launch_bounds__(64) k_pipe_feedback(PipeArgs p) {
   const double* us0 = p.us + (size_t)b * p.N * m;
   const double* K0 = p.gains + (size_t)b * (p.N + 1) * p.gain_stride + p.oK;
   const double* xd = p.knots + ((size_t)b * (p.N + 1) + p.slot0) * p.knot_stride + p.oXD;
+  bool held = false;
+  if (HELD) {
+    held = plan_latency_in_force(h, b);
+    if (held) { x0 = h.held + (size_t)b * h.W; us0 = x0 + nx; K0 = us0 + m; xd = K0 + (size_t)m * n - nv; }  // (the record keeps xdot[nv .. nv + 6))
+  }
   __shared__ double dd[PIPE_MAX_N];
   if (lane == 0) {
     const M3 Rx = quat_to_rot(x + 3), R0 = quat_to_rot(x0 + 3);
@@ -49,6 +57,7 @@ __global__ void __launch_bounds__(64) k_pipe_feedback(PipeArgs p) {
   }
   if (lane < 6) p.acc[(size_t)b * nv + lane] = xd[nv + lane];
   for (int i = lane; i < nx; i += 64) p.xrob[(size_t)b * nx + i] = x[i];
+  if (HELD) plan_latency_count(h, b, held, lane);
 }
 
 // tau = clamp(QP torque, +-tau_max) into the simulator's input ; forces + df (with `used`: 0 for a contact the QP did not use)

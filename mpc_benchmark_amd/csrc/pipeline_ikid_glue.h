@@ -5,6 +5,7 @@
 // kinematics of ~30 bodies, one body per lane, and vectors of a few hundred bytes.
 #pragma once
 #include "solver_args.h"
+#include "plan_latency.h"
 
 #define CG_THREADS 64
 #define CG_MAX_NJ 64        // moving joints of the model (one lane each)
@@ -115,7 +116,8 @@ DEV void cg_frame(const int32_t* mi, const double* md, const CgBodies& K, int fi
 //   feet      e = [p_ref0 - p ; -log3(R_ref0^T R)],  de = [(p_ref1 - p_ref0) / dt - v_lin ; log3(R_ref0^T R_ref1) / dt - v_ang]   (LOCAL velocity)
 //   base, torso  e = -log3(R_RFref0^T R),  de = log3(R_RFref0^T R_RFref1) / dt - v_ang
 //   dH        xdot[3:9] of the plan's knot 0 (centroidal_talos.py:409)
-__global__ void __launch_bounds__(CG_THREADS) k_ikid_task_errors(IkidGlueArgs a) {
+// HELD (include/mpc_plan_latency.h): dH from the held record of a robot whose first step of this call reads it ; the clock is not advanced here.
+template <bool HELD> __global__ void __launch_bounds__(CG_THREADS) k_ikid_task_errors(IkidGlueArgs a, PlanLatencyArgs h) {
   const int b = blockIdx.x, tid = threadIdx.x, nq = a.nq, nv = a.nv, nx = nq + nv;
   __shared__ CgBodies K;
   const double* x = a.x_ik + (size_t)b * nx;
@@ -161,6 +163,12 @@ __global__ void __launch_bounds__(CG_THREADS) k_ikid_task_errors(IkidGlueArgs a)
     } else ik[iv] = -(x[iq] - x0[iq]);
   }
   for (int i = tid; i < nv; i += CG_THREADS) ik[nv + i] = -(x[nq + i] - x0[nq + i]);
+  if (HELD) {
+    if (plan_latency_in_force(h, b)) {  // (the record keeps xdot[3 .. 9) behind K_1)
+      if (tid < 6) ik[2 * nv + 36 + tid] = h.held[(size_t)b * h.W + CG_NC + a.m + (size_t)a.m * CG_NC + tid];
+      return;
+    }
+  }
   if (tid < 6) ik[2 * nv + 36 + tid] = a.knots[((size_t)b * (a.N + 1) + a.slot0) * a.knot_stride + a.oXD + 3 + tid];
 }
 
@@ -193,7 +201,9 @@ DEV void cg_centroidal(const int32_t* mi, const double* md, const CgBodies& K, d
 
 // Per step: new_x = [com ; hg] of the measured state, forces = us[0] - K_0 (xs[0] - new_x) (centroidal_talos.py:420-434), the QP inputs, and on the
 // last step new_x into c_prev.
-__global__ void __launch_bounds__(CG_THREADS) k_pipe_centroidal_feedback(IkidGlueArgs a) {
+// HELD (include/mpc_plan_latency.h): a robot whose hand-over latency has not run out takes xs, us and K from its held record (knot 1 of the plan
+// before) instead; then one lane advances its clock.
+template <bool HELD> __global__ void __launch_bounds__(CG_THREADS) k_pipe_centroidal_feedback(IkidGlueArgs a, PlanLatencyArgs h) {
   const int b = blockIdx.x, tid = threadIdx.x, nx = a.nq + a.nv, nf = 6 * a.nk;
   __shared__ CgBodies K;
   __shared__ double body[10 * CG_MAX_NJ];
@@ -204,6 +214,11 @@ __global__ void __launch_bounds__(CG_THREADS) k_pipe_centroidal_feedback(IkidGlu
   const double* xs0 = a.xs + (size_t)b * (a.N + 1) * CG_NC;
   const double* us0 = a.us + (size_t)b * a.N * a.m;
   const double* K0 = a.gains + (size_t)b * (a.N + 1) * a.gain_stride + a.oK;
+  bool held = false;
+  if (HELD) {
+    held = plan_latency_in_force(h, b);
+    if (held) { xs0 = h.held + (size_t)b * h.W; us0 = xs0 + CG_NC; K0 = us0 + a.m; }
+  }
   for (int i = tid; i < nf; i += CG_THREADS) {
     double su = 0.0;
     for (int j = 0; j < CG_NC; ++j) su += K0[i * CG_NC + j] * (xs0[j] - cx[j]);
@@ -211,6 +226,7 @@ __global__ void __launch_bounds__(CG_THREADS) k_pipe_centroidal_feedback(IkidGlu
   }
   for (int i = tid; i < nx; i += CG_THREADS) a.xrob[(size_t)b * nx + i] = x[i];
   if (a.last && tid < CG_NC) a.c_prev[(size_t)b * CG_NC + tid] = cx[tid];
+  if (HELD) plan_latency_count(h, b, held, tid);
 }
 
 // the QP's torque into the simulator's input (no clamp: the QP's torque box is the limit, centroidal_talos.py:435-447) ; forces + df (with `used`: 0 for a

@@ -2,8 +2,20 @@
 // sim_step_enqueue), with nothing but kernels in between.  mpc_qp_low_level_steps (kinodynamic, include/mpc_qp_abi.h), mpc_qp_ikid_low_level_steps
 // (centroidal, the same header) and mpc_feedback_low_level_steps (full dynamics, include/mpc_feedback_pipeline.h).  The controllers read sim_measured(sim): the measurement of
 // the sensor model when it is on (include/mpc_sim_sensors.h), the true state otherwise; x_out, the record, the metrics and the contact rule are the
-// true state's.  Included at the end of mpc_hip.hip, after sim_host.h.
+// true state's.  With a hand-over latency armed on the plan (include/mpc_plan_latency.h, host side below) the loops launch the second instantiation of
+// their feedback kernels (plan_latency.h), which read every robot's held record while its countdown runs; off, they launch what they always did.
+// Included at the end of mpc_hip.hip, after sim_host.h.
 #pragma once
+
+// include/mpc_plan_latency.h: the three parts of the handle's buffer, and what the second instantiations of the feedback kernels get
+static size_t plan_latency_width(const Layout& P) { return (size_t)MPC_PLAN_LATENCY_HELD(P.nx, P.n, P.m); }
+static double* plan_latency_state(const mpc_solver* plan) { return plan->d_plan_lat + (size_t)plan->L.B * MPC_PLAN_LATENCY_PARAMS; }
+static double* plan_latency_held(const mpc_solver* plan) { return plan_latency_state(plan) + (size_t)plan->L.B * MPC_PLAN_LATENCY_STATE; }
+static PlanLatencyArgs plan_latency_args(const mpc_solver* plan) {
+  PlanLatencyArgs h;
+  h.state = plan_latency_state(plan); h.held = plan_latency_held(plan); h.W = (int)plan_latency_width(plan->L);
+  return h;
+}
 
 // include/mpc_qp_contacts.h: a loop call on a QP handle whose contact source is not the schedule.  The checks (throws), then the arguments of
 // k_pipe_contact_states: the caller's contact_states go to the schedule buffer and q.cs becomes an output of that kernel, once per step.
@@ -68,7 +80,8 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
       if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(d_xprev, sim_measured(sim), B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(k_pipe_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
+      if (plan->d_plan_lat) hipLaunchKernelGGL(k_pipe_feedback<true>, dim3((unsigned)B), dim3(64), 0, st, p, plan_latency_args(plan));
+      else hipLaunchKernelGGL(k_pipe_feedback<false>, dim3((unsigned)B), dim3(64), 0, st, p, PlanLatencyArgs{});
       if (from_plant) pipe_contacts_enqueue(pc, st);
       qp_id_enqueue(qp, S, kd);
       qp_launch_solve(qp, S);
@@ -149,14 +162,16 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     g.x = sim_measured(sim); g.xrob = q.xrob; g.f = q.f; g.c_prev = d_cprev;
     g.sol = q.sol; g.nk = nk; g.qn = q.n; g.sim_u = sim->plant.d_simu; g.f_new = d_fnew;
     g.used = from_plant ? qc.used : nullptr;
-    hipLaunchKernelGGL(k_ikid_task_errors, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+    if (plan->d_plan_lat) hipLaunchKernelGGL(k_ikid_task_errors<true>, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g, plan_latency_args(plan));
+    else hipLaunchKernelGGL(k_ikid_task_errors<false>, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g, PlanLatencyArgs{});
     HIP_OK(hipGetLastError());
     if (ik_out) HIP_OK(hipMemcpyAsync(ik_out, q.ik, B * nik * sizeof(double), hipMemcpyDeviceToHost, st));
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
       g.last = (step == steps - 1);
       if (g.last) HIP_OK(hipMemcpyAsync(d_xprev, sim_measured(sim), B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(k_pipe_centroidal_feedback, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+      if (plan->d_plan_lat) hipLaunchKernelGGL(k_pipe_centroidal_feedback<true>, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g, plan_latency_args(plan));
+      else hipLaunchKernelGGL(k_pipe_centroidal_feedback<false>, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g, PlanLatencyArgs{});
       if (from_plant) pipe_contacts_enqueue(pc, st);
       qp_ikid_enqueue(qp, S);
       qp_launch_solve(qp, S);
@@ -208,7 +223,8 @@ int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
       if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(sim->plant.d_xlast, sim_measured(sim), B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(k_pipe_state_feedback, dim3((unsigned)B), dim3(64), 0, st, p);
+      if (plan->d_plan_lat) hipLaunchKernelGGL(k_pipe_state_feedback<true>, dim3((unsigned)B), dim3(64), 0, st, p, plan_latency_args(plan));
+      else hipLaunchKernelGGL(k_pipe_state_feedback<false>, dim3((unsigned)B), dim3(64), 0, st, p, PlanLatencyArgs{});
       sim_step_enqueue(sim, st, za, 1, dt, wrenches != nullptr);
     }
     if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, sim->plant.d_xlast, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -217,6 +233,71 @@ int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double
     if (wrenches) HIP_OK(hipMemcpyAsync(wrenches, sim->plant.d_simwr, B * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     sim->perfect_feedback = false;
+  })
+}
+
+// include/mpc_plan_latency.h: arm and reset, or (params = NULL) turn off and free.  Every check comes before anything changes.
+int mpc_plan_latency(mpc_solver* plan, const double* params) {
+  MPC_TRY(plan, {
+    if (!plan) throw std::runtime_error("plan_latency: null handle");
+    if (plan->async_pending > 0) throw std::runtime_error("plan_latency: the plan has ticks in flight (mpc_wait first)");
+    const Layout& P = plan->L;
+    const size_t B = P.B;
+    if (params) {
+      if (P.N < 2) throw std::runtime_error("plan_latency: the held record is knot 1 of the plan: a horizon of at least 2 knots is needed");
+      if (P.n < (P.space == MPC_SPACE_MULTIBODY ? 12 : 9))  // (the xdot part: xdot[n/2 .. n/2 + 6) or xdot[3 .. 9))
+        throw std::runtime_error("plan_latency: the plan must be one of the three pipelines' (multibody with a free-flyer base, or centroidal with n = 9)");
+      const double hi[MPC_PLAN_LATENCY_PARAMS] = {MPC_PLAN_LATENCY_MAX_STEPS, MPC_PLAN_LATENCY_MAX_STEPS, 4294967295.0, 0.0};
+      const char* name[MPC_PLAN_LATENCY_PARAMS] = {"steps", "jitter", "seed", "the reserved entry"};
+      for (size_t b = 0; b < B; ++b)
+        for (int i = 0; i < MPC_PLAN_LATENCY_PARAMS; ++i) {
+          const double v = params[b * MPC_PLAN_LATENCY_PARAMS + i];
+          const std::string who = std::string(name[i]) + " of robot " + std::to_string(b);
+          if (!std::isfinite(v)) throw std::runtime_error("plan_latency: non-finite " + who);
+          if (v != std::floor(v)) throw std::runtime_error("plan_latency: " + who + " is not an integer");
+          if (v < 0.0 || v > hi[i]) throw std::runtime_error("plan_latency: " + who + " out of range (0 .. " + std::to_string((long long)hi[i]) + ")");
+        }
+    }
+    HIP_OK(hipStreamSynchronize(plan->stream));
+    if (!params) {
+      if (plan->d_plan_lat) { HIP_OK(hipFree(plan->d_plan_lat)); plan->d_plan_lat = nullptr; }
+      return 0;
+    }
+    const size_t doubles = B * (MPC_PLAN_LATENCY_PARAMS + MPC_PLAN_LATENCY_STATE + plan_latency_width(P));
+    if (!plan->d_plan_lat) HIP_OK(hipMalloc((void**)&plan->d_plan_lat, doubles * sizeof(double)));
+    HIP_OK(hipMemsetAsync(plan->d_plan_lat, 0, doubles * sizeof(double), plan->stream));
+    copy_sync(plan, plan->d_plan_lat, params, B * MPC_PLAN_LATENCY_PARAMS * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+// include/mpc_plan_latency.h: every robot's held record from knot 1 of the plan in the buffers, its draw and its countdown.  On the plan's stream:
+// behind the run that made the plan, ahead of the run that replaces it ; the loops drain that stream before they read the rows.
+int mpc_plan_latency_publish(mpc_solver* plan) {
+  MPC_TRY(plan, {
+    if (!plan) throw std::runtime_error("plan_latency_publish: null handle");
+    if (!plan->d_plan_lat) throw std::runtime_error("plan_latency_publish: the latency model is off on this handle (arm it with mpc_plan_latency)");
+    if (plan->async_pending > 0) throw std::runtime_error("plan_latency_publish: the plan has ticks in flight (mpc_wait first)");
+    if (!plan->has_run) throw std::runtime_error("plan_latency_publish: the handle has never run: there is no plan to hold");
+    const Layout& P = plan->L;
+    PlanPublishArgs a;
+    a.xs = plan->d_xs; a.us = plan->d_us; a.gains = plan->d_gains; a.knots = plan->d_knots;
+    a.N = P.N; a.nx = P.nx; a.n = P.n; a.m = P.m; a.gain_stride = P.gain_stride; a.oK = P.oK; a.knot_stride = P.knot_stride; a.oXD = P.oXD;
+    a.slot1 = (plan->khead + 1) % P.N;
+    a.xd_off = P.space == MPC_SPACE_MULTIBODY ? P.n / 2 : 3;
+    a.params = plan->d_plan_lat; a.state = plan_latency_state(plan); a.held = plan_latency_held(plan); a.W = (int)plan_latency_width(P);
+    hipLaunchKernelGGL(k_plan_latency_publish, dim3((unsigned)P.B), dim3(PLAN_LAT_THREADS), 0, plan->stream, a);
+    HIP_OK(hipGetLastError());
+  })
+}
+
+int mpc_plan_latency_read(mpc_solver* plan, double* params, double* state, double* held) {
+  MPC_TRY(plan, {
+    if (!plan) throw std::runtime_error("plan_latency_read: null handle");
+    if (!plan->d_plan_lat) throw std::runtime_error("plan_latency_read: the latency model is off on this handle (arm it with mpc_plan_latency)");
+    const size_t B = plan->L.B;
+    if (params) copy_sync(plan, params, plan->d_plan_lat, B * MPC_PLAN_LATENCY_PARAMS * sizeof(double), hipMemcpyDeviceToHost);
+    if (state) copy_sync(plan, state, plan_latency_state(plan), B * MPC_PLAN_LATENCY_STATE * sizeof(double), hipMemcpyDeviceToHost);
+    if (held) copy_sync(plan, held, plan_latency_held(plan), B * plan_latency_width(plan->L) * sizeof(double), hipMemcpyDeviceToHost);
   })
 }
 

@@ -96,7 +96,15 @@ plus a delay, a duration, a rectangular or half-sine shape, and a force and poin
 every robot, or one list of events per robot), armed on the simulator handle when the pipeline is built (mpc_sim_disturbances,
 include/mpc_sim_disturbances.h; HIP library only).  The device times the events step by step inside the low-level loop; contact triggers need
 ``contact_rule``.  ``disturbance_state()`` returns the clock, the counters and what acted; ``set_disturbances`` changes or removes the table later.
-While a table is armed ``tick(push=...)`` raises."""
+While a table is armed ``tick(push=...)`` raises.
+
+``latency`` (all three pipelines): None, every robot follows knot 0 of a new plan from the first low-level step after the solve; or the rows of the
+plan's per-robot hand-over latency (``plan_latency``: ``steps``, ``jitter``, ``seed``; an int, (B,) steps, (B, 4) rows or a dict).  Directly after the
+low-level loop of a tick, before the next plan is solved, the pipeline publishes: knot 1 of the outgoing plan is held by value for every robot and
+its latency L_b drawn; for its first L_b low-level steps after the solve the robot's controller reads that held record, then knot 0 of the new
+plan.  The device loops read the held record and keep the countdown on the device (mpc_plan_latency, include/mpc_plan_latency.h; HIP library
+only); ``tick(host_glue=True)`` applies the same rule with calls both libraries have and the mirror's clock.  ``plan_latency.from_solve_ms`` turns a
+measured solve time into steps.  ``latency_state()`` returns the countdown and the counters; ``set_latency`` arms again or removes the model."""
 from __future__ import annotations
 
 import contextlib
@@ -107,6 +115,7 @@ from . import _capi as K
 from . import contact_rule as _contact_rule
 from . import disturbance_model as _disturbance_model
 from . import foot_sensors as _foot_sensors
+from . import plan_latency as _plan_latency
 from . import qp_utils
 from . import torque_simulator as _tsim
 from .aligator import manifolds as _manifolds
@@ -232,10 +241,11 @@ class _Pipeline:
         """(the hook of the pipelines with a low-level QP, ``_QpContactSource``)"""
 
     def _check_arguments(self, problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts, contact_source=None,
-                         disturbances=None):
+                         disturbances=None, latency=None):
         """the arguments every pipeline takes, checked before the library is loaded -> (walk, detected_contacts)"""
         name = type(self).__name__
         self.pd, self.batch = problem_def, int(batch)
+        self._latency = _plan_latency.rows(latency, self.batch)
         self._init_contact_source(name, contact_source, contact_rule)
         detected_contacts = self._check_detected(name, foot_sensors, detected_contacts, contact_rule, self.contact_source)
         self.terrain = _checked_terrain(name, terrain, contact_rule, self.batch)
@@ -286,6 +296,7 @@ class _Pipeline:
         self.x_prev = self.x_est.copy()      # the measurement of the period before (the solve's initial condition)
         self.torques = np.zeros((self.batch, self.nv - 6))
         self._plan_stale = True
+        self._reset_latency()
 
     def _set_sim_contacts(self, mask):
         if self.contact_rule is None:   # (else the rule decides every robot's contacts on the device)
@@ -366,6 +377,80 @@ class _Pipeline:
     def friction_state(self):
         """the state rows of the friction model by ``friction_model.unpack`` (``v``, ``sliding``, ``slip_dist`` ...); None without ``friction``"""
         return self.sim_models.friction_state()
+
+    # -- the hand-over latency of the plan (``plan_latency``, include/mpc_plan_latency.h): ``None`` turns it off ------------------------------------
+    def _reset_latency(self):
+        """the mirror's state rows as after arming; the device model, if a device tick armed one, is armed again with the rows in force (or off)"""
+        self._lat_state = None if self._latency is None else _plan_latency.initial_state(self.batch)
+        self._lat_held = None
+        self._lat_form = None          # "host" or "device": the form of the ticks since arming (the two clocks are not one)
+        if getattr(self, "_lat_on_device", False):
+            self.mpc.native.plan_latency(None)
+        self._lat_on_device = False
+
+    def set_latency(self, rows):
+        """Arm (and reset) the per-robot hand-over latency of the plan: ``rows`` in the forms of ``plan_latency.rows`` (None: off; an int; (B,)
+        steps; (B, 4) rows; a dict of ``steps`` / ``jitter`` / ``seed``).  After every publication — directly after the low-level loop of a tick,
+        before the next plan is solved — robot b keeps running knot 1 of the outgoing plan for its first L_b low-level steps.  Checked before
+        anything changes."""
+        self._latency = _plan_latency.rows(rows, self.batch)
+        self._reset_latency()
+
+    def latency_state(self):
+        """the state rows of the latency model by ``plan_latency.unpack`` (``remaining``, ``drawn``, ``plans``, ``late_steps``, ``steps_total``,
+        ``max_drawn``, ``held_valid``): the device's after device ticks, the mirror's after host-glue ticks; None without ``latency``"""
+        if self._latency is None:
+            return None
+        if self._lat_on_device:
+            r = self.mpc.native.read_plan_latency()
+            return {k: r[k] for k in _plan_latency.STATE_FIELDS[:7]}
+        return _plan_latency.unpack(self._lat_state)
+
+    def _latency_tick(self, host_glue):
+        """at the head of a tick: the two forms keep two clocks (the mirror's on the host, the kernels' on the device), so a pipeline with a latency
+        armed runs one form until it is armed again; the first device tick arms the model on the plan handle"""
+        if self._latency is None:
+            return
+        form = "host" if host_glue else "device"
+        if self._lat_form not in (None, form):
+            raise RuntimeError("%s: latency is armed and the ticks so far were %s ticks: the %s form keeps a clock of its own (set_latency arms "
+                               "again, for either form)" % (type(self).__name__, self._lat_form, form))
+        if form == "device" and not self._lat_on_device:
+            self.mpc.native.plan_latency(self._latency)
+            self._lat_on_device = True
+        self._lat_form = form
+
+    def _latency_publish(self, host_glue):
+        """directly after the low-level loop of a tick, the outgoing plan still in the handle: every robot's held record and its draw.  Device: one
+        kernel (mpc_plan_latency_publish).  Host glue: knot 1 fetched by calls both libraries have, the draw and the countdown by the mirror."""
+        if self._latency is None:
+            return
+        if not host_glue:
+            self.mpc.native.publish_plan()
+            return
+        nat = self.mpc.native
+        r = nat.get_results(gains=False)
+        o = _plan_latency.xdot_offset(nat.dims.space == K.SPACE_MULTIBODY, nat.dims.ndx)
+        self._lat_held = dict(xs=r["xs"][:, 1].copy(), us=r["us"][:, 1].copy(), K=nat.get_gain(1)[0],
+                              xdot=nat.get_stage_data(1)[0][:, o:o + _plan_latency.XDOT_PART].copy())
+        self._lat_state = _plan_latency.publish(self._lat_state, self._latency)
+
+    def _latency_first(self):
+        """host glue: (B,) bool, who reads the held record on the next low-level step (nothing counted); None without ``latency``"""
+        return None if self._latency is None else _plan_latency.step(self._lat_state)[0]
+
+    def _knot_in_force(self, xdot0=None):
+        """host glue, once per low-level step: the clock of every robot advances, and -> (xs, us, K[, xdot part]) of the record each robot's
+        controller reads on this step: knot 0 of the plan, or the held record while the robot's countdown runs"""
+        plan = (self.xs0, self.us0, self.K0) + (() if xdot0 is None else (xdot0,))
+        if self._latency is None:
+            return plan
+        use, self._lat_state = _plan_latency.step(self._lat_state)
+        if not use.any():
+            return plan
+        h = self._lat_held
+        held = (h["xs"], h["us"], h["K"]) + (() if xdot0 is None else (h["xdot"],))
+        return tuple(np.where(use.reshape((-1,) + (1,) * (a.ndim - 1)), a, b) for a, b in zip(held, plan))
 
     # -- the loop ---------------------------------------------------------------------------------------------------------------------
     def _walk_kwargs(self):
@@ -470,15 +555,15 @@ class _QpContactSource(_Pipeline):
 class KinodynamicPipeline(_QpContactSource):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
                  terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, foot_sensors=None,
-                 detected_contacts=(), plant=None, friction=None, disturbances=None, **ens_kw):
+                 detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
         ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model, ``sensors``: None or the rows of the
         sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the rows of the foot force sensors,
         ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model, ``friction``: None or the rows of
-        the ground friction (module docstring)."""
+        the ground friction, ``latency``: None or the rows of the plan's hand-over latency (module docstring)."""
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
-                                                        contact_source, disturbances=disturbances)
+                                                        contact_source, disturbances=disturbances, latency=latency)
         plant = _checked_plant(plant, self.batch, problem_def)
         self._load(library, substeps, sim_dt)
         rb, m = problem_def.robot, self.model
@@ -504,10 +589,12 @@ class KinodynamicPipeline(_QpContactSource):
             self._fetch()
         nq, nv = self.nq, self.nv
         x = self.x_est
-        d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], self.xs0[:, :nq]), self.xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
+        xs0, us0, K0, ab = self._knot_in_force(self.xdot0[:, nv:nv + 6])
+        d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], xs0[:, :nq]), xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
         a0 = self.xdot0[:, nv:].copy()
-        a0[:, 6:] = self.us0[:, 12:] - np.einsum("bij,bj->bi", self.K0[:, 12:], d)
-        forces = self.us0[:, :12] - np.einsum("bij,bj->bi", self.K0[:, :12], d)
+        a0[:, :6] = ab
+        a0[:, 6:] = us0[:, 12:] - np.einsum("bij,bj->bi", K0[:, 12:], d)
+        forces = us0[:, :12] - np.einsum("bij,bj->bi", K0[:, :12], d)
         a_new, f_new, tau = self.qp.solve_batch_device(x, a0, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
         tau = np.clip(tau, -self.umax, self.umax)
         self.x = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt)
@@ -528,6 +615,7 @@ class KinodynamicPipeline(_QpContactSource):
         ``push``: (B, 3) world force at the base origin or (B, 6) (force, world point), armed on the simulator for the low-level steps of this period
         only (mpc_sim_set_push, HIP library; ``push_schedule``)."""
         push = self._checked_push(push)
+        self._latency_tick(host_glue)
         cs = self.contact_state()
         self._set_sim_contacts(cs)
         with self._pushed(push):
@@ -542,6 +630,7 @@ class KinodynamicPipeline(_QpContactSource):
                         self.forces = _contact_rule.qp_zero_unused(self.forces, used)
             else:
                 x_last = self.low_level_loop(cs)
+        self._latency_publish(host_glue)
         return self._solve_from_x_prev(x_last)
 
 
@@ -602,17 +691,17 @@ class CentroidalPipeline(_QpContactSource):
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
                  sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, sensors=None,
-                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, **ens_kw):
+                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
         dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model,
         ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the
         rows of the foot force sensors, ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model,
-        ``friction``: None or the rows of the ground friction (module docstring)."""
+        ``friction``: None or the rows of the ground friction, ``latency``: None or the rows of the plan's hand-over latency (module docstring)."""
         from .ensemble import ensemble_initial_states
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
-                                                        contact_source, disturbances=disturbances)
+                                                        contact_source, disturbances=disturbances, latency=latency)
         plant = _checked_plant(plant, self.batch, problem_def)
         self._load(library, substeps, sim_dt)
         rb, m = problem_def.robot, self.model
@@ -678,7 +767,8 @@ class CentroidalPipeline(_QpContactSource):
             self._fetch()
         x = self.x_est
         new_x = centroidal_state(self.model, x)
-        forces = self.us0 - np.einsum("bij,bj->bi", self.K0, self.xs0 - new_x)   # us[0] - K_0 difference(new_x, xs[0])
+        xs0, us0, K0 = self._knot_in_force()
+        forces = us0 - np.einsum("bij,bj->bi", K0, xs0 - new_x)   # us[0] - K_0 difference(new_x, xs[0])
         _, f_new, tau = self.qp.solve_batch_device_ik(x, ik, forces, np.broadcast_to(np.asarray(cs, dtype=np.int32), (self.batch, 2)))
         self.x = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt)
         self.torques, self.forces = self.sim_models.applied_torques(tau), f_new
@@ -700,6 +790,7 @@ class CentroidalPipeline(_QpContactSource):
         library call is tested against).  ``push``: (B, 3) world force at the base origin or (B, 6) (force, world point), armed on the simulator for
         the low-level steps of this period only (mpc_sim_set_push, HIP library; ``push_schedule``)."""
         push = self._checked_push(push)
+        self._latency_tick(host_glue)
         e = self.mpc
         cs = self.contact_state()
         w = e._walk
@@ -716,7 +807,9 @@ class CentroidalPipeline(_QpContactSource):
             if host_glue:
                 if self._plan_stale:
                     self._fetch()
-                self.ik = self.qp.task_errors(self.x_prev, self.x_posture, refs, self.ref_dt, self.dH)
+                first = self._latency_first()    # (dH of the record every robot's first step of the period reads)
+                dH = self.dH if first is None or not first.any() else np.where(first[:, None], self._lat_held["xdot"], self.dH)
+                self.ik = self.qp.task_errors(self.x_prev, self.x_posture, refs, self.ref_dt, dH)
                 for _ in range(self.substeps):
                     x_last = self.x_est.copy()    # (the script's x_measured is read BEFORE the last execute of the period)
                     used = self._host_contact_set(cs)
@@ -727,6 +820,7 @@ class CentroidalPipeline(_QpContactSource):
                 self._xik_on_device = False
             else:
                 self.low_level_loop(cs, refs)
+        self._latency_publish(host_glue)
         e.native.set_x0(self.c_prev)
         st = e.solve_tick()
         self._plan_stale = True   # (knot 0 of the new plan is read on the device; the host copies only when the host glue asks)
@@ -752,15 +846,17 @@ class FullDynamicPipeline(_Pipeline):
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
-                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, **ens_kw):
+                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None,
+                 **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
         actuator model, ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state
         estimator, ``foot_sensors``: None or the rows of the foot force sensors, ``detected_contacts``: () or ("estimator",), ``plant``: None or the rows of the plant
-        model, ``friction``: None or the rows of the ground friction (module docstring of pipeline.py)."""
+        model, ``friction``: None or the rows of the ground friction, ``latency``: None or the rows of the plan's hand-over latency (module docstring
+        of pipeline.py)."""
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
-                                                        disturbances=disturbances)
+                                                        disturbances=disturbances, latency=latency)
         if ens_kw.get("closed_loop") is not None:
             raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
                              "EnsembleMPC(closed_loop=...) would simulate a second time)")
@@ -780,8 +876,9 @@ class FullDynamicPipeline(_Pipeline):
             self._fetch()
         nq = self.nq
         x = self.x_est
-        d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], self.xs0[:, :nq]), self.xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
-        tau = self.us0 - np.einsum("bij,bj->bi", self.K0, d)
+        xs0, us0, K0 = self._knot_in_force()
+        d = np.concatenate([pin.difference_batch(self.model, x[:, :nq], xs0[:, :nq]), xs0[:, nq:] - x[:, nq:]], axis=1)  # space.difference(x_measured, xs[0])
+        tau = us0 - np.einsum("bij,bj->bi", K0, d)
         self.x, wr = self.sim.simulate_torque(self.x, tau, 1, self.sim_dt, wrenches=True)
         self.torques, self.wrenches = self.sim_models.applied_torques(tau), wr
         return tau
@@ -798,6 +895,7 @@ class FullDynamicPipeline(_Pipeline):
         at the base origin or (B, 6) (force, world point), armed on the simulator for the low-level steps of this period only (mpc_sim_set_push,
         HIP library; ``push_schedule``)."""
         push = self._checked_push(push)
+        self._latency_tick(host_glue)
         cs = self.contact_state()
         self._set_sim_contacts(cs)
         with self._pushed(push):
@@ -809,4 +907,5 @@ class FullDynamicPipeline(_Pipeline):
                     self.low_level_step(cs)
             else:
                 x_last = self.low_level_loop(cs)
+        self._latency_publish(host_glue)
         return self._solve_from_x_prev(x_last)
