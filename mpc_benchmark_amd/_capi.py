@@ -19,6 +19,7 @@ from . import foot_sensors as _foot_sensors
 from . import plant_model as _plant_model
 from . import disturbance_model as _disturbance_model
 from . import friction_model as _friction_model
+from . import tipping_model as _tipping_model
 from . import plan_latency as _plan_latency
 from . import contact_rule as _contact_rule
 from . import locomotion_metrics as _metrics
@@ -216,6 +217,14 @@ _SIM_FRICTION_SIGNATURES = {
     "mpc_sim_friction_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_tipping.h: exported by the HIP library alone, bound when present (``NativeSolver.tipping`` / ``read_tipping`` / ``set_tipping``)
+_SIM_TIPPING_SIGNATURES = {
+    "mpc_sim_tipping": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_tipping_read": (C.c_int, [C.c_void_p, _DP, _DP]),
+    "mpc_sim_tipping_set": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_tipping_width": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_sim_disturbances.h: exported by the HIP library alone, bound when present (``NativeSolver.disturbances`` / ``read_disturbances`` /
 # ``reset_disturbances``)
 _SIM_DISTURBANCES_SIGNATURES = {
@@ -287,6 +296,7 @@ _HIP_ONLY = (
     ("mpc_sim_foot_sensors.h", _SIM_FOOT_SENSORS_SIGNATURES, "the foot force sensors of torque-driven simulator steps are HIP only", RuntimeError),
     ("mpc_sim_plant.h", _SIM_PLANT_SIGNATURES, "the plant model of torque-driven simulator steps is HIP only", RuntimeError),
     ("mpc_sim_friction.h", _SIM_FRICTION_SIGNATURES, "the ground friction of torque-driven simulator steps is HIP only", RuntimeError),
+    ("mpc_sim_tipping.h", _SIM_TIPPING_SIGNATURES, "the sole tipping of torque-driven simulator steps is HIP only", RuntimeError),
     ("mpc_sim_disturbances.h", _SIM_DISTURBANCES_SIGNATURES, "the push schedules of torque-driven simulator steps are HIP only", RuntimeError),
     ("mpc_sim_terrain.h", _SIM_TERRAIN_SIGNATURES, "the terrain of the contact rule needs the HIP library", NotImplementedError),
     ("mpc_walk_poses.h", _WALK_POSES_SIGNATURES, "the device generator of the contact-pose references is HIP only", RuntimeError),
@@ -766,6 +776,30 @@ class NativeSolver:
         """Impose the state rows of the friction model (mpc_sim_friction_set): (B, 17), e.g. ``read_friction(raw=True)`` of an earlier point."""
         fn, w = self._hip("mpc_sim_friction_set"), self._width("mpc_sim_friction_width")
         self._check(fn(self._h, _dp(self._checked_rows("set_friction: state rows", state, w))), "mpc_sim_friction_set")
+
+    # -- include/mpc_sim_tipping.h (HIP library only): per-robot sole tipping in the torque-driven simulator steps --------------------------------
+    def tipping(self, params, base=None):
+        """Make every held sole of every robot of this simulator handle a rectangle that rolls about an edge when the centre of pressure leaves it
+        (mpc_sim_tipping; ``tipping_model`` is the definition).  Needs the contact rule (``contacts``).  ``params``: (B, 8) rows, one row of 8 for
+        every robot, or a dict by ``tipping_model.FIELDS`` name (``half_length`` / ``half_width``: both soles) of scalars or (B,) arrays, missing
+        fields as in ``base`` (``tipping_model.rows``); turns the model on with every sole flat and at rest.  None turns it off."""
+        fn = self._hip("mpc_sim_tipping")
+        if params is None:
+            self._check(fn(self._h, None), "mpc_sim_tipping")
+            return
+        p = _f64(_tipping_model.rows(params, self.dims.batch, base))
+        self._check(fn(self._h, _dp(p)), "mpc_sim_tipping")
+
+    def read_tipping(self, raw=False):
+        """The tipping model as it stands (mpc_sim_tipping_read) -> dict: ``params`` (B, 8) the rows in force, and the state rows by
+        ``tipping_model.unpack`` (``v`` (B, 2, 3), ``th`` (B, 2, 2), ``tipping``, ``tip_steps``, ``peak_angle``, ``peak_excess``, ``landings``
+        (B, 2), ``steps``); ``raw``: the (B, 21) rows as ``set_tipping`` takes them."""
+        return self._read_model("tipping", _tipping_model, raw)
+
+    def set_tipping(self, state):
+        """Impose the state rows of the tipping model (mpc_sim_tipping_set): (B, 21), e.g. ``read_tipping(raw=True)`` of an earlier point."""
+        fn, w = self._hip("mpc_sim_tipping_set"), self._width("mpc_sim_tipping_width")
+        self._check(fn(self._h, _dp(self._checked_rows("set_tipping: state rows", state, w))), "mpc_sim_tipping_set")
 
     # -- include/mpc_sim_terrain.h (HIP library only): the box terrain under the contact rule ------------------------------------------------------
     def terrain(self, boxes):

@@ -35,6 +35,10 @@ table from the rows in force.
 mpc_sim_friction, include/mpc_sim_friction.h): a sole whose tangential force leaves the cone ``mu f_z`` slips, and turns when its yaw moment leaves
 ``mu_spin f_z``.  ``setFrictionCoefficients(link_id, lateral, spinning)``, the reference's knob, sets ``mu`` and ``mu_spin`` of one sole.  Without
 either every sole holds whatever force it takes, as before.
+``tipping=`` / ``setTipping(rows)`` (HIP library only, with ``device_contacts=True``) make every held sole a rectangle that rolls about an edge
+(``tipping_model``; mpc_sim_tipping, include/mpc_sim_tipping.h): a sole whose roll moment leaves ``half_width f_z`` or whose pitch moment leaves
+``half_length f_z`` tips about the edge where the centre of pressure saturates.  ``tippingState()`` returns the tip velocities, angles and counters.
+Without it every sole transmits whatever moment it takes, as before.
 ``disturbances=`` / ``setDisturbances(events)`` (HIP library only) give the robot a schedule of pushes on any link, timed on the device by the
 simulator's step clock or by the touchdowns and lift-offs of its soles (``disturbance_model``; mpc_sim_disturbances,
 include/mpc_sim_disturbances.h; contact triggers need ``device_contacts=True``).  ``disturbanceState()`` returns the clock, the counters and what
@@ -59,7 +63,8 @@ class BulletRobot:
 
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
                  inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
-                 device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None, plant=None, friction=None, disturbances=None):
+                 device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None, plant=None, friction=None, disturbances=None,
+                 tipping=None):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -78,6 +83,7 @@ class BulletRobot:
         self._foot_sensors = None if foot_sensors is None else (foot_sensors, ())  # (params, detected_contacts) of setFootSensors, armed at initializeJoints
         self._plant = None if plant is None else (plant, None)  # (rows, link_scale) of setPlant, armed at initializeJoints
         self._friction = friction  # rows of setFriction, armed at initializeJoints
+        self._tipping = tipping  # rows of setTipping, armed at initializeJoints
         self._disturbances = disturbances  # events of setDisturbances, armed at initializeJoints
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
@@ -119,6 +125,7 @@ class BulletRobot:
         self._pulling = [0, 0]   # consecutive steps with a negative normal force
         self._contact_pose = [self.data.oMf[f].copy() for f in self.frame_ids]
         self._refuse_friction_without_rule(self._friction)
+        self._refuse_tipping_without_rule(self._tipping)
         self._build_native()
         if self.device_contacts:  # stage 0 is double support once; the rule on the device picks each step's contacts
             self._upload_mask()
@@ -128,7 +135,7 @@ class BulletRobot:
                 self._native.terrain(self.terrain)
         self._sim_models = _tsim.SimulatorModels(self._native, m, self.frame_ids, self.dt)
         self._sim_models.arm(self.x, self.x[:m.nq], self._plant, self._friction, self._actuators, self._sensors, self._foot_sensors, self._estimator,
-                             None if self._disturbances is None else (self._disturbances, self.device_contacts))
+                             None if self._disturbances is None else (self._disturbances, self.device_contacts), tipping=self._tipping)
 
     def _build_native(self):
         """the handle (opened once) with the model, the terminal stage and the contact-mask stages at the anchors ``_contact_pose`` as they stand"""
@@ -332,6 +339,24 @@ class BulletRobot:
     def frictionState(self):
         """the state rows of the friction model by ``friction_model.unpack`` (``v``, ``sliding``, ``slip_dist`` ...); None without one"""
         return None if self._sim_models is None else self._sim_models.friction_state()
+
+    def setTipping(self, rows):
+        """The sole tipping (``tipping_model``; HIP library only, needs ``device_contacts=True``): ``rows`` one row of 8, (1, 8), or a dict by field
+        name (``half_length`` / ``half_width``: both soles; missing fields as in ``tipping_model.defaults`` of this robot: extents +inf, slider
+        inertia from its mass and posture); None: off.  Arms the model with every sole flat and at rest; before ``initializeJoints`` it is kept for
+        then."""
+        self._refuse_tipping_without_rule(rows)
+        self._tipping = rows
+        if self._sim_models is not None:
+            self._sim_models.set_tipping(rows, self.x[:self.model.nq])
+
+    def _refuse_tipping_without_rule(self, rows):
+        if rows is not None and not self.device_contacts:
+            raise ValueError("setTipping: the tipping model needs device_contacts=True (it tips the soles the device contact rule holds)")
+
+    def tippingState(self):
+        """the state rows of the tipping model by ``tipping_model.unpack`` (``v``, ``th``, ``tipping``, ``peak_angle`` ...); None without one"""
+        return None if self._sim_models is None else self._sim_models.tipping_state()
 
     def addStairs(self, path, position, orientation):
         raise NotImplementedError("headless BulletRobot: flat ground only")  # (a URDF staircase; createStairs / setTerrain lay boxes under the contact rule)

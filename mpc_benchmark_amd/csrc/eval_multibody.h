@@ -216,7 +216,7 @@ DEV void jlog6_blocks(const M3& Ji, const M3& Q, double sgn, double* out) {
 // on the dofs below robot b's own link.  An instantiation of its own, launched only while a schedule is armed, so that k_eval_multibody<2>, which
 // every other simulator step runs, keeps the parent's instructions, registers and scratch (profiles/sim_disturbances.txt).
 template <int TRIAL, int FJ = 0, int FV = 0, int FU = 0, bool FCD = true, bool LINKED = false>
-__global__ void __launch_bounds__(EVAL_THREADS, EVAL_MIN_WAVES) k_eval_multibody(SolverArgs a, Layout KL, double* records, MbArgs mb, int cand0) {
+__global__ void __launch_bounds__(EVAL_THREADS, EVAL_MIN_WAVES) k_eval_multibody(SolverArgs a, Layout KL, double* records, typename MbArgsOf<TRIAL>::type mb, int cand0) {
   constexpr bool FX = FJ > 0;
   constexpr MbLds SC_ = FX ? make_mb_lds(FJ, FV, FV + 1, FU, 2 * FV + FU, FCD) : MbLds{};
   MbLds S_ = mb.lds;
@@ -818,6 +818,11 @@ sim_u_set:
         if (mb.sim_friction && cid < 2) {
           const double* fr = mb.sim_friction + (size_t)b * MPC_SIM_FRICTION_WIDTH + 3 * cid;
           vs[0] = fr[0]; vs[1] = fr[1]; vs[5] = fr[2];
+        }
+        // the tipping model (include/mpc_sim_tipping.h) fills the components friction leaves at zero: (v_z, w_x, w_y) of a sole that rolls about an edge
+        if (mb.sim_tipping && cid < 2) {
+          const double* tp = mb.sim_tipping + (size_t)b * MPC_SIM_TIPPING_WIDTH + 3 * cid;
+          vs[2] = tp[0]; vs[3] = tp[1]; vs[4] = tp[2];
         }
         for (int r = 0; r < 6; ++r) gam[6 * tid + r] = acb.v[r] + cm[30 + r] * (vcb.v[r] - vs[r]) - cm[24 + r] * gam[6 * tid + r];
       } else {

@@ -37,11 +37,13 @@ void launch_sim_multibody(hipStream_t stream, const SolverArgs& a, const Layout&
   const Layout& L = a.L;
   int dev = 0;
   (void)hipGetDevice(&dev);
-  MbArgs mb = mb_args(L, scratch, scratch_stride, /*contact_dyn=*/true, dev);
+  MbSimArgs mb = {};
+  static_cast<MbArgs&>(mb) = mb_args(L, scratch, scratch_stride, /*contact_dyn=*/true, dev);
   mb.sim_substeps = step.substeps; mb.sim_dt = step.dt; mb.f_ext = step.push; mb.f_ext_width = step.width; mb.sim_u = step.torques; mb.sim_wrench = step.wrenches;
   mb.sim_contacts = step.contact_rows;
   mb.sim_model = step.model_tables; mb.sim_model_stride = step.model_stride;
   mb.sim_friction = step.friction_rows;
+  mb.sim_tipping = step.tipping_rows;
   if (step.linked) hipLaunchKernelGGL((k_eval_multibody<2, 0, 0, 0, true, true>), dim3(1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, 0);
   else hipLaunchKernelGGL(k_eval_multibody<2>, dim3(1, L.B, 1), dim3(EVAL_THREADS), mb.lds.total_bytes, stream, a, LT, records, mb, 0);
 }

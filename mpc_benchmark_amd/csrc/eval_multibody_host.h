@@ -5,6 +5,7 @@
 #include "solver_args.h"
 #include "../../include/mpc_sim_contacts.h"
 #include "../../include/mpc_sim_friction.h"
+#include "../../include/mpc_sim_tipping.h"
 
 #ifndef EVAL_THREADS
 #define EVAL_THREADS 256  // threads per stage workgroup: 4 wavefronts, two workgroups per CU (measured against 512 = 8 wavefronts with a 128-VGPR cap, profiles/r03_*)
@@ -143,6 +144,16 @@ struct MbArgs {
 };
 static_assert(sizeof(MbLds) % 8 == 4 && sizeof(MbArgs) == sizeof(MbLds) + 4 + 11 * 8, "MbArgs: f_ext_width fills the padding after lds");
 
+// What the simulator form (TRIAL == 2) takes: MbArgs and, behind it, what only that form reads.  MbArgs has no padding left, and a member more in it
+// would move cand0 and the hidden arguments of every instantiation.  A type of its own for TRIAL == 2 leaves the signature of every other
+// instantiation as it was, so they compile to the instructions they had (profiles/sim_tipping.txt)
+struct MbSimArgs : MbArgs {
+  const double* sim_tipping;  // the state rows of the tipping model [B][MPC_SIM_TIPPING_WIDTH] (include/mpc_sim_tipping.h), or nullptr: no held
+                              // sole rolls or pitches
+};
+template <int TRIAL> struct MbArgsOf { using type = MbArgs; };
+template <> struct MbArgsOf<2> { using type = MbSimArgs; };
+
 
 // One call of the simulator form of the stage kernel (TRIAL == 2): what the MbArgs members of the same names take (above)
 struct MbSimStep {
@@ -157,6 +168,7 @@ struct MbSimStep {
   const double* model_tables = nullptr;  // sim_model ...
   size_t model_stride = 0;               // ... and sim_model_stride
   const double* friction_rows = nullptr; // sim_friction
+  const double* tipping_rows = nullptr;  // sim_tipping (MbSimArgs)
 };
 
 // defined in eval_multibody.hip: the solver's forms of the stage kernel (the knot records, the trial candidates cand0 .. cand0 + ncand - 1, the

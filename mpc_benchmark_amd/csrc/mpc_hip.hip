@@ -40,6 +40,7 @@
 #include "sim_foot_sensors.h"
 #include "sim_plant.h"
 #include "sim_friction.h"
+#include "sim_tipping.h"
 #include "sim_disturbances.h"
 #include "../../include/mpc_sim_ext.h"
 #include "../../include/mpc_feedback_pipeline.h"
@@ -118,11 +119,13 @@ struct SimPlant {
   size_t plant_off = 0;  // doubles before the tables, with the joint count the rows were armed on
   // include/mpc_sim_friction.h: the per-robot ground friction (off: every held sole is held to rest) ; h: params
   SimModel fr{"the friction model is off on this handle (turn it on with mpc_sim_friction)", true};
+  // include/mpc_sim_tipping.h: the per-robot sole tipping (off: every held sole transmits any roll or pitch moment) ; h: params
+  SimModel tip{"the tipping model is off on this handle (turn it on with mpc_sim_tipping)", true};
   // include/mpc_sim_disturbances.h: the per-robot push schedule (the dynamics read what it writes in place of d_push) ; h: events
   SimModel dis{"the disturbance schedule is off on this handle (turn it on with mpc_sim_disturbances)", false};
   int dis_ne = 0;
   bool dis_contact = false;  // an event of the table has a contact trigger: the table goes with the contact rule
-  SimModel* const models[8] = {&act, &sen, &pm, &ter, &fr, &est, &fs, &dis};
+  SimModel* const models[9] = {&act, &sen, &pm, &ter, &fr, &tip, &est, &fs, &dis};
   // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
   void free_owned() {
     for (double** p : {&d_rec, &d_met, &d_con}) if (*p) { (void)hipFree(*p); *p = nullptr; }

@@ -127,7 +127,7 @@ struct SimLayout {
   size_t tail = 0;                // what follows `out`
   size_t total = 0;
 };
-// params [B][P] | state rows [B][W]: the foot sensors and the contact detector (P 16, W 232), the friction model (P 8, W 17)
+// params [B][P] | state rows [B][W]: the foot sensors and the contact detector (P 16, W 232), the friction model (P 8, W 17), the tipping model (P 8, W 21)
 static SimLayout sim_rows_layout(const Layout& L, size_t P, size_t W) {
   SimLayout l;
   l.np = l.rows = (size_t)L.B * P;
@@ -137,6 +137,7 @@ static SimLayout sim_rows_layout(const Layout& L, size_t P, size_t W) {
 }
 static SimLayout sim_foot_sensors_layout(const Layout& L) { return sim_rows_layout(L, MPC_SIM_FOOT_SENSORS_PARAMS, MPC_SIM_FOOT_SENSORS_WIDTH); }
 static SimLayout sim_friction_layout(const Layout& L) { return sim_rows_layout(L, MPC_SIM_FRICTION_PARAMS, MPC_SIM_FRICTION_WIDTH); }
+static SimLayout sim_tipping_layout(const Layout& L) { return sim_rows_layout(L, MPC_SIM_TIPPING_PARAMS, MPC_SIM_TIPPING_WIDTH); }
 // the actuator model: params [B][8] | tables: limit [nu] | tables_b: friction shape [nu] | state rows [B][18 nu + 2].  The mirror holds all before the rows
 static SimLayout sim_actuators_layout(const Layout& L) {
   SimLayout l;
@@ -424,6 +425,15 @@ static void sim_friction_enqueue(mpc_solver* s, hipStream_t st, double dt_step) 
   hipLaunchKernelGGL(k_sim_friction, dim3((unsigned)((2 * s->L.B + SIM_FR_THREADS - 1) / SIM_FR_THREADS)), dim3(SIM_FR_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
 }
+// the tipping model of the step of length dt_step just enqueued on stream st, after the contact rule and friction (sim_tipping.h), when the model is on
+static void sim_tipping_enqueue(mpc_solver* s, hipStream_t st, double dt_step) {
+  const SimPlant& p = s->plant;
+  if (!p.tip.on()) return;
+  SimTippingArgs a;
+  a.B = s->L.B; a.wr = p.d_simwr; a.con = p.d_con; a.params = p.tip.d; a.rows = p.tip.d + sim_tipping_layout(s->L).rows; a.dt = dt_step;
+  hipLaunchKernelGGL(k_sim_tipping, dim3((unsigned)((2 * s->L.B + SIM_TP_THREADS - 1) / SIM_TP_THREADS)), dim3(SIM_TP_THREADS), 0, st, a);
+  HIP_OK(hipGetLastError());
+}
 
 // the plant model's tables, built from the rows in force (the mirror) and the handle's nominal table: when the model is armed, and when mpc_set_model
 // replaced the nominal table of an armed handle (the joint count is then unchanged; the table may have grown by a frame).  Synchronous: the tables
@@ -469,7 +479,7 @@ static void sim_steps_begin(mpc_solver* s, hipStream_t st, const double* x) {
 }
 // the dynamics write the wrenches of the step when the caller or anything after the dynamics reads them
 static bool sim_wrenches_wanted(const SimPlant& p, bool by_caller) {
-  return by_caller || p.rec_cap > 0 || p.d_met || p.d_con || p.fs.on() || p.fr.on();
+  return by_caller || p.rec_cap > 0 || p.d_met || p.d_con || p.fs.on() || p.fr.on() || p.tip.on();
 }
 // One step of the plant on stream st: `substeps` integration steps of length dt under the torque the caller put into plant.d_simu.  The order is the
 // contract of the extensions; a stage whose model is off launches nothing.  Each event covers the whole step (substeps * dt).
@@ -477,18 +487,20 @@ static bool sim_wrenches_wanted(const SimPlant& p, bool by_caller) {
 //                    this step's dynamics, in place of the armed push
 //    2 actuators     reads the commanded torque and the state ; writes the applied torque in place: everything after it sees the applied torque
 //    3 dynamics      reads the applied torque, the push, the contact rows of the step BEFORE (the rows the low-level QPs of pipeline_loops.h read
-//                    for this step), the slip velocities friction set after the step before, robot b's own model table (the plant model, built
+//                    for this step), the slip and tip velocities friction and tipping set after the step before, robot b's own model table (the plant model, built
 //                    when it was armed: it launches nothing here) ; writes the new state and, when wanted (sim_wrenches_wanted), the wrenches
 //    4 record        reads the new state, the applied torque, the wrenches, the push, the plant's model tables ; writes its slot of the ring
 //    5 metrics       reads the same and the contact rows the step was integrated with ; writes the metric rows
 //    6 contact rule  reads the new state and this step's wrenches ; rewrites the contact rows, for the NEXT step
 //    7 friction      reads this step's wrenches and the flags the rule just wrote ; writes the slip velocity each held sole has in the NEXT step's
 //                    dynamics and advances the anchors of the soles that slid in this one
-//    8 sensors       reads the new state ; writes the measurement
-//    9 foot sensors  reads this step's wrenches ; writes the detected pair: an estimator fed by detection reads the pair this step's event left,
+//    8 tipping       reads this step's wrenches, the flags the rule just wrote and the anchors as friction left them ; writes the tip velocity
+//                    (v_z, w_x, w_y) each held sole has in the NEXT step's dynamics and advances the anchors of the soles that tipped in this one
+//    9 sensors       reads the new state ; writes the measurement
+//   10 foot sensors  reads this step's wrenches ; writes the detected pair: an estimator fed by detection reads the pair this step's event left,
 //                    and the low-level QPs of the next step the same pair
-//   10 estimator     reads that measurement (the true state without a sensor model) and the contact rows the rule, or the detector, just wrote ;
-//                    writes the estimate.  Nothing of this step reads 8 to 10: the controllers of the next step do (sim_measured)
+//   11 estimator     reads that measurement (the true state without a sensor model) and the contact rows the rule, or the detector, just wrote ;
+//                    writes the estimate.  Nothing of this step reads 9 to 11: the controllers of the next step do (sim_measured)
 static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& args, int substeps, double dt, bool want_wrenches) {
   const SimPlant& p = s->plant;
   sim_disturbances_enqueue(s, st, substeps * dt);
@@ -500,12 +512,14 @@ static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& ar
   step.contact_rows = p.d_con;
   step.model_tables = p.pm.on() ? sim_plant_tables(s) : nullptr; step.model_stride = sim_plant_stride(s);
   step.friction_rows = p.fr.on() ? p.fr.d + sim_friction_layout(s->L).rows : nullptr;
+  step.tipping_rows = p.tip.on() ? p.tip.d + sim_tipping_layout(s->L).rows : nullptr;
   launch_sim_multibody(st, args, s->LT, s->d_tknots, s->d_mbwork, s->mb_work_stride, step);
   HIP_OK(hipGetLastError());
   sim_record_enqueue(s, st);
   sim_metrics_enqueue(s, st, substeps * dt);
   sim_contacts_enqueue(s, st);
   sim_friction_enqueue(s, st, substeps * dt);
+  sim_tipping_enqueue(s, st, substeps * dt);
   sim_sensors_enqueue(s, st, s->d_x0, substeps * dt);
   sim_foot_sensors_enqueue(s, st, substeps * dt);
   sim_estimator_enqueue(s, st, sim_sensed(s), s->d_x0);
@@ -1016,6 +1030,59 @@ int mpc_sim_friction_set(mpc_solver* s, const double* state) {
 }
 
 int32_t mpc_sim_friction_width(mpc_solver* s) { return sim_width(s, "sim_friction_width", [&] { return MPC_SIM_FRICTION_WIDTH; }); }
+
+// ---- include/mpc_sim_tipping.h: per-robot sole tipping ---------------------------------------------------------------------------------------------
+int mpc_sim_tipping(mpc_solver* s, const double* params) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_tipping");
+    const Layout& L = s->L;
+    const SimLayout l = sim_tipping_layout(L);
+    SimModel& m = s->plant.tip;
+    if (!params) { sim_drop(s, m); return 0; }
+    for (int b = 0; b < L.B; ++b) {  // (every check before anything changes: a bad row leaves the previous configuration in force; an extent may be +inf)
+      const double* r = params + (size_t)b * MPC_SIM_TIPPING_PARAMS;
+      const std::string row = "sim_tipping: row " + std::to_string(b);
+      for (int e = 0; e < 4; ++e)
+        if (std::isnan(r[e]) || r[e] < 0.0)
+          throw std::runtime_error(row + ": half_length and half_width must be >= 0 (+inf: the sole never tips on that axis), entry " + std::to_string(e));
+      for (int e = 4; e < 7; ++e)
+        if (!std::isfinite(r[e]) || !(r[e] > 0.0)) throw std::runtime_error(row + ": I_tip, w_max and th_max must be finite and > 0, entry " + std::to_string(e));
+      sim_reserved_check(row, r, 7, MPC_SIM_TIPPING_PARAMS);
+    }
+    if (m.needs_rule) sim_rule_check(s, "sim_tipping");
+    sim_realloc(s, m.d, l.total);
+    m.h.assign(params, params + l.np);
+    sim_ensure(s);
+    std::vector<double> h(m.h);
+    h.resize(l.total, 0.0);  // (the state rows after a reset: all 0)
+    copy_sync(s, m.d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+int mpc_sim_tipping_read(mpc_solver* s, double* params, double* state) {
+  MPC_TRY(s, { sim_model_read(s, "sim_tipping_read", s->plant.tip, sim_tipping_layout(s->L), params, state); })
+}
+
+int mpc_sim_tipping_set(mpc_solver* s, const double* state) {
+  MPC_TRY(s, {
+    const SimLayout l = sim_tipping_layout(s->L);
+    SimModel& m = s->plant.tip;
+    sim_rows_set(s, "sim_tipping_set", m, l, state, -1, [&](const std::string& row, const double* r, int b) {
+      const double th_max = m.h[(size_t)b * MPC_SIM_TIPPING_PARAMS + 6];
+      for (int i = 0; i < 2; ++i) {
+        sim_flags_check(row, "tipping", r + SIM_TP_O_TIPPING + i, 1);
+        const double* th = r + SIM_TP_O_TH + 2 * i;
+        if (r[SIM_TP_O_TIPPING + i] == 0.0 && (r[3 * i] != 0.0 || r[3 * i + 1] != 0.0 || r[3 * i + 2] != 0.0 || th[0] != 0.0 || th[1] != 0.0))
+          throw std::runtime_error(row + ": sole " + std::to_string(i) + " holds a rate or an angle but its tipping flag is 0");
+        if (std::fabs(th[0]) > th_max || std::fabs(th[1]) > th_max)
+          throw std::runtime_error(row + ": sole " + std::to_string(i) + " holds an angle beyond th_max (" + std::to_string(th_max) + ")");
+      }
+      sim_nonneg_check(row, "tip_steps, peak_angle, peak_excess, landings and steps", r + SIM_TP_O_STEPS, (int)l.width - SIM_TP_O_STEPS);
+    });
+  })
+}
+
+int32_t mpc_sim_tipping_width(mpc_solver* s) { return sim_width(s, "sim_tipping_width", [&] { return MPC_SIM_TIPPING_WIDTH; }); }
 
 // ---- include/mpc_sim_disturbances.h: per-robot push schedules on any link ----------------------------------------------------------------------
 int mpc_sim_disturbances(mpc_solver* s, const double* events, int32_t n_events) {

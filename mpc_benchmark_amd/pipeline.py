@@ -90,6 +90,14 @@ armed on the simulator handle when the pipeline is built (mpc_sim_friction, incl
 sole whose force leaves its cone slips.  The MPC stages and the low-level QPs keep their own cones (``mu = 0.8``).  ``friction_state()`` returns the
 slip velocities and counters; ``set_friction`` changes or removes the model later.
 
+``tipping`` (all three pipelines, with ``contact_rule``): None, every held sole transmits whatever roll and pitch moment it takes; or the parameter
+rows of the per-robot sole tipping (``tipping_model``: ``half_length`` and ``half_width`` of each sole, the slider's inertia and bounds; (B, 8), one
+row of 8 for every robot, or a dict by field name whose missing fields are the identity extents and ``tipping_model.defaults`` of the robot), armed
+on the simulator handle when the pipeline is built (mpc_sim_tipping, include/mpc_sim_tipping.h; HIP library only).  Only the plant changes: a sole
+whose centre of pressure leaves its rectangle rolls about that edge.  The MPC stages and the low-level QPs keep their own sole
+(``FOOT_HALF_LENGTH``, ``FOOT_HALF_WIDTH``).  ``tipping_state()`` returns the tip velocities, angles and counters; ``set_tipping`` changes or
+removes the model later.
+
 ``disturbances`` (all three pipelines): None, the only push is the one ``tick(push=...)`` arms for a whole period; or every robot's own schedule of
 pushes (``disturbance_model``: up to 8 events per robot, each an absolute step of the simulator's clock or the n-th touchdown or lift-off of a sole
 plus a delay, a duration, a rectangular or half-sine shape, and a force and point on any link in world or link axes; (B, n, 16) tables, one table for
@@ -185,6 +193,12 @@ def _checked_friction(name, friction, contact_rule):
         raise ValueError("%s: friction needs contact_rule (the model slides the soles the unilateral contact rule holds; contact_rule={} turns it on)" % name)
 
 
+def _checked_tipping(name, tipping, contact_rule):
+    """``tipping`` of a pipeline needs the contact rule: checked before any library call (the rows themselves when the model is armed)"""
+    if tipping is not None and contact_rule is None:
+        raise ValueError("%s: tipping needs contact_rule (the model tips the soles the unilateral contact rule holds; contact_rule={} turns it on)" % name)
+
+
 def _checked_disturbances(name, events, contact_rule, batch, problem_def):
     """``disturbances`` of a pipeline: None, or the tables (B, n, 16) checked before any library call (``disturbance_model.validate``); contact
     triggers are refused without ``contact_rule``"""
@@ -241,7 +255,7 @@ class _Pipeline:
         """(the hook of the pipelines with a low-level QP, ``_QpContactSource``)"""
 
     def _check_arguments(self, problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts, contact_source=None,
-                         disturbances=None, latency=None):
+                         disturbances=None, latency=None, tipping=None):
         """the arguments every pipeline takes, checked before the library is loaded -> (walk, detected_contacts)"""
         name = type(self).__name__
         self.pd, self.batch = problem_def, int(batch)
@@ -251,6 +265,7 @@ class _Pipeline:
         self.terrain = _checked_terrain(name, terrain, contact_rule, self.batch)
         walk = _checked_walk(name, walk, self.batch)
         _checked_friction(name, friction, contact_rule)
+        _checked_tipping(name, tipping, contact_rule)
         self._disturbances = _checked_disturbances(name, disturbances, contact_rule, self.batch, problem_def)
         self.contact_rule = None if contact_rule is None else dict(contact_rule)
         return walk, detected_contacts
@@ -275,7 +290,7 @@ class _Pipeline:
         self.nq, self.nv = m.nq, m.nv
         self.substeps, self.sim_dt = int(substeps), float(sim_dt)
 
-    def _build_simulator(self, plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=None):
+    def _build_simulator(self, plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=None, tipping=None):
         """The simulator stand-in (``build_torque_simulator``) with its contact rule and terrain, stage 0 on ``stage0`` if one is given, and the
         models armed at ``self.x``; ``x_prev`` starts from what the controllers read then."""
         rb = self.pd.robot
@@ -292,7 +307,7 @@ class _Pipeline:
         self.sim_models = _tsim.SimulatorModels(self.sim, self.model, rb.foot_frame_ids, self.sim_dt)
         self.sim_models.arm(self.x, rb.x0[:self.nq], plant, friction, None if actuators is None else (actuators,), sensors,
                             None if foot_sensors is None else (foot_sensors, detected_contacts), estimator,
-                            None if self._disturbances is None else (self._disturbances, self.contact_rule is not None))
+                            None if self._disturbances is None else (self._disturbances, self.contact_rule is not None), tipping=tipping)
         self.x_prev = self.x_est.copy()      # the measurement of the period before (the solve's initial condition)
         self.torques = np.zeros((self.batch, self.nv - 6))
         self._plan_stale = True
@@ -331,6 +346,12 @@ class _Pipeline:
         missing fields from ``friction_model.defaults`` of the nominal robot; needs ``contact_rule``."""
         _checked_friction(type(self).__name__, rows, self.contact_rule)
         self.sim_models.set_friction(rows, self.pd.robot.x0[:self.nq])   # (a simulator step is one low-level period)
+
+    def set_tipping(self, rows):
+        """Arm the per-robot sole tipping on ``self.sim`` with every sole flat and at rest: ``rows`` in the forms of ``NativeSolver.tipping``, a
+        dict's missing fields from ``tipping_model.defaults`` of the nominal robot; needs ``contact_rule``."""
+        _checked_tipping(type(self).__name__, rows, self.contact_rule)
+        self.sim_models.set_tipping(rows, self.pd.robot.x0[:self.nq])   # (a simulator step is one low-level period)
 
     def set_actuators(self, params, limit=None, friction_shape=None):
         """Arm (and reset) the per-robot actuator model on ``self.sim``: ``params`` in the forms of ``NativeSolver.actuators``, a dict may also carry
@@ -377,6 +398,10 @@ class _Pipeline:
     def friction_state(self):
         """the state rows of the friction model by ``friction_model.unpack`` (``v``, ``sliding``, ``slip_dist`` ...); None without ``friction``"""
         return self.sim_models.friction_state()
+
+    def tipping_state(self):
+        """the state rows of the tipping model by ``tipping_model.unpack`` (``v``, ``th``, ``tipping``, ``peak_angle`` ...); None without ``tipping``"""
+        return self.sim_models.tipping_state()
 
     # -- the hand-over latency of the plan (``plan_latency``, include/mpc_plan_latency.h): ``None`` turns it off ------------------------------------
     def _reset_latency(self):
@@ -555,15 +580,16 @@ class _QpContactSource(_Pipeline):
 class KinodynamicPipeline(_QpContactSource):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
                  terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, foot_sensors=None,
-                 detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, **ens_kw):
+                 detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, tipping=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
         ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model, ``sensors``: None or the rows of the
         sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the rows of the foot force sensors,
         ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model, ``friction``: None or the rows of
-        the ground friction, ``latency``: None or the rows of the plan's hand-over latency (module docstring)."""
+        the ground friction, ``tipping``: None or the rows of the sole tipping, ``latency``: None or the rows of the plan's hand-over latency (module
+        docstring)."""
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
-                                                        contact_source, disturbances=disturbances, latency=latency)
+                                                        contact_source, disturbances=disturbances, latency=latency, tipping=tipping)
         plant = _checked_plant(plant, self.batch, problem_def)
         self._load(library, substeps, sim_dt)
         rb, m = problem_def.robot, self.model
@@ -575,7 +601,7 @@ class KinodynamicPipeline(_QpContactSource):
         self.qp.enable_device_assembly()
         self.umax = np.asarray(m.effortLimit, dtype=float)[6:]
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
-        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator)
+        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, tipping=tipping)
         self.forces = np.zeros((self.batch, 12))
 
     def _fetch(self):
@@ -691,17 +717,18 @@ class CentroidalPipeline(_QpContactSource):
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
                  sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, sensors=None,
-                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, **ens_kw):
+                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, tipping=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
         dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model,
         ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the
         rows of the foot force sensors, ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model,
-        ``friction``: None or the rows of the ground friction, ``latency``: None or the rows of the plan's hand-over latency (module docstring)."""
+        ``friction``: None or the rows of the ground friction, ``tipping``: None or the rows of the sole tipping, ``latency``: None or the rows of
+        the plan's hand-over latency (module docstring)."""
         from .ensemble import ensemble_initial_states
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
-                                                        contact_source, disturbances=disturbances, latency=latency)
+                                                        contact_source, disturbances=disturbances, latency=latency, tipping=tipping)
         plant = _checked_plant(plant, self.batch, problem_def)
         self._load(library, substeps, sim_dt)
         rb, m = problem_def.robot, self.model
@@ -724,7 +751,7 @@ class CentroidalPipeline(_QpContactSource):
                                          batch=self.batch)
         self.qp.enable_device_assembly()
         # (the schedule starts in double support; ``x_prev`` is the stale measurement the task errors are taken at)
-        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=(True, True))
+        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=(True, True), tipping=tipping)
         self.forces = np.zeros((self.batch, 12))
         self.ik = None                 # the task errors of the last period
         self._xik_on_device = False    # the QP handle keeps x_prev of its last device loop
@@ -846,17 +873,17 @@ class FullDynamicPipeline(_Pipeline):
     mpc_feedback_low_level_steps) is HIP only, the host glue (``tick(host_glue=True)``) runs on either library."""
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
-                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None,
+                 sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, tipping=None,
                  **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
         actuator model, ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state
         estimator, ``foot_sensors``: None or the rows of the foot force sensors, ``detected_contacts``: () or ("estimator",), ``plant``: None or the rows of the plant
-        model, ``friction``: None or the rows of the ground friction, ``latency``: None or the rows of the plan's hand-over latency (module docstring
+        model, ``friction``: None or the rows of the ground friction, ``tipping``: None or the rows of the sole tipping, ``latency``: None or the rows of the plan's hand-over latency (module docstring
         of pipeline.py)."""
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
-                                                        disturbances=disturbances, latency=latency)
+                                                        disturbances=disturbances, latency=latency, tipping=tipping)
         if ens_kw.get("closed_loop") is not None:
             raise ValueError("FullDynamicPipeline: closed_loop is not an option here (the pipeline's simulator is the closed loop; "
                              "EnsembleMPC(closed_loop=...) would simulate a second time)")
@@ -866,7 +893,7 @@ class FullDynamicPipeline(_Pipeline):
         self.mpc = EnsembleMPC(problem_def, batch=batch, library=self.lib, x0=x0, **ens_kw)
         self._walk_args = walk
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
-        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator)
+        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, tipping=tipping)
         self.wrenches = np.zeros((self.batch, 2, 6))     # contact wrenches of the last simulator step (LOCAL frame of the sole)
 
     def low_level_step(self, cs):

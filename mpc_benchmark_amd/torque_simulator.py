@@ -12,6 +12,7 @@ from . import actuator_model as _actuator_model
 from . import disturbance_model as _disturbance_model
 from . import foot_sensors as _foot_sensors
 from . import friction_model as _friction_model
+from . import tipping_model as _tipping_model
 from . import plant_model as _plant_model
 from . import sensor_model as _sensor_model
 from . import state_estimator as _state_estimator
@@ -91,9 +92,9 @@ def checked_plant(rows, link_scale, batch, nj):
 class SimulatorModels:
     """The per-robot models of one simulator handle of batch B (module docstring of pipeline.py): which are in force, and the rules of arming them.
     The caller hands in what is its own: ``x``, the true states (B, nx) (or (nx,) for B = 1) as they stand, wherever a model arms at them or falls
-    back to them, and ``q``, the configuration the defaults of the friction model are taken at (nothing here refers back to the caller).
+    back to them, and ``q``, the configuration the defaults of the friction and tipping models are taken at (nothing here refers back to the caller).
     ``rows[name]`` is what model ``name`` was armed with, None while it is off; turning a model off touches the library only if it was on.  Refusals that name their caller (a model that needs the contact rule) are the caller's, before it calls here."""
-    NAMES = ("disturbances", "plant", "friction", "actuators", "sensors", "foot_sensors", "estimator")
+    NAMES = ("disturbances", "plant", "friction", "tipping", "actuators", "sensors", "foot_sensors", "estimator")
 
     def __init__(self, sim, model, sole_frames, sim_dt):
         self.sim, self.model, self.batch = sim, model, sim.dims.batch
@@ -101,7 +102,8 @@ class SimulatorModels:
         self.rows = dict.fromkeys(self.NAMES)
         self.consumers = ()      # who works from the detected contacts (``foot_sensors.CONSUMERS``)
 
-    def arm(self, x, q, plant=None, friction=None, actuators=None, sensors=None, foot_sensors=None, estimator=None, disturbances=None):
+    def arm(self, x, q, plant=None, friction=None, actuators=None, sensors=None, foot_sensors=None, estimator=None, disturbances=None,
+            tipping=None):
         """Arm the models that are given, in the one order.  ``plant``, ``actuators`` and ``foot_sensors``: the argument tuples of their ``set_*``;
         ``disturbances``: (events, contact_rule) of ``set_disturbances``."""
         if disturbances is not None:
@@ -110,6 +112,8 @@ class SimulatorModels:
             self.set_plant(*plant)
         if friction is not None:
             self.set_friction(friction, q)
+        if tipping is not None:
+            self.set_tipping(tipping, q)
         if actuators is not None:
             self.set_actuators(*actuators)
         if sensors is not None:
@@ -164,6 +168,20 @@ class SimulatorModels:
     def friction_state(self):
         """the state rows of the friction model by ``friction_model.unpack`` (``v``, ``sliding``, ``slip_dist`` ...); None while it is off"""
         return None if self.rows["friction"] is None else self.sim.read_friction()
+
+    def set_tipping(self, rows, q=None):
+        """``rows`` in the forms of ``NativeSolver.tipping``, a dict's missing fields from ``tipping_model.defaults`` of the nominal robot at ``q`` and the
+        simulator's step length; checked before any library call; every sole flat and at rest.  None: off."""
+        if rows is None:
+            return self._turn_off("tipping")
+        base = _tipping_model.defaults(self.model, q, self._sole_frames, self._sim_dt)
+        checked = _tipping_model.validate(_tipping_model.rows(rows, self.batch, base))
+        self.sim.tipping(checked)
+        self.rows["tipping"] = checked
+
+    def tipping_state(self):
+        """the state rows of the tipping model by ``tipping_model.unpack`` (``v``, ``th``, ``tipping``, ``peak_angle`` ...); None while it is off"""
+        return None if self.rows["tipping"] is None else self.sim.read_tipping()
 
     def set_actuators(self, params, limit=None, friction_shape=None):
         """``params`` in the forms of ``NativeSolver.actuators``, a dict may also carry ``limit`` and ``friction_shape``; ``limit`` defaults to the
