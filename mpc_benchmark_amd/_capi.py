@@ -13,6 +13,7 @@ import os
 import numpy as np
 
 from . import actuator_model as _actuator_model
+from . import joint_stops as _joint_stops
 from . import sensor_model as _sensor_model
 from . import state_estimator as _state_estimator
 from . import foot_sensors as _foot_sensors
@@ -176,6 +177,15 @@ _SIM_ACTUATORS_SIGNATURES = {
     "mpc_sim_actuators_width": (C.c_int32, [C.c_void_p]),
 }
 
+# include/mpc_sim_joint_stops.h: exported by the HIP library alone, bound when present (``NativeSolver.joint_stops`` / ``read_joint_stops`` /
+# ``set_joint_stops``)
+_SIM_JOINT_STOPS_SIGNATURES = {
+    "mpc_sim_joint_stops": (C.c_int, [C.c_void_p, _DP, _DP, _DP, _DP]),
+    "mpc_sim_joint_stops_read": (C.c_int, [C.c_void_p, _DP, _DP, _DP, _DP]),
+    "mpc_sim_joint_stops_set": (C.c_int, [C.c_void_p, _DP]),
+    "mpc_sim_joint_stops_width": (C.c_int32, [C.c_void_p]),
+}
+
 # include/mpc_sim_sensors.h: exported by the HIP library alone, bound when present (``NativeSolver.sensors`` / ``read_sensors`` / ``set_sensors``)
 _SIM_SENSORS_SIGNATURES = {
     "mpc_sim_sensors": (C.c_int, [C.c_void_p, _DP, _DP]),
@@ -291,6 +301,7 @@ _HIP_ONLY = (
     ("mpc_sim_metrics.h", _SIM_METRICS_SIGNATURES, "the locomotion metrics of torque-driven simulator steps are HIP only", RuntimeError),
     ("mpc_sim_contacts.h", _SIM_CONTACTS_SIGNATURES, "the contact rule of torque-driven simulator steps is HIP only", RuntimeError),
     ("mpc_sim_actuators.h", _SIM_ACTUATORS_SIGNATURES, "the actuator model of torque-driven simulator steps is HIP only", RuntimeError),
+    ("mpc_sim_joint_stops.h", _SIM_JOINT_STOPS_SIGNATURES, "the joint end-stops of torque-driven simulator steps are HIP only", RuntimeError),
     ("mpc_sim_sensors.h", _SIM_SENSORS_SIGNATURES, "the sensor model of torque-driven simulator steps is HIP only", RuntimeError),
     ("mpc_sim_estimator.h", _SIM_ESTIMATOR_SIGNATURES, "the base-state estimator of torque-driven simulator steps is HIP only", RuntimeError),
     ("mpc_sim_foot_sensors.h", _SIM_FOOT_SENSORS_SIGNATURES, "the foot force sensors of torque-driven simulator steps are HIP only", RuntimeError),
@@ -776,6 +787,54 @@ class NativeSolver:
         """Impose the state rows of the friction model (mpc_sim_friction_set): (B, 17), e.g. ``read_friction(raw=True)`` of an earlier point."""
         fn, w = self._hip("mpc_sim_friction_set"), self._width("mpc_sim_friction_width")
         self._check(fn(self._h, _dp(self._checked_rows("set_friction: state rows", state, w))), "mpc_sim_friction_set")
+
+    # -- include/mpc_sim_joint_stops.h (HIP library only): the per-robot joint end-stops of the torque-driven simulator steps -----------------------
+    def joint_stops(self, params, lo=None, hi=None, scale=None):
+        """Add to the torque every torque-driven simulator step of this handle integrates the stop torque of every actuated joint that stands beyond
+        its robot's own range (mpc_sim_joint_stops; ``joint_stops`` is the definition).  ``params``: (B, 8) rows, one row of 8 for every robot, or a
+        dict by ``joint_stops.FIELDS`` name (``k``, ``d``, ``cap``) of scalars or (B,) arrays (missing fields: ``joint_stops.DEFAULTS``); ``lo``,
+        ``hi``: (B, nu) or (nu,) in rad (-inf / +inf: no stop on that side); ``scale``: (nu,) in N m, None: ones.  Turns the model on and resets its
+        state rows.  None turns it off."""
+        fn = self._hip("mpc_sim_joint_stops")
+        if params is None:
+            self._check(fn(self._h, None, None, None, None), "mpc_sim_joint_stops")
+            return
+        d = self.dims
+        p = _f64(_joint_stops.rows(params, d.batch))
+        tabs = []
+        for name, a in (("lo", lo), ("hi", hi)):
+            if a is None:
+                raise ValueError("joint_stops: %s is needed (joint_stops.limits builds the tables of a model)" % name)
+            a = np.asarray(a, dtype=float)
+            if a.shape == (d.nu,):
+                a = np.tile(a, (d.batch, 1))
+            if a.shape != (d.batch, d.nu):
+                raise ValueError("joint_stops: %s of shape (%d, %d) or (%d,) expected, got %s" % (name, d.batch, d.nu, d.nu, a.shape))
+            tabs.append(_f64(a))
+        sc = None if scale is None else _f64(scale)
+        if sc is not None and sc.shape != (d.nu,):
+            raise ValueError("joint_stops: scale of shape (%d,) expected, got %s" % (d.nu, sc.shape))
+        self._check(fn(self._h, _dp(p), _dp(tabs[0]), _dp(tabs[1]), _dp(sc)), "mpc_sim_joint_stops")
+
+    def read_joint_stops(self, raw=False):
+        """The joint stops as they stand (mpc_sim_joint_stops_read) -> dict: ``params`` (B, 8), ``lo`` and ``hi`` (B, nu) in force, and the state rows
+        by ``joint_stops.unpack`` (``tau_stop``, ``pen``, ``peak_pen``, ``stop_steps``, ``hits`` (B, nu), ``any_steps``, ``steps``); ``raw``: the
+        (B, 5 nu + 2) rows as ``set_joint_stops`` takes them."""
+        fn, out = self._hip("mpc_sim_joint_stops_read"), self._state_rows("mpc_sim_joint_stops_width")
+        d = self.dims
+        par, lo, hi = np.zeros((d.batch, _joint_stops.PARAMS)), np.zeros((d.batch, d.nu)), np.zeros((d.batch, d.nu))
+        self._check(fn(self._h, _dp(par), _dp(lo), _dp(hi), _dp(out)), "mpc_sim_joint_stops_read")
+        if raw:
+            return out
+        r = _joint_stops.unpack(out, d.nu)
+        r["params"], r["lo"], r["hi"] = par, lo, hi
+        return r
+
+    def set_joint_stops(self, state):
+        """Impose the state rows of the joint stops (mpc_sim_joint_stops_set): (B, 5 nu + 2), e.g. ``read_joint_stops(raw=True)`` of an earlier point."""
+        fn = self._hip("mpc_sim_joint_stops_set")
+        r = self._checked_rows("set_joint_stops: state rows", state, _joint_stops.width(self.dims.nu))
+        self._check(fn(self._h, _dp(r)), "mpc_sim_joint_stops_set")
 
     # -- include/mpc_sim_tipping.h (HIP library only): per-robot sole tipping in the torque-driven simulator steps --------------------------------
     def tipping(self, params, base=None):

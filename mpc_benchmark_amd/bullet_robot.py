@@ -18,6 +18,10 @@ box terrain under the rule, host or device: a foot is caught on the highest box 
 risers, soles hanging over an edge and slopes are not modelled.  ``addStairs`` (a URDF in the reference) stays unavailable.
 ``actuators=`` / ``setActuators(params, limit=None, friction_shape=None)`` (HIP library only) put the actuator model of ``actuator_model`` between
 ``execute(torques)`` and the dynamics (mpc_sim_actuators, include/mpc_sim_actuators.h): delay, gain error, lag, saturation, joint friction.
+``joint_stops=`` / ``setJointStops(params, lo=None, hi=None, scale=None)`` (HIP library only) give every controlled joint the end-stops of
+``joint_stops`` (mpc_sim_joint_stops, include/mpc_sim_joint_stops.h), which Bullet applies to the revolute joints of the reference's URDF: a joint
+beyond its range is pushed back by a one-sided spring and damper.  The range defaults to the model's position limits.  ``jointStopState()`` returns
+the stop torques, penetrations and counters.  Without it every joint turns freely, as before.
 ``sensors=`` / ``setSensors(params)`` (HIP library only) put the sensor model of ``sensor_model`` between the dynamics and ``measureState()``
 (mpc_sim_sensors, include/mpc_sim_sensors.h): latency, encoder resolution, calibration offsets, noise, finite-difference velocities.  ``x``, the
 contact rule and ``history`` stay the true state; ``measureState()`` returns the measurement.
@@ -64,7 +68,7 @@ class BulletRobot:
     def __init__(self, controlledJoints, modelPath=None, URDF_filename=None, simuStep=1e-3, rmodelComplete=None, robotPose=(0.0, 0.0, 1.01927),
                  inertiaOffset=True, talos=True, library=None, contact_frames=("left_sole_link", "right_sole_link"), ground_tol=5e-3, release_steps=5, release_force=1.0,
                  device_contacts=False, actuators=None, sensors=None, estimator=None, foot_sensors=None, plant=None, friction=None, disturbances=None,
-                 tipping=None):
+                 tipping=None, joint_stops=None):
         if rmodelComplete is None:
             raise ValueError("the complete robot model is needed (5th positional argument, as in the scripts)")
         self._lib = library
@@ -84,6 +88,7 @@ class BulletRobot:
         self._plant = None if plant is None else (plant, None)  # (rows, link_scale) of setPlant, armed at initializeJoints
         self._friction = friction  # rows of setFriction, armed at initializeJoints
         self._tipping = tipping  # rows of setTipping, armed at initializeJoints
+        self._joint_stops = None if joint_stops is None else (joint_stops, None, None, None)  # (params, lo, hi, scale) of setJointStops, armed at initializeJoints
         self._disturbances = disturbances  # events of setDisturbances, armed at initializeJoints
         self.robotPose = np.asarray(robotPose, dtype=float)
         self.localInertiaPos = np.zeros(3)
@@ -135,7 +140,8 @@ class BulletRobot:
                 self._native.terrain(self.terrain)
         self._sim_models = _tsim.SimulatorModels(self._native, m, self.frame_ids, self.dt)
         self._sim_models.arm(self.x, self.x[:m.nq], self._plant, self._friction, self._actuators, self._sensors, self._foot_sensors, self._estimator,
-                             None if self._disturbances is None else (self._disturbances, self.device_contacts), tipping=self._tipping)
+                             None if self._disturbances is None else (self._disturbances, self.device_contacts), tipping=self._tipping,
+                             joint_stops=self._joint_stops)
 
     def _build_native(self):
         """the handle (opened once) with the model, the terminal stage and the contact-mask stages at the anchors ``_contact_pose`` as they stand"""
@@ -383,6 +389,19 @@ class BulletRobot:
         self._actuators = None if params is None else (params, limit, friction_shape)
         if self._sim_models is not None:
             self._sim_models.set_actuators(params, limit, friction_shape)
+
+    def setJointStops(self, params, lo=None, hi=None, scale=None):
+        """The joint end-stops between the actuators and the dynamics (``joint_stops``; HIP library only): ``params`` one row of 8, (1, 8), or a dict
+        by field name (``k``, ``d``, ``cap``; missing fields: ``joint_stops.DEFAULTS``), which may also carry ``lo``, ``hi``, ``scale``,
+        ``range_scale``, ``margin`` and ``lock``; the range defaults to the model's position limits, ``scale`` to its effort limits; None: off.
+        Arms and resets the model; before ``initializeJoints`` it is kept for then."""
+        self._joint_stops = None if params is None else (params, lo, hi, scale)
+        if self._sim_models is not None:
+            self._sim_models.set_joint_stops(params, lo, hi, scale)
+
+    def jointStopState(self):
+        """the state rows of the joint stops by ``joint_stops.unpack`` (``tau_stop``, ``pen``, ``peak_pen``, ``hits`` ...); None without them"""
+        return None if self._sim_models is None else self._sim_models.joint_stop_state()
 
     def setPlant(self, rows, link_scale=None):
         """The plant's own link inertias (``plant_model``; HIP library only): ``rows`` one row of 16, (1, 16), or a dict by field name (missing fields:

@@ -35,6 +35,7 @@
 #include "sim_metrics.h"
 #include "sim_contacts.h"
 #include "sim_actuators.h"
+#include "sim_joint_stops.h"
 #include "sim_sensors.h"
 #include "sim_estimator.h"
 #include "sim_foot_sensors.h"
@@ -104,6 +105,8 @@ struct SimPlant {
   mpc_sim_terrain_config ter_cfg = {};
   // include/mpc_sim_actuators.h ; h: params | limit | shape
   SimModel act{"the actuator model is off on this handle (turn it on with mpc_sim_actuators)", false};
+  // include/mpc_sim_joint_stops.h: the per-robot joint end-stops (off: every joint turns freely) ; h: params | lo | hi | scale
+  SimModel js{"the joint stops are off on this handle (turn them on with mpc_sim_joint_stops)", false};
   // include/mpc_sim_sensors.h (off: the controllers read the true state) ; h: params
   SimModel sen{"the sensor model is off on this handle (turn it on with mpc_sim_sensors)", false};
   // include/mpc_sim_estimator.h: the base-state estimator ; h: params
@@ -125,7 +128,7 @@ struct SimPlant {
   SimModel dis{"the disturbance schedule is off on this handle (turn it on with mpc_sim_disturbances)", false};
   int dis_ne = 0;
   bool dis_contact = false;  // an event of the table has a contact trigger: the table goes with the contact rule
-  SimModel* const models[9] = {&act, &sen, &pm, &ter, &fr, &tip, &est, &fs, &dis};
+  SimModel* const models[10] = {&act, &js, &sen, &pm, &ter, &fr, &tip, &est, &fs, &dis};
   // the buffers above that come from hipMalloc (they are resized or dropped while the handle lives); the others are in mpc_solver::allocs
   void free_owned() {
     for (double** p : {&d_rec, &d_met, &d_con}) if (*p) { (void)hipFree(*p); *p = nullptr; }

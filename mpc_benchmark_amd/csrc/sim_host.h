@@ -121,6 +121,7 @@ static void sim_x0_check(const mpc_solver* s, const char* who, const double* x0,
 struct SimLayout {
   size_t np = 0;                  // doubles of the params: what follows them starts here
   size_t tables = 0, tables_b = 0;  // what all the rows share, or the caller's second array
+  size_t tables_c = 0;            // ... and third
   size_t out = 0;                 // what the model hands on (the consumers read it in place)
   size_t stage = 0;               // staging of the states to arm on
   size_t rows = 0, width = 0;     // the state rows [B][width]
@@ -145,6 +146,19 @@ static SimLayout sim_actuators_layout(const Layout& L) {
   l.tables_b = l.tables + L.m;
   l.rows = l.tables_b + L.m;
   l.width = (size_t)(MPC_SIM_ACTUATORS_RING + 2) * L.m + 2;
+  l.total = l.rows + (size_t)L.B * l.width;
+  return l;
+}
+// the joint stops: params [B][8] | tables: lo [B][nu] | tables_b: hi [B][nu] | tables_c: scale [nu] | out: what the dynamics integrate [B][nu] |
+// state rows [B][5 nu + 2].  The mirror holds all before `out`
+static SimLayout sim_joint_stops_layout(const Layout& L) {
+  SimLayout l;
+  l.np = l.tables = (size_t)L.B * MPC_SIM_JOINT_STOPS_PARAMS;
+  l.tables_b = l.tables + (size_t)L.B * L.m;
+  l.tables_c = l.tables_b + (size_t)L.B * L.m;
+  l.out = l.tables_c + L.m;
+  l.rows = l.out + (size_t)L.B * L.m;
+  l.width = (size_t)5 * L.m + 2;
   l.total = l.rows + (size_t)L.B * l.width;
   return l;
 }
@@ -349,6 +363,25 @@ static void sim_actuators_enqueue(mpc_solver* s, hipStream_t st, double dt_step)
   HIP_OK(hipGetLastError());
 }
 
+// the joint stops of the step about to be enqueued on stream st (sim_joint_stops.h), when they are on: after the actuator model, before the dynamics
+static void sim_joint_stops_enqueue(mpc_solver* s, hipStream_t st) {
+  const SimPlant& p = s->plant;
+  if (!p.js.on()) return;
+  const Layout& L = s->L;
+  const SimLayout l = sim_joint_stops_layout(L);
+  SimJointStopsArgs a;
+  a.nv = L.n / 2; a.nq = L.nx - L.n / 2; a.nu = L.m;
+  a.x = s->d_x0; a.tau = p.d_simu;
+  a.params = p.js.d; a.lo = p.js.d + l.tables; a.hi = p.js.d + l.tables_b; a.scale = p.js.d + l.tables_c;
+  a.out = p.js.d + l.out; a.rows = p.js.d + l.rows;
+  hipLaunchKernelGGL(k_sim_joint_stops, dim3((unsigned)L.B), dim3(SIM_JS_THREADS), 0, st, a);
+  HIP_OK(hipGetLastError());
+}
+// the torque the dynamics of a step integrate, [B][nu]: what the joint stops wrote when they are on, the step's torque buffer otherwise
+static const double* sim_integrated_torques(const mpc_solver* s) {
+  return s->plant.js.on() ? s->plant.js.d + sim_joint_stops_layout(s->L).out : s->plant.d_simu;
+}
+
 // what the sensors deliver, [B][nx]: the measurement of the sensor model when it is on, the true state otherwise
 static const double* sim_sensed(const mpc_solver* s) { return s->plant.sen.on() ? s->plant.sen.d + sim_sensors_layout(s->L).out : s->d_x0; }
 // the state the controllers read, [B][nx]: the estimate of the base-state estimator when it is on, what the sensors deliver otherwise
@@ -486,7 +519,9 @@ static bool sim_wrenches_wanted(const SimPlant& p, bool by_caller) {
 //    1 disturbances  reads the state the step starts from and the contact rows of the step BEFORE ; writes the force, point and link that act in
 //                    this step's dynamics, in place of the armed push
 //    2 actuators     reads the commanded torque and the state ; writes the applied torque in place: everything after it sees the applied torque
-//    3 dynamics      reads the applied torque, the push, the contact rows of the step BEFORE (the rows the low-level QPs of pipeline_loops.h read
+//    2b joint stops  reads the TRUE state the step starts from and the applied torque ; writes, into a buffer of its own, the applied torque plus the
+//                    stop torque of every joint beyond its range: the dynamics alone read that buffer, everything after them keeps the applied torque
+//    3 dynamics      reads the applied torque (with the joint stops on: their sum), the push, the contact rows of the step BEFORE (the rows the low-level QPs of pipeline_loops.h read
 //                    for this step), the slip and tip velocities friction and tipping set after the step before, robot b's own model table (the plant model, built
 //                    when it was armed: it launches nothing here) ; writes the new state and, when wanted (sim_wrenches_wanted), the wrenches
 //    4 record        reads the new state, the applied torque, the wrenches, the push, the plant's model tables ; writes its slot of the ring
@@ -505,10 +540,11 @@ static void sim_step_enqueue(mpc_solver* s, hipStream_t st, const SolverArgs& ar
   const SimPlant& p = s->plant;
   sim_disturbances_enqueue(s, st, substeps * dt);
   sim_actuators_enqueue(s, st, substeps * dt);
+  sim_joint_stops_enqueue(s, st);
   MbSimStep step;
   step.substeps = substeps; step.dt = dt;
   step.push = sim_push(s); step.width = p.dis.on() ? 6 : (p.push_width ? p.push_width : 3); step.linked = p.dis.on();
-  step.torques = p.d_simu; step.wrenches = sim_wrenches_wanted(p, want_wrenches) ? p.d_simwr : nullptr;
+  step.torques = sim_integrated_torques(s); step.wrenches = sim_wrenches_wanted(p, want_wrenches) ? p.d_simwr : nullptr;
   step.contact_rows = p.d_con;
   step.model_tables = p.pm.on() ? sim_plant_tables(s) : nullptr; step.model_stride = sim_plant_stride(s);
   step.friction_rows = p.fr.on() ? p.fr.d + sim_friction_layout(s->L).rows : nullptr;
@@ -808,6 +844,72 @@ int mpc_sim_actuators_set(mpc_solver* s, const double* state) {
 }
 
 int32_t mpc_sim_actuators_width(mpc_solver* s) { return sim_width(s, "sim_actuators_width", [&] { return sim_actuators_layout(s->L).width; }); }
+
+// ---- include/mpc_sim_joint_stops.h: the per-robot joint end-stops of the torque-driven simulator steps -----------------------------------------
+int mpc_sim_joint_stops(mpc_solver* s, const double* params, const double* lo, const double* hi, const double* scale) {
+  MPC_TRY(s, {
+    sim_check(s, "sim_joint_stops");
+    const Layout& L = s->L;
+    const SimLayout l = sim_joint_stops_layout(L);
+    SimModel& m = s->plant.js;
+    if (!params) { sim_drop(s, m); return 0; }
+    // (every check before anything changes: a refused call leaves the previous configuration in force; cap and the limits may be infinite)
+    if (!lo || !hi) throw std::runtime_error("sim_joint_stops: lo and hi must not be null");
+    const size_t nu = L.m;
+    std::vector<double> h(params, params + l.np);
+    h.resize(l.total, 0.0);  // (params | lo | hi | scale | out, then the state rows after a reset: all 0)
+    for (int b = 0; b < L.B; ++b) {
+      const double* r = params + (size_t)b * MPC_SIM_JOINT_STOPS_PARAMS;
+      const std::string row = "sim_joint_stops: row " + std::to_string(b);
+      if (!std::isfinite(r[0]) || !std::isfinite(r[1])) throw std::runtime_error(row + ": k and d must be finite");
+      sim_nonneg_check(row, "k and d", r, 2);
+      if (!(r[2] > 0.0)) throw std::runtime_error(row + ": cap must be > 0 (+inf: none)");
+      sim_reserved_check(row, r, 3, MPC_SIM_JOINT_STOPS_PARAMS);
+      for (size_t j = 0; j < nu; ++j) {
+        const double lj = lo[b * nu + j], hj = hi[b * nu + j];
+        const std::string joint = row + ", joint " + std::to_string(j);
+        if (std::isnan(lj) || std::isnan(hj)) throw std::runtime_error(joint + ": a limit is NaN");
+        if (lj > hj) throw std::runtime_error(joint + ": lo > hi");
+        if (lj == std::numeric_limits<double>::infinity() || hj == -std::numeric_limits<double>::infinity())
+          throw std::runtime_error(joint + ": lo must be < +inf and hi > -inf (-inf / +inf: no stop on that side)");
+        h[l.tables + b * nu + j] = lj;
+        h[l.tables_b + b * nu + j] = hj;
+      }
+    }
+    for (size_t j = 0; j < nu; ++j) {
+      const double sc = scale ? scale[j] : 1.0;
+      if (!std::isfinite(sc) || !(sc > 0.0)) throw std::runtime_error("sim_joint_stops: scale must be finite and > 0 (joint " + std::to_string(j) + ")");
+      h[l.tables_c + j] = sc;
+    }
+    sim_realloc(s, m.d, l.total);
+    m.h.assign(h.begin(), h.begin() + l.out);
+    copy_sync(s, m.d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+  })
+}
+
+int mpc_sim_joint_stops_read(mpc_solver* s, double* params, double* lo, double* hi, double* state) {
+  MPC_TRY(s, {
+    const SimLayout l = sim_joint_stops_layout(s->L);
+    const SimModel& m = s->plant.js;
+    sim_model_read(s, "sim_joint_stops_read", m, l, params, state);
+    if (lo) std::copy(m.h.begin() + l.tables, m.h.begin() + l.tables_b, lo);
+    if (hi) std::copy(m.h.begin() + l.tables_b, m.h.begin() + l.tables_c, hi);
+  })
+}
+
+int mpc_sim_joint_stops_set(mpc_solver* s, const double* state) {
+  MPC_TRY(s, {
+    const SimLayout l = sim_joint_stops_layout(s->L);
+    const int nu = s->L.m;
+    sim_rows_set(s, "sim_joint_stops_set", s->plant.js, l, state, -1, [&](const std::string& row, const double* r, int) {
+      sim_nonneg_check(row, "peak_pen, stop_steps, hits, any_steps and steps", r + 2 * nu, 3 * nu + 2);
+      for (int j = 0; j < nu; ++j)
+        if (std::fabs(r[nu + j]) > r[2 * nu + j]) throw std::runtime_error(row + ": joint " + std::to_string(j) + " holds a |pen| above its peak_pen");
+    });
+  })
+}
+
+int32_t mpc_sim_joint_stops_width(mpc_solver* s) { return sim_width(s, "sim_joint_stops_width", [&] { return sim_joint_stops_layout(s->L).width; }); }
 
 // ---- include/mpc_sim_sensors.h, include/mpc_sim_estimator.h: the two per-robot models between the simulator steps and the controllers ----------
 int mpc_sim_sensors(mpc_solver* s, const double* params, const double* x0) {

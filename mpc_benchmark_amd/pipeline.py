@@ -47,6 +47,15 @@ field name of scalars or (B,) arrays, which may also carry ``limit`` and ``frict
 torque of the last step on both forms of a tick (the device loop returns it; the host glue reads it back after each step), and so are the record's
 torque columns and the metrics' power and energy.  ``set_actuators`` changes or removes the model later.
 
+``joint_stops`` (all three pipelines): None, every joint of the plant turns freely; or the parameter rows of the per-robot joint end-stops
+(``joint_stops``: stiffness ``k``, damping ``d`` and ``cap`` in units of ``scale``; (B, 8), one row of 8 for every robot, or a dict by field name of
+scalars or (B,) arrays, which may also carry the tables ``lo`` / ``hi`` (B, nu), or the ``range_scale``, ``margin`` and ``lock`` that
+``joint_stops.limits`` builds them from, and ``scale``), armed on the simulator handle after the actuators (mpc_sim_joint_stops,
+include/mpc_sim_joint_stops.h; HIP library only).  The tables default to the model's position limits, ``scale`` to its effort limits.  Only the plant
+changes: a joint beyond its range is pushed back by a one-sided spring and damper that the dynamics integrate with the actuators' torque.
+``torques``, the record's torque columns and the metrics' power stay the actuators' torque: a stop is not a motor.  ``joint_stop_state()`` returns
+the stop torques, penetrations and counters; ``set_joint_stops`` changes or removes the model later.
+
 ``sensors`` (all three pipelines): None, the controllers read the simulator's exact state; or the parameter rows of the per-robot sensor model
 (``sensor_model``: latency, encoder resolution, calibration offsets, joint and floating-base noise, finite-difference joint velocities, their low-pass;
 (B, 16), one row of 16 for every robot, or a dict by field name of scalars or (B,) arrays), armed on the simulator handle at the pipeline's true
@@ -290,7 +299,8 @@ class _Pipeline:
         self.nq, self.nv = m.nq, m.nv
         self.substeps, self.sim_dt = int(substeps), float(sim_dt)
 
-    def _build_simulator(self, plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=None, tipping=None):
+    def _build_simulator(self, plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=None, tipping=None,
+                         joint_stops=None):
         """The simulator stand-in (``build_torque_simulator``) with its contact rule and terrain, stage 0 on ``stage0`` if one is given, and the
         models armed at ``self.x``; ``x_prev`` starts from what the controllers read then."""
         rb = self.pd.robot
@@ -307,7 +317,8 @@ class _Pipeline:
         self.sim_models = _tsim.SimulatorModels(self.sim, self.model, rb.foot_frame_ids, self.sim_dt)
         self.sim_models.arm(self.x, rb.x0[:self.nq], plant, friction, None if actuators is None else (actuators,), sensors,
                             None if foot_sensors is None else (foot_sensors, detected_contacts), estimator,
-                            None if self._disturbances is None else (self._disturbances, self.contact_rule is not None), tipping=tipping)
+                            None if self._disturbances is None else (self._disturbances, self.contact_rule is not None), tipping=tipping,
+                            joint_stops=None if joint_stops is None else (joint_stops,))
         self.x_prev = self.x_est.copy()      # the measurement of the period before (the solve's initial condition)
         self.torques = np.zeros((self.batch, self.nv - 6))
         self._plan_stale = True
@@ -358,6 +369,12 @@ class _Pipeline:
         ``limit`` and ``friction_shape``; ``limit`` defaults to the model's effort limits."""
         self.sim_models.set_actuators(params, limit, friction_shape)
 
+    def set_joint_stops(self, params, lo=None, hi=None, scale=None):
+        """Arm (and reset) the per-robot joint end-stops on ``self.sim``: ``params`` in the forms of ``NativeSolver.joint_stops``, a dict may also
+        carry ``lo``, ``hi``, ``scale``, ``range_scale``, ``margin`` and ``lock``; the tables default to the model's position limits, ``scale`` to
+        its effort limits."""
+        self.sim_models.set_joint_stops(params, lo, hi, scale)
+
     def set_sensors(self, params):
         """Arm (and reset) the per-robot sensor model on ``self.sim`` at the current true states ``self.x``: ``params`` in the forms of
         ``NativeSolver.sensors``.  An estimator in force arms again, after the sensors."""
@@ -402,6 +419,10 @@ class _Pipeline:
     def tipping_state(self):
         """the state rows of the tipping model by ``tipping_model.unpack`` (``v``, ``th``, ``tipping``, ``peak_angle`` ...); None without ``tipping``"""
         return self.sim_models.tipping_state()
+
+    def joint_stop_state(self):
+        """the state rows of the joint stops by ``joint_stops.unpack`` (``tau_stop``, ``pen``, ``peak_pen``, ``hits`` ...); None without ``joint_stops``"""
+        return self.sim_models.joint_stop_state()
 
     # -- the hand-over latency of the plan (``plan_latency``, include/mpc_plan_latency.h): ``None`` turns it off ------------------------------------
     def _reset_latency(self):
@@ -580,13 +601,13 @@ class _QpContactSource(_Pipeline):
 class KinodynamicPipeline(_QpContactSource):
     def __init__(self, problem_def, batch=1, library=None, walk=None, weights_id=(1.0, 10000.0), substeps=10, sim_dt=1e-3, x0=None, contact_rule=None,
                  terrain=None, contact_source="schedule", actuators=None, sensors=None, estimator=None, foot_sensors=None,
-                 detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, tipping=None, **ens_kw):
+                 detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, tipping=None, joint_stops=None, **ens_kw):
         """``problem_def``: a KinodynamicProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.3 m steps)
         or None (references frozen at the initial footholds).  ``contact_rule``: None or a config dict, ``terrain``: None or boxes,
         ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model, ``sensors``: None or the rows of the
         sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the rows of the foot force sensors,
         ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model, ``friction``: None or the rows of
-        the ground friction, ``tipping``: None or the rows of the sole tipping, ``latency``: None or the rows of the plan's hand-over latency (module
+        the ground friction, ``tipping``: None or the rows of the sole tipping, ``joint_stops``: None or the rows of the joint end-stops, ``latency``: None or the rows of the plan's hand-over latency (module
         docstring)."""
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
                                                         contact_source, disturbances=disturbances, latency=latency, tipping=tipping)
@@ -601,7 +622,8 @@ class KinodynamicPipeline(_QpContactSource):
         self.qp.enable_device_assembly()
         self.umax = np.asarray(m.effortLimit, dtype=float)[6:]
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
-        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, tipping=tipping)
+        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, tipping=tipping,
+                              joint_stops=joint_stops)
         self.forces = np.zeros((self.batch, 12))
 
     def _fetch(self):
@@ -717,14 +739,14 @@ class CentroidalPipeline(_QpContactSource):
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, seed=20250304, perturb=True, sigma_q=0.02,
                  sigma_v=0.05, perturb_dofs=None, contact_rule=None, terrain=None, contact_source="schedule", actuators=None, sensors=None,
-                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, tipping=None, **ens_kw):
+                 estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, tipping=None, joint_stops=None, **ens_kw):
         """``problem_def``: a CentroidalProblem.  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk`` ({} = the script's 0.2 m steps, one plan for
         every robot; ``dict(per_instance=True)``: every robot's own, from its measured soles; with ``generator="device"`` planned on the device) or None
         (references frozen at the initial footholds).  ``x0``: explicit whole-body initial states [B][nq+nv].  ``contact_rule``: None or a config
         dict, ``terrain``: None or boxes, ``contact_source``: "schedule", "plant" or "both", ``actuators``: None or the rows of the actuator model,
         ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state estimator, ``foot_sensors``: None or the
         rows of the foot force sensors, ``detected_contacts``: who works from the detected contacts, ``plant``: None or the rows of the plant model,
-        ``friction``: None or the rows of the ground friction, ``tipping``: None or the rows of the sole tipping, ``latency``: None or the rows of
+        ``friction``: None or the rows of the ground friction, ``tipping``: None or the rows of the sole tipping, ``joint_stops``: None or the rows of the joint end-stops, ``latency``: None or the rows of
         the plan's hand-over latency (module docstring)."""
         from .ensemble import ensemble_initial_states
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
@@ -751,7 +773,8 @@ class CentroidalPipeline(_QpContactSource):
                                          batch=self.batch)
         self.qp.enable_device_assembly()
         # (the schedule starts in double support; ``x_prev`` is the stale measurement the task errors are taken at)
-        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=(True, True), tipping=tipping)
+        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, stage0=(True, True), tipping=tipping,
+                              joint_stops=joint_stops)
         self.forces = np.zeros((self.batch, 12))
         self.ik = None                 # the task errors of the last period
         self._xik_on_device = False    # the QP handle keeps x_prev of its last device loop
@@ -874,13 +897,13 @@ class FullDynamicPipeline(_Pipeline):
 
     def __init__(self, problem_def, batch=1, library=None, walk=None, substeps=10, sim_dt=1e-3, x0=None, contact_rule=None, terrain=None, actuators=None,
                  sensors=None, estimator=None, foot_sensors=None, detected_contacts=(), plant=None, friction=None, disturbances=None, latency=None, tipping=None,
-                 **ens_kw):
+                 joint_stops=None, **ens_kw):
         """``problem_def``: a FullDynamicsProblem (reduced or complete model).  ``walk``: keyword arguments of ``EnsembleMPC.enable_walk``
         ({} = the script's steps) or None (references frozen at the initial footholds).  ``ens_kw``: EnsembleMPC's, but not ``closed_loop``:
         the pipeline is the closed loop.  ``contact_rule``: None or a config dict, ``terrain``: None or boxes, ``actuators``: None or the rows of the
         actuator model, ``sensors``: None or the rows of the sensor model, ``estimator``: None or the rows of the base-state
         estimator, ``foot_sensors``: None or the rows of the foot force sensors, ``detected_contacts``: () or ("estimator",), ``plant``: None or the rows of the plant
-        model, ``friction``: None or the rows of the ground friction, ``tipping``: None or the rows of the sole tipping, ``latency``: None or the rows of the plan's hand-over latency (module docstring
+        model, ``friction``: None or the rows of the ground friction, ``tipping``: None or the rows of the sole tipping, ``joint_stops``: None or the rows of the joint end-stops, ``latency``: None or the rows of the plan's hand-over latency (module docstring
         of pipeline.py)."""
         walk, detected_contacts = self._check_arguments(problem_def, batch, contact_rule, terrain, walk, friction, foot_sensors, detected_contacts,
                                                         disturbances=disturbances, latency=latency, tipping=tipping)
@@ -893,7 +916,8 @@ class FullDynamicPipeline(_Pipeline):
         self.mpc = EnsembleMPC(problem_def, batch=batch, library=self.lib, x0=x0, **ens_kw)
         self._walk_args = walk
         self.x = np.array(self.mpc.x0, dtype=float)      # measured states, one row per robot
-        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, tipping=tipping)
+        self._build_simulator(plant, friction, actuators, sensors, foot_sensors, detected_contacts, estimator, tipping=tipping,
+                              joint_stops=joint_stops)
         self.wrenches = np.zeros((self.batch, 2, 6))     # contact wrenches of the last simulator step (LOCAL frame of the sole)
 
     def low_level_step(self, cs):

@@ -12,6 +12,7 @@ from . import actuator_model as _actuator_model
 from . import disturbance_model as _disturbance_model
 from . import foot_sensors as _foot_sensors
 from . import friction_model as _friction_model
+from . import joint_stops as _joint_stops
 from . import tipping_model as _tipping_model
 from . import plant_model as _plant_model
 from . import sensor_model as _sensor_model
@@ -94,7 +95,7 @@ class SimulatorModels:
     The caller hands in what is its own: ``x``, the true states (B, nx) (or (nx,) for B = 1) as they stand, wherever a model arms at them or falls
     back to them, and ``q``, the configuration the defaults of the friction and tipping models are taken at (nothing here refers back to the caller).
     ``rows[name]`` is what model ``name`` was armed with, None while it is off; turning a model off touches the library only if it was on.  Refusals that name their caller (a model that needs the contact rule) are the caller's, before it calls here."""
-    NAMES = ("disturbances", "plant", "friction", "tipping", "actuators", "sensors", "foot_sensors", "estimator")
+    NAMES = ("disturbances", "plant", "friction", "tipping", "actuators", "joint_stops", "sensors", "foot_sensors", "estimator")
 
     def __init__(self, sim, model, sole_frames, sim_dt):
         self.sim, self.model, self.batch = sim, model, sim.dims.batch
@@ -103,9 +104,9 @@ class SimulatorModels:
         self.consumers = ()      # who works from the detected contacts (``foot_sensors.CONSUMERS``)
 
     def arm(self, x, q, plant=None, friction=None, actuators=None, sensors=None, foot_sensors=None, estimator=None, disturbances=None,
-            tipping=None):
-        """Arm the models that are given, in the one order.  ``plant``, ``actuators`` and ``foot_sensors``: the argument tuples of their ``set_*``;
-        ``disturbances``: (events, contact_rule) of ``set_disturbances``."""
+            tipping=None, joint_stops=None):
+        """Arm the models that are given, in the one order.  ``plant``, ``actuators``, ``joint_stops`` and ``foot_sensors``: the argument tuples of their
+        ``set_*``; ``disturbances``: (events, contact_rule) of ``set_disturbances``."""
         if disturbances is not None:
             self.set_disturbances(*disturbances)
         if plant is not None:
@@ -116,6 +117,8 @@ class SimulatorModels:
             self.set_tipping(tipping, q)
         if actuators is not None:
             self.set_actuators(*actuators)
+        if joint_stops is not None:
+            self.set_joint_stops(*joint_stops)
         if sensors is not None:
             self.set_sensors(sensors, x)
         if foot_sensors is not None:   # (before the estimator: its arming event already reads the pair it will be fed)
@@ -201,6 +204,33 @@ class SimulatorModels:
     def applied_torques(self, tau):
         """after a simulator step under ``tau``: what the step integrated (the actuator model's output; ``tau`` itself while it is off)"""
         return tau if self.rows["actuators"] is None else self.sim.read_actuators()["applied"].copy()
+
+    def set_joint_stops(self, params, lo=None, hi=None, scale=None):
+        """``params`` in the forms of ``NativeSolver.joint_stops``; a dict may also carry ``lo``, ``hi``, ``scale`` and the ``range_scale``,
+        ``margin`` and ``lock`` of ``joint_stops.limits``, which builds the tables from the model's position limits when ``lo`` / ``hi`` are not
+        given.  ``scale`` defaults to the model's effort limits.  Checked before any library call; arms and resets the model.  None: off."""
+        if params is None:
+            return self._turn_off("joint_stops")
+        lim = {}
+        if isinstance(params, dict):
+            params = dict(params)
+            lo, hi, scale = params.pop("lo", lo), params.pop("hi", hi), params.pop("scale", scale)
+            lim = {k: params.pop(k) for k in ("range_scale", "margin", "lock") if k in params}
+        if lim and (lo is not None or hi is not None):
+            raise ValueError("joint_stops: range_scale, margin and lock build the tables: give them or lo / hi, not both")
+        if lo is None or hi is None:   # (the model's limits for the table that is not given)
+            nominal = _joint_stops.limits(self.model, self.batch, **lim)
+            lo, hi = (t if a is None else a for a, t in zip((lo, hi), nominal))
+        lo, hi = (np.broadcast_to(np.asarray(a, dtype=float), (self.batch, self.model.nv - 6)) for a in (lo, hi))
+        if scale is None:
+            scale = np.asarray(self.model.effortLimit, dtype=float)[6:]
+        checked = _joint_stops.validate(_joint_stops.rows(params, self.batch), lo, hi, scale)
+        self.sim.joint_stops(*checked)
+        self.rows["joint_stops"] = checked
+
+    def joint_stop_state(self):
+        """the state rows of the joint stops by ``joint_stops.unpack`` (``tau_stop``, ``pen``, ``peak_pen``, ``hits`` ...); None while they are off"""
+        return None if self.rows["joint_stops"] is None else self.sim.read_joint_stops()
 
     def set_sensors(self, params, x):
         """``params`` in the forms of ``NativeSolver.sensors``.  Arms and resets the model at the true states ``x``; an estimator in force arms again, after
