@@ -2,10 +2,21 @@
 // sim_step_enqueue), with nothing but kernels in between.  mpc_qp_low_level_steps (kinodynamic, include/mpc_qp_abi.h), mpc_qp_ikid_low_level_steps
 // (centroidal, the same header) and mpc_feedback_low_level_steps (full dynamics, include/mpc_feedback_pipeline.h).  The controllers read sim_measured(sim): the measurement of
 // the sensor model when it is on (include/mpc_sim_sensors.h), the true state otherwise; x_out, the record, the metrics and the contact rule are the
-// true state's.  With a hand-over latency armed on the plan (include/mpc_plan_latency.h, host side below) the loops launch the second instantiation of
-// their feedback kernels (plan_latency.h), which read every robot's held record while its countdown runs; off, they launch what they always did.
-// Included at the end of mpc_hip.hip, after sim_host.h.
+// true state's.  What the loops share is written once, ahead of them: where the plan lives (plan_view), the checks (loop_check_*), the choice of a
+// feedback kernel's instantiation (loop_launch_feedback: HELD while a hand-over latency is armed on the plan, include/mpc_plan_latency.h, host side
+// below) and the read-backs (loop_finish).  Each loop keeps its model checks, scratch, arguments and step.  Included at the end of mpc_hip.hip, after sim_host.h.
 #pragma once
+
+// the plan of a handle as the kernels find it (plan_view.h)
+static PlanView plan_view(const mpc_solver* plan) {
+  const Layout& P = plan->L;
+  PlanView v;
+  v.xs = plan->d_xs; v.us = plan->d_us; v.gains = plan->d_gains; v.knots = plan->d_knots;
+  v.N = P.N; v.nx = P.nx; v.n = P.n; v.m = P.m; v.gain_stride = P.gain_stride; v.oK = P.oK; v.knot_stride = P.knot_stride; v.oXD = P.oXD;
+  v.xd_off = P.space == MPC_SPACE_MULTIBODY ? P.n / 2 : 3;
+  v.slot0 = plan->khead % P.N;
+  return v;
+}
 
 // include/mpc_plan_latency.h: the three parts of the handle's buffer, and what the second instantiations of the feedback kernels get
 static size_t plan_latency_width(const Layout& P) { return (size_t)MPC_PLAN_LATENCY_HELD(P.nx, P.n, P.m); }
@@ -34,6 +45,55 @@ static void pipe_contacts_enqueue(const PipeContactsArgs& c, hipStream_t st) {
   hipLaunchKernelGGL(k_pipe_contact_states, dim3((unsigned)((2 * c.B + 63) / 64)), dim3(64), 0, st, c);
 }
 
+// The frame of a loop, part one: its handles (`handles`: "two" or "three" of them) live on one device and hold one batch size ...
+static void loop_check_handles(const char* who, const char* handles, const mpc_solver* plan, const mpc_solver* sim, int device, int B) {
+  if (plan->dims.device != device || sim->dims.device != device) throw std::runtime_error(std::string(who) + ": the " + handles + " handles must live on one device");
+  if (plan->L.B != B || sim->L.B != B) throw std::runtime_error(std::string(who) + ": the " + handles + " handles must have the same batch size");
+}
+// ... part two, behind the loop's own model checks: the plan is at rest, the simulator can take the steps, the streams other than the loop's are drained
+static void loop_check_idle(const char* who, const mpc_solver* plan, mpc_solver* sim, int need, int steps, hipStream_t st) {
+  if (plan->async_pending > 0) throw std::runtime_error(std::string(who) + ": the plan has ticks in flight (mpc_wait first)");
+  sim_steps_check(sim, who, need, steps);
+  HIP_OK(hipStreamSynchronize(plan->stream));
+  if (sim->stream != st) HIP_OK(hipStreamSynchronize(sim->stream));
+}
+// the measurement a step starts from, kept (before the last step of a call: x_prev)
+static void loop_keep_measurement(const mpc_solver* sim, hipStream_t st, double* d_xprev) {
+  HIP_OK(hipMemcpyAsync(d_xprev, sim_measured(sim), (size_t)sim->L.B * sim->L.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+}
+// one workgroup of one wavefront per robot of a feedback kernel: its HELD instantiation while a latency is armed on the plan, its plain one otherwise
+template <class Args> static void loop_launch_feedback(void (*held)(Args, PlanLatencyArgs), void (*plain)(Args, PlanLatencyArgs), const mpc_solver* plan, hipStream_t st, const Args& a) {
+  const dim3 grid((unsigned)plan->L.B), block(64);
+  if (plan->d_plan_lat) hipLaunchKernelGGL(held, grid, block, 0, st, a, plan_latency_args(plan));
+  else hipLaunchKernelGGL(plain, grid, block, 0, st, a, PlanLatencyArgs{});
+}
+// ... part three, behind the last step: what the caller asked for into its arrays and the one synchronisation.  d_forces [B][nf]: forces + df, or wrenches
+static void loop_finish(mpc_solver* sim, hipStream_t st, const double* d_xprev, double* x_prev, double* x_out, double* tau, const double* d_forces, int nf,
+                        double* forces, const mpc_qp_info* d_info = nullptr, mpc_qp_info* info = nullptr) {
+  const size_t B = sim->L.B, nx = sim->L.nx, nu = sim->L.m;
+  if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (tau) HIP_OK(hipMemcpyAsync(tau, sim->plant.d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (forces) HIP_OK(hipMemcpyAsync(forces, d_forces, B * nf * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (info) HIP_OK(hipMemcpyAsync(info, d_info, B * sizeof(mpc_qp_info), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  sim->perfect_feedback = false;
+}
+
+// the two QP loops: the contact states of a call go to the QP, or (a source other than the schedule) to the schedule buffer k_pipe_contact_states reads
+static PipeContactsArgs loop_contacts_begin(const char* who, const QpContactSource& qc, const QpIdBuffers& q, const mpc_solver* sim, int nk, const int32_t* contact_states) {
+  const bool from_plant = qc.source != MPC_QP_CONTACTS_SCHEDULE;
+  HIP_OK(hipMemcpyAsync(from_plant ? qc.sched : q.cs, contact_states, (size_t)q.B * nk * sizeof(int32_t), hipMemcpyHostToDevice, q.stream));
+  return from_plant ? pipe_contacts_args(who, qc, sim, nk, q.B, q.cs) : PipeContactsArgs{};
+}
+// ... and their torque kernel (pipeline_glue.h): one wavefront per robot behind the QP's solve
+static void loop_torque_enqueue(const QpIdBuffers& q, const QpContactSource& qc, int nk, const mpc_solver* sim, double* d_fnew, const double* d_taumax) {
+  PipeTorqueArgs t;
+  t.sol = q.sol; t.qn = q.n; t.nv = q.nv; t.nk = nk; t.f = q.f; t.f_new = d_fnew; t.sim_u = sim->plant.d_simu; t.tau_max = d_taumax;
+  t.used = qc.source != MPC_QP_CONTACTS_SCHEDULE ? qc.used : nullptr;
+  hipLaunchKernelGGL(k_pipe_torque, dim3((unsigned)q.B), dim3(64), 0, q.stream, t);
+}
+
 extern "C" {
 
 // include/mpc_qp_abi.h: the low-level loop of the kinodynamic pipeline with nothing but the kernels between its stages.  Everything is enqueued on
@@ -43,58 +103,43 @@ int mpc_qp_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc_solv
                            const double* x, int32_t steps, double dt, double* x_prev, double* x_out, double* tau, double* forces, mpc_qp_info* info) {
   if (!qp) return -2;
   try {
+    const char* who = "qp_low_level_steps";
     if (!S || !plan || !sim || !contact_states || !tau_max) throw std::runtime_error("qp_low_level_steps: null argument");
     if (steps <= 0 || !(dt > 0.0)) throw std::runtime_error("qp_low_level_steps: steps and dt must be positive");
     const QpContactSource qc = qp_contact_source(qp);
     const bool from_plant = qc.source != MPC_QP_CONTACTS_SCHEDULE;
-    if (from_plant) (void)pipe_contacts_args("qp_low_level_steps", qc, sim, nk, 0, nullptr);  // (the checks, before anything is allocated for another nk)
+    if (from_plant) (void)pipe_contacts_args(who, qc, sim, nk, 0, nullptr);  // (the checks, before anything is allocated for another nk)
     qp_id_prepare(qp, nk, frames, weights, cone);
     const QpIdBuffers q = qp_id_buffers(qp);
     const Layout& P = plan->L;
     const Layout& Z = sim->L;
     const int nx = q.nq + q.nv, nu = q.nv - 6, nf = 6 * nk;
-    if (plan->dims.device != q.device || sim->dims.device != q.device) throw std::runtime_error("qp_low_level_steps: the three handles must live on one device");
-    if (P.B != q.B || Z.B != q.B) throw std::runtime_error("qp_low_level_steps: the three handles must have the same batch size");
+    loop_check_handles(who, "three", plan, sim, q.device, q.B);
     if (P.space != MPC_SPACE_MULTIBODY || P.nx != nx || P.n != 2 * q.nv || P.m != nf + nu || P.n > PIPE_MAX_N)
       throw std::runtime_error("qp_low_level_steps: the plan must be a multibody problem with nx = nq + nv and controls (6 nk contact wrench components, nv - 6 joint accelerations)");
     if (Z.nx != nx || Z.m != nu) throw std::runtime_error("qp_low_level_steps: the simulator handle must have the QP's model (nx = nq + nv, nu = nv - 6)");
-    if (plan->async_pending > 0) throw std::runtime_error("qp_low_level_steps: the plan has ticks in flight (mpc_wait first)");
-    sim_steps_check(sim, "qp_low_level_steps", SIM_STAGE0, steps);
-    HIP_OK(hipStreamSynchronize(plan->stream));
-    HIP_OK(hipStreamSynchronize(sim->stream));
+    hipStream_t st = q.stream;
+    loop_check_idle(who, plan, sim, SIM_STAGE0, steps, st);
     const size_t B = q.B;
     double* scr = qp_scratch(qp, B * nx + B * nf + nu);  // x before the last period | forces + df | tau_max
     double *d_xprev = scr, *d_fnew = scr + B * nx, *d_taumax = d_fnew + B * nf;
-    hipStream_t st = q.stream;
     sim_steps_begin(sim, st, x);
-    HIP_OK(hipMemcpyAsync(from_plant ? qc.sched : q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const PipeContactsArgs pc = loop_contacts_begin(who, qc, q, sim, nk, contact_states);
     HIP_OK(hipMemcpyAsync(d_taumax, tau_max, nu * sizeof(double), hipMemcpyHostToDevice, st));
-    PipeContactsArgs pc = {};
-    if (from_plant) pc = pipe_contacts_args("qp_low_level_steps", qc, sim, nk, (int)B, q.cs);
     PipeArgs p;
-    p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains; p.knots = plan->d_knots;
-    p.N = P.N; p.nx = nx; p.nq = q.nq; p.nv = q.nv; p.n = P.n; p.m = P.m; p.gain_stride = P.gain_stride; p.oK = P.oK; p.knot_stride = P.knot_stride; p.oXD = P.oXD;
-    p.slot0 = plan->khead % P.N;
-    p.x = sim_measured(sim); p.xrob = q.xrob; p.acc = q.acc; p.f = q.f; p.sol = q.sol; p.nk = nk; p.qn = q.n; p.tau_max = d_taumax; p.sim_u = sim->plant.d_simu; p.f_new = d_fnew;
-    p.used = from_plant ? qc.used : nullptr;
+    p.plan = plan_view(plan); p.nq = q.nq; p.nv = q.nv; p.nk = nk;
+    p.x = sim_measured(sim); p.xrob = q.xrob; p.acc = q.acc; p.f = q.f;
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
-      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(d_xprev, sim_measured(sim), B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      if (plan->d_plan_lat) hipLaunchKernelGGL(k_pipe_feedback<true>, dim3((unsigned)B), dim3(64), 0, st, p, plan_latency_args(plan));
-      else hipLaunchKernelGGL(k_pipe_feedback<false>, dim3((unsigned)B), dim3(64), 0, st, p, PlanLatencyArgs{});
+      if (step == steps - 1 && x_prev) loop_keep_measurement(sim, st, d_xprev);
+      loop_launch_feedback(k_pipe_feedback<true>, k_pipe_feedback<false>, plan, st, p);
       if (from_plant) pipe_contacts_enqueue(pc, st);
       qp_id_enqueue(qp, S, kd);
       qp_launch_solve(qp, S);
-      hipLaunchKernelGGL(k_pipe_torque, dim3((unsigned)B), dim3(64), 0, st, p);
+      loop_torque_enqueue(q, qc, nk, sim, d_fnew, d_taumax);
       sim_step_enqueue(sim, st, za, 1, dt, false);
     }
-    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->plant.d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (forces) HIP_OK(hipMemcpyAsync(forces, d_fnew, B * nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (info) HIP_OK(hipMemcpyAsync(info, q.info, B * sizeof(mpc_qp_info), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    sim->perfect_feedback = false;
+    loop_finish(sim, st, d_xprev, x_prev, x_out, tau, d_fnew, nf, forces, q.info, info);
     return 0;
   } catch (const std::exception& e) {
     qp_set_error(qp, e.what());
@@ -112,6 +157,7 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
                                 double* forces, mpc_qp_info* info, double* ik_out) {
   if (!qp) return -2;
   try {
+    const char* who = "qp_ikid_low_level_steps";
     if (!S || !plan || !sim || !frames || !weights || !gains || !cone || !l_box || !u_box || !x_posture || !contact_states)
       throw std::runtime_error("qp_ikid_low_level_steps: null argument");
     // foot_refs = NULL: the samples the plan's own generator keeps on the device (mpc_walk_poses_update) ; without one that is the null argument it was
@@ -120,73 +166,53 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
     if (nk != 2) throw std::runtime_error("qp_ikid_low_level_steps: two contacts (nk = 2) expected");
     const QpContactSource qc = qp_contact_source(qp);
     const bool from_plant = qc.source != MPC_QP_CONTACTS_SCHEDULE;
-    if (from_plant) (void)pipe_contacts_args("qp_ikid_low_level_steps", qc, sim, nk, 0, nullptr);
+    if (from_plant) (void)pipe_contacts_args(who, qc, sim, nk, 0, nullptr);
     qp_ikid_prepare(qp, nk, frames, base_frame, torso_frame, weights, gains, cone, l_box, u_box);
     const QpIdBuffers q = qp_id_buffers(qp);
     const Layout& P = plan->L;
     const Layout& Z = sim->L;
     const int nx = q.nq + q.nv, nu = q.nv - 6, nf = 6 * nk, nik = CG_IK_DOUBLES(q.nv);
-    if (plan->dims.device != q.device || sim->dims.device != q.device) throw std::runtime_error("qp_ikid_low_level_steps: the three handles must live on one device");
-    if (P.B != q.B || Z.B != q.B) throw std::runtime_error("qp_ikid_low_level_steps: the three handles must have the same batch size");
+    loop_check_handles(who, "three", plan, sim, q.device, q.B);
     if (P.space != MPC_SPACE_VECTOR || P.nx != CG_NC || P.n != CG_NC || P.m != nf)
       throw std::runtime_error("qp_ikid_low_level_steps: the plan must be a centroidal problem (vector space, nx = 9) with controls of 6 nk contact wrench components");
     if (Z.nx != nx || Z.m != nu) throw std::runtime_error("qp_ikid_low_level_steps: the simulator handle must have the QP's model (nx = nq + nv, nu = nv - 6)");
     if (q.nj > CG_MAX_NJ) throw std::runtime_error("qp_ikid_low_level_steps: more moving joints than the glue kernels hold (64)");
-    if (plan->async_pending > 0) throw std::runtime_error("qp_ikid_low_level_steps: the plan has ticks in flight (mpc_wait first)");
-    sim_steps_check(sim, "qp_ikid_low_level_steps", SIM_STAGE0, steps);
-    HIP_OK(hipStreamSynchronize(plan->stream));
-    HIP_OK(hipStreamSynchronize(sim->stream));
+    hipStream_t st = q.stream;
+    loop_check_idle(who, plan, sim, SIM_STAGE0, steps, st);
     const size_t B = q.B;
     bool* kept = nullptr;
     // x before the last step (kept for the next call) | its new_x | forces + df | x_posture | foot references
     double* scr = qp_ikid_scratch(qp, B * nx + B * CG_NC + B * nf + nx + B * 48, &kept);
     double *d_xprev = scr, *d_cprev = d_xprev + B * nx, *d_fnew = d_cprev + B * CG_NC, *d_xpost = d_fnew + B * nf, *d_refs = d_xpost + nx;
     if (!x_ik && !*kept) throw std::runtime_error("qp_ikid_low_level_steps: x_ik is NULL and no earlier call kept a measurement");
-    hipStream_t st = q.stream;
     sim_steps_begin(sim, st, x);
     if (x_ik) HIP_OK(hipMemcpyAsync(d_xprev, x_ik, B * nx * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(from_plant ? qc.sched : q.cs, contact_states, B * nk * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    PipeContactsArgs pc = {};
-    if (from_plant) pc = pipe_contacts_args("qp_ikid_low_level_steps", qc, sim, nk, (int)B, q.cs);
+    const PipeContactsArgs pc = loop_contacts_begin(who, qc, q, sim, nk, contact_states);
     HIP_OK(hipMemcpyAsync(d_xpost, x_posture, nx * sizeof(double), hipMemcpyHostToDevice, st));
     if (foot_refs) HIP_OK(hipMemcpyAsync(d_refs, foot_refs, B * 48 * sizeof(double), hipMemcpyHostToDevice, st));
     else HIP_OK(hipMemcpyAsync(d_refs, plan->d_poses_samples, B * 48 * sizeof(double), hipMemcpyDeviceToDevice, st));
     IkidGlueArgs g = {};
-    g.mi = q.mi; g.md = q.md; g.nq = q.nq; g.nv = q.nv;
-    g.xs = plan->d_xs; g.us = plan->d_us; g.gains = plan->d_gains; g.knots = plan->d_knots;
-    g.N = P.N; g.m = P.m; g.gain_stride = P.gain_stride; g.oK = P.oK; g.knot_stride = P.knot_stride; g.oXD = P.oXD;
-    g.slot0 = plan->khead % P.N;
+    g.mi = q.mi; g.md = q.md; g.nq = q.nq; g.nv = q.nv; g.nk = nk; g.plan = plan_view(plan);
     g.x_ik = d_xprev; g.x_post = d_xpost; g.refs = d_refs; g.ref_dt = ref_dt;
-    g.fr[0] = frames[0]; g.fr[1] = frames[1]; g.fr[2] = base_frame; g.fr[3] = torso_frame;
-    g.ik = q.ik;
+    g.fr[0] = frames[0]; g.fr[1] = frames[1]; g.fr[2] = base_frame; g.fr[3] = torso_frame; g.ik = q.ik;
     g.x = sim_measured(sim); g.xrob = q.xrob; g.f = q.f; g.c_prev = d_cprev;
-    g.sol = q.sol; g.nk = nk; g.qn = q.n; g.sim_u = sim->plant.d_simu; g.f_new = d_fnew;
-    g.used = from_plant ? qc.used : nullptr;
-    if (plan->d_plan_lat) hipLaunchKernelGGL(k_ikid_task_errors<true>, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g, plan_latency_args(plan));
-    else hipLaunchKernelGGL(k_ikid_task_errors<false>, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g, PlanLatencyArgs{});
+    loop_launch_feedback(k_ikid_task_errors<true>, k_ikid_task_errors<false>, plan, st, g);
     HIP_OK(hipGetLastError());
     if (ik_out) HIP_OK(hipMemcpyAsync(ik_out, q.ik, B * nik * sizeof(double), hipMemcpyDeviceToHost, st));
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
       g.last = (step == steps - 1);
-      if (g.last) HIP_OK(hipMemcpyAsync(d_xprev, sim_measured(sim), B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      if (plan->d_plan_lat) hipLaunchKernelGGL(k_pipe_centroidal_feedback<true>, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g, plan_latency_args(plan));
-      else hipLaunchKernelGGL(k_pipe_centroidal_feedback<false>, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g, PlanLatencyArgs{});
+      if (g.last) loop_keep_measurement(sim, st, d_xprev);
+      loop_launch_feedback(k_pipe_centroidal_feedback<true>, k_pipe_centroidal_feedback<false>, plan, st, g);
       if (from_plant) pipe_contacts_enqueue(pc, st);
       qp_ikid_enqueue(qp, S);
       qp_launch_solve(qp, S);
-      hipLaunchKernelGGL(k_pipe_ikid_torque, dim3((unsigned)B), dim3(CG_THREADS), 0, st, g);
+      loop_torque_enqueue(q, qc, nk, sim, d_fnew, nullptr);  // (no clamp: the QP's torque box is the limit)
       sim_step_enqueue(sim, st, za, 1, dt, false);
     }
-    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, d_xprev, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     if (c_prev) HIP_OK(hipMemcpyAsync(c_prev, d_cprev, B * CG_NC * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->plant.d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (forces) HIP_OK(hipMemcpyAsync(forces, d_fnew, B * nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (info) HIP_OK(hipMemcpyAsync(info, q.info, B * sizeof(mpc_qp_info), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
+    loop_finish(sim, st, d_xprev, x_prev, x_out, tau, d_fnew, nf, forces, q.info, info);
     *kept = true;
-    sim->perfect_feedback = false;
     return 0;
   } catch (const std::exception& e) {
     qp_set_error(qp, e.what());
@@ -200,39 +226,28 @@ int mpc_qp_ikid_low_level_steps(mpc_qp_solver* qp, const mpc_qp_settings* S, mpc
 int mpc_feedback_low_level_steps(mpc_solver* plan, mpc_solver* sim, const double* x, int32_t steps, double dt, double* x_prev, double* x_out, double* tau,
                                  double* wrenches) {
   MPC_TRY(plan, {
+    const char* who = "feedback_low_level_steps";
     if (!plan || !sim) throw std::runtime_error("feedback_low_level_steps: null handle");
     if (steps <= 0 || !(dt > 0.0)) throw std::runtime_error("feedback_low_level_steps: steps and dt must be positive");
-    if (plan->dims.device != sim->dims.device) throw std::runtime_error("feedback_low_level_steps: the two handles must live on one device");
     const Layout& P = plan->L;
     const Layout& Z = sim->L;
-    if (P.B != Z.B) throw std::runtime_error("feedback_low_level_steps: the two handles must have the same batch size");
+    loop_check_handles(who, "two", plan, sim, sim->dims.device, Z.B);
     if (P.space != MPC_SPACE_MULTIBODY || P.nx != Z.nx || P.n != Z.n || P.m != Z.m || P.n > PIPE_MAX_N)
       throw std::runtime_error("feedback_low_level_steps: the plan must be a multibody problem with the simulator's nx and joint-torque controls (m = nu = nv - 6)");
-    if (plan->async_pending > 0) throw std::runtime_error("feedback_low_level_steps: the plan has ticks in flight (mpc_wait first)");
-    sim_steps_check(sim, "feedback_low_level_steps", SIM_NU | SIM_STAGE0, steps);
-    HIP_OK(hipStreamSynchronize(plan->stream));
-    const size_t B = Z.B;
-    const int nx = Z.nx, nu = Z.m;
-    if (x_prev && !sim->plant.d_xlast) sim->plant.d_xlast = sim->alloc<double>(B * nx);
     hipStream_t st = sim->stream;
+    loop_check_idle(who, plan, sim, SIM_NU | SIM_STAGE0, steps, st);
+    if (x_prev && !sim->plant.d_xlast) sim->plant.d_xlast = sim->alloc<double>((size_t)Z.B * Z.nx);
     sim_steps_begin(sim, st, x);
     FdPipeArgs p;
-    p.xs = plan->d_xs; p.us = plan->d_us; p.gains = plan->d_gains;
-    p.N = P.N; p.nx = nx; p.nv = Z.n / 2; p.nq = nx - Z.n / 2; p.n = P.n; p.m = nu; p.gain_stride = P.gain_stride; p.oK = P.oK;
+    p.plan = plan_view(plan); p.nv = Z.n / 2; p.nq = Z.nx - Z.n / 2;
     p.x = sim_measured(sim); p.sim_u = sim->plant.d_simu;
     const SolverArgs za = sim->args();
     for (int step = 0; step < steps; ++step) {
-      if (step == steps - 1 && x_prev) HIP_OK(hipMemcpyAsync(sim->plant.d_xlast, sim_measured(sim), B * nx * sizeof(double), hipMemcpyDeviceToDevice, st));
-      if (plan->d_plan_lat) hipLaunchKernelGGL(k_pipe_state_feedback<true>, dim3((unsigned)B), dim3(64), 0, st, p, plan_latency_args(plan));
-      else hipLaunchKernelGGL(k_pipe_state_feedback<false>, dim3((unsigned)B), dim3(64), 0, st, p, PlanLatencyArgs{});
+      if (step == steps - 1 && x_prev) loop_keep_measurement(sim, st, sim->plant.d_xlast);
+      loop_launch_feedback(k_pipe_state_feedback<true>, k_pipe_state_feedback<false>, plan, st, p);
       sim_step_enqueue(sim, st, za, 1, dt, wrenches != nullptr);
     }
-    if (x_prev) HIP_OK(hipMemcpyAsync(x_prev, sim->plant.d_xlast, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (x_out) HIP_OK(hipMemcpyAsync(x_out, sim->d_x0, B * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (tau) HIP_OK(hipMemcpyAsync(tau, sim->plant.d_simu, B * nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (wrenches) HIP_OK(hipMemcpyAsync(wrenches, sim->plant.d_simwr, B * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    sim->perfect_feedback = false;
+    loop_finish(sim, st, sim->plant.d_xlast, x_prev, x_out, tau, sim->plant.d_simwr, 12, wrenches);
   })
 }
 
@@ -278,14 +293,10 @@ int mpc_plan_latency_publish(mpc_solver* plan) {
     if (!plan->d_plan_lat) throw std::runtime_error("plan_latency_publish: the latency model is off on this handle (arm it with mpc_plan_latency)");
     if (plan->async_pending > 0) throw std::runtime_error("plan_latency_publish: the plan has ticks in flight (mpc_wait first)");
     if (!plan->has_run) throw std::runtime_error("plan_latency_publish: the handle has never run: there is no plan to hold");
-    const Layout& P = plan->L;
     PlanPublishArgs a;
-    a.xs = plan->d_xs; a.us = plan->d_us; a.gains = plan->d_gains; a.knots = plan->d_knots;
-    a.N = P.N; a.nx = P.nx; a.n = P.n; a.m = P.m; a.gain_stride = P.gain_stride; a.oK = P.oK; a.knot_stride = P.knot_stride; a.oXD = P.oXD;
-    a.slot1 = (plan->khead + 1) % P.N;
-    a.xd_off = P.space == MPC_SPACE_MULTIBODY ? P.n / 2 : 3;
-    a.params = plan->d_plan_lat; a.state = plan_latency_state(plan); a.held = plan_latency_held(plan); a.W = (int)plan_latency_width(P);
-    hipLaunchKernelGGL(k_plan_latency_publish, dim3((unsigned)P.B), dim3(PLAN_LAT_THREADS), 0, plan->stream, a);
+    a.plan = plan_view(plan); a.slot1 = (plan->khead + 1) % plan->L.N;
+    a.params = plan->d_plan_lat; a.state = plan_latency_state(plan); a.held = plan_latency_held(plan); a.W = (int)plan_latency_width(plan->L);
+    hipLaunchKernelGGL(k_plan_latency_publish, dim3((unsigned)plan->L.B), dim3(PLAN_LAT_THREADS), 0, plan->stream, a);
     HIP_OK(hipGetLastError());
   })
 }

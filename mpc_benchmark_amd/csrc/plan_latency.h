@@ -1,10 +1,10 @@
-// plan_latency.h — the per-robot hand-over latency of the plan (include/mpc_plan_latency.h), device side: the publication kernel that takes every
-// robot's HELD record (knot 1 of the outgoing plan, by value) and draws its latency, and what the feedback kernels of the three device loops
-// (pipeline_glue.h, pipeline_ikid_glue.h, pipeline_fd_glue.h) share to read a record and to advance the countdown.  The host side (mpc_plan_latency,
-// mpc_plan_latency_publish, mpc_plan_latency_read) is in pipeline_loops.h, with the loops.  The numpy mirror, the definition:
-// mpc_benchmark_amd/plan_latency.py.
+// plan_latency.h — the per-robot hand-over latency of the plan (include/mpc_plan_latency.h), device side: the layout of a robot's HELD record (knot 1
+// of the outgoing plan, by value), the publication kernel that writes it and draws the latency, and what the feedback kernels of the three device
+// loops (pipeline_*glue.h) share to pick the record in force and to advance the countdown.  The host side (mpc_plan_latency, mpc_plan_latency_publish,
+// mpc_plan_latency_read) is in pipeline_loops.h, with the loops.  The numpy mirror, the definition: mpc_benchmark_amd/plan_latency.py.
 #pragma once
 #include "../../include/mpc_plan_latency.h"
+#include "plan_view.h"
 #include "sim_sensors.h"  // sim_sen_philox
 
 #define PLAN_LAT_THREADS 256
@@ -12,14 +12,31 @@
 // What the second instantiation of a feedback kernel gets beside its own arguments (the first one's arguments stay as they are).
 struct PlanLatencyArgs {
   double* state;       // [B][MPC_PLAN_LATENCY_STATE]
-  const double* held;  // [B][W]: xs[1] | us[1] | K_1 row-major | xdot part
+  const double* held;  // [B][W] held records: the feedback kernels only read them
   int W;
 };
+
+// Robot b's record in `held`.  The layout, here and nowhere else: x [nx] | u [m] | K [m][n] row-major | xd [MPC_PLAN_LATENCY_XDOT] (W = MPC_PLAN_LATENCY_HELD(nx, n, m))
+template <class T> DEV PlanRecordOf<T> plan_held_record(T* held, int b, int W, int nx, int m, int n) {
+  PlanRecordOf<T> r;
+  r.x = held + (size_t)b * W; r.u = r.x + nx; r.K = r.u + m; r.xd = r.K + (size_t)m * n;
+  return r;
+}
 
 // Does robot b read its held record on this step?  Every lane reads the row; plan_latency_count writes it behind a barrier.
 DEV bool plan_latency_in_force(const PlanLatencyArgs& h, int b) {
   const double* s = h.state + (size_t)b * MPC_PLAN_LATENCY_STATE;
   return s[0] > 0.0 && s[6] != 0.0;
+}
+
+// The record in force for robot b: knot 0 of the plan, or (HELD, `h` is read by that instantiation alone) the held one while its latency runs.
+template <bool HELD> DEV PlanRecord plan_record_in_force(const PlanView& v, const PlanLatencyArgs& h, int b, bool& held) {
+  held = false;
+  if (HELD) {
+    held = plan_latency_in_force(h, b);
+    if (held) return plan_held_record(h.held, b, h.W, v.nx, v.m, v.n);
+  }
+  return plan_knot(v, b, 0, v.slot0);
 }
 
 // One lane per robot advances the clock of a low-level step.  The barrier separates it from the other lanes' read of `remaining`.
@@ -32,12 +49,10 @@ DEV void plan_latency_count(const PlanLatencyArgs& h, int b, bool held, int lane
 }
 
 struct PlanPublishArgs {
-  const double *xs, *us, *gains, *knots;  // the outgoing plan, where the loops read it
-  int N, nx, n, m, gain_stride, oK, knot_stride, oXD;
-  int slot1;   // ring slot of knot 1's stage data
-  int xd_off;  // first entry of the xdot part
+  PlanView plan;         // the outgoing plan, where the loops read it
+  int slot1;             // ring slot of knot 1's stage data
   const double* params;  // [B][MPC_PLAN_LATENCY_PARAMS]
-  double *state, *held;
+  double *state, *held;  // [B][MPC_PLAN_LATENCY_STATE], [B][W]: the publication writes both
   int W;
 };
 
@@ -47,24 +62,20 @@ struct PlanPublishArgs {
 // so a pair travels as two doubles.)  Lane 0 draws the latency and resets the countdown; stream order serialises the publications.
 __global__ void __launch_bounds__(PLAN_LAT_THREADS) k_plan_latency_publish(PlanPublishArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int nx = a.nx, n = a.n, m = a.m;
-  double* h = a.held + (size_t)b * a.W;
-  const double* x1 = a.xs + ((size_t)b * (a.N + 1) + 1) * nx;
-  const double* u1 = a.us + ((size_t)b * a.N + 1) * m;
-  const double* K1 = a.gains + ((size_t)b * (a.N + 1) + 1) * a.gain_stride + a.oK;
-  const double* xd = a.knots + ((size_t)b * (a.N + 1) + a.slot1) * a.knot_stride + a.oXD + a.xd_off;
-  for (int i = tid; i < nx; i += PLAN_LAT_THREADS) h[i] = x1[i];
-  for (int i = tid; i < m; i += PLAN_LAT_THREADS) h[nx + i] = u1[i];
-  double* hK = h + nx + m;
+  const int nx = a.plan.nx, n = a.plan.n, m = a.plan.m;
+  const PlanRecord k1 = plan_knot(a.plan, b, 1, a.slot1);
+  const PlanRecordOf<double> h = plan_held_record(a.held, b, a.W, nx, m, n);
+  for (int i = tid; i < nx; i += PLAN_LAT_THREADS) h.x[i] = k1.x[i];
+  for (int i = tid; i < m; i += PLAN_LAT_THREADS) h.u[i] = k1.u[i];
   for (int r = wave; r < m; r += PLAN_LAT_THREADS / 64) {
-    const double* src = K1 + (size_t)r * n;
-    double* dst = hK + (size_t)r * n;
+    const double* src = k1.K + (size_t)r * n;
+    double* dst = h.K + (size_t)r * n;
     for (int c = 2 * lane; c < n; c += 128) {
       dst[c] = src[c];
       if (c + 1 < n) dst[c + 1] = src[c + 1];
     }
   }
-  if (tid < MPC_PLAN_LATENCY_XDOT) hK[(size_t)m * n + tid] = xd[tid];
+  if (tid < MPC_PLAN_LATENCY_XDOT) h.xd[tid] = k1.xd[tid];
   if (tid == 0) {
     const double* p = a.params + (size_t)b * MPC_PLAN_LATENCY_PARAMS;
     double* s = a.state + (size_t)b * MPC_PLAN_LATENCY_STATE;

@@ -1,7 +1,7 @@
 // sim_contacts.h — the unilateral foot-contact rule of a torque-driven simulator handle (mpc_sim_contacts, include/mpc_sim_contacts.h): after every
 // simulator step of a handle with the rule on, one wavefront per robot takes the sole heights of the state the step left and the step's LOCAL
 // contact wrenches, and updates that robot's row: which soles are held, and where the ground side of each lies.  The next step's stage kernel
-// (k_eval_multibody<2>) integrates the contacts of that row.  The kinematics are the centroidal pipeline's (pipeline_ikid_glue.h), the sole
+// (k_eval_multibody<2>) integrates the contacts of that row.  The kinematics are those of body_kinematics.h, the sole
 // placements the record's (sim_record.h); the rule itself is one lane's scalar work, BulletRobot._update_contacts in its order (the numpy mirror:
 // mpc_benchmark_amd/contact_rule.py).  One workgroup owns each row and stream order serialises the steps: no atomics.  With a terrain
 // (mpc_sim_terrain, sim_terrain.h) the ground under each sole is the height function at the sole's origin: lanes 0 - 31 test the 2 x 16 boxes they

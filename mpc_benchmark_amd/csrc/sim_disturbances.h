@@ -4,10 +4,10 @@
 // and writes what acts in the step: world force and world point into out[b][6], the link into link[b] (-1: nothing).  The step's stage kernel
 // (k_eval_multibody<2>) reads the two in place of the armed push and applies the wrench on the dofs below that link.  The clock, the transitions
 // and the pick are one lane's scalar work (the numpy mirror: mpc_benchmark_amd/disturbance_model.py); the forward kinematics
-// (pipeline_ikid_glue.h) run only when the acting event has a body-fixed frame, a branch the whole workgroup takes together.  One workgroup owns
+// (body_kinematics.h) run only when the acting event has a body-fixed frame, a branch the whole workgroup takes together.  One workgroup owns
 // each row and stream order serialises the steps: plain stores, no atomics.
 #pragma once
-#include "pipeline_ikid_glue.h"
+#include "body_kinematics.h"
 #include "../../include/mpc_sim_contacts.h"
 #include "../../include/mpc_sim_disturbances.h"
 

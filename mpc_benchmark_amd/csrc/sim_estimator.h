@@ -3,7 +3,7 @@
 // true state), runs the kinematics of the measured joints and orientation with the base at the origin and at rest, and replaces the base position
 // and the base linear velocity by a blend of the measurement and of leg odometry through the soles the contact rule holds.  The ESTIMATE goes into
 // the robot's state row and into the contiguous [B][nx] buffer the controllers of the device loops read.  Lanes stride over the state index (nx = 77
-// of the complete model takes a second pass); the kinematics are the centroidal pipeline's (pipeline_ikid_glue.h, one body per lane), the sole
+// of the complete model takes a second pass); the kinematics are those of body_kinematics.h (one body per lane), the sole
 // placements the record's (sim_record.h); lanes 0 and 1 take one sole each, the rule itself is lane 0's scalar work.  A launch is a chain of short
 // dependent phases for a few hundred bytes per robot: its time is latency, as k_sim_contacts'.  Plain fp64; one workgroup owns each row and stream
 // order serialises the events: no atomics.  The numpy mirror, the definition: mpc_benchmark_amd/state_estimator.py.

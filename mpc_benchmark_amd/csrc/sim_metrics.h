@@ -1,8 +1,8 @@
 // sim_metrics.h — the locomotion metrics of a torque-driven simulator handle (mpc_sim_metrics, include/mpc_sim_metrics.h): after every simulator
 // step of a handle with metrics on, one wavefront per robot folds what the step left into that robot's row of accumulators, so that plot.py's
 // evaluation of a run (centre of pressure against the support box, angular momentum, joint power and energy) and a fall verdict are read once at the
-// end instead of downloading the per-step record.  The kinematics, centre of mass and centroidal momentum are the centroidal pipeline's
-// (pipeline_ikid_glue.h), the sole placements the record's (sim_record.h).  One workgroup owns each row and stream order serialises the steps: no
+// end instead of downloading the per-step record.  The kinematics, centre of mass and centroidal momentum are those of body_kinematics.h
+// (one body per lane), the sole placements the record's (sim_record.h).  One workgroup owns each row and stream order serialises the steps: no
 // atomics, and the same sums in the same order on every run.  On a handle with a terrain (mpc_sim_terrain, sim_terrain.h) the heights of the fall
 // verdict are taken above the ground: a sole's above the terrain under its origin, the base's above the mean anchor height of the soles in contact.
 #pragma once

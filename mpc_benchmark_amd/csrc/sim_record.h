@@ -1,9 +1,9 @@
 // sim_record.h — the per-step record of a torque-driven simulator handle (mpc_sim_record, include/mpc_sim_ext.h): after every simulator step of a
 // handle with recording on, one wavefront per robot appends what the step left to the device ring, so that the 1 kHz response of the device loops
 // (mpc_qp_low_level_steps, mpc_qp_ikid_low_level_steps) can be read without a host round trip per step.  The kinematics, centre of mass and
-// centroidal momentum are the centroidal pipeline's (pipeline_ikid_glue.h).
+// centroidal momentum are those of body_kinematics.h.
 #pragma once
-#include "pipeline_ikid_glue.h"
+#include "body_kinematics.h"
 
 #define SIM_REC_TAIL 51  // doubles after x and tau: wrenches 12, com 3, momentum 6, soles 24, push 6
 static inline __host__ __device__ int sim_record_width(int nx, int nu) { return nx + nu + SIM_REC_TAIL; }

@@ -113,7 +113,7 @@ def sole_kinematics(model, frame_ids, x):
     """The soles of one robot at the state ``x`` (nx,): ``r`` (2, 3) the world positions of the origins of the frames ``frame_ids`` (left, right) and
     ``u`` (2, 3) the world velocities of those points.  Every joint on the way from the sole to the root adds its spatial velocity at the world
     origin, ``(p_j x w_j, w_j) v_j`` for a rotation about the world axis ``w_j`` through ``p_j`` and the body axes for the translations of the
-    floating base; the point velocity is ``v_O + omega x r`` (csrc/pipeline_ikid_glue.h cg_kinematics, in its order)."""
+    floating base; the point velocity is ``v_O + omega x r`` (csrc/body_kinematics.h cg_kinematics, in its order)."""
     nq = model.nq
     q, v = np.asarray(x[:nq], dtype=float), np.asarray(x[nq:], dtype=float)
     data = model.createData()
